@@ -76,6 +76,14 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              FMA3, the host setting of record), 0 = the stable order (weight, index) of rounds 1-3 (= sklearn
  *                              with that call forced to kind='stable'). */
 #define RHCCQ_OPT_REASSIGN_ORDER 7
+/*   RHCCQ_OPT_FRAME_CHAINS     rhccq_encode_frame: 1 (default) = the k-means++ chains of every level-1 MiniBatchKMeans problem of a
+ *                              frame (init samples <= 98 304 each) are drawn, ordered and run in ONE launch on the context's
+ *                              stream before the class pipelines start, which then wait for it; 0 = every problem draws and
+ *                              runs its chain on its own lane.  Same results.  Why: the runtime maps the lanes' streams onto
+ *                              GPU_MAX_HW_QUEUES hardware queues (4 by default); two streams on one queue run their kernels
+ *                              one after the other, so a chain of one class could hold up the other class for its whole
+ *                              length.  Every step after the chains needs them all, so one launch loses nothing. */
+#define RHCCQ_OPT_FRAME_CHAINS 8
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */

@@ -300,43 +300,90 @@ void free_frame_state(void* p) { delete (FrameState*)p; }
 
 // ---- MiniBatchKMeans(k, batch_size=1000, random_state=42, n_init='auto').fit_predict of ONE palette resident on the device
 // (ops.py::minibatch_kmeans for one problem; reference call site clustering.py:207-218) --------------------------------------
-void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out) {
+// The draws of one fit ahead of its k-means++ chain (sklearn _init_centroids with init_size, then kmeans_plusplus): host only
+struct MbkDraws {
+  int64_t init_size = 0;
+  std::vector<int32_t> init_idx;
+  int32_t first = 0;
+  int T = 0;
+  int64_t pos = 0;                                     // raw MT19937 word of the first k-means++ uniform
+  int64_t nu = 0;                                      // uniforms of the chain
+  int64_t cursor0 = 0;                                 // stream position behind the k-means++ uniforms
+};
+
+MbkDraws mbk_draws(int64_t n, int64_t k) {
+  MtTable& mt = MtTable::get();
+  MbkDraws d;
+  const int64_t bs = std::min<int64_t>(1000, n);
+  d.init_size = 3 * bs;
+  if (d.init_size < k) d.init_size = 3 * k;
+  d.init_size = std::min(d.init_size, n);
+  int64_t pos = 0;
+  pos += mt.randint(pos, n, d.init_size, nullptr);                       // validation_indices: stream position only
+  d.init_idx.resize((size_t)d.init_size);
+  if (d.init_size < n) pos += mt.randint(pos, n, d.init_size, d.init_idx.data());
+  else for (int64_t i = 0; i < n; ++i) d.init_idx[(size_t)i] = (int32_t)i;
+  d.first = first_centre_index(d.init_size, mt.dbl(pos));
+  pos += 2;
+  d.T = 2 + (int)std::log((double)k);
+  d.nu = std::max<int64_t>((k - 1) * d.T, 1);
+  d.pos = pos;
+  d.cursor0 = pos + 2 * (k - 1) * d.T;
+  return d;
+}
+
+// A chain run ahead for one fit (RHCCQ_OPT_FRAME_CHAINS): its centres once `done` has fired
+struct PreChain {
+  int64_t n = 0, k = 0;
+  MbkDraws draws;
+  double* centres = nullptr;                           // [k][4], written by the chain, then the fit's own
+  hipEvent_t done = nullptr;
+};
+
+// the third-generation chain's LDS limit (k8_init3.h): problems above it are left to their lanes, so that a frame's launch never
+// moves a problem to another generation of the chain than the one it gets alone
+constexpr int64_t kFrameChainMaxInit = 98304;
+
+void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out, const PreChain* pre = nullptr) {
   rhccq_ctx* c = L.ctx;
   MtTable& mt = MtTable::get();
   const bool tr = trace_on();
   double tt[6] = {now_ms(), 0, 0, 0, 0, 0};
+  double ts[4] = {0, 0, 0, 0};                                           // (trace) set-up: host draws, word table, uniforms + upload
   const int64_t bs = std::min<int64_t>(1000, n);
-  int64_t init_size = 3 * bs;
-  if (init_size < k) init_size = 3 * k;
-  init_size = std::min(init_size, n);
-  int64_t pos = 0;
-  pos += mt.randint(pos, n, init_size, nullptr);                         // validation_indices: stream position only
-  std::vector<int32_t> init_idx((size_t)init_size);
-  if (init_size < n) pos += mt.randint(pos, n, init_size, init_idx.data());
-  else for (int64_t i = 0; i < n; ++i) init_idx[(size_t)i] = (int32_t)i;
-  const int32_t first = first_centre_index(init_size, mt.dbl(pos));
-  pos += 2;
-  const int T = 2 + (int)std::log((double)k);
-  const int64_t nu = std::max<int64_t>((k - 1) * T, 1);
-  const int64_t cursor0 = pos + 2 * (k - 1) * T;                         // stream position behind the k-means++ uniforms
-  const uint32_t* words;
-  int64_t n_words;
-  mt.device(L.device, pos + 2 * nu, &words, &n_words);
-  double* d_rand = L.dalloc<double>((size_t)nu);
-  EF_RC(c, rhccq_mt_uniforms(c, words, pos, nu, d_rand));
-  int32_t* d_init = L.upload(init_idx.data(), (size_t)init_size);
+  MbkDraws own;
+  if (!pre) own = mbk_draws(n, k);
+  else if (pre->n != n || pre->k != k) throw Err{RHCCQ_E_ARG, "mbk_fit: the frame's chain was run for another problem"};
+  const MbkDraws& dr = pre ? pre->draws : own;
+  const int64_t init_size = dr.init_size, cursor0 = dr.cursor0;
   rhccq_mbk_problem prob;
   prob.off = 0; prob.n = n; prob.k = k; prob.koff = 0; prob.init_off = 0; prob.init_n = init_size; prob.rand_off = 0;
-  prob.first = first; prob.T = T;
-  const int64_t obytes = rhccq_mbk_order_bytes(init_size);
-  void* otmp = L.arena.alloc((size_t)obytes);
-  int32_t* d_perm = L.dalloc<int32_t>((size_t)init_size);
-  EF_RC(c, rhccq_mbk_order(c, keys, &prob, 1, d_init, d_perm, otmp, obytes));
-  double* centres = L.dzeros<double>((size_t)k * 4);
-  int32_t* chosen = L.dzeros<int32_t>((size_t)k);
-  if (tr) { L.sync(); tt[1] = now_ms(); }
-  EF_RC(c, rhccq_mbk_init(c, keys, &prob, 1, d_init, d_perm, d_rand, centres, chosen));
-  if (tr) { L.sync(); tt[2] = now_ms(); }
+  prob.first = dr.first; prob.T = dr.T;
+  const uint32_t* words;
+  int64_t n_words;
+  double* centres;
+  if (pre) {                                                             // the frame's launch ran the chain: wait for it on this lane
+    EF_HIP(hipStreamWaitEvent(L.stream, pre->done, 0));
+    centres = pre->centres;
+    if (tr) { tt[1] = now_ms(); L.sync(); tt[2] = now_ms(); }
+  } else {
+    if (tr) ts[0] = now_ms();
+    mt.device(L.device, dr.pos + 2 * dr.nu, &words, &n_words);
+    if (tr) ts[1] = now_ms();
+    double* d_rand = L.dalloc<double>((size_t)dr.nu);
+    EF_RC(c, rhccq_mt_uniforms(c, words, dr.pos, dr.nu, d_rand));
+    int32_t* d_init = L.upload(dr.init_idx.data(), (size_t)init_size);
+    if (tr) { L.sync(); ts[2] = now_ms(); }
+    const int64_t obytes = rhccq_mbk_order_bytes(init_size);
+    void* otmp = L.arena.alloc((size_t)obytes);
+    int32_t* d_perm = L.dalloc<int32_t>((size_t)init_size);
+    EF_RC(c, rhccq_mbk_order(c, keys, &prob, 1, d_init, d_perm, otmp, obytes));
+    centres = L.dzeros<double>((size_t)k * 4);
+    int32_t* chosen = L.dzeros<int32_t>((size_t)k);
+    if (tr) { L.sync(); tt[1] = now_ms(); }
+    EF_RC(c, rhccq_mbk_init(c, keys, &prob, 1, d_init, d_perm, d_rand, centres, chosen));
+    if (tr) { L.sync(); tt[2] = now_ms(); }
+  }
   double* weights = L.dzeros<double>((size_t)k);
   double st[16] = {0};
   st[8] = (double)k;                                                     // every centre starts with zero weight
@@ -422,8 +469,13 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
   if (tr) {
     L.sync();
     tt[4] = now_ms();
-    fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms, chain %.2f ms (%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", (long long)n,
-            (long long)k, tt[1] - tt[0], tt[2] - tt[1], (tt[2] - tt[1]) * 1e3 / (double)k, (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
+    if (pre)
+      fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: chain in the frame's launch, waited %.2f ms for it, %lld steps %.2f ms, assign %.2f ms\n", (long long)n,
+              (long long)k, tt[2] - tt[0], (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
+    else
+      fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms (host draws %.2f, word table %.2f, uniforms+upload %.2f, order %.2f), chain %.2f ms "
+              "(%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", (long long)n, (long long)k, tt[1] - tt[0], ts[0] - tt[0], ts[1] - ts[0],
+              ts[2] - ts[1], tt[1] - ts[2], tt[2] - tt[1], (tt[2] - tt[1]) * 1e3 / (double)k, (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
   }
 }
 
@@ -449,6 +501,7 @@ struct Job {
   bool have_labels = false;
   int32_t* labels_dev = nullptr;
   int64_t k = 0;
+  const PreChain* pre = nullptr;                       // its k-means++ chain ran in the frame's launch (resident level-1 jobs)
 };
 
 int64_t n_splits(int64_t n, int64_t mc) {             // split_large_cluster's n_splits (clustering.py:739-747); 0 = do not split
@@ -510,7 +563,7 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
             n = (int64_t)nbk.size();
           }
           jb.labels_dev = S.dalloc<int32_t>((size_t)n);
-          mbk_fit(S, keys, n, jb.k, jb.labels_dev);
+          mbk_fit(S, keys, n, jb.k, jb.labels_dev, jb.pre);
         }
         S.sync();
       } catch (const Err& e) {
@@ -909,6 +962,8 @@ struct FrameCtx {
   int32_t* e1map = nullptr;                            // [n_classes][H * W] entry every pixel shows
   std::vector<int64_t> ebase;                          // first entry id of a class's slice (= palette entries of the classes before)
   hipEvent_t ready = nullptr;
+  std::map<int, PreChain> pre;                         // job -> its level-1 chain in the frame's launch (RHCCQ_OPT_FRAME_CHAINS)
+  hipEvent_t chains_done = nullptr;
 };
 
 struct ClassOut {
@@ -962,6 +1017,8 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
     if (big) {
       jb.keys_dev = F.keys_dev + F.pal_off[(size_t)j];
       jb.has_black = F.has_black[(size_t)j] != 0;
+      const auto it = F.pre.find(j);
+      if (it != F.pre.end()) jb.pre = &it->second;
     } else {
       const size_t a = (size_t)(F.pal_off[(size_t)j] - F.pal_off[(size_t)small_lo]);
       jb.keys.assign(chunk.begin() + a, chunk.begin() + a + (size_t)jb.P);
@@ -1043,6 +1100,78 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
   }
   EF_HIP(hipEventRecord(out.done, L.stream));
   L.sync();
+}
+
+// RHCCQ_OPT_FRAME_CHAINS: the k-means++ chains of every resident level-1 MiniBatchKMeans problem of the frame in ONE launch on the
+// caller's stream (one workgroup per problem, as a batch), before the class pipelines start.  The lanes' streams share the
+// runtime's few hardware queues; a chain on a queue holds up every other stream mapped there for its whole length (a 106 ms chain
+// of one class delayed the other class's set-up or steps by as much).  Nothing after the chains can start before they end, so
+// one launch costs no time and leaves no chain to block another stream.  The draws, uniforms and Morton order are the ones
+// mbk_fit makes for a lone problem (mbk_draws; rhccq_mbk_order / rhccq_mbk_init treat the problems of a batch independently).
+void frame_chains(FrameCtx& F, hipStream_t stream) {
+  rhccq_ctx* c = F.root;
+  FrameState& FS = *(FrameState*)c->frame_state;
+  Arena& A = FS.root_arena;
+  const bool tr = trace_on();
+  const double t0 = now_ms();
+  std::vector<int> ids;
+  std::vector<rhccq_mbk_problem> probs;
+  int64_t ktot = 0, itot = 0, utot = 0, need_words = 1;
+  for (int ci = 0; ci < F.n_classes; ++ci)
+    for (int j = F.job_base[(size_t)ci]; j < F.job_base[(size_t)ci + 1]; ++j) {
+      const int64_t hb = F.has_black[(size_t)j] ? 1 : 0;
+      const int64_t n = F.P[(size_t)j] - hb;
+      if (!F.present[(size_t)j] || n < kMinibatchThreshold) continue;
+      const int64_t k = mbk_k(n, F.classes[ci].quality);
+      PreChain pc;
+      pc.n = n;
+      pc.k = k;
+      pc.draws = mbk_draws(n, k);
+      if (pc.draws.init_size > kFrameChainMaxInit) continue;
+      rhccq_mbk_problem q;
+      q.off = F.pal_off[(size_t)j] + hb; q.n = n; q.k = k; q.koff = ktot; q.init_off = itot; q.init_n = pc.draws.init_size; q.rand_off = utot;
+      q.first = pc.draws.first; q.T = pc.draws.T;
+      probs.push_back(q);
+      ids.push_back(j);
+      ktot += k;
+      itot += pc.draws.init_size;
+      utot += pc.draws.nu;
+      need_words = std::max<int64_t>(need_words, pc.draws.pos + 2 * pc.draws.nu);
+      F.pre[j] = std::move(pc);
+    }
+  if (probs.empty()) return;
+  const uint32_t* words;
+  int64_t n_words;
+  MtTable::get().device(c->device, need_words, &words, &n_words);
+  double* d_rand = (double*)A.alloc((size_t)utot * 8);
+  std::vector<int32_t> init_idx;
+  init_idx.reserve((size_t)itot);
+  for (size_t i = 0; i < probs.size(); ++i) {
+    const MbkDraws& d = F.pre[ids[i]].draws;
+    EF_RC(c, rhccq_mt_uniforms(c, words, d.pos, d.nu, d_rand + probs[i].rand_off));
+    init_idx.insert(init_idx.end(), d.init_idx.begin(), d.init_idx.end());
+  }
+  int32_t* d_init = (int32_t*)A.alloc((size_t)itot * 4);
+  EF_HIP(hipMemcpyAsync(d_init, init_idx.data(), (size_t)itot * 4, hipMemcpyHostToDevice, stream));   // pageable: staged on return
+  const int64_t obytes = rhccq_mbk_order_bytes(itot);
+  void* otmp = A.alloc((size_t)obytes);
+  int32_t* d_perm = (int32_t*)A.alloc((size_t)itot * 4);
+  EF_RC(c, rhccq_mbk_order(c, F.keys_dev, probs.data(), (int32_t)probs.size(), d_init, d_perm, otmp, obytes));
+  double* centres = (double*)A.alloc((size_t)ktot * 4 * 8);
+  int32_t* chosen = (int32_t*)A.alloc((size_t)ktot * 4);
+  EF_HIP(hipMemsetAsync(centres, 0, (size_t)ktot * 4 * 8, stream));
+  EF_HIP(hipMemsetAsync(chosen, 0, (size_t)ktot * 4, stream));
+  const double t1 = now_ms();
+  EF_RC(c, rhccq_mbk_init(c, F.keys_dev, probs.data(), (int32_t)probs.size(), d_init, d_perm, d_rand, centres, chosen));
+  EF_HIP(hipEventCreateWithFlags(&F.chains_done, hipEventDisableTiming));
+  EF_HIP(hipEventRecord(F.chains_done, stream));
+  for (size_t i = 0; i < probs.size(); ++i) {
+    PreChain& pc = F.pre[ids[i]];
+    pc.centres = centres + 4 * probs[i].koff;
+    pc.done = F.chains_done;
+  }
+  if (tr) fprintf(stderr, "[rhccq] frame chains: %zu problems, %lld init samples, set-up %.2f ms (host), launched after %.2f ms\n", probs.size(),
+                  (long long)itot, t1 - t0, now_ms() - t0);
 }
 
 int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const rhccq_class_desc* classes, int32_t n_classes, uint8_t* palette_out,
@@ -1185,6 +1314,7 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   EF_HIP(hipStreamSynchronize(stream));                  // (the host tables above are staged; pal_off is read by the lanes)
   res->ms[1] = now_ms() - t0;
   t0 = now_ms();
+  if (ctx->opt_frame_chains) frame_chains(F, stream);
   // ---- levels 1 and 2: every class a pipeline of its own (nothing of a class's chain depends on the other class; only
   // quantize_image needs both: regions.py:9-70 is called once per class, rhccq.ipynb:1001-1013)
   std::vector<ClassOut> outs((size_t)n_classes);
@@ -1209,6 +1339,7 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
     for (auto& o : outs)
       if (o.done) (void)hipEventDestroy(o.done);
     if (F.ready) (void)hipEventDestroy(F.ready);
+    if (F.chains_done) (void)hipEventDestroy(F.chains_done);
   };
   for (auto& e : errs)
     if (e.code) {
