@@ -578,6 +578,15 @@ int rhccq_dct_quant(rhccq_ctx* ctx, const float* plane, int32_t H, int32_t W, in
 int rhccq_luma_qstep(rhccq_ctx* ctx, const uint8_t* rgb, const uint8_t* roi_mask, int32_t H, int32_t W,
                      int32_t block, float q_roi, float q_bg, float* luma_out, float* qstep_out);
 
+/* ---- EXTENSION: zlib stream (RFC 1950 / 1951) on the device, for the .rhccq container layers --------------------
+ * Format-compatible with zlib's inflate (zlib.decompress reads it), not byte-identical to zlib.compress(level=9);
+ * the output bytes are a function of the input bytes alone (not of the stream, earlier calls or the workspace's
+ * contents).  Each DEFLATE block takes the cheapest of dynamic, fixed and stored, so *out_len <= out_bound. */
+/* host only: workspace and worst-case output size for n input bytes */
+int rhccq_zlib_sizes(int64_t n, int64_t* workspace_bytes, int64_t* out_bound);
+/* zlib stream (RFC 1950/1951) of in[0..n) into out; async on the context stream; *out_len (device int64) receives the length */
+int rhccq_zlib_compress(rhccq_ctx* ctx, const void* in, int64_t n, void* workspace, uint8_t* out, int64_t out_cap, int64_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

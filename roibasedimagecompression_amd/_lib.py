@@ -144,6 +144,8 @@ PROTOTYPES = {
     "rhccq_decode": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
     "rhccq_dct_quant": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rhccq_luma_qstep": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
+    "rhccq_zlib_sizes": (c_int32, [c_int64, C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rhccq_zlib_compress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -1241,6 +1241,39 @@ class Rhccq:
         self._check(self.lib.rhccq_dct_quant(self.ctx, self._p(plane), H, W, block, self._p(qstep), self._p(coef), self._p(q)), "dct_quant")
         return coef, q
 
+    # -- zlib (csrc/zlib_deflate.hip) -------------------------------------------------------------
+    def zlib_sizes(self, n):
+        """-> (workspace bytes, worst-case output bytes) of a zlib stream of n input bytes (host only)"""
+        ws, bound = C.c_int64(), C.c_int64()
+        rc = self._raw.rhccq_zlib_sizes(int(n), C.byref(ws), C.byref(bound))
+        if rc:
+            raise RhccqError(f"rhccq_zlib_sizes({n}) failed ({rc})")
+        return ws.value, bound.value
+
+    def zlib_compress_async(self, t, out=None, workspace=None):
+        """contiguous device tensor (its raw bytes) -> (uint8 device buffer, int64 device length): the zlib stream is
+        out[:length]; nothing waits for the device.  out / workspace: caller-owned uint8 device buffers (default: allocated
+        at the sizes rhccq_zlib_sizes gives; an out smaller than the bound is refused)"""
+        if not t.is_cuda or not t.is_contiguous():
+            raise RhccqError("zlib_compress: a contiguous device tensor is required")
+        n = t.numel() * t.element_size()
+        ws, bound = self.zlib_sizes(n)
+        work = self.empty((max(ws, 1),), torch.uint8) if workspace is None else workspace
+        if work.numel() < ws:
+            raise RhccqError(f"zlib_compress: workspace of {work.numel()} bytes, {ws} needed")
+        out = self.empty((bound,), torch.uint8) if out is None else out
+        length = self.empty((1,), torch.int64)
+        self._check(self.lib.rhccq_zlib_compress(self.ctx, self._p(t), n, self._p(work), self._p(out), out.numel(), self._p(length)),
+                    "zlib_compress")
+        return out, length
+
+    def zlib_compress(self, t):
+        """zlib stream (RFC 1950) of the raw bytes of a contiguous device tensor, as bytes: zlib.decompress() gives
+        them back; format-compatible with zlib.compress, not byte-identical to it"""
+        out, length = self.zlib_compress_async(t)
+        n = int(length.item())
+        return self.to_host(out[:n]).tobytes()
+
     def sync(self):
         self._check(self.lib.rhccq_sync(self.ctx), "sync")
 
