@@ -587,6 +587,30 @@ int rhccq_zlib_sizes(int64_t n, int64_t* workspace_bytes, int64_t* out_bound);
 /* zlib stream (RFC 1950/1951) of in[0..n) into out; async on the context stream; *out_len (device int64) receives the length */
 int rhccq_zlib_compress(rhccq_ctx* ctx, const void* in, int64_t n, void* workspace, uint8_t* out, int64_t out_cap, int64_t* out_len);
 
+/* ---- EXTENSION: zlib stream (RFC 1950 / 1951) decoder on the device, the read side of the container layers ----------
+ * Accepts what zlib.decompress accepts (bytes after the Adler-32 trailer ignored; FDICT and CINFO > 7 rejected).  A distance
+ * is checked against the start of the output and the 32 KiB limit only, not against a smaller window the header declares.
+ * Output positions are int32: n and out_cap must be below 2^31 (RHCCQ_E_LIMIT otherwise).  The workspace is not sized by the
+ * call: the caller passes one of at least rhccq_zlib_inflate_sizes bytes. */
+#define RHCCQ_ZS_OK 0
+#define RHCCQ_ZS_BAD_HEADER 1   /* zlib header is invalid (check, method, window, preset dictionary) */
+#define RHCCQ_ZS_BAD_DATA 2     /* invalid block type, code lengths, symbol or distance */
+#define RHCCQ_ZS_TRUNCATED 3    /* stream ends early */
+#define RHCCQ_ZS_ADLER 4        /* Adler-32 does not match */
+#define RHCCQ_ZS_CAPACITY 5     /* output is larger than out_cap; *out_len holds the length needed */
+/* host only: workspace bytes for decoding n compressed bytes into at most out_cap bytes */
+int rhccq_zlib_inflate_sizes(int64_t n, int64_t out_cap, int64_t* workspace_bytes);
+/* async on the context stream; *out_len (device int64): decoded length, or the length needed when *status is
+   RHCCQ_ZS_CAPACITY; *status (device int32): RHCCQ_ZS_* */
+int rhccq_zlib_decompress(rhccq_ctx* ctx, const uint8_t* in, int64_t n, void* workspace,
+                          uint8_t* out, int64_t out_cap, int64_t* out_len, int32_t* status);
+/* async: after rhccq_zlib_decompress with the same n, out_cap and workspace, stats (device int64[4]) receives the number of
+   candidate block starts, candidates whose speculative decode failed, chained workers, and blocks on the chain */
+int rhccq_zlib_inflate_stats(rhccq_ctx* ctx, int64_t n, int64_t out_cap, const void* workspace, int64_t* stats);
+/* the same decoder functions run serially on the host (tests; no GPU needed) */
+int rhccq_zlib_decompress_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t out_cap,
+                               int64_t* out_len, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,10 @@ PROTOTYPES = {
     "rhccq_luma_qstep": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
     "rhccq_zlib_sizes": (c_int32, [c_int64, C.POINTER(c_int64), C.POINTER(c_int64)]),
     "rhccq_zlib_compress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_zlib_inflate_sizes": (c_int32, [c_int64, c_int64, C.POINTER(c_int64)]),
+    "rhccq_zlib_decompress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_zlib_inflate_stats": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "rhccq_zlib_decompress_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, C.POINTER(c_int64), C.POINTER(c_int32)]),
 }
 
 

@@ -3,14 +3,18 @@ lossless_compress_optimized + save_compressed (compression.py:119-142,151-220), 
 the device encoder (csrc/zlib_deflate.hip) instead of zlib.compress(level=9) on one host core.
 
 The files are format-compatible, not byte-identical: load_compressed / lossless_decompress read them unchanged, but
-the zlib streams differ from zlib's own.  The host path (api.compression) is the one for byte-identical files.  There
-is no CPU fallback: without a GPU these functions raise like Rhccq(0) does."""
+the zlib streams differ from zlib's own.  The host path (api.compression) is the one for byte-identical files.  The read
+side (load_compressed_device, lossless_decompress_device, read_frame) inflates every layer with the device decoder
+(csrc/zlib_inflate.hip) and leaves the index map on the device.  There is no CPU fallback: without a GPU these functions
+raise like Rhccq(0) does."""
+import io
 import pickle
 import struct
 
 import numpy as np
 import torch
 
+from .api.uncompression import _SafeUnpickler
 from .ops import RhccqError, default_context
 from .segment import IndexList, as_index_array
 
@@ -84,3 +88,53 @@ def write_frame(result, filename, rh=None):
         raise RhccqError("write_frame: a FrameEncoder result (palette, indices, shape) is required")
     pkg = lossless_compress_device(result["palette"], result["indices"], result["shape"], rh)
     return save_compressed_device(pkg, filename, rh)
+
+
+def load_compressed_device(path, rh=None):
+    """load_compressed with the outer zlib layer inflated on the device: the framing is read on the host, the pickle comes
+    back through page-locked memory and is parsed by the same allow-list unpickler.  Returns the same dict."""
+    rh = rh or default_context()
+    with open(path, "rb") as f:
+        if f.read(5) != b"RHCCQ":
+            raise ValueError("Invalid file format")
+        size = struct.unpack("<I", f.read(4))[0]
+        body = f.read(size)
+    raw = rh.to_host(rh.zlib_decompress(body)).tobytes()
+    return _SafeUnpickler(io.BytesIO(raw)).load()
+
+
+_DTYPES = {"uint8": (1, torch.uint8), "uint16": (2, torch.int16), "uint32": (4, torch.int32)}
+
+
+def lossless_decompress_device(pkg, rh=None):
+    """lossless_decompress with "p" and "i" inflated on the device -> (palette uint8[l, 3] device, indices device tensor in
+    the map's dtype -- uint8, int16 holding uint16, int32 holding uint32 -- flat, shape)"""
+    rh = rh or default_context()
+    h, w = pkg["s"]
+    n_pal = int(pkg["l"])
+    pal = rh.zlib_decompress(pkg["p"])
+    if pal.numel() < 3 * n_pal:
+        raise RhccqError(f"palette stream of {pal.numel()} bytes, {3 * n_pal} needed for {n_pal} colours")
+    raw = rh.zlib_decompress(pkg["i"])
+    name = pkg.get("d", "uint16")
+    if name not in _DTYPES:                     # decompress_indices_simple's rule for an unknown dtype name
+        bpp = raw.numel() / (h * w) if h * w > 0 else 2
+        name = "uint8" if bpp <= 1 else "uint16" if bpp <= 2 else "uint32"
+    eb, dt = _DTYPES[name]
+    if raw.numel() != h * w * eb:
+        raise RhccqError(f"index stream of {raw.numel()} bytes, {h * w * eb} expected for a {h}x{w} {name} map")
+    return pal[:3 * n_pal].reshape(n_pal, 3), raw.view(dt), (h, w)
+
+
+def read_frame(path, rh=None):
+    """a .rhccq file -> {"image": uint8[H, W, 3] device, "palette", "indices", "shape", "dtype"} with every zlib layer
+    inflated and the palette gather done on the device (rhccq_decode: an index past the palette reads entry 0, as
+    decompress_color_quantization does)"""
+    rh = rh or default_context()
+    pkg = load_compressed_device(path, rh)
+    pal, idx, (h, w) = lossless_decompress_device(pkg, rh)
+    name = {torch.uint8: "uint8", torch.int16: "uint16", torch.int32: "uint32"}[idx.dtype]
+    if pal.shape[0] == 0:
+        raise RhccqError("read_frame: empty palette")
+    img = rh.decode(idx, pal).reshape(h, w, 3)
+    return {"image": img, "palette": pal, "indices": idx, "shape": (h, w), "dtype": name}

@@ -1274,6 +1274,77 @@ class Rhccq:
         n = int(length.item())
         return self.to_host(out[:n]).tobytes()
 
+    # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
+    ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
+    _ZS_MSG = {1: "incorrect header check", 2: "invalid block type, code lengths, symbol or distance",
+               3: "incomplete or truncated stream", 4: "incorrect data check"}
+
+    def zlib_inflate_sizes(self, n, out_cap):
+        """-> workspace bytes for decoding n compressed bytes into at most out_cap bytes (host only)"""
+        ws = C.c_int64()
+        rc = self._raw.rhccq_zlib_inflate_sizes(int(n), int(out_cap), C.byref(ws))
+        if rc:
+            raise RhccqError(f"rhccq_zlib_inflate_sizes({n}, {out_cap}) failed ({rc})")
+        return ws.value
+
+    def _zbuf(self, buf):
+        """bytes-like or uint8 device tensor -> contiguous uint8 device tensor"""
+        if isinstance(buf, torch.Tensor):
+            if not buf.is_cuda or buf.dtype != torch.uint8:
+                raise RhccqError("zlib_decompress: a uint8 device tensor or a bytes-like object is required")
+            return buf.reshape(-1).contiguous()
+        return self.dev(np.frombuffer(bytes(buf), dtype=np.uint8))
+
+    def zlib_decompress_async(self, buf, out_cap, out=None, workspace=None):
+        """zlib stream (bytes-like or uint8 device tensor) -> (uint8 device out, int64 device length, int32 device status):
+        the decoded bytes are out[:length] when status is ZS_OK; on ZS_CAPACITY length is the size needed.  Nothing waits
+        for the device.  out / workspace: caller-owned uint8 device buffers (default: allocated at out_cap and
+        zlib_inflate_sizes)."""
+        src = self._zbuf(buf)
+        n, cap = src.numel(), int(out_cap)
+        ws = self.zlib_inflate_sizes(n, cap)
+        work = self.empty((max(ws, 1),), torch.uint8) if workspace is None else workspace
+        if work.numel() < ws:
+            raise RhccqError(f"zlib_decompress: workspace of {work.numel()} bytes, {ws} needed")
+        out = self.empty((max(cap, 1),), torch.uint8) if out is None else out
+        if out.numel() < cap:
+            raise RhccqError(f"zlib_decompress: out of {out.numel()} bytes, out_cap {cap}")
+        length = self.empty((1,), torch.int64)
+        status = self.empty((1,), torch.int32)
+        self._check(self.lib.rhccq_zlib_decompress(self.ctx, self._p(src), n, self._p(work), self._p(out), cap, self._p(length),
+                                                   self._p(status)), "zlib_decompress")
+        self.__dict__["_zlast"] = (n, cap, work)
+        return out, length, status
+
+    def zlib_inflate_stats(self):
+        """after zlib_decompress(_async): (candidates, candidates whose decode failed, chained workers, blocks on the chain)"""
+        n, cap, work = self._zlast
+        st = self.empty((4,), torch.int64)
+        self._check(self.lib.rhccq_zlib_inflate_stats(self.ctx, n, cap, self._p(work), self._p(st)), "zlib_inflate_stats")
+        return tuple(int(v) for v in self.to_host(st))
+
+    def zlib_decompress(self, buf, out_cap=None):
+        """zlib.decompress on the device: -> uint8 device tensor of the exact decoded length.  A bad stream raises RhccqError
+        with zlib's wording.  Without out_cap the first try is sized from the input, and a stream that decodes to more is
+        decoded once more at the length it reported."""
+        src = self._zbuf(buf)
+        cap = int(out_cap) if out_cap is not None else min(4 * src.numel() + 65536, (1 << 31) - 1)
+        for attempt in range(2):
+            out, length, status = self.zlib_decompress_async(src, cap)
+            ln, st = (int(v[0]) for v in self.to_host(length, status))
+            if st == self.ZS_CAPACITY and out_cap is None and attempt == 0:
+                if ln > (1 << 31) - 1:
+                    raise RhccqError(f"Error -3 while decompressing data: output of {ln} bytes is beyond the 2 GiB limit")
+                cap = ln
+                continue
+            break
+        if st == self.ZS_CAPACITY:
+            raise RhccqError(f"Error -5 while decompressing data: output of {ln} bytes exceeds out_cap {cap}")
+        if st != self.ZS_OK:
+            code = -5 if st == self.ZS_TRUNCATED else -3
+            raise RhccqError(f"Error {code} while decompressing data: {self._ZS_MSG.get(st, f'status {st}')}")
+        return out[:ln]
+
     def sync(self):
         self._check(self.lib.rhccq_sync(self.ctx), "sync")
 
