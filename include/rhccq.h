@@ -579,7 +579,8 @@ int rhccq_luma_qstep(rhccq_ctx* ctx, const uint8_t* rgb, const uint8_t* roi_mask
                      int32_t block, float q_roi, float q_bg, float* luma_out, float* qstep_out);
 
 /* ---- EXTENSION: zlib stream (RFC 1950 / 1951) on the device, for the .rhccq container layers --------------------
- * Format-compatible with zlib's inflate (zlib.decompress reads it), not byte-identical to zlib.compress(level=9);
+ * Format-compatible with zlib's inflate (zlib.decompress reads it), not byte-identical to zlib.compress(level=9)
+ * (rhccq_zlib9_compress below is);
  * the output bytes are a function of the input bytes alone (not of the stream, earlier calls or the workspace's
  * contents).  Each DEFLATE block takes the cheapest of dynamic, fixed and stored, so *out_len <= out_bound. */
 /* host only: workspace and worst-case output size for n input bytes */
@@ -610,6 +611,20 @@ int rhccq_zlib_inflate_stats(rhccq_ctx* ctx, int64_t n, int64_t out_cap, const v
 /* the same decoder functions run serially on the host (tests; no GPU needed) */
 int rhccq_zlib_decompress_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t out_cap,
                                int64_t* out_len, int32_t* status);
+
+/* ---- EXTENSION: zlib level 9, byte for byte, on the device (csrc/zlib_deflate9.hip) ---------------------------------
+ * The output is exactly zlib 1.2.11's compress(data, 9) (windowBits 15, memLevel 8, default strategy), a function of the
+ * input bytes alone.  n must be below 2^31 (RHCCQ_E_LIMIT); null pointers, n < 0 and out_cap below the bound: RHCCQ_E_ARG. */
+/* host only: workspace and output bound (>= zlib's compressBound(n)) for n input bytes */
+int rhccq_zlib9_sizes(int64_t n, int64_t* workspace_bytes, int64_t* out_bound);
+/* async on the context stream; *out_len (device int64) receives the length */
+int rhccq_zlib9_compress(rhccq_ctx* ctx, const void* in, int64_t n, void* workspace,
+                         uint8_t* out, int64_t out_cap, int64_t* out_len);
+/* the same functions run serially on the host (tests; no GPU needed) */
+int rhccq_zlib9_compress_host(const void* in, int64_t n, uint8_t* out, int64_t out_cap, int64_t* out_len);
+/* async: after rhccq_zlib9_compress with the same n and workspace, stats (device int64[6]) receives candidates examined,
+   parse nodes, pointer-jumping rounds (max over segments), and stored / fixed / dynamic blocks */
+int rhccq_zlib9_stats(rhccq_ctx* ctx, int64_t n, const void* workspace, int64_t* stats);
 
 #ifdef __cplusplus
 }

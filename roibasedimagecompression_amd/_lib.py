@@ -150,6 +150,10 @@ PROTOTYPES = {
     "rhccq_zlib_decompress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rhccq_zlib_inflate_stats": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "rhccq_zlib_decompress_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, C.POINTER(c_int64), C.POINTER(c_int32)]),
+    "rhccq_zlib9_sizes": (c_int32, [c_int64, C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rhccq_zlib9_compress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_zlib9_compress_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_zlib9_stats": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

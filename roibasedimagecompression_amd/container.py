@@ -3,7 +3,8 @@ lossless_compress_optimized + save_compressed (compression.py:119-142,151-220), 
 the device encoder (csrc/zlib_deflate.hip) instead of zlib.compress(level=9) on one host core.
 
 The files are format-compatible, not byte-identical: load_compressed / lossless_decompress read them unchanged, but
-the zlib streams differ from zlib's own.  The host path (api.compression) is the one for byte-identical files.  The read
+the zlib streams differ from zlib's own.  With exact=True every layer goes through the level-9 encoder of
+csrc/zlib_deflate9.hip instead, and the file is byte-identical to the host path's (api.compression).  The read
 side (load_compressed_device, lossless_decompress_device, read_frame) inflates every layer with the device decoder
 (csrc/zlib_inflate.hip) and leaves the index map on the device.  There is no CPU fallback: without a GPU these functions
 raise like Rhccq(0) does."""
@@ -60,21 +61,24 @@ def narrow_indices(indices, rh=None):
     return t.view(torch.uint8), "uint32"
 
 
-def lossless_compress_device(palette, indices, shape, rh=None):
+def lossless_compress_device(palette, indices, shape, rh=None, exact=False):
     """lossless_compress_optimized with the device encoder: the same dict (s, l, p, i, d); "i" and "p" decompress to
-    exactly the bytes the host function compresses"""
+    exactly the bytes the host function compresses.  exact=True: "p" and "i" are also byte-identical to the host's
+    (the level-9 encoder of csrc/zlib_deflate9.hip); the shape is kept as given, as the host function keeps it"""
     rh = rh or default_context()
     pal = np.array(palette, dtype=np.uint8)
     idx, name = narrow_indices(indices, rh)
-    return {"s": shape, "l": len(palette), "p": rh.zlib_compress(rh.dev(pal.reshape(-1))), "i": rh.zlib_compress(idx), "d": name}
+    return {"s": shape, "l": len(palette), "p": rh.zlib_compress(rh.dev(pal.reshape(-1)), exact=exact),
+            "i": rh.zlib_compress(idx, exact=exact), "d": name}
 
 
-def save_compressed_device(compressed_data, filename, rh=None):
+def save_compressed_device(compressed_data, filename, rh=None, exact=False):
     """save_compressed with the outer zlib layer on the device: b"RHCCQ", <I length, zlib of the protocol-5 pickle;
-    returns what save_compressed returns (the body's length + 8)"""
+    returns what save_compressed returns (the body's length + 8).  exact=True: the file is byte-identical to
+    save_compressed's"""
     rh = rh or default_context()
     raw = np.frombuffer(pickle.dumps(compressed_data, protocol=5), dtype=np.uint8).copy()
-    body = rh.zlib_compress(rh.dev(raw))
+    body = rh.zlib_compress(rh.dev(raw), exact=exact)
     with open(filename, "wb") as f:
         f.write(b"RHCCQ")
         f.write(struct.pack("<I", len(body)))
@@ -82,12 +86,14 @@ def save_compressed_device(compressed_data, filename, rh=None):
     return len(body) + 8
 
 
-def write_frame(result, filename, rh=None):
-    """the result dict of FrameEncoder.encode / encode_native straight to a .rhccq file; returns save_compressed's value"""
+def write_frame(result, filename, rh=None, exact=False):
+    """the result dict of FrameEncoder.encode / encode_native straight to a .rhccq file; returns save_compressed's value.
+    exact=True: every layer through the level-9 encoder, so the file is byte-identical to
+    save_compressed(lossless_compress_optimized(palette, indices, shape), filename)"""
     if "palette" not in result or "indices" not in result or "shape" not in result:
         raise RhccqError("write_frame: a FrameEncoder result (palette, indices, shape) is required")
-    pkg = lossless_compress_device(result["palette"], result["indices"], result["shape"], rh)
-    return save_compressed_device(pkg, filename, rh)
+    pkg = lossless_compress_device(result["palette"], result["indices"], result["shape"], rh, exact=exact)
+    return save_compressed_device(pkg, filename, rh, exact=exact)
 
 
 def load_compressed_device(path, rh=None):

@@ -1242,35 +1242,46 @@ class Rhccq:
         return coef, q
 
     # -- zlib (csrc/zlib_deflate.hip) -------------------------------------------------------------
-    def zlib_sizes(self, n):
-        """-> (workspace bytes, worst-case output bytes) of a zlib stream of n input bytes (host only)"""
+    def zlib_sizes(self, n, exact=False):
+        """-> (workspace bytes, worst-case output bytes) of a zlib stream of n input bytes (host only); exact=True: of the
+        byte-exact level-9 encoder (csrc/zlib_deflate9.hip)"""
         ws, bound = C.c_int64(), C.c_int64()
-        rc = self._raw.rhccq_zlib_sizes(int(n), C.byref(ws), C.byref(bound))
+        fn = self._raw.rhccq_zlib9_sizes if exact else self._raw.rhccq_zlib_sizes
+        rc = fn(int(n), C.byref(ws), C.byref(bound))
         if rc:
-            raise RhccqError(f"rhccq_zlib_sizes({n}) failed ({rc})")
+            raise RhccqError(f"rhccq_zlib{'9' if exact else ''}_sizes({n}) failed ({rc})")
         return ws.value, bound.value
 
-    def zlib_compress_async(self, t, out=None, workspace=None):
+    def zlib_compress_async(self, t, out=None, workspace=None, exact=False):
         """contiguous device tensor (its raw bytes) -> (uint8 device buffer, int64 device length): the zlib stream is
         out[:length]; nothing waits for the device.  out / workspace: caller-owned uint8 device buffers (default: allocated
-        at the sizes rhccq_zlib_sizes gives; an out smaller than the bound is refused)"""
+        at the sizes rhccq_zlib_sizes gives; an out smaller than the bound is refused).  exact=True: the stream is byte for
+        byte zlib.compress(data, 9) (rhccq_zlib9_compress)"""
         if not t.is_cuda or not t.is_contiguous():
             raise RhccqError("zlib_compress: a contiguous device tensor is required")
         n = t.numel() * t.element_size()
-        ws, bound = self.zlib_sizes(n)
+        ws, bound = self.zlib_sizes(n, exact)
         work = self.empty((max(ws, 1),), torch.uint8) if workspace is None else workspace
         if work.numel() < ws:
             raise RhccqError(f"zlib_compress: workspace of {work.numel()} bytes, {ws} needed")
         out = self.empty((bound,), torch.uint8) if out is None else out
         length = self.empty((1,), torch.int64)
-        self._check(self.lib.rhccq_zlib_compress(self.ctx, self._p(t), n, self._p(work), self._p(out), out.numel(), self._p(length)),
-                    "zlib_compress")
+        fn = self.lib.rhccq_zlib9_compress if exact else self.lib.rhccq_zlib_compress
+        self._check(fn(self.ctx, self._p(t), n, self._p(work), self._p(out), out.numel(), self._p(length)), "zlib_compress")
         return out, length
 
-    def zlib_compress(self, t):
+    def zlib9_stats(self, n, workspace):
+        """after zlib_compress_async(exact=True) of n bytes with this workspace: (candidates examined, parse nodes, pointer
+        jumping rounds, stored / fixed / dynamic blocks) as a host tuple (waits for the device)"""
+        st = self.empty((6,), torch.int64)
+        self._check(self.lib.rhccq_zlib9_stats(self.ctx, int(n), self._p(workspace), self._p(st)), "zlib9_stats")
+        return tuple(int(v) for v in self.to_host(st))
+
+    def zlib_compress(self, t, exact=False):
         """zlib stream (RFC 1950) of the raw bytes of a contiguous device tensor, as bytes: zlib.decompress() gives
-        them back; format-compatible with zlib.compress, not byte-identical to it"""
-        out, length = self.zlib_compress_async(t)
+        them back; format-compatible with zlib.compress, not byte-identical to it -- unless exact=True, which gives
+        zlib.compress(data, 9) byte for byte"""
+        out, length = self.zlib_compress_async(t, exact=exact)
         n = int(length.item())
         return self.to_host(out[:n]).tobytes()
 
