@@ -18,10 +18,16 @@ A "step" = one pass of the hot path over one batch of synthetic input resident i
   stream  (configs[4]) a stream of 4K frames per GPU through stream.StreamEncoder (batches in flight on host threads
           with their own HIP streams), 16x16 DCT extension, two quality tiers; value = pixels of all ranks / time ("weak").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frame|batch|tiled|stream] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frame|batch|tiled|stream] [--dump-outputs DIR] [--full]
 
 `ms_per_step` of the result line is the wall time of one timed step.  --dump-outputs DIR writes what the last timed step
 returned (see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump, print the result line.  --full
+adds everything else the line can carry, each measured after the timed steps: the per-stage clocks of one more step
+(`stages_ms`), the HBM probe (`roofline_hbm`) and the CPU baseline (`cpu_baseline`, --cpu-sample) in every mode; in frame mode
+with one frame per step at N = 1, unless --no-probes, also the other host side (`other_host`), the chain probe (`roofline`) and
+the upstream, ROI-stage, neighbour-pass and pixel-pass probes.
 
 With --gpus N > 1 and no torch.distributed environment the script starts the N ranks itself (torch.distributed.run on
 127.0.0.1) BEFORE anything touches a GPU, and exits with their code; the driver's own launch line
@@ -59,8 +65,11 @@ def parse():
     ap.add_argument("--quality-bg", type=int, default=None, help="background tier (stream / tiled modes default to 10: rhccq_20_10)")
     ap.add_argument("--sigma", type=float, default=2.0, help="sensor-noise sigma of the synthetic photo")
     ap.add_argument("--block", type=int, default=None, help="DCT extension block (8; 16 in stream mode)")
-    ap.add_argument("--cpu-sample", type=int, default=1280, help="edge of the CPU-baseline crop (0 = skip)")
-    ap.add_argument("--no-probes", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=1280, help="--full: edge of the CPU-baseline crop (0 = skip)")
+    ap.add_argument("--no-probes", action="store_true",
+                    help="--full: skip the other host and the chain, upstream, ROI-stage, neighbour-pass and pixel-pass probes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the stage clocks, the other host, the roofline and upstream probes and the CPU baseline")
     ap.add_argument("--host", choices=["native", "python"], default="native",
                     help="frame mode: host side of the encoder -- rhccq_encode_frame (C++, csrc/encode_frame.hip) or the Python FrameEncoder")
     ap.add_argument("--frames-per-step", type=int, default=None,
@@ -615,10 +624,10 @@ def main():
         dt = time.perf_counter() - t0
         if last:
             dump_outputs(args.dump_outputs, last)          # before the probes below run the path again
-        if rank == 0:
+        if args.full and rank == 0:
             one_step(rh, enc, rgb, specs, roi_mask, block, stage_acc=stages, extra=extra, native=native)
         other_host = None
-        if rank == 0 and B == 1 and world == 1 and not args.no_probes:
+        if args.full and rank == 0 and B == 1 and world == 1 and not args.no_probes:
             # the other host side on the same frame (same kernels, same result): how much of the step is the host language
             for _ in range(2):
                 one_step(rh, enc, rgb, specs, roi_mask, block, native=not native)
@@ -657,6 +666,7 @@ def main():
             line["other_host"] = other_host
         line["final_colours"] = int(len(out["palette"]))
         line["unique_colours_per_segment"] = [int(v) for v in out["n_unique"]]
+    if rank == 0 and args.full:
         probes = not args.no_probes and world == 1 and mode == "frame" and B == 1
         roof = hbm_probe(rh, rgb, specs)                  # per rank: this rank's frame (its tile in tiled mode)
         dom = chain_probe(rh, enc, rgb, specs, dt / args.steps * 1e3) if probes else None
@@ -678,6 +688,7 @@ def main():
             # key; the N = 1 figure of record rides along under a key of its own
             line["cpu_baseline"] = None
             line["cpu_baseline_carried"] = carried_cpu_baseline()
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
