@@ -626,6 +626,41 @@ int rhccq_zlib9_compress_host(const void* in, int64_t n, uint8_t* out, int64_t o
    parse nodes, pointer-jumping rounds (max over segments), and stored / fixed / dynamic blocks */
 int rhccq_zlib9_stats(rhccq_ctx* ctx, int64_t n, const void* workspace, int64_t* stats);
 
+/* ---- EXTENSION: image -> .rhccq in one device-resident flow (api/image.py ImageEncoder) -------------------------------------
+ * Regions are boxes of a frame W wide whose mask is (labels0 or labels1)[y][x] == label.  All calls are async on the context stream;
+ * every table is device memory, block tables (block_item / block_region int32[n_blocks], block_first int32[items]) cover each item
+ * with consecutive workgroups of 256 pixels (split_stats_regions: one workgroup per 32 x 8 tile of the region's box). */
+/* rhccq_split_stats for every region at once: regions int32[n][6] = (y0, x0, h, w, map, label); partial double[n_blocks][12] (row b:
+   tile b - block_first[r] of region r, as rhccq_split_stats numbers the tiles of the crop); hist int32[n][42] (zeroed here) */
+int rhccq_split_stats_regions(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const int32_t* labels0, const int32_t* labels1,
+                              const int32_t* regions, int32_t n_regions, const int32_t* block_region, const int32_t* block_first,
+                              int64_t n_blocks, double* partial, int32_t* hist);
+/* host only: workspace bytes of rhccq_slic_sweeps_regions */
+int64_t rhccq_slic_regions_work_bytes(int32_t n_regions, int32_t max_iter);
+/* the two _slic_cython loops of max_iter sweeps (colour ignored, then used) of every region's small image: img double[][3], mask
+   uint8[], labels int32[] (out) at px_off (a multiple of 256) of regions int32[n][5] = (px_off, H, W, K, seg_off); seg double[][5]
+   (in: the seeded centroids; out: the final ones); steps double[n]; seg_region int32[n_seg]: region of every centroid; max_k: the
+   largest K.  Centroid means are np.bincount's raster-order float64 sums; a region whose sweep labels nothing stops, as _sweeps does. */
+int rhccq_slic_sweeps_regions(rhccq_ctx* ctx, const double* img, const uint8_t* mask, double* seg, const int32_t* regions, const double* steps,
+                              int32_t n_regions, int32_t max_k, const int32_t* block_region, const int32_t* block_first, int64_t n_blocks,
+                              const int32_t* seg_region, int32_t n_seg, int32_t max_iter, void* work, int64_t work_bytes, int32_t* labels);
+/* regions int32[n][11] = (y0, x0, h, w, map, label, small_off, small_w, yx_off, sid_off, layer); a region's SLIC id at (y, x) of its
+   box is small[small_off + yx[yx_off + y] * small_w + yx[yx_off + h + x]] (the nearest-neighbour upscale).
+   seg_counts: counts int32[n_sid] (zeroed here) += the in-mask pixels of every (region, id) at sid_off + id */
+int rhccq_image_seg_counts(rhccq_ctx* ctx, const int32_t* labels0, const int32_t* labels1, int32_t H, int32_t W, const int32_t* regions,
+                           const int32_t* small, const int32_t* yx, const int32_t* block_item, const int32_t* block_first, int64_t n_blocks,
+                           int32_t* counts, int64_t n_sid);
+/* hit int32[n_pairs] (zeroed here): 1 when, for pairs[i] = (r, q), a pixel of both masks holds a segment of q with ids[q's sid] > 0;
+   the block tables cover the intersection of the two boxes */
+int rhccq_image_overlap(rhccq_ctx* ctx, const int32_t* labels0, const int32_t* labels1, int32_t H, int32_t W, const int32_t* regions,
+                        const int32_t* small, const int32_t* yx, const int32_t* ids, const int32_t* pairs, int32_t n_pairs,
+                        const int32_t* block_item, const int32_t* block_first, int64_t n_blocks, int32_t* hit);
+/* layers int32[][H][W] (zeroed by the caller): layers[layer][y0 + y][x0 + x] = ids[sid_off + id] for the in-mask pixels with id > 0 and
+   ids[...] > 0; regions with layer < 0 are skipped */
+int rhccq_image_paint(rhccq_ctx* ctx, const int32_t* labels0, const int32_t* labels1, int32_t H, int32_t W, const int32_t* regions,
+                      const int32_t* small, const int32_t* yx, const int32_t* ids, const int32_t* block_item, const int32_t* block_first,
+                      int64_t n_blocks, int32_t* layers);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,17 @@ PROTOTYPES = {
     "rhccq_zlib9_compress": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_zlib9_compress_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, C.POINTER(c_int64)]),
     "rhccq_zlib9_stats": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_split_stats_regions": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_void_p]),
+    "rhccq_slic_regions_work_bytes": (c_int64, [c_int32, c_int32]),
+    "rhccq_slic_sweeps_regions": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "rhccq_image_seg_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_int64]),
+    "rhccq_image_overlap": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_image_paint": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_void_p]),
 }
 
 

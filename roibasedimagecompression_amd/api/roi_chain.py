@@ -314,7 +314,8 @@ def directional_region_unification(binary_image, border_sensitivity=0.3, min_reg
     return cleaned, (cleaned > 0).astype(np.uint8)
 
 
-def _unify_borders(d, borders_dev, original_image, rgb_dev=None):
+def _unify_borders_dev(d, borders_dev, original_image, rgb_dev=None):
+    """the chain after the border map, left on the device: -> (unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask)"""
     import torch
     m = d.remove_thin(borders_dev, 0.10, 25)
     m = d.remove_small_noise(m, 75)
@@ -329,7 +330,11 @@ def _unify_borders(d, borders_dev, original_image, rgb_dev=None):
     if rgb_dev is None:
         rgb_dev = torch.from_numpy(np.array(original_image, dtype=np.uint8, order="C")).to(d.rh.device)
     ri, ni, m1, m0 = d.rh.roi_buffer(region_dev, rgb_dev, 3)
-    unified, region_map, roi_image, non_image, roi_mask, non_mask = d.rh.to_host(u_dev, region_dev, ri, ni, m1, m0)
+    return u_dev, region_dev, ri, ni, m1, m0
+
+
+def _unify_borders(d, borders_dev, original_image, rgb_dev=None):
+    unified, region_map, roi_image, non_image, roi_mask, non_mask = d.rh.to_host(*_unify_borders_dev(d, borders_dev, original_image, rgb_dev))
     return unified, region_map, roi_image, non_image, roi_mask, non_mask
 
 
@@ -349,6 +354,21 @@ def get_regions(image_rgb):
     values, the smallest non-zero one is 1/9, the threshold a few thousandths: its last bits cannot move the mask)."""
     image_rgb = np.asarray(image_rgb)
     d = _Dev()
+    borders, rgb_dev = _borders_resident(d, image_rgb)
+    return _unify_borders(d, borders, image_rgb, rgb_dev=rgb_dev)
+
+
+def get_regions_resident(image_rgb, rh=None):
+    """get_regions with every result left on the device: -> (unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask,
+    rgb) device tensors, rgb the uploaded uint8[H,W,3] image (api/image.py ImageEncoder)"""
+    image_rgb = np.asarray(image_rgb)
+    d = _Dev(rh)
+    borders, rgb_dev = _borders_resident(d, image_rgb)
+    return _unify_borders_dev(d, borders, image_rgb, rgb_dev=rgb_dev) + (rgb_dev,)
+
+
+def _borders_resident(d, image_rgb):
+    """roi.py:14-33: the border map of get_regions (device) and the uploaded RGB image (None for a gray one)"""
     a, edge = _edges.edge_map_resident(image_rgb, d.rh)
     counts = d.rh.box_count(edge, 3)
     hist = d.rh.masked_hist(edge, counts, 10)
@@ -357,4 +377,4 @@ def get_regions(image_rgb):
     threshold = (float(np.dot(hist, table.astype(np.float64))) / n_edge if n_edge else 0.1) / 100
     above = np.flatnonzero(table > np.float32(threshold))
     borders = d.rh.value_mask(counts, int(above[0]) if len(above) else 10, edge)
-    return _unify_borders(d, borders, image_rgb, rgb_dev=a.rgb if image_rgb.ndim == 3 else None)
+    return borders, (a.rgb if image_rgb.ndim == 3 else None)

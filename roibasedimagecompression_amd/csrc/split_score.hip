@@ -42,13 +42,16 @@ __device__ __forceinline__ double ss_sobel(const double (*p)[kSsLW], int y, int 
   return sqrt((h * h + v * v) / 2.0);
 }
 
-__global__ __launch_bounds__(256) void split_stats_kernel(const uint8_t* __restrict__ rgb, int H, int W, const uint8_t* __restrict__ mask,
-                                                          double* __restrict__ partial, int* __restrict__ hist) {
+// One 32 x 8 tile of an H x W image: px(y, x) -> the pixel's 3 bytes, in_mask(y, x, gray) -> whether it counts.  The tile's 12
+// sums go to partial_out[0..11], its histogram counts are added to hist[0..41].
+template <typename Px, typename InMask>
+__device__ __forceinline__ void split_stats_tile(const Px& px, const InMask& in_mask, int H, int W, int tile, double* __restrict__ partial_out,
+                                                 int* __restrict__ hist) {
   __shared__ SsTile t;
   __shared__ int s_hist[kSsHist];
   __shared__ double s_red[4][kSsSums];
   const int tiles_x = (W + kSsTW - 1) / kSsTW;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+  const int ty = tile / tiles_x, tx = tile % tiles_x;
   const int y0 = ty * kSsTH, x0 = tx * kSsTW;
   if (threadIdx.x < kSsHist) s_hist[threadIdx.x] = 0;
   for (int i = threadIdx.x; i < kSsLW * kSsLH; i += 256) {
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(256) void split_stats_kernel(const uint8_t* __restr
     x = x < 0 ? -x - 1 : (x >= W ? 2 * W - 1 - x : x);
     y = min(max(y, 0), H - 1);                                        // (tiles overhanging the image by more than one pixel)
     x = min(max(x, 0), W - 1);
-    ss_convert(rgb + ((size_t)y * W + x) * 3, t.g[ly][lx], t.L[ly][lx], t.A[ly][lx], t.B[ly][lx]);
+    ss_convert(px(y, x), t.g[ly][lx], t.L[ly][lx], t.A[ly][lx], t.B[ly][lx]);
   }
   __syncthreads();
   const int ly = (threadIdx.x >> 5) + 1, lx = (threadIdx.x & 31) + 1;
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void split_stats_kernel(const uint8_t* __restr
   for (int q = 0; q < kSsSums; ++q) v[q] = 0.0;
   if (y < H && x < W) {
     const double g = t.g[ly][lx];
-    const bool in = mask ? mask[(size_t)y * W + x] != 0 : g > 0.01;
+    const bool in = in_mask(y, x, g);
     if (in) {
       const double L = t.L[ly][lx], A = t.A[ly][lx], B = t.B[ly][lx];
       const double sL = ss_sobel(t.L, ly, lx), sA = ss_sobel(t.A, ly, lx), sB = ss_sobel(t.B, ly, lx), sg = ss_sobel(t.g, ly, lx);
@@ -123,9 +126,33 @@ __global__ __launch_bounds__(256) void split_stats_kernel(const uint8_t* __restr
   __syncthreads();
   if (threadIdx.x < kSsSums) {
     const int q = threadIdx.x;
-    partial[(size_t)blockIdx.x * kSsSums + q] = ((s_red[0][q] + s_red[1][q]) + s_red[2][q]) + s_red[3][q];
+    partial_out[q] = ((s_red[0][q] + s_red[1][q]) + s_red[2][q]) + s_red[3][q];
   }
   if (threadIdx.x < kSsHist && s_hist[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_hist[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void split_stats_kernel(const uint8_t* __restrict__ rgb, int H, int W, const uint8_t* __restrict__ mask,
+                                                          double* __restrict__ partial, int* __restrict__ hist) {
+  split_stats_tile([&](int y, int x) { return rgb + ((size_t)y * W + x) * 3; },
+                   [&](int y, int x, double g) { return mask ? mask[(size_t)y * W + x] != 0 : g > 0.01; }, H, W, blockIdx.x,
+                   partial + (size_t)blockIdx.x * kSsSums, hist);
+}
+
+// All regions of a frame in one launch.  Region r is the box regions[r] = (y0, x0, h, w, map, label) of the frame; its mask is
+// labels_map[y][x] == label over that box, and its image the frame's crop there, so every tile is the tile rhccq_split_stats
+// computes on the crop.  Block b works on tile b - block_first[r] of region r = block_region[b] and writes partial row b;
+// hist[r][42] collects region r's histograms.
+__global__ __launch_bounds__(256) void split_stats_regions_kernel(const uint8_t* __restrict__ rgb, int FW, const int32_t* __restrict__ labels0,
+                                                                  const int32_t* __restrict__ labels1, const int32_t* __restrict__ regions,
+                                                                  const int32_t* __restrict__ block_region, const int32_t* __restrict__ block_first,
+                                                                  double* __restrict__ partial, int* __restrict__ hist) {
+  const int r = block_region[blockIdx.x];
+  const int32_t* reg = regions + (size_t)r * 6;
+  const int ry = reg[0], rx = reg[1], h = reg[2], w = reg[3], lab = reg[5];
+  const int32_t* lm = reg[4] ? labels1 : labels0;
+  split_stats_tile([&](int y, int x) { return rgb + ((size_t)(ry + y) * FW + (rx + x)) * 3; },
+                   [&](int y, int x, double) { return lm[(size_t)(ry + y) * FW + (rx + x)] == lab; }, h, w, blockIdx.x - block_first[r],
+                   partial + (size_t)blockIdx.x * kSsSums, hist + (size_t)r * kSsHist);
 }
 
 }  // namespace rhccq
@@ -146,6 +173,22 @@ int rhccq_split_stats(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, 
   if (n_blocks > 0x7fffffffll) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "split_stats: image too large");
   RHCCQ_HIP(ctx, hipMemsetAsync(hist42, 0, sizeof(int32_t) * kSsHist, ctx->stream));
   hipLaunchKernelGGL(split_stats_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, rgb, H, W, mask, partial, hist42);
+  RHCCQ_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+int rhccq_split_stats_regions(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const int32_t* labels0, const int32_t* labels1,
+                              const int32_t* regions, int32_t n_regions, const int32_t* block_region, const int32_t* block_first, int64_t n_blocks,
+                              double* partial, int32_t* hist) {
+  if (!ctx || !rgb || !labels0 || !labels1 || !regions || !block_region || !block_first || !partial || !hist || H <= 0 || W <= 0 || n_regions < 0 ||
+      n_blocks < 0)
+    return rhccq_fail(ctx, RHCCQ_E_ARG, "split_stats_regions: bad argument");
+  if (n_blocks > 0x7fffffffll) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "split_stats_regions: too many tiles");
+  if (n_regions == 0) return 0;
+  RHCCQ_HIP(ctx, hipMemsetAsync(hist, 0, sizeof(int32_t) * kSsHist * (size_t)n_regions, ctx->stream));
+  if (n_blocks == 0) return 0;
+  hipLaunchKernelGGL(split_stats_regions_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, rgb, W, labels0, labels1, regions, block_region,
+                     block_first, partial, hist);
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
 }

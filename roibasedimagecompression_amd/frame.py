@@ -307,13 +307,17 @@ class FrameEncoder:
         self._t("merge1", t0)
         return per_class
 
-    def level2_jobs(self, S, per_class):
-        """merge per class on the frame canvas (regions.py:34-46) -> one clustering job per class."""
+    def level2_jobs(self, S, per_class, groups=None):
+        """merge per class on the frame canvas (regions.py:34-46) -> one clustering job per class.
+        groups: [(quality, [(class, region), ...]), ...] merges the listed region components, in that order, as one call of
+        region_quantization each instead (several ClassSpec layers of one call; api/image.py)."""
         H, W = S["H"], S["W"]
+        if groups is None:
+            groups = [(cls.quality, [(ci, r) for r in range(len(per_class[ci]))]) for ci, cls in enumerate(S["classes"])]
         lvl2, q2s = [], []
-        for ci, cls in enumerate(S["classes"]):
-            regs = [r for r in per_class[ci] if r is not None]
-            q2 = min(cls.quality * 2, 100)
+        for ci, (quality, members) in enumerate(groups):
+            regs = [per_class[c][r] for c, r in members if per_class[c][r] is not None]
+            q2 = min(quality * 2, 100)
             q2s.append(q2)
             if not regs:
                 continue                                                                  # rhccq.ipynb:1009-1013

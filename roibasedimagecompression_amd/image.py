@@ -1,0 +1,430 @@
+"""Image -> .rhccq in one device-resident flow: ImageEncoder.encode computes what flow.script_flow computes (encoder/compression/
+test.py:77-151: get_regions, extract_regions, subregion_quantization per class, region_quantization per class, quantize_image),
+bit for bit, without the host round trips of the reference-shaped functions.
+
+  regions      the resident get_regions chain stops at the device masks; both are labelled on the device (Rhccq.ccl) and only the
+               stats tables come back.  A region is (call, label map, label, bbox): no RegionDict, no bbox_mask.
+  split score  every region's masked statistics in ONE launch (rhccq_split_stats_regions, the tiles rhccq_split_stats uses on the
+               crop), one read-back; scores_from_stats / normalize_result on the host as before.
+  SLIC         the resizes on the device (the gauss1d / zoom kernels of api/slic.py); the <= 500 x 500 images and masks come back in
+               one copy, the Lab image, its sigma-1 Gaussian and the centroid seeding stay the host code of slic_masked; the 2 x 10 sweeps
+               of all regions run with no read-back (rhccq_slic_sweeps_regions); the labels come back in one copy for the
+               connectivity pass (host) and go up again in one copy.
+  layers       the upscale is never materialised: per-(region, SLIC id) in-mask counts (drop test included), the overlap test that
+               places a region in its layer, and the painting of the int32 layers are three launches (csrc/image_flow.hip).
+  levels       FrameEncoder.prepare / level1 over all layers, level 2 per call (FrameEncoder.level2_jobs groups), level 3, remap.
+The ROI and SLIC stages are the same parity-unpinned restatements script_flow runs."""
+import ctypes as C
+import math
+import time
+
+import numpy as np
+import torch
+
+from .api import roi_chain
+from .api.roi import min_region_size
+from .api.slic import _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
+from .api.split_score import normalize_result, scores_from_stats
+from .frame import ClassSpec, FrameEncoder
+from .ops import default_context
+from .palette import cluster_palettes
+
+__all__ = ["ImageEncoder", "Region"]
+
+_SLIC_SWEEPS = 10          # slic_masked's max_num_iter
+_COMPACTNESS = 10.0        # enhanced_slic_with_texture's compactness
+
+
+class Region:
+    """One region of extract_regions: call 0 = ROI / 1 = non-ROI list, map 0 = ROI / 1 = non-ROI label map, its label there and
+    its bbox (minr, minc, maxr, maxc)"""
+    __slots__ = ("call", "map", "label", "bbox", "area")
+
+    def __init__(self, call, map_, label, bbox, area):
+        self.call, self.map, self.label, self.bbox, self.area = call, map_, label, bbox, area
+
+    @property
+    def hw(self):
+        return self.bbox[2] - self.bbox[0], self.bbox[3] - self.bbox[1]
+
+
+def _block_tables(sizes, per_block=256):
+    """consecutive workgroups over items of `sizes` units: (block_item, block_first) int32"""
+    nb = (np.asarray(sizes, np.int64) + per_block - 1) // per_block
+    first = np.concatenate([[0], np.cumsum(nb)[:-1]]).astype(np.int32)
+    return np.repeat(np.arange(len(nb), dtype=np.int32), nb), first
+
+
+def overlap_candidates(regions, painted):
+    """pairs (i, j), j < i, of regions of one call, of different label maps, with intersecting boxes and region j painting some
+    pixel (painted[j]): the only pairs whose pixels can meet (regions of one map are disjoint).  In extract_regions' lists these are
+    the small ROI regions at the end of the non-ROI list against the non-ROI regions before them."""
+    if not regions:
+        return []
+    call = np.array([r.call for r in regions])
+    map_ = np.array([r.map for r in regions])
+    bb = np.array([r.bbox for r in regions], np.int64).reshape(-1, 4)
+    painted = np.asarray(painted, bool)
+    pairs = []
+    for i in np.nonzero(map_ != call)[0]:                  # a region listed in the other map's call
+        j = np.arange(i)
+        ok = (call[j] == call[i]) & (map_[j] != map_[i]) & painted[j]
+        ok &= (np.maximum(bb[j, 0], bb[i, 0]) < np.minimum(bb[j, 2], bb[i, 2])) & (np.maximum(bb[j, 1], bb[i, 1]) < np.minimum(bb[j, 3], bb[i, 3]))
+        pairs += [(int(i), int(q)) for q in j[ok]]
+    return pairs
+
+
+def place_layers(regions, kept, hit):
+    """subregion_quantization's layer placement: per call, in list order, a region goes to the first layer none of whose painted
+    pixels lie in its mask (hit[(i, j)]: region i's mask meets region j's painted pixels), else to a new layer; layers that end
+    up with no segment are dropped.  kept[i]: region i's kept SLIC ids, ascending.
+    -> ([(call, {"members", "bboxes", "seg_region", "segments": [(region, id)] in id order})], per region (layer, local index) or
+    (-1, -1))"""
+    out, place = [], [(-1, -1)] * len(regions)
+    for call in (0, 1):
+        layers = []
+        for i, r in enumerate(regions):
+            if r.call != call:
+                continue
+            layer = next((l for l in layers if not any(hit.get((i, j), False) for j in l["members"])), None)
+            if layer is None:
+                layer = {"members": [], "bboxes": [], "seg_region": [], "segments": []}
+                layers.append(layer)
+            local = len(layer["members"])
+            layer["members"].append(i)
+            layer["bboxes"].append(r.bbox)
+            for s in kept[i]:
+                layer["segments"].append((i, s))
+                layer["seg_region"].append(local)
+        for l in layers:
+            if l["segments"]:
+                for local, i in enumerate(l["members"]):
+                    place[i] = (len(out), local)
+                out.append((call, l))
+    return out, place
+
+
+def _pack_bits(mask_u8):
+    """device uint8 0 / 1 [n] -> uint8[ceil(n / 8)], bit i % 8 of byte i / 8 (np.unpackbits(bitorder="little") order)"""
+    n = mask_u8.numel()
+    padded = torch.zeros(((n + 7) // 8) * 8, dtype=torch.int32, device=mask_u8.device)
+    padded[:n] = mask_u8
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=mask_u8.device)
+    return (padded.view(-1, 8) * weights).sum(dim=1).to(torch.uint8)
+
+
+class ImageEncoder:
+    def __init__(self, rh=None):
+        self.rh = rh or default_context()
+
+    # ---- stage 1 ---------------------------------------------------------------------------------------------------------------
+    def regions(self, image):
+        """get_regions + extract_regions on the device -> (regions [Region] in the order of the ROI list then the non-ROI list,
+        label maps (ROI, non-ROI) device int32[H,W], uploaded RGB, stats)"""
+        rh = self.rh
+        unified, region_map, _, _, roi_mask, non_mask, rgb = roi_chain.get_regions_resident(image, rh)
+        frac = rh.to_host(torch.stack([region_map.sum(dtype=torch.int64), (unified != 0).sum(dtype=torch.int64)]))
+        n1, lab1, st1 = rh.ccl(roi_mask, 8)
+        n0, lab0, st0 = rh.ccl(non_mask, 8)
+        mn = min_region_size(image)
+
+        def listed(call, map_, n, st):
+            out = []
+            for lab in range(1, n + 1):
+                x, y, w, h, area = (int(v) for v in st[lab])
+                out.append(Region(call, map_, lab, (y, x, y + h, x + w), area))
+            return out
+        roi, non = listed(0, 0, n1, st1), listed(1, 1, n0, st0)
+        small = [r for r in roi if r.area < mn]                    # roi.py:76-84: small ROI regions go to the end of the non-ROI list
+        for r in small:
+            r.call = 1
+        non += small
+        roi = [r for r in roi if r.area >= mn]
+        hw = image.shape[0] * image.shape[1]
+        stats = {"region_map_roi_fraction": float(frac[0]) / hw, "edge_fraction": float(frac[1]) / hw,
+                 "roi_regions": len(roi), "nonroi_regions": len(non)}
+        return roi + non, (lab1, lab0), rgb, stats
+
+    # ---- stage 2 ---------------------------------------------------------------------------------------------------------------
+    def split_stats(self, rgb, maps, regions):
+        """Rhccq.split_stats of every region's crop and mask in one launch and one read-back -> [(sums, lbp_hist, gray_hist)]"""
+        rh = self.rh
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        if not regions:
+            return []
+        table = np.array([[r.bbox[0], r.bbox[1], r.hw[0], r.hw[1], r.map, r.label] for r in regions], np.int32)
+        nb = np.array([rh.lib.rhccq_split_stats_blocks(int(h), int(w)) for h, w in table[:, 2:4]], np.int64)
+        first = np.concatenate([[0], np.cumsum(nb)[:-1]]).astype(np.int32)
+        item = np.repeat(np.arange(len(nb), dtype=np.int32), nb)
+        part = rh.empty((int(nb.sum()), 12), torch.float64)
+        hist = rh.empty((len(regions), 42), torch.int32)
+        d_t, d_i, d_f = rh.dev(table), rh.dev(item), rh.dev(first)
+        rh._check(rh.lib.rhccq_split_stats_regions(rh.ctx, rh._p(rgb), H, W, rh._p(maps[0]), rh._p(maps[1]), rh._p(d_t), len(regions), rh._p(d_i),
+                                                   rh._p(d_f), int(nb.sum()), rh._p(part), rh._p(hist)), "split_stats_regions")
+        part_h, hist_h = rh.to_host(part, hist)
+        hist_h = hist_h.astype(np.int64)
+        return [(part_h[first[k]:first[k] + nb[k]].sum(axis=0), hist_h[k, :10], hist_h[k, 10:]) for k in range(len(regions))]
+
+    def split_segments(self, rgb, maps, regions):
+        """_reference_segmenter's segment count of every region"""
+        overall = np.zeros(len(regions))
+        scored = [i for i, r in enumerate(regions) if r.area >= 100]   # split_score.py:25-27
+        for i, (sums, lbp, gray) in zip(scored, self.split_stats(rgb, maps, [regions[i] for i in scored])):
+            if sums[0] >= 100:
+                overall[i] = scores_from_stats(sums, lbp, gray)[0]
+        out = []
+        for i, r in enumerate(regions):
+            size = r.hw[0] * r.hw[1] * 3
+            window = math.ceil(math.ceil(math.log(size, 10)) * math.log(size))
+            optimal = math.ceil(normalize_result(overall[i], window))
+            out.append(optimal if optimal > 0 else 1)
+        return out
+
+    # ---- stage 3 ---------------------------------------------------------------------------------------------------------------
+    def _resize_linear(self, crop_u8, lo, hi, oh, ow):
+        """api/slic.py _resize(order 1, anti_aliasing) of a device uint8[h,w,3] crop, device float64 out"""
+        rh = self.rh
+        H, W = int(crop_u8.shape[0]), int(crop_u8.shape[1])
+        work = crop_u8.to(torch.float64)
+        keep = []
+        for axis, (n_in, n_out) in enumerate(((H, oh), (W, ow))):
+            sigma = max(0.0, (n_in / n_out - 1) / 2)
+            if sigma <= 1e-15:
+                continue
+            radius = int(4.0 * sigma + 0.5)
+            outer, length, inner = (1, H, W * 3) if axis == 0 else (H, W, 3)
+            nxt = torch.empty_like(work)
+            d_w = rh.dev(_gaussian_weights(sigma, radius))
+            rh._check(rh.lib.rhccq_gauss1d_f64(rh.ctx, rh._p(work), outer, length, inner, rh._p(d_w), radius, rh._p(nxt)), "gauss1d_f64")
+            keep += [work, d_w]
+            work = nxt
+        cy, cx = _zoom_coordinates(H, oh), _zoom_coordinates(W, ow)
+        y0, x0 = np.floor(cy).astype(np.int64), np.floor(cx).astype(np.int64)
+        ty, tx = cy - np.floor(cy), cx - np.floor(cx)
+        yi = np.stack([_mirror_index(y0, H), _mirror_index(y0 + 1, H)]).astype(np.int32)
+        xi = np.stack([_mirror_index(x0, W), _mirror_index(x0 + 1, W)]).astype(np.int32)
+        wy, wx = np.stack([1 - ty, ty]), np.stack([1 - tx, tx])
+        out = rh.empty((oh, ow, 3), torch.float64)
+        d_yi, d_wy, d_xi, d_wx = rh.dev(yi), rh.dev(wy), rh.dev(xi), rh.dev(wx)
+        rh._check(rh.lib.rhccq_zoom_linear_f64(rh.ctx, rh._p(work), H, W, 3, rh._p(d_yi), rh._p(d_wy), rh._p(d_xi), rh._p(d_wx), oh, ow,
+                                               float(lo), float(hi), rh._p(out)), "zoom_linear_f64")
+        keep += [work, d_yi, d_wy, d_xi, d_wx]
+        return out, keep
+
+    @staticmethod
+    def _nearest_tables(n_in, n_out):
+        return _mirror_index(np.floor(_zoom_coordinates(n_in, n_out) + 0.5).astype(np.int64), n_in).astype(np.int32)
+
+    def _resize_mask(self, mask_u8, oh, ow):
+        rh = self.rh
+        H, W = int(mask_u8.shape[0]), int(mask_u8.shape[1])
+        d_yi, d_xi = rh.dev(self._nearest_tables(H, oh)), rh.dev(self._nearest_tables(W, ow))
+        out = rh.empty((oh, ow), torch.uint8)
+        rh._check(rh.lib.rhccq_zoom_nearest(rh.ctx, rh._p(mask_u8), 1, H, W, 1, rh._p(d_yi), rh._p(d_xi), oh, ow, rh._p(out)), "zoom_nearest")
+        return out, [mask_u8, d_yi, d_xi]
+
+    def slic(self, image, rgb, maps, regions, n_segments):
+        """enhanced_slic_with_texture of every region -> per region (small connected labels int32[nh,nw] host, (nh, nw))"""
+        from scipy import ndimage as ndi
+        rh = self.rh
+        smalls, masks, sizes, keep = [], [], [], []
+        for r, n in zip(regions, n_segments):
+            minr, minc, maxr, maxc = r.bbox
+            h, w = r.hw
+            scale = round(500 / max(h, w, 3), 1)
+            if scale > 1:
+                scale = 1
+            nh, nw = int(h * scale), int(w * scale)
+            crop = image[minr:maxr, minc:maxc]
+            lin, k = self._resize_linear(rgb[minr:maxr, minc:maxc].contiguous(), crop.min(), crop.max(), nh, nw)
+            keep += k
+            smalls.append(lin.to(torch.uint8).reshape(-1, 3))
+            m, k = self._resize_mask((maps[r.map][minr:maxr, minc:maxc] == r.label).to(torch.uint8).contiguous(), nh, nw)
+            keep += k
+            masks.append(m.reshape(-1))
+            sizes.append((nh, nw, math.ceil(n * scale * scale)))
+        if not regions:
+            return []
+        # one read-back: the small masks as bits and the colours of their in-mask pixels only (what slic_masked reads: it zeroes the rest)
+        mask_cat = torch.cat(masks)
+        bits, colours = rh.to_host(_pack_bits(mask_cat), torch.cat(smalls)[mask_cat.bool()])
+        del keep
+        mask_flat = np.unpackbits(bits, bitorder="little")[:len(mask_cat)].astype(bool)
+        img_flat = np.zeros((len(mask_flat), 3), np.uint8)
+        img_flat[mask_flat] = colours
+        # host: what slic_masked computes on the small image before its sweeps
+        o, prep = 0, []
+        for nh, nw, n_seg in sizes:
+            prep.append((img_flat[o:o + nh * nw].reshape(nh, nw, 3), mask_flat[o:o + nh * nw].reshape(nh, nw)))
+            o += nh * nw
+        px_off, seg_off, tab, steps, imgs, segs = 0, 0, [], [], [], []
+        for (masked, mask), (nh, nw, n_seg) in zip(prep, sizes):
+            lab = _rgb2lab(masked)
+            centroids, st = _mask_centroids(mask, n_seg)
+            lab = ndi.gaussian_filter(lab[None], [1.0, 1.0, 1.0, 0], mode="reflect")[0]
+            K = len(centroids)
+            segs.append(np.concatenate([centroids, np.zeros((K, 3))], axis=-1))
+            steps.append(float(max(st)))
+            imgs.append(np.ascontiguousarray(lab * (1.0 / _COMPACTNESS)).reshape(-1, 3))
+            tab.append((px_off, nh, nw, K, seg_off))
+            px_off += (nh * nw + 255) // 256 * 256
+            seg_off += K
+        img_all = np.zeros((px_off, 3))
+        mask_all = np.zeros(px_off, np.uint8)
+        for (o, nh, nw, K, so), im, (_, mask) in zip(tab, imgs, prep):
+            img_all[o:o + nh * nw] = im
+            mask_all[o:o + nh * nw] = mask.reshape(-1)
+        tab = np.array(tab, np.int32)
+        item, first = _block_tables(tab[:, 1].astype(np.int64) * tab[:, 2])
+        seg_region = np.repeat(np.arange(len(tab), dtype=np.int32), tab[:, 3])
+        wb = int(rh.lib.rhccq_slic_regions_work_bytes(len(tab), _SLIC_SWEEPS))
+        d = [rh.dev(a) for a in (img_all, mask_all, np.concatenate(segs), tab, np.array(steps), item, first, seg_region)]
+        work = rh.empty((wb,), torch.uint8)
+        labels = rh.zeros((px_off,), torch.int32)
+        rh._check(rh.lib.rhccq_slic_sweeps_regions(rh.ctx, rh._p(d[0]), rh._p(d[1]), rh._p(d[2]), rh._p(d[3]), rh._p(d[4]), len(tab),
+                                                   int(tab[:, 3].max()), rh._p(d[5]), rh._p(d[6]), len(item), rh._p(d[7]), len(seg_region),
+                                                   _SLIC_SWEEPS, rh._p(work), wb, rh._p(labels)), "slic_sweeps_regions")
+        # the labels of the in-mask pixels only (every other one is 0), in the narrowest type that holds K
+        narrow = torch.uint8 if int(tab[:, 3].max()) < 256 else torch.int16
+        lab_all = np.zeros(px_off, np.int32)
+        lab_all[mask_all != 0] = rh.to_host(labels[d[1].bool()].to(narrow))
+        out = []
+        for (o, nh, nw, K, so), (_, mask) in zip(tab, prep):
+            lab = np.ascontiguousarray(lab_all[o:o + nh * nw].reshape(nh, nw))
+            seg_size = mask.sum() / K
+            conn = np.empty((nh, nw), np.int32)
+            rc = rh._raw.rhccq_slic_connectivity_host(C.c_void_p(lab.ctypes.data), int(nh), int(nw), int(0.5 * seg_size), int(3 * seg_size),
+                                                      C.c_void_p(conn.ctypes.data))
+            if rc:
+                raise ValueError("slic connectivity: bad arguments")
+            out.append(conn)
+        return out
+
+    # ---- stage 4 ---------------------------------------------------------------------------------------------------------------
+    def layers(self, maps, regions, small_labels, qualities):
+        """subregion_quantization's label layers of both calls -> ([(call, ClassSpec)], per region (class index or -1, local index),
+        per call {segments, segments_dropped, layers})"""
+        rh = self.rh
+        H, W = int(maps[0].shape[0]), int(maps[0].shape[1])
+        R = len(regions)
+        if R == 0:
+            return [], [], [{"segments": 0, "segments_dropped": 0, "layers": 0} for _ in range(2)]
+        nsid = np.array([int(s.max(initial=0)) + 1 for s in small_labels], np.int64)
+        sid_off = np.concatenate([[0], np.cumsum(nsid)[:-1]]).astype(np.int64)
+        sm_off = np.concatenate([[0], np.cumsum([s.size for s in small_labels])[:-1]]).astype(np.int64)
+        yx, yx_off = [], 0
+        tab = np.zeros((R, 11), np.int32)
+        for i, (r, s) in enumerate(zip(regions, small_labels)):
+            h, w = r.hw
+            yx += [self._nearest_tables(s.shape[0], h), self._nearest_tables(s.shape[1], w)]
+            tab[i] = (r.bbox[0], r.bbox[1], h, w, r.map, r.label, sm_off[i], s.shape[1], yx_off, sid_off[i], -1)
+            yx_off += h + w
+        area = tab[:, 2].astype(np.int64) * tab[:, 3]
+        item, first = _block_tables(area)
+        d_small = rh.dev(np.concatenate([s.reshape(-1) for s in small_labels]).astype(np.int32))
+        d_yx, d_item, d_first = rh.dev(np.concatenate(yx)), rh.dev(item), rh.dev(first)
+        d_tab = rh.dev(tab)
+        n_sid = int(nsid.sum())
+        counts = rh.empty((n_sid,), torch.int32)
+        rh._check(rh.lib.rhccq_image_seg_counts(rh.ctx, rh._p(maps[0]), rh._p(maps[1]), H, W, rh._p(d_tab), rh._p(d_small), rh._p(d_yx), rh._p(d_item),
+                                                rh._p(d_first), len(item), rh._p(counts), n_sid), "image_seg_counts")
+        cnt = rh.to_host(counts)
+        # the kept segments of every region in subregion_quantization's order (ascending ids, find_contours' drop rule)
+        keep = np.zeros(n_sid, np.int32)
+        kept = []
+        stats = [{"segments": 0, "segments_dropped": 0, "layers": 0} for _ in range(2)]
+        for i, r in enumerate(regions):
+            h, w = r.hw
+            c = cnt[sid_off[i]:sid_off[i] + nsid[i]]
+            ids = [s for s in range(1, int(nsid[i])) if c[s] > 0]
+            drop = [s for s in ids if h >= 2 and w >= 2 and c[s] == h * w]
+            stats[r.call]["segments_dropped"] += len(drop)
+            ks = [s for s in ids if s not in drop]
+            stats[r.call]["segments"] += len(ks)
+            keep[sid_off[i] + np.array(ks, np.int64)] = 1
+            kept.append(ks)
+        # overlaps: only regions of different label maps can share pixels (the small ROI regions at the end of the non-ROI list)
+        pairs = overlap_candidates(regions, [bool(k) for k in kept])
+        hit = {}
+        if pairs:
+            pr = np.array(pairs, np.int32)
+            ia = np.maximum(tab[pr[:, 0], 0], tab[pr[:, 1], 0]), np.minimum(tab[pr[:, 0], 0] + tab[pr[:, 0], 2], tab[pr[:, 1], 0] + tab[pr[:, 1], 2])
+            ib = np.maximum(tab[pr[:, 0], 1], tab[pr[:, 1], 1]), np.minimum(tab[pr[:, 0], 1] + tab[pr[:, 0], 3], tab[pr[:, 1], 1] + tab[pr[:, 1], 3])
+            p_item, p_first = _block_tables((ia[1] - ia[0]).astype(np.int64) * (ib[1] - ib[0]))
+            d_hit = rh.empty((len(pairs),), torch.int32)
+            d_keep, d_pr, d_pi, d_pf = rh.dev(keep), rh.dev(pr), rh.dev(p_item), rh.dev(p_first)
+            rh._check(rh.lib.rhccq_image_overlap(rh.ctx, rh._p(maps[0]), rh._p(maps[1]), H, W, rh._p(d_tab), rh._p(d_small), rh._p(d_yx), rh._p(d_keep),
+                                                 rh._p(d_pr), len(pairs), rh._p(d_pi), rh._p(d_pf), len(p_item), rh._p(d_hit)), "image_overlap")
+            hit = {p: bool(v) for p, v in zip(pairs, rh.to_host(d_hit))}
+        ids = np.zeros(n_sid, np.int32)
+        layers, place = place_layers(regions, kept, hit)
+        specs = []
+        for call, l in layers:
+            stats[call]["layers"] += 1
+            for n, (i, s) in enumerate(l["segments"], 1):      # ids per layer: regions in list order, SLIC ids ascending
+                ids[sid_off[i] + s] = n
+            for i in l["members"]:
+                tab[i, 10] = len(specs)
+            specs.append((call, l))
+        d_layers = rh.zeros((max(len(specs), 1), H, W), torch.int32)
+        if specs:
+            d_tab2, d_ids = rh.dev(tab), rh.dev(ids)
+            rh._check(rh.lib.rhccq_image_paint(rh.ctx, rh._p(maps[0]), rh._p(maps[1]), H, W, rh._p(d_tab2), rh._p(d_small), rh._p(d_yx), rh._p(d_ids),
+                                               rh._p(d_item), rh._p(d_first), len(item), rh._p(d_layers)), "image_paint")
+        classes = [(call, ClassSpec(d_layers[k], l["seg_region"], l["bboxes"], qualities[call])) for k, (call, l) in enumerate(specs)]
+        return classes, place, stats
+
+    # ---- the whole flow --------------------------------------------------------------------------------------------------------
+    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False):
+        """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
+        indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
+        ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
+        container.write_frame(exact=exact)."""
+        rh = self.rh
+        if torch.is_tensor(image):
+            image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("ImageEncoder.encode: a uint8 H x W x 3 image is expected")
+        H, W = image.shape[:2]
+        t, t0 = {}, time.perf_counter()
+
+        def lap(name):
+            nonlocal t0
+            now = time.perf_counter()
+            t[name] = now - t0
+            t0 = now
+        regions, maps, rgb, stats = self.regions(image)
+        lap("regions")
+        n_seg = self.split_segments(rgb, maps, regions)
+        lap("split_score")
+        small = self.slic(image, rgb, maps, regions, n_seg)
+        lap("slic")
+        classes, place, seg_stats = self.layers(maps, regions, small, (roi_quality, nonroi_quality))
+        lap("layers")
+        stats.update(roi_segments=seg_stats[0]["segments"], nonroi_segments=seg_stats[1]["segments"],
+                     segments_dropped=seg_stats[0]["segments_dropped"] + seg_stats[1]["segments_dropped"],
+                     roi_layers=seg_stats[0]["layers"], nonroi_layers=seg_stats[1]["layers"])
+        if not classes:
+            raise IndexError("no segments in either class")       # quantize_image([]): merged[0] of an empty list
+        enc = FrameEncoder(rh)
+        S = enc.prepare(rgb, [c for _, c in classes])
+        per_class = enc.level1(S)
+        lap("level1")
+        groups = [(q, [place[i] for i, r in enumerate(regions) if r.call == call and place[i][0] >= 0])
+                  for call, q in ((0, roi_quality), (1, nonroi_quality))]
+        lvl2, q2s, jobs2 = enc.level2_jobs(S, per_class, groups)
+        comps3 = enc.level2_finish(lvl2, cluster_palettes(rh, jobs2))
+        m3c, q3, job3 = enc.level3_job(S, comps3, q2s)
+        (res3,) = cluster_palettes(rh, [job3])
+        res = enc.finish(S, comps3, m3c, q3, res3)
+        torch.cuda.current_stream(rh.device).synchronize()
+        lap("levels23")
+        if out_path:
+            from . import container
+            container.write_frame(res, out_path, rh, exact=exact)
+            lap("container")
+        stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
+        res["classes"] = classes
+        res["stats"] = stats
+        return res

@@ -97,3 +97,11 @@ def frame_classes(H, W, tiles, device=None):
         bbox = (int(rows.min()), int(cols.min()), int(rows.max()) + 1, int(cols.max()) + 1)
         out.append((lab, n, bbox))
     return out
+
+
+def kodak_mosaic(images, H=2160, W=3840, cols=5, rows=4):
+    """A structured 4K frame: `rows` x `cols` tiles of 512 x 768 photographs (portrait ones turned), padded to H x W by mirroring the
+    edge rows / columns (not with black: black pixels have rules of their own in the encoder)."""
+    tiles = [im if im.shape[0] <= im.shape[1] else np.ascontiguousarray(np.rot90(im)) for im in images[:cols * rows]]
+    grid = np.concatenate([np.concatenate(tiles[r * cols:(r + 1) * cols], axis=1) for r in range(rows)], axis=0)
+    return np.ascontiguousarray(np.pad(grid, ((0, H - grid.shape[0]), (0, W - grid.shape[1]), (0, 0)), mode="symmetric"))
