@@ -69,7 +69,7 @@ __all__ = [
     "eps_components", "kmeanspp_int", "kmeans_labels", "split_large_cluster",
     "minibatch_kmeans_labels", "minibatch_kmeans_native", "npy_argsort_scalar", "kmeanspp_picks_native", "cluster_palette", "merge_components", "segment_crop",
     "level1_region", "region_quantization", "quantize_image", "optimal_index_dtype",
-    "encode_frame", "pack_container", "container_bytes", "load_container", "decode_container",
+    "encode_frame", "region_segment_count", "find_contours_drops", "kept_segments", "script_flow", "pack_container", "container_bytes", "load_container", "decode_container",
     "dct_quant_blocks", "adaptive_quality_metrics", "split_score", "normalize_result", "enhanced_slic", "slic_masked", "slic_sweeps", "slic_enforce_connectivity",
     "slic_mask_centroids", "sk_resize", "sk_rgb2lab", "sk_rgb2gray", "sk_sobel", "sk_lbp_uniform_8_1",
 ]
@@ -816,6 +816,94 @@ def encode_frame(image, classes, qualities, kmeans=kmeans_labels, minibatch=mini
     q3 = min(sum(q2s), 100)
     fin = quantize_image(lvl2, H, W, q3, kmeans, minibatch)
     return {"level1": l1_all, "level2": lvl2, "final": fin}
+
+
+# --------------------------------------------------------------------------------------
+# The image -> .rhccq script flow (encoder/compression/test.py:77-151) and the glue of subregion_quantization between the
+# upstream stages and level 1 (subregions.py:90-161,315-317,634-679; slic.py:143-214).  Stated from the oracle's own
+# stage functions; the ROI and SLIC stages inherit their PARITY UNPINNED status.
+# --------------------------------------------------------------------------------------
+def region_segment_count(region_image, bbox_mask):
+    """subregions.py:125-161: split score -> window -> ceil(normalize_result) -> at least 1.
+    Returns (optimal_segments, normalize_result value, overall split score)."""
+    overall = split_score(region_image, bbox_mask)[0]        # 0 below 100 masked pixels (split_score.py:25-27)
+    size = region_image.size                                  # h * w * 3
+    window = math.ceil(math.ceil(math.log(size, 10)) * math.log(size))
+    nr = normalize_result(overall, window)
+    optimal = math.ceil(nr)
+    if optimal <= 0:
+        optimal = 1
+    return optimal, nr, overall
+
+
+def find_contours_drops(segment_mask):
+    """slic.py:164-206 for one segment mask of the region box's shape.  A box thinner than 2 px takes the tiny-segment branch
+    and is always kept.  Otherwise skimage.measure.find_contours(mask, 0.5) finds a contour iff some neighbouring pixels
+    differ; a mask without a level crossing is constant, i.e. (it is not empty) fills the box, and is skipped."""
+    rows, cols = segment_mask.shape
+    if rows < 2 or cols < 2:
+        return False
+    return bool(segment_mask.all())
+
+
+def kept_segments(seglabels, bbox_mask):
+    """extract_slic_segment_boundaries' ids in ascending order (slic.py:158-160), without empty and dropped segments.
+    Returns (kept ids, dropped ids, label map restricted to the mask with only the kept ids left)."""
+    seglabels = np.asarray(seglabels)
+    bbox_mask = np.asarray(bbox_mask, bool)
+    kept, dropped = [], []
+    ids = np.unique(seglabels)
+    for sid in ids[ids != 0]:
+        m = (seglabels == sid) & bbox_mask
+        if not m.any():
+            continue
+        (dropped if find_contours_drops(m) else kept).append(int(sid))
+    out = np.where(bbox_mask & np.isin(seglabels, kept), seglabels, 0).astype(np.int32)
+    return kept, dropped, out
+
+
+def script_flow(image, roi_quality=20, nonroi_quality=10, kmeans=kmeans_labels, minibatch=minibatch_kmeans_labels):
+    """encoder/compression/test.py:77-151: get_regions -> extract_regions -> subregion_quantization per class ->
+    region_quantization per class (any exception of either call swallowed: the script's bare `except:`) -> quantize_image
+    (not guarded: an image without any component raises here) -> lossless_compress_optimized -> save_compressed.
+
+    Returns a dict of every intermediate: region_map, roi_regions / nonroi_regions (bbox, area, type, bbox_mask),
+    per class and region the segment count, normalize_result value, kept / dropped SLIC ids and the label map after drops
+    ("regions"), level1 per class (one list per region, as subregion_quantization returns it), level2 per class (None where
+    region_quantization raised, with the exception's type name in level2_error), final, pkg and the file bytes."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    H, W = image.shape[:2]
+    unified, region_map, _, _, roi_mask, non_mask = get_regions(image)
+    roi_regions, nonroi_regions = extract_regions(image, roi_mask, non_mask)
+    out = {"region_map": np.asarray(region_map), "roi_regions": roi_regions, "nonroi_regions": nonroi_regions}
+    per_class, level1, level2, errors = [], [], [], []
+    for regions, q in ((roi_regions, roi_quality), (nonroi_regions, nonroi_quality)):
+        info, l1 = [], []
+        for region in regions:
+            minr, minc, maxr, maxc = region["bbox"]
+            bbox_region = image[minr:maxr, minc:maxc]
+            bbox_mask = np.asarray(region["bbox_mask"], bool)
+            n_seg, nr, overall = region_segment_count(bbox_region, bbox_mask)
+            seglabels = enhanced_slic(bbox_region, bbox_mask, n_segments=n_seg)
+            kept, dropped, labels = kept_segments(seglabels, bbox_mask)
+            info.append({"n_segments": n_seg, "normalize_result": nr, "split_score": overall, "kept": kept, "dropped": dropped,
+                         "labels": labels})
+            l1.append(level1_region(image, region["bbox"], bbox_mask, labels, q, kmeans, minibatch))
+        per_class.append(info)
+        level1.append(l1)
+        q2 = min(q * 2, 100)
+        try:
+            level2.append(region_quantization([c for comps in l1 for c in comps], H, W, q2, kmeans, minibatch))
+            errors.append(None)
+        except Exception as e:                                   # noqa: BLE001  (test.py:128-132: bare except)
+            level2.append(None)
+            errors.append(type(e).__name__)
+    out.update(regions=per_class, level1=level1, level2=level2, level2_error=errors)
+    q3 = min(min(roi_quality * 2, 100) + min(nonroi_quality * 2, 100), 100)
+    final = quantize_image([c for c in level2 if c is not None], H, W, q3, kmeans, minibatch)
+    pkg = pack_container(final["palette"], final["indices"], final["shape"])
+    out.update(final=final, pkg=pkg, file_bytes=container_bytes(pkg))
+    return out
 
 
 # --------------------------------------------------------------------------------------

@@ -52,6 +52,16 @@ class _TableOverflow(Exception):
     pass
 
 
+def _window(indices, top_left, shape):
+    """the final index map of the result: the frame raster [H, W] cut to the component's window (the whole frame when several
+    components were merged on the frame canvas)"""
+    r, c = int(top_left[0]), int(top_left[1])
+    h, w = int(shape[0]), int(shape[1])
+    if (r, c, h, w) == (0, 0) + tuple(indices.shape):
+        return indices
+    return indices[r:r + h, c:c + w].contiguous()
+
+
 class _Comp:
     """A component of the hierarchy in palette space."""
     __slots__ = ("keys", "fp", "top_left", "shape", "maps", "merged")
@@ -374,6 +384,8 @@ class FrameEncoder:
         self._t("compose", t0)
         t0 = time.perf_counter()
         out = self._remap_pass(S, S["lut1"], default_index, out_dtype, d_lut2)
+        if not multi:                                   # a single component passes through as it is (merging.py:16-21): its own window
+            out = _window(out, m3c.top_left, m3c.shape)
         self._t("remap", t0, sync=profile)
         result = {"palette": unpack_rgb(fk3), "indices": out, "indices_dtype": dtype_name,
                   "shape": (H, W) if multi else tuple(m3c.shape), "top_left": (0, 0) if multi else tuple(m3c.top_left),
@@ -506,7 +518,7 @@ class FrameEncoder:
 
     def encode(self, rgb, classes, want_levels=False, profile=False):
         """rgb: uint8[H,W,3] device tensor; classes: [ClassSpec] in precedence order (ROI first).
-        Returns dict(palette uint8[K,3], indices (device tensor [H,W], dtype by max index),
+        Returns dict(palette uint8[K,3], indices (device tensor [H,W], or the window shape x top_left of a single final component; dtype by max index),
         indices_dtype, shape, top_left, levels (optional))."""
         rh = self.rh
         self.timings = {}
@@ -579,7 +591,7 @@ class FrameEncoder:
             break
         eb = int(res.index_bytes)
         dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[eb]
-        idx = out.view(torch.uint8)[:H * W * eb].view(dt).reshape(H, W)
+        idx = _window(out.view(torch.uint8)[:H * W * eb].view(dt).reshape(H, W), res.top_left, res.shape)    # (the C entry writes the frame raster)
         names = ("scan", "unique", "levels_1_2_per_class", "level3", "compose", "remap", "total")
         self.timings = {n: res.ms[i] * 1e-3 for i, n in enumerate(names)}
         cn = ("level1_cluster", "first_positions_merge", "level2_cluster", "level2_finish")
