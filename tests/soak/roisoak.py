@@ -1,5 +1,8 @@
 """one-off soak: get_regions + extract_regions on the device vs the numpy / scipy restatement over random synthetic images:
-python tests/soak/roisoak.py FIRST COUNT [MIN_EDGE MAX_EDGE]"""
+python tests/soak/roisoak.py FIRST COUNT [MIN_EDGE MAX_EDGE]
+The suite itself now covers both ends of the size range against the oracle: image edges below 60 down to 1 x 1, step by step
+(tests/test_gpu_roi_shapes.py), and 2160 x 3840 (tests/test_gpu_roi_fullsize.py).  This soak is still for what a fixed list cannot
+give: many random sizes in between (default edges 60..360) and random contents through the whole chain."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
