@@ -9,10 +9,16 @@
 //                                                      (floor means), oversize clusters split by KMeans depth-first, uint16 mapping
 //   encoder/compression/merging.py:16-21,52-82         single-component passthrough, reversed painting, first-seen global palette
 //   encoder/compression/regions.py:9-70, image.py:243-286   per class merge + cluster(2q); classes merged + cluster(q3); index dtype
-// Host structure: the calling thread runs the per-pixel passes on the context's stream; every region class is a std::thread with a
+// Host structure: the calling thread runs the per-pixel passes on the context's stream; every region class is a host thread with a
 // sibling context (HIP stream + device arena of its own) that runs level 1 -> merges -> level 2 of its class; the MiniBatchKMeans
 // problems of a class (>= 10 000 colours) run side by side on further sibling contexts.  No interpreter, no global lock; the only
 // synchronisation points are the k-sized read-backs the ordering rules need.
+// Ownership (host_raii.h): threads, events, streams, pinned memory and sibling contexts belong to owners whose destructors release them.
+// The invariant on every exit path, an exception included: no host buffer that an asynchronous copy reads or writes is destroyed before
+// its stream has been synchronised, and no event is destroyed while a thread that may still record or wait on it is running.  The second
+// half is declaration order (events before the run_lanes call that joins the threads).  The first half is Lane::download for single
+// copies (complete on return) and a SyncOnUnwind declared after the buffers wherever something can throw between a copy and its
+// synchronisation; a pageable source of a host-to-device copy is staged before the call returns (Lane::upload) and needs neither.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -22,9 +28,9 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <vector>
 
+#include "host_raii.h"
 #include "rhccq_common.h"
 
 namespace {
@@ -34,19 +40,10 @@ constexpr int64_t kFpNone = kIntMax;
 constexpr int64_t kMinibatchThreshold = 10000;      // clustering.py:207
 constexpr int kMaxJobs = 2048;
 
-struct Err {
-  int code;
-  std::string msg;
-};
 #define EF_RC(ctx, call)                                                                               \
   do {                                                                                                 \
     const int rc_ = (call);                                                                            \
     if (rc_) throw Err{rc_, std::string(#call) + ": " + rhccq_last_error(ctx)};                        \
-  } while (0)
-#define EF_HIP(expr)                                                                                   \
-  do {                                                                                                 \
-    const hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) throw Err{RHCCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)};   \
   } while (0)
 
 // RHCCQ_TRACE=1: per-phase host clocks of every MiniBatchKMeans fit on stderr (diagnostic: adds stream synchronisations)
@@ -224,33 +221,26 @@ struct Arena {
 };
 
 struct Lane {
-  rhccq_ctx* ctx = nullptr;
-  hipStream_t stream = nullptr;
+  // (members are released in the reverse of this order: sub-lanes, events, pinned buffer, context, stream, arena)
   int device = 0;
   Arena arena;
-  double* pinned = nullptr;                            // 3 x 16 doubles: landing buffers of the asynchronous state polls
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  Stream stream;
+  Ctx ctx;
+  Pinned<double> pinned;                               // 3 x 16 doubles: landing buffers of the asynchronous state polls
+  Event ev[3];
   std::vector<std::unique_ptr<Lane>> sub;              // further siblings (the MiniBatchKMeans problems of a class)
 
-  explicit Lane(int dev) : device(dev) {
+  explicit Lane(int dev) : device(dev) {               // (a throw half way releases what exists: the members are complete objects by now)
     EF_HIP(hipSetDevice(dev));
-    EF_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (rhccq_ctx_create(dev, stream, &ctx)) throw Err{RHCCQ_E_HIP, "rhccq_ctx_create failed"};
-    EF_HIP(hipHostMalloc((void**)&pinned, 3 * 16 * sizeof(double)));
-    for (auto& e : ev) EF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  ~Lane() {
-    sub.clear();
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (pinned) (void)hipHostFree(pinned);
-    if (ctx) rhccq_ctx_destroy(ctx);
-    if (stream) (void)hipStreamDestroy(stream);
+    stream = make_stream();
+    ctx = make_ctx(dev, stream.get());
+    pinned = make_pinned<double>(3 * 16);
+    for (auto& e : ev) e = make_event();
   }
   Lane& sublane(size_t i) {
     while (sub.size() <= i) {
-      sub.emplace_back(new Lane(device));
-      sub.back()->adopt_options(ctx);
+      sub.push_back(std::make_unique<Lane>(device));
+      sub.back()->adopt_options(ctx.get());
     }
     return *sub[i];
   }
@@ -275,21 +265,21 @@ struct Lane {
   template <typename T>
   T* dzeros(size_t n) {
     T* p = dalloc<T>(n);
-    EF_HIP(hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), stream));
+    EF_HIP(hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), stream.get()));
     return p;
   }
   template <typename T>
   T* upload(const T* host, size_t n) {                 // pageable source: the copy is staged before the call returns
     T* p = dalloc<T>(n);
-    if (n) EF_HIP(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, stream));
+    if (n) EF_HIP(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, stream.get()));
     return p;
   }
   template <typename T>
   void download(T* host, const T* dev, size_t n) {     // complete on return
-    if (n) EF_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream));
-    EF_HIP(hipStreamSynchronize(stream));
+    if (n) EF_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream.get()));
+    EF_HIP(hipStreamSynchronize(stream.get()));
   }
-  void sync() { EF_HIP(hipStreamSynchronize(stream)); }
+  void sync() { EF_HIP(hipStreamSynchronize(stream.get())); }
 };
 
 struct FrameState {
@@ -345,7 +335,7 @@ struct PreChain {
 constexpr int64_t kFrameChainMaxInit = 98304;
 
 void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out, const PreChain* pre = nullptr) {
-  rhccq_ctx* c = L.ctx;
+  rhccq_ctx* c = L.ctx.get();
   MtTable& mt = MtTable::get();
   const bool tr = trace_on();
   double tt[6] = {now_ms(), 0, 0, 0, 0, 0};
@@ -363,7 +353,7 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
   int64_t n_words;
   double* centres;
   if (pre) {                                                             // the frame's launch ran the chain: wait for it on this lane
-    EF_HIP(hipStreamWaitEvent(L.stream, pre->done, 0));
+    EF_HIP(hipStreamWaitEvent(L.stream.get(), pre->done, 0));
     centres = pre->centres;
     if (tr) { tt[1] = now_ms(); L.sync(); tt[2] = now_ms(); }
   } else {
@@ -430,15 +420,15 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
           step += ns;
           const int slot = n_chunk % 3;
           ++n_chunk;
-          EF_HIP(hipMemcpyAsync(L.pinned + 16 * slot, state, 16 * sizeof(double), hipMemcpyDeviceToHost, L.stream));
-          EF_HIP(hipEventRecord(L.ev[slot], L.stream));
+          EF_HIP(hipMemcpyAsync(L.pinned.get() + 16 * slot, state, 16 * sizeof(double), hipMemcpyDeviceToHost, L.stream.get()));
+          EF_HIP(hipEventRecord(L.ev[slot].get(), L.stream.get()));
           pending.push_back(Pending{slot});
         }
         if (pending.size() >= 2 || step >= limit) {
           const int slot = pending.front().slot;
           pending.erase(pending.begin());
-          EF_HIP(hipEventSynchronize(L.ev[slot]));
-          std::memcpy(st, L.pinned + 16 * slot, sizeof(st));
+          EF_HIP(hipEventSynchronize(L.ev[slot].get()));
+          std::memcpy(st, L.pinned.get() + 16 * slot, sizeof(st));
           cur_known = (int64_t)std::max(st[9], st[14]);
           steps_known = (int64_t)st[5];
           if (st[4] >= 3.0 || st[11] != 0.0 || st[5] >= (double)limit) stop = true;
@@ -446,8 +436,8 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
         }
       }
       if (!pending.empty()) {                                             // launches queued behind the stop: they return at once
-        EF_HIP(hipEventSynchronize(L.ev[pending.back().slot]));
-        std::memcpy(st, L.pinned + 16 * pending.back().slot, sizeof(st));
+        EF_HIP(hipEventSynchronize(L.ev[pending.back().slot].get()));
+        std::memcpy(st, L.pinned.get() + 16 * pending.back().slot, sizeof(st));
       }
       check(st);
       break;
@@ -524,12 +514,9 @@ struct Node {
 void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
   // every problem a pipeline of its own: host thread + sibling context (stream), as ops.py::_minibatch_lanes
   if (tasks.empty()) return;
-  hipEvent_t ready;
-  EF_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-  EF_HIP(hipEventRecord(ready, L.stream));
-  std::vector<std::thread> th;
+  const Event ready = make_event();
+  EF_HIP(hipEventRecord(ready.get(), L.stream.get()));
   const size_t n_lanes = std::min<size_t>(tasks.size(), 8);
-  std::vector<Err> errs(n_lanes, Err{0, ""});
   for (size_t i = 0; i < n_lanes; ++i) L.sublane(i);   // (created here: the vector must not grow under the threads)
   // longest chains first, each to the lane with the least work so far
   std::vector<size_t> order(tasks.size());
@@ -542,12 +529,12 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
     groups[g].push_back(i);
     load[g] += tasks[i]->k;
   }
-  for (size_t g = 0; g < n_lanes; ++g) {
-    th.emplace_back([&, g]() {
-      Lane& S = *L.sub[g];
-      try {
+  run_lanes(
+      n_lanes,
+      [&](size_t g) {
+        Lane& S = *L.sub[g];
         EF_HIP(hipSetDevice(S.device));
-        EF_HIP(hipStreamWaitEvent(S.stream, ready, 0));
+        EF_HIP(hipStreamWaitEvent(S.stream.get(), ready.get(), 0));
         for (size_t i : groups[g]) {
           Job& jb = *tasks[i];
           const uint32_t* keys;
@@ -566,23 +553,12 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
           mbk_fit(S, keys, n, jb.k, jb.labels_dev, jb.pre);
         }
         S.sync();
-      } catch (const Err& e) {
-        errs[g] = e;
-        (void)hipStreamSynchronize(S.stream);
-      } catch (const std::exception& e) {
-        errs[g] = Err{RHCCQ_E_HIP, e.what()};
-        (void)hipStreamSynchronize(S.stream);
-      }
-    });
-  }
-  for (auto& t : th) t.join();
-  (void)hipEventDestroy(ready);
-  for (auto& e : errs)
-    if (e.code) throw e;
+      },
+      [&](size_t g) { (void)hipStreamSynchronize(L.sub[g]->stream.get()); });
 }
 
 void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
-  rhccq_ctx* c = L.ctx;
+  rhccq_ctx* c = L.ctx.get();
   const size_t S = jobs.size();
   // ---- which branch: resident MiniBatch jobs, host MiniBatch jobs, DBSCAN jobs, only-black palettes
   std::vector<Job*> mbk;
@@ -678,7 +654,7 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
         for (auto& v : lut) v += jb.base;
         int32_t* d_lut = L.upload(lut.data(), lut.size());
         EF_RC(c, rhccq_remap(c, jb.labels_dev, n, d_lut, jb.k, jb.lut_dev + nblack));
-        if (nblack) EF_HIP(hipMemcpyAsync(jb.lut_dev, &jb.base, 4, hipMemcpyHostToDevice, L.stream));
+        if (nblack) EF_HIP(hipMemcpyAsync(jb.lut_dev, &jb.base, 4, hipMemcpyHostToDevice, L.stream.get()));
         L.sync();                                       // (`lut` is staged: it may die now)
       } else {
         std::vector<int32_t> lab((size_t)n);
@@ -817,7 +793,7 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
       if (jb.lut_dev && jb.P) {
         std::vector<int32_t> m(jb.mapping);
         for (auto& v : m) v += jb.base;
-        EF_HIP(hipMemcpyAsync(jb.lut_dev, m.data(), m.size() * 4, hipMemcpyHostToDevice, L.stream));
+        EF_HIP(hipMemcpyAsync(jb.lut_dev, m.data(), m.size() * 4, hipMemcpyHostToDevice, L.stream.get()));
         L.sync();
       }
       continue;
@@ -865,7 +841,7 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
     if (jb.lut_dev) {
       std::vector<int32_t> m(jb.mapping);
       for (auto& v : m) v += jb.base;
-      EF_HIP(hipMemcpyAsync(jb.lut_dev, m.data(), m.size() * 4, hipMemcpyHostToDevice, L.stream));
+      EF_HIP(hipMemcpyAsync(jb.lut_dev, m.data(), m.size() * 4, hipMemcpyHostToDevice, L.stream.get()));
       L.sync();
     }
   }
@@ -961,9 +937,9 @@ struct FrameCtx {
   int32_t* lut1 = nullptr;                             // (job, rank) -> frame-wide entry id of the clustered level-1 palettes
   int32_t* e1map = nullptr;                            // [n_classes][H * W] entry every pixel shows
   std::vector<int64_t> ebase;                          // first entry id of a class's slice (= palette entries of the classes before)
-  hipEvent_t ready = nullptr;
+  Event ready;
   std::map<int, PreChain> pre;                         // job -> its level-1 chain in the frame's launch (RHCCQ_OPT_FRAME_CHAINS)
-  hipEvent_t chains_done = nullptr;
+  Event chains_done;
 };
 
 struct ClassOut {
@@ -971,14 +947,14 @@ struct ClassOut {
   std::shared_ptr<Comp> comp3;                         // the class's level-2 result (NULL: the class contributes nothing)
   int q2 = 0;
   double ms[4] = {0, 0, 0, 0};
-  hipEvent_t done = nullptr;
+  Event done;
 };
 
 // level 1 -> merge per region -> merge per class -> level 2 of one class on its own lane (frame.py::_class_pipeline)
 void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
-  rhccq_ctx* c = L.ctx;
+  rhccq_ctx* c = L.ctx.get();
   EF_HIP(hipSetDevice(L.device));
-  EF_HIP(hipStreamWaitEvent(L.stream, F.ready, 0));
+  EF_HIP(hipStreamWaitEvent(L.stream.get(), F.ready.get(), 0));
   double t_prev = now_ms();
   auto mark = [&](int slot) {
     const double t = now_ms();
@@ -1006,7 +982,6 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
     chunk.resize((size_t)(F.pal_off[(size_t)small_hi + 1] - F.pal_off[(size_t)small_lo]));
     L.download(chunk.data(), F.keys_dev + F.pal_off[(size_t)small_lo], chunk.size());
   }
-  int64_t new_total = 0;                                // (upper bound of this class's clustered entries so far: ids are assigned after)
   for (size_t i = 0; i < ids.size(); ++i) {
     const int j = ids[i];
     Job& jb = jobs[i];
@@ -1024,7 +999,6 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
       jb.keys.assign(chunk.begin() + a, chunk.begin() + a + (size_t)jb.P);
     }
   }
-  (void)new_total;
   // entry ids: a job's clustered palette never has more entries than the palette itself, so the job's slice of the frame-wide id
   // space starts at ebase[class] + (palette entries of the class's jobs before it) -- known BEFORE the clustering, which lets the
   // device-resident mappings be written straight into lut1 (frame.py reserves a tighter heuristic bound and falls back when a
@@ -1042,18 +1016,19 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
   int32_t* fp = L.dalloc<int32_t>((size_t)std::max<int64_t>(class_entries, 1));
   for (size_t i = 0; i < ids.size(); ++i)               // INT_MAX over the entries in use (a 32-bit pattern fill per job)
     if (!jobs[i].new_keys.empty())
-      EF_HIP(hipMemsetD32Async((hipDeviceptr_t)(fp + (F.pal_off[(size_t)ids[i]] - F.pal_off[(size_t)jb0])), (int)kIntMax, jobs[i].new_keys.size(), L.stream));
+      EF_HIP(hipMemsetD32Async((hipDeviceptr_t)(fp + (F.pal_off[(size_t)ids[i]] - F.pal_off[(size_t)jb0])), (int)kIntMax, jobs[i].new_keys.size(), L.stream.get()));
   const int32_t* lab_ptr[1] = {cls.labels};
   const int32_t jbase[1] = {jb0};
   EF_RC(c, rhccq_job_index_entries(c, F.rgb, F.H, F.W, 1, lab_ptr, jbase, F.bitmaps, F.prefix, F.d_pal_off, F.fix_key,
                                     fp - F.ebase[(size_t)ci], F.lut1, F.e1map + (size_t)ci * (size_t)F.H * (size_t)F.W));
   // (only the clustered entries come back: a job's slice is as long as its palette, its clustered palette ~100x shorter)
   std::vector<std::vector<int32_t>> fp_host(ids.size());
+  const SyncOnUnwind drain(L.stream.get());
   for (size_t i = 0; i < ids.size(); ++i) {
     const int64_t lo = F.pal_off[(size_t)ids[i]] - F.pal_off[(size_t)jb0];
     fp_host[i].resize(jobs[i].new_keys.size());
     if (!jobs[i].new_keys.empty())
-      EF_HIP(hipMemcpyAsync(fp_host[i].data(), fp + lo, jobs[i].new_keys.size() * 4, hipMemcpyDeviceToHost, L.stream));
+      EF_HIP(hipMemcpyAsync(fp_host[i].data(), fp + lo, jobs[i].new_keys.size() * 4, hipMemcpyDeviceToHost, L.stream.get()));
   }
   L.sync();
   std::map<int, std::shared_ptr<Comp>> seg_comp;
@@ -1098,7 +1073,7 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
     out.comp3 = clustered(*comp, j2[0]);
     mark(3);
   }
-  EF_HIP(hipEventRecord(out.done, L.stream));
+  EF_HIP(hipEventRecord(out.done.get(), L.stream.get()));
   L.sync();
 }
 
@@ -1123,6 +1098,7 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
       const int64_t n = F.P[(size_t)j] - hb;
       if (!F.present[(size_t)j] || n < kMinibatchThreshold) continue;
       const int64_t k = mbk_k(n, F.classes[ci].quality);
+      if (k < 1) continue;                              // (a quality rhccq_params refuses: the class's own pipeline reports it)
       PreChain pc;
       pc.n = n;
       pc.k = k;
@@ -1163,12 +1139,12 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
   EF_HIP(hipMemsetAsync(chosen, 0, (size_t)ktot * 4, stream));
   const double t1 = now_ms();
   EF_RC(c, rhccq_mbk_init(c, F.keys_dev, probs.data(), (int32_t)probs.size(), d_init, d_perm, d_rand, centres, chosen));
-  EF_HIP(hipEventCreateWithFlags(&F.chains_done, hipEventDisableTiming));
-  EF_HIP(hipEventRecord(F.chains_done, stream));
+  F.chains_done = make_event();
+  EF_HIP(hipEventRecord(F.chains_done.get(), stream));
   for (size_t i = 0; i < probs.size(); ++i) {
     PreChain& pc = F.pre[ids[i]];
     pc.centres = centres + 4 * probs[i].koff;
-    pc.done = F.chains_done;
+    pc.done = F.chains_done.get();
   }
   if (tr) fprintf(stderr, "[rhccq] frame chains: %zu problems, %lld init samples, set-up %.2f ms (host), launched after %.2f ms\n", probs.size(),
                   (long long)itot, t1 - t0, now_ms() - t0);
@@ -1183,7 +1159,7 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
     ctx->frame_state_free = free_frame_state;
   }
   FrameState& FS = *(FrameState*)ctx->frame_state;
-  while ((int)FS.classes.size() < n_classes) FS.classes.emplace_back(new Lane(ctx->device));
+  while ((int)FS.classes.size() < n_classes) FS.classes.push_back(std::make_unique<Lane>(ctx->device));
   for (auto& l : FS.classes) {
     l->adopt_options(ctx);
     l->reset();
@@ -1266,6 +1242,7 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
     EF_HIP(hipStreamSynchronize(stream));
     std::vector<uint32_t> fk((size_t)n_jobs, 0u);
     std::vector<uint8_t> px((size_t)n_jobs * 3, 0);
+    const SyncOnUnwind drain_px(stream);
     for (int j = 0; j < n_jobs; ++j)
       if (needs_fix[(size_t)j]) {
         const unsigned long long pos = hb[(size_t)j] & ((1ull << 40) - 1ull);
@@ -1309,8 +1286,8 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   F.e1map = (int32_t*)A.alloc((size_t)n_classes * n_px * 4);
   F.ebase.assign((size_t)n_classes + 1, 0);
   for (int ci = 0; ci < n_classes; ++ci) F.ebase[(size_t)ci + 1] = F.pal_off[(size_t)F.job_base[(size_t)ci + 1]];
-  EF_HIP(hipEventCreateWithFlags(&F.ready, hipEventDisableTiming));
-  EF_HIP(hipEventRecord(F.ready, stream));
+  F.ready = make_event();
+  EF_HIP(hipEventRecord(F.ready.get(), stream));
   EF_HIP(hipStreamSynchronize(stream));                  // (the host tables above are staged; pal_off is read by the lanes)
   res->ms[1] = now_ms() - t0;
   t0 = now_ms();
@@ -1318,34 +1295,11 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   // ---- levels 1 and 2: every class a pipeline of its own (nothing of a class's chain depends on the other class; only
   // quantize_image needs both: regions.py:9-70 is called once per class, rhccq.ipynb:1001-1013)
   std::vector<ClassOut> outs((size_t)n_classes);
-  std::vector<Err> errs((size_t)n_classes, Err{0, ""});
-  std::vector<std::thread> th;
-  for (int ci = 0; ci < n_classes; ++ci) {
-    EF_HIP(hipEventCreateWithFlags(&outs[(size_t)ci].done, hipEventDisableTiming));
-    th.emplace_back([&, ci]() {
-      try {
-        class_pipeline(F, ci, *FS.classes[(size_t)ci], outs[(size_t)ci]);
-      } catch (const Err& e) {
-        errs[(size_t)ci] = e;
-        (void)hipStreamSynchronize(FS.classes[(size_t)ci]->stream);
-      } catch (const std::exception& e) {
-        errs[(size_t)ci] = Err{RHCCQ_E_HIP, e.what()};
-        (void)hipStreamSynchronize(FS.classes[(size_t)ci]->stream);
-      }
-    });
-  }
-  for (auto& t : th) t.join();
-  auto cleanup = [&]() {
-    for (auto& o : outs)
-      if (o.done) (void)hipEventDestroy(o.done);
-    if (F.ready) (void)hipEventDestroy(F.ready);
-    if (F.chains_done) (void)hipEventDestroy(F.chains_done);
-  };
-  for (auto& e : errs)
-    if (e.code) {
-      cleanup();
-      throw e;
-    }
+  for (auto& o : outs) o.done = make_event();            // (all of them before the first thread starts)
+  const SyncOnUnwind drain(stream);                      // (F, outs and the host tables above outlive whatever the caller's stream still does)
+  run_lanes(
+      (size_t)n_classes, [&](size_t ci) { class_pipeline(F, (int)ci, *FS.classes[ci], outs[ci]); },
+      [&](size_t ci) { (void)hipStreamSynchronize(FS.classes[ci]->stream.get()); });
   res->ms[2] = now_ms() - t0;
   for (int ci = 0; ci < n_classes && ci < 4; ++ci) std::memcpy(res->class_ms[ci], outs[(size_t)ci].ms, sizeof(outs[(size_t)ci].ms));
   t0 = now_ms();
@@ -1353,25 +1307,19 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   std::vector<std::shared_ptr<Comp>> comps3;
   int q3 = 0;
   for (int ci = 0; ci < n_classes; ++ci) {
-    EF_HIP(hipStreamWaitEvent(stream, outs[(size_t)ci].done, 0));
+    EF_HIP(hipStreamWaitEvent(stream, outs[(size_t)ci].done.get(), 0));
     q3 += outs[(size_t)ci].q2;
     if (outs[(size_t)ci].comp3) comps3.push_back(outs[(size_t)ci].comp3);
   }
   q3 = std::min(q3, 100);
-  if (comps3.empty()) {
-    cleanup();
-    throw Err{RHCCQ_E_ARG, "encode_frame: no components"};
-  }
+  if (comps3.empty()) throw Err{RHCCQ_E_ARG, "encode_frame: no components"};
   auto m3c = merge_comps(comps3, 0, 0, H, W);
   Lane& L3 = *FS.classes[0];
   std::vector<Job> j3(1);
   j3[0].keys = m3c->keys;
   j3[0].P = (int64_t)m3c->keys.size();
   j3[0].quality = q3;
-  if (rhccq_params(j3[0].P, (double)q3, &j3[0].eps, &j3[0].mc)) {
-    cleanup();
-    throw Err{RHCCQ_E_ARG, "rhccq_params failed"};
-  }
+  if (rhccq_params(j3[0].P, (double)q3, &j3[0].eps, &j3[0].mc)) throw Err{RHCCQ_E_ARG, "rhccq_params failed"};
   cluster_jobs(L3, j3);
   L3.sync();
   res->ms[3] = now_ms() - t0;
@@ -1383,6 +1331,7 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   int32_t* d_lut2 = (int32_t*)A.alloc((size_t)std::max<int64_t>(total, 1) * 4);
   int64_t max_index = 0;
   std::vector<std::vector<int32_t>> staged;             // (kept alive until the copies are issued and the stream has taken them)
+  const SyncOnUnwind drain_staged(stream);
   for (auto& c2 : comps3)
     for (auto& kv : c2->maps) {
       const int job = kv.first;
@@ -1414,7 +1363,6 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   EF_RC(ctx, rhccq_frame_remap_entries(ctx, H, W, n_classes, labels.data(), F.job_base.data(), F.e1map, d_lut2, default_index, indices_out, elem));
   EF_HIP(hipStreamSynchronize(stream));
   res->ms[5] = now_ms() - t0;
-  cleanup();
   res->n_colours = (int32_t)fk3.size();
   res->index_bytes = elem;
   res->quality3 = q3;
@@ -1449,7 +1397,9 @@ extern "C" int rhccq_encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H,
   try {
     return encode_frame(ctx, rgb, H, W, classes, n_classes, palette_out, pal_cap, indices_out, n_unique_out, res);
   } catch (const Err& e) {
-    (void)hipDeviceSynchronize();                       // (no lane may still be writing when the caller frees its buffers)
+    // (second line of defence, kept: the lanes and encode_frame drain their own streams while they unwind, but a throw ahead of
+    // encode_frame's first guard leaves kernels on the caller's stream that read rgb and the label maps, which the caller may free now)
+    (void)hipDeviceSynchronize();
     ctx->err = e.msg;
     return e.code;
   } catch (const std::exception& e) {

@@ -358,7 +358,8 @@ def test_fine_grid_4k_frame_through_the_sort_path(rh):
 def test_native_entry_many_jobs_regions_and_errors(rh):
     """rhccq_encode_frame beyond what the fuzz frames reach: more than 64 jobs (the scan sets colour bits with atomics instead of byte flags),
     several regions per class with overlapping boxes, a class without any pixel, and the error paths of the C entry (palette buffer too small ->
-    RHCCQ_E_LIMIT with the needed size, more than 2 048 segments -> RHCCQ_E_LIMIT, a segment naming a region that does not exist -> RHCCQ_E_ARG)."""
+    RHCCQ_E_LIMIT with the needed size, more than 2 048 segments -> RHCCQ_E_LIMIT, a segment naming a region that does not exist -> RHCCQ_E_ARG,
+    a quality of 0 refused inside a class thread -> RHCCQ_E_ARG)."""
     import ctypes as C
     import torch
     from roibasedimagecompression_amd import synth
@@ -418,6 +419,12 @@ def test_native_entry_many_jobs_regions_and_errors(rh):
     descs[0].n_seg = 3000
     rc = rh.lib.rhccq_encode_frame(rh.ctx, rh._p(rgb), H, W, descs, 2, pal.ctypes.data, 1 << 16, rh._p(out), None, C.byref(res))
     assert rc == -3 and b"2048" in rh._raw.rhccq_last_error(rh.ctx)
+    # a quality of 0 is refused by rhccq_params INSIDE a class thread, after the frame's and the classes' events exist: the error comes back
+    # as a return value through the joined threads
+    descs[0].n_seg = specs2[0].n_seg
+    descs[1].quality = 0
+    rc = rh.lib.rhccq_encode_frame(rh.ctx, rh._p(rgb), H, W, descs, 2, pal.ctypes.data, 1 << 16, rh._p(out), None, C.byref(res))
+    assert rc == -1 and b"rhccq_params" in rh._raw.rhccq_last_error(rh.ctx)         # RHCCQ_E_ARG
     # ... and the context still works afterwards
     assert same_result(ref, enc.encode_native(rgb, specs2))
 
