@@ -405,6 +405,25 @@ int64_t rhccq_ssim7_blocks(int32_t H, int32_t W);
 int rhccq_ssim7_sums(rhccq_ctx* ctx, const uint8_t* a, const uint8_t* b, int32_t H, int32_t W, double* partial,
                      int64_t n_blocks);
 
+/* ---- per-class quality metrics (EXTENSION: no reference counterpart; csrc/region_metrics.hip) -----------------------------
+ * The sums above kept apart by a class map: cls (device, uint8 per pixel, any alignment) names the row a pixel goes to; a
+ * value >= n_classes (255, say) leaves the pixel out of every row.  n_classes: 1..16, else RHCCQ_E_ARG.
+ * sums (device, uint64[n_classes][6]): row c = {sum of squared differences R, G, B, sum of |differences|, max |difference|,
+ * pixels} over the pixels of class c; a and b as for the whole-picture entry above.  The _indexed form compares a with
+ * palette[idx] without writing that image out: idx (1, 2 or 4 bytes per element, unsigned) and palette as for the decode
+ * entry (an index past the palette reads entry 0). */
+int rhccq_class_error_sums(rhccq_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* cls, int64_t n_pixels,
+                           int32_t n_classes, uint64_t* sums);
+int rhccq_class_error_sums_indexed(rhccq_ctx* ctx, const uint8_t* a, const void* idx, int32_t idx_elem_bytes,
+                                   const uint8_t* palette, int64_t pal_n, const uint8_t* cls, int64_t n_pixels,
+                                   int32_t n_classes, uint64_t* sums);
+/* SSIM per class: a window belongs to the class of its centre pixel.  partial (device, double[n_blocks][n_classes][4]) receives
+ * per workgroup tile and class the sum of S for R, G, B and the number of window centres; the host adds the tiles in order.
+ * The window statistics are the exact integer sums of the whole-picture entry. */
+int64_t rhccq_class_ssim7_blocks(int32_t H, int32_t W);
+int rhccq_class_ssim7_sums(rhccq_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* cls, int32_t H, int32_t W,
+                           int32_t n_classes, double* partial, int64_t n_blocks);
+
 /* ---- split score of a region (encoder/subregions/split_score.py:15-142 calculate_split_score) ------------
  * One pass over the region image (uint8 RGB interleaved, device) and its mask (uint8, 0 / non-0, may be NULL: then
  * gray > 0.01 as the reference does): gray + CIE-Lab per pixel (scikit-image's rgb2gray / rgb2lab, float64), Sobel magnitude

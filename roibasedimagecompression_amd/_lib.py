@@ -91,6 +91,10 @@ PROTOTYPES = {
     "rhccq_error_tables": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rhccq_ssim7_blocks": (c_int64, [c_int32, c_int32]),
     "rhccq_ssim7_sums": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64]),
+    "rhccq_class_error_sums": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "rhccq_class_error_sums_indexed": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    "rhccq_class_ssim7_blocks": (c_int64, [c_int32, c_int32]),
+    "rhccq_class_ssim7_sums": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64]),
     "rhccq_split_stats_blocks": (c_int64, [c_int32, c_int32]),
     "rhccq_split_stats": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_slic_assign": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_int32, c_void_p]),

@@ -59,6 +59,85 @@ def metrics_from_device(rh, a, b):
     return m
 
 
+# ---- EXTENSION (no reference counterpart; not re-exported by the mirrored decoder/uncompression/comparison.py): the same metrics
+# per class of a class map, e.g. inside and outside the ROI -------------------------------------------------------------------------
+def _metrics_row(row, ssim_sum, ssim_count):
+    """one entry of the per-class dict from an integer row {sum d^2 R, G, B, sum |d|, max |d|, pixels} and the sums of S per
+    channel over `ssim_count` window centres: metrics_from_device's arithmetic and scalar types"""
+    n_ch = int(row[5])
+    if n_ch == 0:
+        return None
+    sq = int(row[0]) + int(row[1]) + int(row[2])
+    mse64 = sq / (3.0 * n_ch)
+    m = {}
+    with np.errstate(divide="ignore"):
+        m["psnr"] = np.float64(10.0) * np.log10(np.float64(255.0 ** 2) / np.float64(mse64))
+    m["ssim"] = np.float64((np.asarray(ssim_sum, np.float64) / float(ssim_count)).mean()) if ssim_count else None
+    m["mse"] = np.float32(mse64)
+    m["rmse"] = np.sqrt(m["mse"])
+    m["mae"] = np.float32(int(row[3]) / (3.0 * n_ch))
+    m["max_error"] = np.float32(int(row[4]))
+    for i, ch in enumerate("rgb"):
+        m[f"mse_{ch}"] = np.float32(int(row[i]) / float(n_ch))
+    m["pixel_count"] = n_ch
+    return m
+
+
+def region_metrics_from_sums(sums, ssim_sums, names):
+    """Pure host arithmetic.  sums: integer [len(names), 6] rows of Rhccq.class_error_sums; ssim_sums: Rhccq.class_ssim7's (float64
+    [len(names), 3], int [len(names)]) or None when no 7x7 window fits the image -> {name: metrics, ..., "all": metrics}.  An entry
+    has calculate_quality_metrics' keys, scalar types and arithmetic plus `pixel_count`; a class without pixels is None, a class (or
+    image) without a window centre has ssim None.  "all" comes from the column sums of the rows (max |d| folded with max)."""
+    sums = np.asarray(sums).astype(np.int64).reshape(-1, 6)
+    names = list(names)
+    if len(names) != len(sums) or "all" in names or len(set(names)) != len(names):
+        raise ValueError("region_metrics_from_sums: one distinct name per row of sums is expected, none of them 'all'")
+    if ssim_sums is None:
+        s_sum, s_cnt = np.zeros((len(names), 3)), np.zeros(len(names), np.int64)
+    else:
+        s_sum, s_cnt = np.asarray(ssim_sums[0], np.float64).reshape(-1, 3), np.asarray(ssim_sums[1]).astype(np.int64).reshape(-1)
+        if len(s_sum) != len(names) or len(s_cnt) != len(names):
+            raise ValueError("region_metrics_from_sums: ssim_sums must have one row per name")
+    out = {name: _metrics_row(sums[k], s_sum[k], int(s_cnt[k])) for k, name in enumerate(names)}
+    total = [int(v) for v in sums.sum(axis=0)]
+    total[4] = int(sums[:, 4].max())
+    out["all"] = _metrics_row(total, s_sum.sum(axis=0), int(s_cnt.sum()))
+    return out
+
+
+def region_metrics_from_device(rh, a, b, cls, names=("nonroi", "roi")):
+    """a, b: uint8[H,W,3] device tensors, cls: uint8 / bool [H,W] device tensor with class k = names[k] (a value >= len(names)
+    keeps the pixel out of every class).  Two device passes; only the len(names) x 6 sums and the SSIM partials come back."""
+    n = len(names)
+    return region_metrics_from_sums(rh.class_error_sums(a, b, cls, n), rh.class_ssim7(a, b, cls, n), names)
+
+
+def _class_map_u8(class_map, shape):
+    class_map = np.asarray(class_map)
+    if class_map.dtype == np.bool_:
+        class_map = class_map.view(np.uint8)
+    if class_map.dtype != np.uint8:
+        raise TypeError("class map: bool or uint8 expected")
+    if class_map.ndim != 2 or tuple(class_map.shape) != tuple(shape):
+        raise ValueError("class map: an H x W array of the image's height and width is expected")
+    return np.ascontiguousarray(class_map)
+
+
+def calculate_region_quality_metrics(original, reconstructed, class_map, names=("nonroi", "roi")):
+    """calculate_quality_metrics per class: numpy uint8 RGB images and a bool / uint8 [H,W] class map in, the dict of
+    region_metrics_from_sums out.  With the 0 / 1 region map of the ROI stage: quality outside and inside the ROI."""
+    rh = _rh()
+    original = np.ascontiguousarray(original)
+    reconstructed = np.ascontiguousarray(reconstructed)
+    if original.shape != reconstructed.shape or original.ndim != 3 or original.shape[2] != 3:
+        raise ValueError("Input images must have the same dimensions.")
+    if original.dtype != np.uint8 or reconstructed.dtype != np.uint8:
+        raise TypeError("calculate_region_quality_metrics: uint8 RGB images expected")
+    class_map = _class_map_u8(class_map, original.shape[:2])
+    a, b = torch.from_numpy(original).to(rh.device), torch.from_numpy(reconstructed).to(rh.device)
+    return region_metrics_from_device(rh, a, b, torch.from_numpy(class_map).to(rh.device), names)
+
+
 def calculate_adaptive_quality_metrics(original, reconstructed):
     """comparison.py:345-536: quality metrics with adaptive outlier exclusion, same keys and nesting as the reference.
 

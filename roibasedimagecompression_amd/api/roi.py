@@ -1,6 +1,7 @@
 """Region extraction of the ROI stage on the MI355X (reference encoder/ROI/roi.py):
 
   extract_roi_nonroi               roi.py:685-718   region map -> ROI / non-ROI masks with the 3-px buffer zone (csrc/ccl.hip roi_buffer_kernel)
+  regions_from_mask                EXTENSION        get_regions' tuple from a caller's ROI mask instead of the detector
   extract_connected_regions_fast   roi.py:285-360   cv2.connectedComponentsWithStats(connectivity=8) -> region dicts
   extract_connected_regions        roi.py:262-283   skimage.measure.label + regionprops -> region dicts
   extract_regions                  roi.py:45-103    both masks -> region lists, small ROI regions moved to the non-ROI list
@@ -180,3 +181,37 @@ def extract_roi_nonroi(original_image, region_map, buffer_size=3, rh=None, rgb_d
         rgb_dev = torch.from_numpy(np.array(original_image, dtype=np.uint8, order="C")).to(rh.device)
     ri, ni, m1, m0 = rh.roi_buffer(region_dev, rgb_dev, buffer_size)
     return tuple(rh.to_host(ri, ni, m1, m0))
+
+
+def region_map_from_mask(image_rgb, roi_mask, rh=None):
+    """a caller's ROI mask (bool or uint8 [H,W], numpy array or device tensor; non-zero = ROI) checked against the image ->
+    the 0 / 1 uint8 region map on the device.  ValueError for another rank or shape, before anything is launched."""
+    import torch
+    shape = tuple(np.shape(image_rgb))
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError("regions_from_mask: an H x W x 3 image is expected")
+    if not torch.is_tensor(roi_mask):
+        roi_mask = np.asarray(roi_mask)
+    if roi_mask.ndim != 2 or tuple(roi_mask.shape) != shape[:2]:
+        raise ValueError(f"regions_from_mask: the ROI mask must be [H, W] = {list(shape[:2])}, got {list(roi_mask.shape)}")
+    if torch.is_tensor(roi_mask):
+        if roi_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("regions_from_mask: a bool or uint8 ROI mask is expected")
+        rh = rh or default_context()
+        return (roi_mask.to(rh.device) != 0).to(torch.uint8).contiguous()
+    if roi_mask.dtype not in (np.bool_, np.uint8):
+        raise TypeError("regions_from_mask: a bool or uint8 ROI mask is expected")
+    rh = rh or default_context()
+    return torch.from_numpy(np.ascontiguousarray(roi_mask != 0).view(np.uint8)).to(rh.device)
+
+
+def regions_from_mask(image_rgb, roi_mask, buffer_size=3):
+    """EXTENSION: get_regions (roi.py:14-40) with the region map given by the caller instead of found by the edge detector ->
+    (unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask) as get_regions returns them: region_map = (roi_mask != 0)
+    as 0 / 1 uint8, unified all zeros (no edge map), the rest extract_roi_nonroi(image, region_map, buffer_size) -- the buffer zone
+    belongs to both classes, as in the reference."""
+    rh = default_context()
+    region_dev = region_map_from_mask(image_rgb, roi_mask, rh)
+    region_map = rh.to_host(region_dev)
+    roi_image, non_image, roi_m, non_m = extract_roi_nonroi(image_rgb, region_map, buffer_size, rh=rh, region_dev=region_dev)
+    return np.zeros(region_map.shape, np.uint8), region_map, roi_image, non_image, roi_m, non_m

@@ -6,6 +6,7 @@
   bridge_small_gaps_fast                                                     small_gaps.py:221-319
   detect_meaningful_borders, protect_border_regions, fill_closed_regions     roi.py:784-918
   directional_region_unification, process_and_unify_borders, get_regions     roi.py:14-40,527-607,720-782
+  regions_from_mask_resident                                                 EXTENSION (api/roi.py regions_from_mask)
 
 PARITY UNPINNED (OpenCV is absent from the build container): connected components with statistics, rectangular / elliptical
 morphology, the one-directional filter2D kernels, the 3x3 chamfer distance transform and the box densities are restated from
@@ -365,6 +366,18 @@ def get_regions_resident(image_rgb, rh=None):
     d = _Dev(rh)
     borders, rgb_dev = _borders_resident(d, image_rgb)
     return _unify_borders_dev(d, borders, image_rgb, rgb_dev=rgb_dev) + (rgb_dev,)
+
+
+def regions_from_mask_resident(image_rgb, roi_mask, rh=None, buffer_size=3):
+    """api.roi.regions_from_mask with every result left on the device: what get_regions_resident returns, from a caller's ROI mask
+    (bool / uint8 [H,W], numpy or device tensor; ValueError for another rank or shape before anything is launched)"""
+    import torch
+    rh = rh or default_context()
+    image_rgb = np.asarray(image_rgb)
+    region_dev = _roi.region_map_from_mask(image_rgb, roi_mask, rh)
+    rgb_dev = torch.from_numpy(np.array(image_rgb, dtype=np.uint8, order="C")).to(rh.device)
+    ri, ni, m1, m0 = rh.roi_buffer(region_dev, rgb_dev, buffer_size)
+    return torch.zeros_like(region_dev), region_dev, ri, ni, m1, m0, rgb_dev
 
 
 def _borders_resident(d, image_rgb):

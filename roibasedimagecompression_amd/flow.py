@@ -5,10 +5,12 @@ restatements of OpenCV / scikit-image."""
 import time
 
 
-def script_flow(image_rgb, roi_quality=20, nonroi_quality=10, out_path=None, container=True):
+def script_flow(image_rgb, roi_quality=20, nonroi_quality=10, out_path=None, container=True, roi_mask=None):
     """encoder/compression/test.py:77-151 (the script twin of the notebook: the flow that wrote images/rhccq_20_10/*.rhccq) with the
     reference's import lines.  (The notebook's own cell 6 inlines the ROI chain and, through a uint8 overflow in
-    `(connected * 255).astype(np.uint8)`, feeds 0 / 1 / 255 images to the later steps; the script calls get_regions.)"""
+    `(connected * 255).astype(np.uint8)`, feeds 0 / 1 / 255 images to the later steps; the script calls get_regions.)
+    roi_mask (extension): a bool / uint8 [H,W] mask, numpy or device tensor, takes the place of get_regions' detector
+    (api.roi.regions_from_mask); everything after the region maps is the same flow."""
     from encoder.ROI.roi import get_regions, extract_regions
     from encoder.compression.subregions import subregion_quantization
     from encoder.compression.regions import region_quantization
@@ -16,7 +18,13 @@ def script_flow(image_rgb, roi_quality=20, nonroi_quality=10, out_path=None, con
     from encoder.compression.compression import lossless_compress_optimized, save_compressed
     t = {}
     t0 = time.perf_counter()
-    unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask = get_regions(image_rgb)
+    if roi_mask is None:
+        unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask = get_regions(image_rgb)
+        source = {}
+    else:
+        from roibasedimagecompression_amd.api.roi import regions_from_mask
+        unified, region_map, roi_image, nonroi_image, roi_mask, nonroi_mask = regions_from_mask(image_rgb, roi_mask)
+        source = {"roi_source": "caller"}
     roi_regions, nonroi_regions = extract_regions(image_rgb, roi_mask, nonroi_mask)
     t["roi_stage"] = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -49,4 +57,4 @@ def script_flow(image_rgb, roi_quality=20, nonroi_quality=10, out_path=None, con
     return final, pkg, {"region_map_roi_fraction": float(region_map.mean()), "roi_regions": len(roi_regions), "nonroi_regions": len(nonroi_regions),
                         "roi_segments": seg_roi.get("segments", 0), "nonroi_segments": seg_non.get("segments", 0),
                         "segments_dropped": seg_roi.get("segments_dropped", 0) + seg_non.get("segments_dropped", 0),
-                        "edge_fraction": float((unified > 0).mean()), "seconds": {k: round(v, 3) for k, v in t.items()}}
+                        "edge_fraction": float((unified > 0).mean()), "seconds": {k: round(v, 3) for k, v in t.items()}, **source}

@@ -116,13 +116,21 @@ def _pack_bits(mask_u8):
 class ImageEncoder:
     def __init__(self, rh=None):
         self.rh = rh or default_context()
+        self.region_map = None         # device uint8[H,W] 0 / 1 region map of the last regions() call
 
     # ---- stage 1 ---------------------------------------------------------------------------------------------------------------
-    def regions(self, image):
+    def regions(self, image, roi_mask=None):
         """get_regions + extract_regions on the device -> (regions [Region] in the order of the ROI list then the non-ROI list,
-        label maps (ROI, non-ROI) device int32[H,W], uploaded RGB, stats)"""
+        label maps (ROI, non-ROI) device int32[H,W], uploaded RGB, stats).  roi_mask: a caller's bool / uint8 [H,W] mask (numpy or
+        device tensor) instead of the detector.  The 0 / 1 device region map of the call stays in self.region_map."""
         rh = self.rh
-        unified, region_map, _, _, roi_mask, non_mask, rgb = roi_chain.get_regions_resident(image, rh)
+        if roi_mask is None:
+            unified, region_map, _, _, roi_mask, non_mask, rgb = roi_chain.get_regions_resident(image, rh)
+            source = {}
+        else:
+            unified, region_map, _, _, roi_mask, non_mask, rgb = roi_chain.regions_from_mask_resident(image, roi_mask, rh)
+            source = {"roi_source": "caller"}
+        self.region_map = region_map
         frac = rh.to_host(torch.stack([region_map.sum(dtype=torch.int64), (unified != 0).sum(dtype=torch.int64)]))
         n1, lab1, st1 = rh.ccl(roi_mask, 8)
         n0, lab0, st0 = rh.ccl(non_mask, 8)
@@ -142,7 +150,7 @@ class ImageEncoder:
         roi = [r for r in roi if r.area >= mn]
         hw = image.shape[0] * image.shape[1]
         stats = {"region_map_roi_fraction": float(frac[0]) / hw, "edge_fraction": float(frac[1]) / hw,
-                 "roi_regions": len(roi), "nonroi_regions": len(non)}
+                 "roi_regions": len(roi), "nonroi_regions": len(non), **source}
         return roi + non, (lab1, lab0), rgb, stats
 
     # ---- stage 2 ---------------------------------------------------------------------------------------------------------------
@@ -374,12 +382,32 @@ class ImageEncoder:
         classes = [(call, ClassSpec(d_layers[k], l["seg_region"], l["bboxes"], qualities[call])) for k, (call, l) in enumerate(specs)]
         return classes, place, stats
 
+    # ---- report ----------------------------------------------------------------------------------------------------------------
+    def quality(self, rgb, res, region_map, names=("nonroi", "roi")):
+        """per-class quality of a result against the uploaded image: the error sums straight from palette[indices] (the decoded
+        picture is never written for them), a device-side decode for the SSIM windows; only the len(names) x 6 sums and the SSIM
+        partials come back.  A result smaller than the image (top_left / shape) is compared on its own rectangle."""
+        from .api.comparison import region_metrics_from_sums
+        rh = self.rh
+        (top, left), (h, w) = res["top_left"], res["shape"]
+        if (top, left, h, w) != (0, 0, int(rgb.shape[0]), int(rgb.shape[1])):
+            rgb = rgb[top:top + h, left:left + w].contiguous()
+            region_map = region_map[top:top + h, left:left + w].contiguous()
+        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+        idx = res["indices"].reshape(-1)
+        sums = rh.class_error_sums_indexed(rgb, idx, pal, region_map, len(names))
+        recon = rh.decode(idx, pal).reshape(h, w, 3)
+        return region_metrics_from_sums(sums, rh.class_ssim7(rgb, recon, region_map, len(names)), names)
+
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
-    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False):
+    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
-        container.write_frame(exact=exact)."""
+        container.write_frame(exact=exact).
+        roi_mask: a caller's ROI mask (bool / uint8 [H,W], numpy or device tensor) instead of the detector: stats["roi_source"] =
+        "caller".  report: stats["quality"] = PSNR / SSIM / ... of the result inside ("roi"), outside ("nonroi") the region map and
+        over the picture ("all") (api.comparison.region_metrics_from_sums), computed on the device from the indices."""
         rh = self.rh
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -394,7 +422,8 @@ class ImageEncoder:
             now = time.perf_counter()
             t[name] = now - t0
             t0 = now
-        regions, maps, rgb, stats = self.regions(image)
+        regions, maps, rgb, stats = self.regions(image, roi_mask)
+        region_map = self.region_map
         lap("regions")
         n_seg = self.split_segments(rgb, maps, regions)
         lap("split_score")
@@ -424,6 +453,9 @@ class ImageEncoder:
             from . import container
             container.write_frame(res, out_path, rh, exact=exact)
             lap("container")
+        if report:
+            stats["quality"] = self.quality(rgb, res, region_map)
+            lap("report")
         stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
         res["classes"] = classes
         res["stats"] = stats

@@ -934,6 +934,52 @@ class Rhccq:
         self._check(self.lib.rhccq_ssim7_sums(self.ctx, self._p(a), self._p(b), H, W, self._p(part), nb), "ssim7")
         return part.cpu().numpy().sum(axis=0) / float((H - 6) * (W - 6))
 
+    # -- per-class quality metrics (EXTENSION: csrc/region_metrics.hip) ------------------------------------
+    def _class_map(self, cls, shape):
+        if cls.dtype == torch.bool:
+            cls = cls.view(torch.uint8)
+        assert cls.dtype == torch.uint8 and cls.is_contiguous() and tuple(cls.shape) == tuple(shape), "class map: uint8 / bool [H,W]"
+        return cls
+
+    def class_error_sums(self, a, b, cls, n_classes):
+        """a, b: uint8[H,W,3] device, cls: uint8 / bool [H,W] device -> int64[n_classes, 6]: per class the sums of squared differences of
+        R, G, B, the sum of |d|, max |d| and the pixel count; pixels with cls >= n_classes are in no row."""
+        assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
+        cls = self._class_map(cls, a.shape[:2])
+        sums = self.empty((max(int(n_classes), 1), 6), torch.int64)
+        self._check(self.lib.rhccq_class_error_sums(self.ctx, self._p(a), self._p(b), self._p(cls), a.numel() // 3, int(n_classes),
+                                                    self._p(sums)), "class_error_sums")
+        return sums.cpu().numpy()
+
+    def class_error_sums_indexed(self, a, idx, palette, cls, n_classes):
+        """class_error_sums(a, palette[idx], cls, n_classes) without the image palette[idx]: idx uint8 / uint16 (int16 storage) / int32
+        device with one element per pixel, palette uint8[K,3] device (Rhccq.decode's arguments)"""
+        assert a.dtype == torch.uint8 and a.is_contiguous() and a.shape[-1] == 3 and idx.is_contiguous() and idx.numel() == a.numel() // 3
+        assert palette.dtype == torch.uint8 and palette.is_contiguous() and palette.shape[-1] == 3
+        cls = self._class_map(cls, a.shape[:2])
+        sums = self.empty((max(int(n_classes), 1), 6), torch.int64)
+        self._check(self.lib.rhccq_class_error_sums_indexed(self.ctx, self._p(a), self._p(idx), idx.element_size(), self._p(palette),
+                                                            palette.shape[0], self._p(cls), a.numel() // 3, int(n_classes), self._p(sums)),
+                    "class_error_sums_indexed")
+        return sums.cpu().numpy()
+
+    def class_ssim7(self, a, b, cls, n_classes):
+        """SSIM (Rhccq.ssim7's definition) by the class of the window's centre pixel -> (float64[n_classes, 3] sums of S per channel,
+        int64[n_classes] window centres); an image no 7x7 window fits gives zero centres."""
+        assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
+        cls = self._class_map(cls, a.shape[:2])
+        if not 1 <= int(n_classes) <= 16:
+            raise RhccqError("class_ssim7: n_classes must be 1..16")
+        H, W = int(a.shape[0]), int(a.shape[1])
+        nb = int(self.lib.rhccq_class_ssim7_blocks(H, W))
+        if nb == 0:
+            return np.zeros((n_classes, 3)), np.zeros(n_classes, np.int64)
+        part = self.empty((nb, int(n_classes), 4), torch.float64)
+        self._check(self.lib.rhccq_class_ssim7_sums(self.ctx, self._p(a), self._p(b), self._p(cls), H, W, int(n_classes), self._p(part), nb),
+                    "class_ssim7")
+        tot = part.cpu().numpy().sum(axis=0)                           # tiles in order, as ssim7 adds them
+        return tot[:, :3], np.rint(tot[:, 3]).astype(np.int64)
+
     # -- split score (split_score.py:15-142) ----------------------------------------------------------
     def split_stats(self, rgb, mask=None):
         """rgb uint8[H,W,3] device, mask uint8[H,W] device or None -> (sums float64[12], lbp_hist int64[10], gray_hist int64[32])"""
