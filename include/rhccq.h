@@ -680,6 +680,25 @@ int rhccq_image_paint(rhccq_ctx* ctx, const int32_t* labels0, const int32_t* lab
                       const int32_t* small, const int32_t* yx, const int32_t* ids, const int32_t* block_item, const int32_t* block_first,
                       int64_t n_blocks, int32_t* layers);
 
+/* ---- EXTENSION: nearest-colour remap onto a given palette (no reference counterpart; csrc/palette_remap.hip) ----------------------
+ * idx_out[p] = argmin over j of the squared distance (dr^2 + dg^2 + db^2, uint8 channels, exact integers) between rgb[p] and
+ * palette[j]; ties go to the lowest j; duplicate rows and a black row are ordinary entries.  rgb (n_pixels x 3) and palette (K x 3)
+ * are interleaved uint8 of any alignment; idx_out has idx_elem_bytes (1, 2 or 4) per element, unsigned, aligned to its element.
+ * sums (uint64[n_classes + 1][2], zeroed by the call): row c = {pixels, sum of the minimal distances} over the pixels with
+ * cls[p] == c; a class value >= n_classes leaves the pixel out of every class row (the rule of the per-class error sums above);
+ * the last row counts every pixel.  cls == NULL: n_classes must be 0 and only that last row is written.
+ * RHCCQ_E_ARG: a null rgb, palette, idx_out or sums; K < 1; n_pixels < 0; n_classes outside 0..16 (or not 0 with cls == NULL);
+ * idx_elem_bytes not 1, 2 or 4; K > 256 with 1-byte indices; a misaligned idx_out or sums.  RHCCQ_E_LIMIT: K > 65536 (the bound of
+ * the reference's uint16 mapping array).  n_pixels == 0 succeeds with zero sums.
+ * Device form: every pointer is device memory; async on the context stream; a grid-stride launch sized to the device; nothing is
+ * allocated.  Host form: the same pack / evaluate / carry functions run serially on host memory (tests; no GPU needed). */
+int rhccq_palette_remap(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K,
+                        const uint8_t* cls, int32_t n_classes, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_remap_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                             int32_t n_classes, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+/* host only: the palette entries the kernel stages at a time; the winner is carried from one such tile to the next */
+int32_t rhccq_palette_remap_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

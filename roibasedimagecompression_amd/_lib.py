@@ -169,6 +169,9 @@ PROTOTYPES = {
                                       c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_image_paint": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int64, c_void_p]),
+    "rhccq_palette_remap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_remap_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_remap_tile": (c_int32, []),
 }
 
 

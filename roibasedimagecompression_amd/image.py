@@ -26,7 +26,7 @@ from .api.roi import min_region_size
 from .api.slic import _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
 from .api.split_score import normalize_result, scores_from_stats
 from .frame import ClassSpec, FrameEncoder
-from .ops import default_context
+from .ops import default_context, psnr_from_sse
 from .palette import cluster_palettes
 
 __all__ = ["ImageEncoder", "Region"]
@@ -460,3 +460,107 @@ class ImageEncoder:
         res["classes"] = classes
         res["stats"] = stats
         return res
+
+    # ---- a given palette (EXTENSION, no reference counterpart) ------------------------------------------------------------------
+    @staticmethod
+    def _remap_row(pixels, sse):
+        pixels, sse = int(pixels), int(sse)
+        return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
+                "psnr": psnr_from_sse(sse, pixels) if pixels else None}
+
+    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False):
+        """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
+        earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
+        shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
+        lowest row), plus `stats`.  One pass over the pixels: no region, SLIC or clustering stage runs.
+        stats["remap"]["all"] = {pixels, sse, mse, psnr} of the result against the image (the kernel's by-product); with roi_mask
+        (as encode takes it) also "roi" and "nonroi", inside and outside the mask.  report: stats["quality"] as encode fills it
+        (regions() for the region map, then quality()).  out_path: container.write_frame(exact=exact)."""
+        rh = self.rh
+        if isinstance(palette, dict):
+            palette = palette["palette"]
+        pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
+        if pal.dtype != torch.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
+            raise ValueError("ImageEncoder.encode_with_palette: a uint8 K x 3 palette, K >= 1, is expected")
+        pal = pal.contiguous()
+        rgb = image.to(rh.device).contiguous() if torch.is_tensor(image) else rh.dev(np.asarray(image))
+        if rgb.dtype != torch.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("ImageEncoder.encode_with_palette: a uint8 H x W x 3 image is expected")
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        t, t0 = {}, time.perf_counter()
+
+        def lap(name):
+            nonlocal t0
+            now = time.perf_counter()
+            t[name] = now - t0
+            t0 = now
+        cls = None
+        if roi_mask is not None:
+            from .api.roi import region_map_from_mask
+            cls = region_map_from_mask(rgb, roi_mask, rh)                     # 0 / 1: quality()'s rows
+            lap("mask")
+        idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
+        sums = rh.to_host(sums)
+        lap("remap")
+        remap = {"all": self._remap_row(*sums[-1])}
+        if cls is not None:
+            remap["nonroi"], remap["roi"] = self._remap_row(*sums[0]), self._remap_row(*sums[1])
+        res = {"palette": rh.to_host(pal), "indices": idx, "indices_dtype": "uint8" if idx.dtype == torch.uint8 else "uint16",
+               "shape": (H, W), "top_left": (0, 0)}
+        stats = {"remap": remap}
+        if out_path:
+            from . import container
+            container.write_frame(res, out_path, rh, exact=exact)
+            lap("container")
+        if report:
+            host = image.cpu().numpy() if torch.is_tensor(image) else np.ascontiguousarray(image, dtype=np.uint8)
+            _, _, rgb_r, rstats = self.regions(host, roi_mask)
+            stats.update(rstats)
+            stats["quality"] = self.quality(rgb_r, res, self.region_map)
+            lap("report")
+        stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
+        res["stats"] = stats
+        return res
+
+    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False):
+        """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
+        every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
+        and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
+        the key.  Both PSNRs are ops.psnr_from_sse over the same pixels: the key frame's sum comes from
+        Rhccq.class_error_sums_indexed over the rectangle its result covers (top_left / shape), the remap's from the kernel's
+        sums, over the whole picture when the key covers it and else over that rectangle (the remap then runs with the rectangle
+        as its roi_mask, and its stats["remap"] has the "roi" / "nonroi" rows too).  A frame of another size than its key's is
+        compared over the whole picture.  Every result has stats["key_frame"] (bool), stats["key_index"] (the frame whose
+        palette it uses) and stats["psnr"]; a remap also stats["key_psnr"].  out_paths: one file per frame (entries may be None)."""
+        rh = self.rh
+        key_pal = key_psnr = key_window = key_frame_shape = None
+        key_index = -1
+        for n, image in enumerate(images):
+            path = out_paths[n] if out_paths is not None else None
+            if key_pal is not None:
+                window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
+                res = self.encode_with_palette(image, key_pal, roi_mask=window)
+                row = res["stats"]["remap"]["all" if window is None else "roi"]
+                if row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db:
+                    if path:
+                        from . import container
+                        container.write_frame(res, path, rh, exact=exact)
+                    res["stats"].update(key_frame=False, key_index=key_index, psnr=row["psnr"], key_psnr=key_psnr)
+                    yield res
+                    continue
+            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact)
+            (top, left), (h, w) = res["top_left"], res["shape"]
+            rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
+            key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))
+            key_window = None
+            if (int(top), int(left), int(h), int(w)) != (0, 0) + key_frame_shape:
+                key_window = torch.zeros(key_frame_shape, dtype=torch.uint8, device=rh.device)
+                key_window[top:top + h, left:left + w] = 1
+            rgb = rgb[top:top + h, left:left + w].contiguous()
+            every = torch.zeros((h, w), dtype=torch.uint8, device=rh.device)      # one class: the whole rectangle
+            key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+            row = rh.class_error_sums_indexed(rgb, res["indices"].reshape(-1), key_pal, every, 1)[0]
+            key_index = n
+            key_psnr = psnr_from_sse(int(row[0]) + int(row[1]) + int(row[2]), int(row[5]))
+            res["stats"].update(key_frame=True, key_index=n, psnr=key_psnr)
+            yield res

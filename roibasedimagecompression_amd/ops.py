@@ -105,6 +105,19 @@ def clustering_params(n_colors, quality):
     return eps.value, 1, mc.value
 
 
+def palette_remap_tile():
+    """the palette entries Rhccq.palette_remap's kernel stages at a time (the winner is carried from tile to tile)"""
+    return int(_lib.load().rhccq_palette_remap_tile())
+
+
+def psnr_from_sse(sse, n_pixels):
+    """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
+    10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
+    if sse == 0:
+        return float("inf")
+    return 10.0 * math.log10(255.0 ** 2 / (float(sse) / (3.0 * float(n_pixels))))
+
+
 def eps_threshold(eps):
     lib = _lib.load()
     thr, bnd, r2 = C.c_int32(), C.c_int32(), C.c_double()
@@ -979,6 +992,41 @@ class Rhccq:
                     "class_ssim7")
         tot = part.cpu().numpy().sum(axis=0)                           # tiles in order, as ssim7 adds them
         return tot[:, :3], np.rint(tot[:, 3]).astype(np.int64)
+
+    # -- nearest-colour remap onto a given palette (EXTENSION: csrc/palette_remap.hip) --------------------------
+    def palette_remap(self, rgb, palette, class_map=None, n_classes=0):
+        """rgb uint8[..., 3], palette uint8[K, 3] (numpy or device), class_map uint8 / bool, one element per pixel, or None ->
+        (indices device tensor of rgb's leading shape: uint8 when K <= 256, else int16 holding uint16; sums device int64
+        [n_classes + 1, 2]: row c = {pixels, sum of squared errors} of class c, the last row over every pixel).  Each index is the
+        nearest palette row in exact integers, ties to the lowest row."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_remap: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
+        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError("palette_remap: rgb [..., 3] and palette [K, 3] are expected")
+        n, K = rgb.numel() // 3, int(palette.shape[0])
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != n:
+                raise ValueError("palette_remap: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_remap: n_classes without a class map")
+        idx = self.empty(tuple(rgb.shape[:-1]), torch.uint8 if K <= 256 else torch.int16)
+        sums = self.empty((int(n_classes) + 1, 2), torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            if not 0 <= int(n_classes) <= 16 or K < 1 or K > 65536:
+                raise RhccqError("palette_remap: K must be 1..65536 and n_classes 0..16")
+            return idx, sums.zero_()
+        self._check(self.lib.rhccq_palette_remap(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), int(n_classes), self._p(idx),
+                                                 idx.element_size(), self._p(sums)), "palette_remap")
+        return idx, sums
 
     # -- split score (split_score.py:15-142) ----------------------------------------------------------
     def split_stats(self, rgb, mask=None):
