@@ -84,6 +84,13 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              one after the other, so a chain of one class could hold up the other class for its whole
  *                              length.  Every step after the chains needs them all, so one launch loses nothing. */
 #define RHCCQ_OPT_FRAME_CHAINS 8
+/*   RHCCQ_OPT_FRAME_LEVEL2     rhccq_encode_frame: 1 (default) = the class threads end with their merged component and the level-2
+ *                              palettes of all classes are clustered in ONE call on one lane, with no other stream of the
+ *                              frame at work: their MiniBatchKMeans problems are drawn, ordered, initialised, stepped
+ *                              (rhccq_mbk_steps_batch) and assigned as one batch; 0 = every class clusters its level-2 palette on
+ *                              its own lane.  Same results.  Why: two host threads and two streams that queue ~700 launches each
+ *                              on the same few hardware queues ran their steps at twice the period of either alone. */
+#define RHCCQ_OPT_FRAME_LEVEL2 9
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -318,6 +325,18 @@ int rhccq_mbk_steps_overlapped(rhccq_ctx* ctx, const uint32_t* keys, const rhccq
                                int32_t n_prob, int64_t step0, int32_t n_steps, const uint32_t* words, int64_t n_words,
                                double* centres, double* weights, double* state, void* work, int64_t work_bytes,
                                int32_t estep_split, int64_t since0, int32_t* carry);
+/* The same for a batch of 1 .. 32 problems that share the step index, each on the schedule its state asks for: bit p of
+ * fast_mask = problem p takes the overlapped schedule above (no zero-weight centre left, k >= 1024), bit p of classic_mask =
+ * it takes the classic sequence of rhccq_mbk_steps (tiled E-step; classic_no_reassign != 0 = RHCCQ_STEPS_NO_REASSIGN for
+ * them), neither = every launch leaves it out (its workgroups return at once).  since0[n_prob] / carry[n_prob]: as above, per
+ * problem (read and written for the problems of fast_mask only).  Problems whose launch parameters agree at a step share its
+ * launches; they differ only around their reassigning steps, so nearly every step is two launches for the whole batch.
+ * Bit-identical to running every problem alone. */
+int rhccq_mbk_steps_batch(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs_host,
+                          int32_t n_prob, int64_t step0, int32_t n_steps, const uint32_t* words, int64_t n_words,
+                          double* centres, double* weights, double* state, void* work, int64_t work_bytes,
+                          int32_t estep_split, uint32_t fast_mask, uint32_t classic_mask, int32_t classic_no_reassign,
+                          const int64_t* since0, int32_t* carry);
 /* final E-step over all points: labels_out int32 at the key offsets (first arg-min of
  * csq_j + (-2 * dot), brute force order-independent; uses a centre grid for pruning) */
 int rhccq_mbk_assign(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs_host,
@@ -361,6 +380,11 @@ typedef struct rhccq_frame_result {
 } rhccq_frame_result;
 int rhccq_encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const rhccq_class_desc* classes, int32_t n_classes,
                        uint8_t* palette_out, int32_t pal_cap, void* indices_out, int64_t* n_unique_out, rhccq_frame_result* res);
+/* The MiniBatchKMeans fits of the level-2 stage of the context's last rhccq_encode_frame (RHCCQ_OPT_FRAME_LEVEL2 = 1; none with 0):
+ * out[6 i ..] = {class, points, k, steps run, schedule: 0 = a lone problem's own fit, 1 = in a batch, classic steps only, 2 = in a
+ * batch and on the overlapped schedule, the step at which it went there (-1: never)} for the first `cap` of them; returns how many
+ * there are (-1: bad argument). */
+int32_t rhccq_encode_frame_level2_info(const rhccq_ctx* ctx, int32_t cap, int64_t* out);
 
 /* ---- K6: index remap gather (clustering.py:373-377) ------------------------------------------ */
 int rhccq_remap(rhccq_ctx* ctx, const int32_t* idx, int64_t n, const int32_t* lut, int64_t lut_n,

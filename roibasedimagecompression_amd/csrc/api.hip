@@ -76,6 +76,10 @@ int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value) {
       if (value != 0 && value != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_FRAME_CHAINS: 0 or 1");
       ctx->opt_frame_chains = (int)value;
       return 0;
+    case RHCCQ_OPT_FRAME_LEVEL2:
+      if (value != 0 && value != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_FRAME_LEVEL2: 0 or 1");
+      ctx->opt_frame_level2 = (int)value;
+      return 0;
     default:
       return rhccq_fail(ctx, RHCCQ_E_ARG, "unknown option");
   }

@@ -10,8 +10,10 @@
 //   encoder/compression/merging.py:16-21,52-82         single-component passthrough, reversed painting, first-seen global palette
 //   encoder/compression/regions.py:9-70, image.py:243-286   per class merge + cluster(2q); classes merged + cluster(q3); index dtype
 // Host structure: the calling thread runs the per-pixel passes on the context's stream; every region class is a host thread with a
-// sibling context (HIP stream + device arena of its own) that runs level 1 -> merges -> level 2 of its class; the MiniBatchKMeans
-// problems of a class (>= 10 000 colours) run side by side on further sibling contexts.  No interpreter, no global lock; the only
+// sibling context (HIP stream + device arena of its own) that runs level 1 -> merges of its class; the MiniBatchKMeans problems of a
+// class (>= 10 000 colours) run side by side on further sibling contexts.  The class threads end with their merged component and
+// level-2 job; the calling thread clusters the level-2 palettes of all classes in one call on one lane, their MiniBatchKMeans
+// problems as one batch (RHCCQ_OPT_FRAME_LEVEL2; 0: level 2 stays in the class threads).  No interpreter, no global lock; the only
 // synchronisation points are the k-sized read-backs the ordering rules need.
 // Ownership (host_raii.h): threads, events, streams, pinned memory and sibling contexts belong to owners whose destructors release them.
 // The invariant on every exit path, an exception included: no host buffer that an asynchronous copy reads or writes is destroyed before
@@ -30,6 +32,7 @@
 #include <mutex>
 #include <vector>
 
+#include "frame_level2_host.h"
 #include "host_raii.h"
 #include "rhccq_common.h"
 
@@ -227,6 +230,8 @@ struct Lane {
   Stream stream;
   Ctx ctx;
   Pinned<double> pinned;                               // 3 x 16 doubles: landing buffers of the asynchronous state polls
+  Pinned<double> pinned_batch;                         // 3 x n_prob x 16 doubles: the same for a batch of problems (mbk_fit_batch), kept between frames
+  size_t pinned_batch_n = 0;
   Event ev[3];
   std::vector<std::unique_ptr<Lane>> sub;              // further siblings (the MiniBatchKMeans problems of a class)
 
@@ -280,11 +285,25 @@ struct Lane {
     EF_HIP(hipStreamSynchronize(stream.get()));
   }
   void sync() { EF_HIP(hipStreamSynchronize(stream.get())); }
+  double* batch_landing(size_t n_prob) {               // (grown while nothing of this lane is in flight: the caller has synchronised)
+    if (pinned_batch_n < n_prob) {
+      pinned_batch = make_pinned<double>(3 * 16 * n_prob);
+      pinned_batch_n = n_prob;
+    }
+    return pinned_batch.get();
+  }
 };
 
+struct Level2Fit {                                       // one MiniBatchKMeans fit of the frame's level-2 stage
+  int32_t cls = 0;
+  int64_t n = 0, k = 0, steps = 0;
+  int32_t schedule = 0;                                // 0 = a fit of its own (lone problem), 1 = in a batch, classic steps only, 2 = in a batch, overlapped
+  int64_t overlapped_from = -1;                        // in a batch: the step at which it went to the overlapped schedule (-1: never)
+};
 struct FrameState {
   std::vector<std::unique_ptr<Lane>> classes;
   Arena root_arena;                                    // the per-pixel tables of a frame (allocated and used on the caller's stream)
+  std::vector<Level2Fit> level2_fits;                  // the last frame's level-2 MiniBatchKMeans fits (rhccq_encode_frame_level2_info)
 };
 void free_frame_state(void* p) { delete (FrameState*)p; }
 
@@ -334,7 +353,8 @@ struct PreChain {
 // moves a problem to another generation of the chain than the one it gets alone
 constexpr int64_t kFrameChainMaxInit = 98304;
 
-void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out, const PreChain* pre = nullptr) {
+// `steps_out`: the steps the fit ran
+void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out, const PreChain* pre = nullptr, int64_t* steps_out = nullptr) {
   rhccq_ctx* c = L.ctx.get();
   MtTable& mt = MtTable::get();
   const bool tr = trace_on();
@@ -455,6 +475,7 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
     running = st[11] == 0.0 && st[5] < (double)limit;
   }
   if (tr) { L.sync(); tt[3] = now_ms(); }
+  if (steps_out) *steps_out = (int64_t)st[5];
   EF_RC(c, rhccq_mbk_assign(c, keys, &prob, 1, centres, work, wbytes, labels_out));
   if (tr) {
     L.sync();
@@ -466,6 +487,193 @@ void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* label
       fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms (host draws %.2f, word table %.2f, uniforms+upload %.2f, order %.2f), chain %.2f ms "
               "(%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", (long long)n, (long long)k, tt[1] - tt[0], ts[0] - tt[0], ts[1] - ts[0],
               ts[2] - ts[1], tt[1] - ts[2], tt[2] - tt[1], (tt[2] - tt[1]) * 1e3 / (double)k, (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
+  }
+}
+
+// ---- the same fit for a BATCH of problems on one lane and one stream (the frame's level-2 stage, RHCCQ_OPT_FRAME_LEVEL2) ----------
+// Every problem keeps what mbk_fit makes for it alone: its MT19937 positions, draws, init samples, T, first centre, step count and
+// stopping rule.  The kernels take (probs, n_prob) and treat the problems of a batch independently; what the batch shares is the
+// launches: one ordering, one chain launch with a workgroup per problem, one step sequence (rhccq_mbk_steps_batch: a problem is on
+// the overlapped schedule from the chunk at which mbk_fit would put it there, on the classic one until then, and masked out once it
+// has stopped), one assignment.  probs: off / n / k set by the caller (key offsets into `keys`); labels_out at the key offsets.
+struct BatchFit {
+  int64_t steps = 0;                                   // out: steps the problem ran
+  int64_t overlapped_from = -1;                        // out: the step at which it went to the overlapped schedule (-1: never)
+};
+
+void mbk_fit_batch(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& probs, int32_t* labels_out, std::vector<BatchFit>& fits) {
+  rhccq_ctx* c = L.ctx.get();
+  MtTable& mt = MtTable::get();
+  const int N = (int)probs.size();
+  if (N < 1 || N > 32) throw Err{RHCCQ_E_ARG, "mbk_fit_batch: 1 .. 32 problems"};
+  const bool tr = trace_on();
+  double tt[5] = {now_ms(), 0, 0, 0, 0};
+  fits.assign((size_t)N, BatchFit());
+  // ---- draws (host), uniforms, Morton order, chains: as frame_chains
+  std::vector<MbkDraws> draws((size_t)N);
+  int64_t ktot = 0, itot = 0, utot = 0, need_words = 1, cur_max = 0, k_max = 0, tiles = 0;
+  for (int p = 0; p < N; ++p) {
+    rhccq_mbk_problem& q = probs[(size_t)p];
+    draws[(size_t)p] = mbk_draws(q.n, q.k);
+    const MbkDraws& d = draws[(size_t)p];
+    q.koff = ktot; q.init_off = itot; q.init_n = d.init_size; q.rand_off = utot; q.first = d.first; q.T = d.T;
+    ktot += q.k;
+    itot += d.init_size;
+    utot += d.nu;
+    need_words = std::max<int64_t>(need_words, d.pos + 2 * d.nu);
+    cur_max = std::max(cur_max, d.cursor0);
+    k_max = std::max(k_max, q.k);
+    tiles += (q.k + 511) / 512;
+  }
+  const uint32_t* words;
+  int64_t n_words;
+  mt.device(L.device, need_words, &words, &n_words);
+  double* d_rand = L.dalloc<double>((size_t)utot);
+  std::vector<int32_t> init_idx;
+  init_idx.reserve((size_t)itot);
+  for (int p = 0; p < N; ++p) {
+    const MbkDraws& d = draws[(size_t)p];
+    EF_RC(c, rhccq_mt_uniforms(c, words, d.pos, d.nu, d_rand + probs[(size_t)p].rand_off));   // (a problem's uniforms start at its own word)
+    init_idx.insert(init_idx.end(), d.init_idx.begin(), d.init_idx.end());
+  }
+  int32_t* d_init = L.upload(init_idx.data(), (size_t)itot);
+  const int64_t obytes = rhccq_mbk_order_bytes(itot);
+  void* otmp = L.arena.alloc((size_t)obytes);
+  int32_t* d_perm = L.dalloc<int32_t>((size_t)itot);
+  EF_RC(c, rhccq_mbk_order(c, keys, probs.data(), N, d_init, d_perm, otmp, obytes));
+  double* centres = L.dzeros<double>((size_t)ktot * 4);
+  int32_t* chosen = L.dzeros<int32_t>((size_t)ktot);
+  if (tr) { L.sync(); tt[1] = now_ms(); }
+  EF_RC(c, rhccq_mbk_init(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen));
+  if (tr) { L.sync(); tt[2] = now_ms(); }
+  // ---- steps
+  double* weights = L.dzeros<double>((size_t)ktot);
+  std::vector<double> st((size_t)N * 16, 0.0);
+  std::vector<int64_t> limit((size_t)N), bs((size_t)N);
+  int64_t limit_max = 0;
+  for (int p = 0; p < N; ++p) {
+    st[(size_t)p * 16 + 8] = (double)probs[(size_t)p].k;                  // every centre starts with zero weight
+    st[(size_t)p * 16 + 9] = (double)draws[(size_t)p].cursor0;            // MT19937 words consumed so far
+    bs[(size_t)p] = std::min<int64_t>(1000, probs[(size_t)p].n);
+    limit[(size_t)p] = (100 * probs[(size_t)p].n) / bs[(size_t)p];
+    limit_max = std::max(limit_max, limit[(size_t)p]);
+  }
+  double* state = L.upload(st.data(), st.size());
+  const int64_t WORDS_PER_STEP = 16384;                                  // kWordsMargin of mbk_update_kernel
+  const int64_t wbytes = rhccq_mbk_work_bytes(probs.data(), N);
+  void* work = L.arena.alloc((size_t)std::max<int64_t>(wbytes, 8));
+  const bool tiled = k_max < 200000;                                     // (mbk_fit's rule for a lone problem; same results either way)
+  int split = 8;
+  for (int sp : {1, 2, 4, 8})
+    if (tiles * 2 * sp >= 1536) { split = sp; break; }
+  L.sync();                                                              // (`st` and `init_idx` are staged; the landing buffer may be regrown)
+  double* landing = L.batch_landing((size_t)N);
+  auto check = [&](const double* s) {
+    if (s[4] == 3.0) throw Err{RHCCQ_E_LIMIT, "mini-batch steps ran past the end of the MT19937 word table (internal sizing error)"};
+    if (s[4] == 4.0) throw Err{RHCCQ_E_LIMIT, "the sharded k-means++ chain gave up waiting for a partner workgroup"};
+    if (s[4] == 5.0) throw Err{RHCCQ_E_LIMIT, "the overlapped mini-batch schedule and the device state disagree about a reassignment"};
+  };
+  // the first steps: classic, all problems (most problems converge within a dozen steps: look early once)
+  int64_t step = 16;
+  mt.device(L.device, cur_max + (16 + 3) * WORDS_PER_STEP, &words, &n_words);
+  EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, 0, 16, words, n_words, centres, weights, state, work, wbytes, tiled ? RHCCQ_ESTEP_TILES : RHCCQ_ESTEP_GRID,
+                           split));
+  L.download(st.data(), state, st.size());
+  std::vector<char> running((size_t)N), fast((size_t)N, 0);
+  std::vector<int64_t> since((size_t)N, 0), cur_known((size_t)N), steps_known((size_t)N);
+  std::vector<int32_t> carry((size_t)N, 0);
+  auto take = [&](const double* snap) {                                  // a state snapshot of all problems
+    std::memcpy(st.data(), snap, st.size() * sizeof(double));
+    for (int p = 0; p < N; ++p) {
+      const double* s = &st[(size_t)p * 16];
+      cur_known[(size_t)p] = (int64_t)std::max(s[9], s[14]);
+      steps_known[(size_t)p] = (int64_t)s[5];
+      running[(size_t)p] = !(s[4] >= 3.0 || s[11] != 0.0 || s[5] >= (double)limit[(size_t)p]);
+    }
+  };
+  take(st.data());
+  for (int p = 0; p < N; ++p) check(&st[(size_t)p * 16]);
+  std::vector<int> pending;                                              // landing slots of the snapshots in flight
+  int n_chunk = 0;
+  while (true) {
+    const int par = (int)(step & 1);
+    uint32_t fast_mask = 0u, classic_mask = 0u;
+    bool no_reassign = true;
+    int64_t need = 0, left = 0;
+    for (int p = 0; p < N; ++p) {
+      if (!running[(size_t)p]) continue;
+      const double* s = &st[(size_t)p * 16];
+      const int64_t k = probs[(size_t)p].k;
+      // a problem whose centres all carry weight goes to the overlapped schedule for the rest of its steps (mbk_fit's rule; a classic
+      // problem's state is always the one of `step`: the loop waits for it below)
+      if (!fast[(size_t)p] && tiled && k >= 1024 && s[par ? 13 : 8] == 0.0) {
+        fast[(size_t)p] = 1;
+        fits[(size_t)p].overlapped_from = step;
+        since[(size_t)p] = (int64_t)s[par ? 12 : 3];
+        carry[(size_t)p] = 0;
+      }
+      left = std::max(left, limit[(size_t)p] - step);
+    }
+    const int ns = (int)std::min<int64_t>(64, left);
+    for (int p = 0; p < N && ns > 0; ++p) {
+      if (!running[(size_t)p]) continue;
+      const double* s = &st[(size_t)p * 16];
+      if (fast[(size_t)p]) {
+        fast_mask |= 1u << p;
+        need = std::max(need, cur_known[(size_t)p] + (step - steps_known[(size_t)p] + ns + 4) * 4200 + 8 * WORDS_PER_STEP);
+      } else {
+        classic_mask |= 1u << p;
+        need = std::max(need, cur_known[(size_t)p] + (ns + 3) * WORDS_PER_STEP);
+        no_reassign = no_reassign && s[par ? 13 : 8] == 0.0 && s[par ? 12 : 3] + (double)(ns * bs[(size_t)p]) < (double)(10 * probs[(size_t)p].k);
+      }
+    }
+    if ((fast_mask | classic_mask) == 0u && pending.empty()) break;
+    if (fast_mask | classic_mask) {
+      mt.device(L.device, need, &words, &n_words);
+      if (tiled)
+        EF_RC(c, rhccq_mbk_steps_batch(c, keys, probs.data(), N, step, ns, words, n_words, centres, weights, state, work, wbytes, split, fast_mask,
+                                       classic_mask, classic_mask && no_reassign ? 1 : 0, since.data(), carry.data()));
+      else                                                               // (the grid E-step: nobody is on the overlapped schedule)
+        EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, step, ns, words, n_words, centres, weights, state, work, wbytes, RHCCQ_ESTEP_GRID, split));
+      for (int p = 0; p < N; ++p)
+        if ((fast_mask >> p) & 1u)
+          for (int i = 0; i < ns; ++i) {                                  // the schedule's own arithmetic (sklearn _random_reassign)
+            since[(size_t)p] += bs[(size_t)p];
+            if (since[(size_t)p] >= 10 * probs[(size_t)p].k) since[(size_t)p] = 0;
+          }
+      step += ns;
+      const int slot = n_chunk % 3;
+      ++n_chunk;
+      EF_HIP(hipMemcpyAsync(landing + (size_t)slot * 16 * N, state, (size_t)16 * N * sizeof(double), hipMemcpyDeviceToHost, L.stream.get()));
+      EF_HIP(hipEventRecord(L.ev[slot].get(), L.stream.get()));
+      pending.push_back(slot);
+    }
+    if (classic_mask || !tiled) {                                        // a classic problem's next chunk depends on its state: wait for the newest
+      EF_HIP(hipEventSynchronize(L.ev[pending.back()].get()));
+      take(landing + (size_t)pending.back() * 16 * N);
+      pending.clear();
+    } else if (pending.size() >= 2 || (fast_mask | classic_mask) == 0u) {  // overlapped problems only: the state two chunks behind
+      EF_HIP(hipEventSynchronize(L.ev[pending.front()].get()));
+      take(landing + (size_t)pending.front() * 16 * N);
+      pending.erase(pending.begin());
+    }
+    for (int p = 0; p < N; ++p) check(&st[(size_t)p * 16]);
+  }
+  for (int p = 0; p < N; ++p) fits[(size_t)p].steps = (int64_t)st[(size_t)p * 16 + 5];
+  if (tr) { L.sync(); tt[3] = now_ms(); }
+  EF_RC(c, rhccq_mbk_assign(c, keys, probs.data(), N, centres, work, wbytes, labels_out));
+  if (tr) {
+    L.sync();
+    tt[4] = now_ms();
+    std::string names;
+    for (int p = 0; p < N; ++p) {
+      char buf[96];
+      snprintf(buf, sizeof(buf), "%s n=%lld k=%lld %lld steps%s", p ? "," : "", (long long)probs[(size_t)p].n, (long long)probs[(size_t)p].k,
+               (long long)fits[(size_t)p].steps, fits[(size_t)p].overlapped_from >= 0 ? " (overlapped)" : "");
+      names += buf;
+    }
+    fprintf(stderr, "[rhccq] mbk batch of %d:%s: draws+order %.2f ms, chains %.2f ms, steps %.2f ms (%d chunks), assign %.2f ms\n", N, names.c_str(),
+            tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2], n_chunk, tt[4] - tt[3]);
   }
 }
 
@@ -492,6 +700,9 @@ struct Job {
   int32_t* labels_dev = nullptr;
   int64_t k = 0;
   const PreChain* pre = nullptr;                       // its k-means++ chain ran in the frame's launch (resident level-1 jobs)
+  int64_t mbk_n = 0, mbk_steps = -1;                   // out (MiniBatchKMeans branch): points, steps run
+  int mbk_schedule = 0;                                // out: Level2Fit::schedule
+  int64_t mbk_overlapped_from = -1;                    // out: Level2Fit::overlapped_from
 };
 
 int64_t n_splits(int64_t n, int64_t mc) {             // split_large_cluster's n_splits (clustering.py:739-747); 0 = do not split
@@ -557,7 +768,47 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
       [&](size_t g) { (void)hipStreamSynchronize(L.sub[g]->stream.get()); });
 }
 
-void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
+// The MiniBatchKMeans problems of `tasks` as batches of at most 32 on L's own stream (mbk_fit_batch); a lone problem takes mbk_fit.
+// Host palettes only (the level-2 stage's): their non-black keys go to the device in one copy.
+void run_mbk_batch(Lane& L, std::vector<Job*>& tasks) {
+  for (size_t lo = 0; lo < tasks.size(); lo += 32) {
+    const size_t hi = std::min(tasks.size(), lo + 32);
+    std::vector<rhccq_mbk_problem> probs(hi - lo);
+    std::vector<uint32_t> cat;
+    for (size_t i = lo; i < hi; ++i) {
+      Job& jb = *tasks[i];
+      rhccq_mbk_problem& q = probs[i - lo];
+      q = rhccq_mbk_problem();
+      q.off = (int64_t)cat.size(); q.n = (int64_t)jb.nb.size(); q.k = jb.k;
+      for (int32_t t : jb.nb) cat.push_back(jb.keys[(size_t)t]);
+      jb.mbk_n = q.n;
+    }
+    const uint32_t* keys = L.upload(cat.data(), cat.size());
+    L.sync();                                           // (`cat` is staged)
+    int32_t* labels = L.dalloc<int32_t>(cat.size());
+    if (probs.size() == 1) {
+      Job& jb = *tasks[lo];
+      mbk_fit(L, keys, probs[0].n, probs[0].k, labels, nullptr, &jb.mbk_steps);
+      jb.mbk_schedule = 0;
+      jb.labels_dev = labels;
+    } else {
+      std::vector<BatchFit> fits;
+      mbk_fit_batch(L, keys, probs, labels, fits);
+      for (size_t i = lo; i < hi; ++i) {
+        Job& jb = *tasks[i];
+        jb.labels_dev = labels + probs[i - lo].off;
+        jb.mbk_steps = fits[i - lo].steps;
+        jb.mbk_schedule = fits[i - lo].overlapped_from >= 0 ? 2 : 1;
+        jb.mbk_overlapped_from = fits[i - lo].overlapped_from;
+      }
+    }
+    L.sync();
+  }
+}
+
+// batch_mbk: the MiniBatchKMeans problems of host palettes run as one batch on L's own stream (run_mbk_batch) instead of side by side
+// on sibling lanes
+void cluster_jobs(Lane& L, std::vector<Job>& jobs, bool batch_mbk = false) {
   rhccq_ctx* c = L.ctx.get();
   const size_t S = jobs.size();
   // ---- which branch: resident MiniBatch jobs, host MiniBatch jobs, DBSCAN jobs, only-black palettes
@@ -618,8 +869,15 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs) {
     }
   }
   if (trace_on() && !db.empty()) fprintf(stderr, "[rhccq] dbscan: %zu palettes, %.2f ms\n", db.size(), now_ms() - t_db);
-  // ---- MiniBatchKMeans problems side by side
-  run_mbk_tasks(L, mbk);
+  // ---- MiniBatchKMeans problems: side by side, or (the frame's level-2 stage) the host palettes as one batch
+  if (batch_mbk) {
+    std::vector<Job*> host_jobs, resident;
+    for (Job* pj : mbk) (pj->keys_dev ? resident : host_jobs).push_back(pj);
+    run_mbk_batch(L, host_jobs);
+    run_mbk_tasks(L, resident);
+  } else {
+    run_mbk_tasks(L, mbk);
+  }
   for (Job* pj : mbk) {
     Job& jb = *pj;
     if (jb.keys_dev) {
@@ -944,14 +1202,34 @@ struct FrameCtx {
 
 struct ClassOut {
   std::map<int, std::pair<int64_t, int64_t>> k1_off;   // job -> [first entry id, end)
+  std::shared_ptr<Comp> comp2;                         // the class's merged component (NULL: the class has no component) and
+  Job job2;                                            // its level-2 job: what the class thread hands to the level-2 stage
   std::shared_ptr<Comp> comp3;                         // the class's level-2 result (NULL: the class contributes nothing)
   int q2 = 0;
   double ms[4] = {0, 0, 0, 0};
   Event done;
 };
 
-// level 1 -> merge per region -> merge per class -> level 2 of one class on its own lane (frame.py::_class_pipeline)
-void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
+// level 2 of the classes `cis` in one clustering call on lane L (one class: that class's own lane, RHCCQ_OPT_FRAME_LEVEL2 = 0; all
+// classes with a component: the frame's level-2 stage).  The call's time is reported as level2_cluster of every class it served.
+void level2_stage(Lane& L, std::vector<ClassOut>& outs, const std::vector<int>& cis, bool batch_mbk, std::vector<Level2Fit>* fits) {
+  level2_handover<Job>(
+      outs, cis, [&](std::vector<Job>& j2) { cluster_jobs(L, j2, batch_mbk); },
+      [&](int ci, ClassOut& out, const Job& jb) {
+        out.comp3 = clustered(*out.comp2, jb);
+        if (fits && jb.mbk_steps >= 0) {
+          Level2Fit f;
+          f.cls = ci; f.n = jb.mbk_n; f.k = jb.k; f.steps = jb.mbk_steps; f.schedule = jb.mbk_schedule; f.overlapped_from = jb.mbk_overlapped_from;
+          fits->push_back(f);
+        }
+      },
+      now_ms);
+}
+
+// level 1 -> merge per region -> merge per class of one class on its own lane (frame.py::_class_pipeline); with level2_here also the
+// class's level 2, on the same lane
+void class_pipeline(FrameCtx& F, int ci, Lane& L, std::vector<ClassOut>& outs, bool level2_here) {
+  ClassOut& out = outs[(size_t)ci];
   rhccq_ctx* c = L.ctx.get();
   EF_HIP(hipSetDevice(L.device));
   EF_HIP(hipStreamWaitEvent(L.stream.get(), F.ready.get(), 0));
@@ -1061,17 +1339,14 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, ClassOut& out) {
   out.q2 = std::min(cls.quality * 2, 100);
   mark(1);
   if (!live.empty()) {                                  // rhccq.ipynb:1009-1013: a class without components contributes nothing
-    auto comp = merge_comps(live, 0, 0, F.H, F.W);
+    out.comp2 = merge_comps(live, 0, 0, F.H, F.W);
+    Job& j2 = out.job2;
+    j2.keys = out.comp2->keys;
+    j2.P = (int64_t)out.comp2->keys.size();
+    j2.quality = out.q2;
+    if (rhccq_params(j2.P, (double)out.q2, &j2.eps, &j2.mc)) throw Err{RHCCQ_E_ARG, "rhccq_params failed"};
     mark(1);
-    std::vector<Job> j2(1);
-    j2[0].keys = comp->keys;
-    j2[0].P = (int64_t)comp->keys.size();
-    j2[0].quality = out.q2;
-    if (rhccq_params(j2[0].P, (double)out.q2, &j2[0].eps, &j2[0].mc)) throw Err{RHCCQ_E_ARG, "rhccq_params failed"};
-    cluster_jobs(L, j2);
-    mark(2);
-    out.comp3 = clustered(*comp, j2[0]);
-    mark(3);
+    if (level2_here) level2_stage(L, outs, std::vector<int>(1, ci), false, nullptr);
   }
   EF_HIP(hipEventRecord(out.done.get(), L.stream.get()));
   L.sync();
@@ -1297,9 +1572,18 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
   std::vector<ClassOut> outs((size_t)n_classes);
   for (auto& o : outs) o.done = make_event();            // (all of them before the first thread starts)
   const SyncOnUnwind drain(stream);                      // (F, outs and the host tables above outlive whatever the caller's stream still does)
+  const bool frame_level2 = ctx->opt_frame_level2 != 0;
   run_lanes(
-      (size_t)n_classes, [&](size_t ci) { class_pipeline(F, (int)ci, *FS.classes[ci], outs[ci]); },
+      (size_t)n_classes, [&](size_t ci) { class_pipeline(F, (int)ci, *FS.classes[ci], outs, !frame_level2); },
       [&](size_t ci) { (void)hipStreamSynchronize(FS.classes[ci]->stream.get()); });
+  FS.level2_fits.clear();
+  if (frame_level2) {
+    // ---- level 2 of every class in ONE clustering call on the first class's lane: the class threads have ended and their streams
+    // are idle, so nothing of the frame queues launches beside it (RHCCQ_OPT_FRAME_LEVEL2)
+    Lane& L2 = *FS.classes[0];
+    level2_stage(L2, outs, level2_classes(outs), true, &FS.level2_fits);
+    L2.sync();
+  }
   res->ms[2] = now_ms() - t0;
   for (int ci = 0; ci < n_classes && ci < 4; ++ci) std::memcpy(res->class_ms[ci], outs[(size_t)ci].ms, sizeof(outs[(size_t)ci].ms));
   t0 = now_ms();
@@ -1383,6 +1667,18 @@ int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const
 }
 
 }  // namespace
+
+extern "C" int32_t rhccq_encode_frame_level2_info(const rhccq_ctx* ctx, int32_t cap, int64_t* out) {
+  if (!ctx || cap < 0 || (cap > 0 && !out)) return -1;
+  if (!ctx->frame_state) return 0;
+  const FrameState& FS = *(const FrameState*)ctx->frame_state;
+  for (size_t i = 0; i < FS.level2_fits.size() && (int32_t)i < cap; ++i) {
+    const Level2Fit& f = FS.level2_fits[i];
+    int64_t* o = out + 6 * i;
+    o[0] = f.cls; o[1] = f.n; o[2] = f.k; o[3] = f.steps; o[4] = f.schedule; o[5] = f.overlapped_from;
+  }
+  return (int32_t)FS.level2_fits.size();
+}
 
 extern "C" int rhccq_encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const rhccq_class_desc* classes, int32_t n_classes,
                                   uint8_t* palette_out, int32_t pal_cap, void* indices_out, int64_t* n_unique_out, rhccq_frame_result* res) {

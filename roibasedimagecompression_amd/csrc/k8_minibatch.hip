@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "mbk_schedule.h"
 #include "rhccq_common.h"
 
 namespace rhccq {
@@ -1406,6 +1407,10 @@ __device__ __forceinline__ bool mbk_stopped(const double* st, long long step, lo
   const long long bs = n < 1000 ? n : 1000;
   return (stop_at != 0.0 && (double)step >= stop_at) || st[4] >= 3.0 || step >= (100 * n) / bs;
 }
+// Problems a launch leaves out (the batched overlapped sequence gives problems whose schedules differ launches of their own): bit p
+// of `pmask` clear = the workgroups of problem p return at once.  Problems 32 and up are never left out (the classic sequence
+// passes ~0u).
+__device__ __forceinline__ bool mbk_masked(unsigned pmask, int p) { return p < 32 && ((pmask >> p) & 1u) == 0u; }
 // Batch inertia of step `step` + sklearn _mini_batch_convergence (EWA early stopping), one wave.  The 1 000 terms (fold
 // kernel, against the centres before the update) are added ONE AFTER THE OTHER in batch order, as sklearn's
 // single-threaded _inertia_dense does -- a chain of ~1 000 dependent float64 additions, ~10 us.  Nothing of step `step`
@@ -1465,9 +1470,10 @@ __device__ __forceinline__ void mbk_inertia_block(const MbkP& P, double* st, lon
 
 // the inertia of the last step of a launch sequence (nothing follows it to ride on)
 __global__ __launch_bounds__(64) void mbk_inertia_kernel(const MbkP* __restrict__ probs, double* __restrict__ state, long long step,
-                                                         const double* __restrict__ pper) {
+                                                         const double* __restrict__ pper, unsigned pmask) {
   __shared__ double s_per[kBatch];
   const int p = blockIdx.x;
+  if (mbk_masked(pmask, p)) return;
   const MbkP P = probs[p];
   double* st = state + p * 16;
   if (step < 0 || mbk_stopped(st, step, P.n)) return;
@@ -1579,8 +1585,9 @@ __global__ __launch_bounds__(256) void mbk_batch_estep_kernel(const uint32_t* __
                                                               const double* __restrict__ centres, double* __restrict__ state,
                                                               long long step, const uint32_t* __restrict__ bkeys, double* __restrict__ pdist,
                                                               int32_t* __restrict__ pidx, const long long* __restrict__ part_off,
-                                                              const double* __restrict__ pper_prev) {
+                                                              const double* __restrict__ pper_prev, unsigned pmask) {
   const int p = blockIdx.y;
+  if (mbk_masked(pmask, p)) return;
   const MbkP P = probs[p];                               // independent table reads, issued together
   const long long po = part_off[p];
   __shared__ __align__(16) double sc[kTileC * 4];
@@ -1604,8 +1611,10 @@ __global__ __launch_bounds__(256) void mbk_batch_estep_kernel(const uint32_t* __
 __global__ __launch_bounds__(64) void mbk_fold_tiles_kernel(const MbkP* __restrict__ probs, const double* __restrict__ state, long long step,
                                                             const double* __restrict__ centres, const uint32_t* __restrict__ bkeys,
                                                             double* __restrict__ pdist, int32_t* __restrict__ pidx,
-                                                            const long long* __restrict__ part_off, double* __restrict__ pper, int tiled) {
+                                                            const long long* __restrict__ part_off, double* __restrict__ pper, int tiled,
+                                                            unsigned pmask) {
   const int p = blockIdx.y;
+  if (mbk_masked(pmask, p)) return;
   const MbkP P = probs[p];
   const long long po = part_off[p];
   if (mbk_stopped(state + p * 16, step, P.n)) return;
@@ -2075,6 +2084,7 @@ struct UpdDraws {
   int* qs_l;
   int* qs_r;
   unsigned* qs_mask;                 // [sum k / 32 + n_prob + 1]: problem p's words start at koff / 32 + p
+  unsigned pmask;                    // problems of this launch (mbk_masked)
 };
 __device__ __forceinline__ QsScratch qs_of(const UpdDraws& dr, const MbkP& P, int p) {
   return QsScratch{dr.qs_e + P.koff, dr.qs_l + P.koff, dr.qs_r + P.koff, dr.qs_mask + (P.koff >> 5) + p};
@@ -2086,6 +2096,7 @@ __device__ __forceinline__ void mbk_update_body(UpdShared& sh, const int p, cons
                                                 const uint32_t* __restrict__ bkeys_cur, const UpdDraws& dr,
                                                 const int32_t* __restrict__ labels_p) {
   const int tid = threadIdx.x;
+  if (mbk_masked(dr.pmask, p)) return;
   double* st = state + p * kStateStride;
   // independent table reads issued together: the kernel is a chain of dependent accesses, every cold miss counts
   const double st_since = st[st_slot(kStSince, step)], st_nzero = st[st_slot(kStNzero, step)];
@@ -2278,6 +2289,7 @@ __global__ __launch_bounds__(kUpdThreads) void mbk_reassign_apply_kernel(const u
                                                                          const uint32_t* __restrict__ bkeys_cur, UpdDraws dr) {
   __shared__ ApplyShared sh;
   const int p = blockIdx.x, role = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (mbk_masked(dr.pmask, p)) return;
   double* st = state + p * kStateStride;
   const MbkP P = probs[p];
   const ReSel* rs = dr.resel + p;
@@ -3041,7 +3053,7 @@ int rhccq_mbk_steps(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_proble
     } else {
 #define RHCCQ_ESTEP_LAUNCH(SS)                                                                                                             \
   hipLaunchKernelGGL(mbk_batch_estep_kernel<SS>, dim3(max_tiles * kPtChunks * SS + 1, n_prob), dim3(256), 0, ctx->stream, keys, v.probs, centres, \
-                     state, step, bk, v.pdist, v.pidx, v.part_off, pprev)
+                     state, step, bk, v.pdist, v.pidx, v.part_off, pprev, ~0u)
       switch (estep_split) {
         case 8: RHCCQ_ESTEP_LAUNCH(8); break;
         case 4: RHCCQ_ESTEP_LAUNCH(4); break;
@@ -3052,9 +3064,9 @@ int rhccq_mbk_steps(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_proble
     }
     // arg-min over the centre tiles (tiled E-step) and every row's inertia term against the centres before the update
     hipLaunchKernelGGL(mbk_fold_tiles_kernel, dim3((1000 + 15) / 16, n_prob), dim3(64), 0, ctx->stream, v.probs, (const double*)state, step,
-                       (const double*)centres, bk, v.pdist, v.pidx, v.part_off, v.pper[step & 1], use_grid ? 0 : 1);
+                       (const double*)centres, bk, v.pdist, v.pidx, v.part_off, v.pper[step & 1], use_grid ? 0 : 1, ~0u);
     const UpdDraws dr{{v.bkeys[0], v.bkeys[1], v.bkeys[2], v.bkeys[3]}, step + 1, 1, 1, no_reassign ? 0 : -1, n_prob, ctx->opt_reassign_lds, v.resel,
-                      ctx->opt_reassign_order == 1 ? v.qs_e : nullptr, v.qs_l, v.qs_r, v.qs_mask};
+                      ctx->opt_reassign_order == 1 ? v.qs_e : nullptr, v.qs_l, v.qs_r, v.qs_mask, ~0u};
     hipLaunchKernelGGL(mbk_update_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state, step,
                        words, (long long)n_words, bk, dr, (const int32_t*)v.pidx, v.part_off, (const int32_t*)nullptr);
     if (!no_reassign)
@@ -3063,95 +3075,133 @@ int rhccq_mbk_steps(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_proble
   }
   if (n_steps > 0)
     hipLaunchKernelGGL(mbk_inertia_kernel, dim3(n_prob), dim3(64), 0, ctx->stream, v.probs, state, step0 + n_steps - 1,
-                       (const double*)v.pper[(step0 + n_steps - 1) & 1]);
+                       (const double*)v.pper[(step0 + n_steps - 1) & 1], ~0u);
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
 }
 
-// The same steps for ONE problem whose centres all carry weight (state: no zero-weight centre), with the E-step of step t + 1
-// started beside the update of step t (k8_overlap.h).  since0 = the problem's "samples since the last reassignment" as step0 sees
-// it (state[3] for an even step0, state[12] for an odd one): with it the host knows which steps of the call reassign.
-// *carry (in/out, 0 before the first call and whenever a classic call came in between): bit 0 = batch step0 + 1 has been
-// drawn, bit 1 = the speculative tile minima of step0 are in `work`.
-int rhccq_mbk_steps_overlapped(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, int64_t step0,
-                               int32_t n_steps, const uint32_t* words, int64_t n_words, double* centres, double* weights, double* state,
-                               void* work, int64_t work_bytes, int32_t estep_split, int64_t since0, int32_t* carry) {
-  if (!ctx || !keys || !probs || !words || !centres || !weights || !state || !work || !carry || n_steps < 0 || n_words <= 0 || step0 < 0 ||
-      since0 < 0 || (*carry & ~3) != 0)
-    return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_overlapped: bad argument");
-  if (n_prob != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_overlapped: exactly one problem");
+// The same steps for a batch of at most 32 problems, every problem on the schedule its own state asks for:
+//   fast_mask     problems whose centres all carry weight (state: no zero-weight centre) and whose k >= 1024: the E-step of step
+//                 t + 1 starts beside the update of step t (k8_overlap.h), two launches per step;
+//   classic_mask  problems that take the classic sequence of rhccq_mbk_steps (tiled E-step) for these steps; classic_no_reassign:
+//                 RHCCQ_STEPS_NO_REASSIGN for them;
+//   neither       the problem is left out of every launch (its workgroups return at once: mbk_masked).
+// `step` is the launch index of all of them, as in rhccq_mbk_steps; a problem that has stopped returns at once on its state.
+// since0[p] = problem p's "samples since the last reassignment" as step0 sees it (state[3] for an even step0, state[12] for an odd
+// one): with it the host knows which steps of the call reassign.  carry[p] (in/out, 0 before the first call and whenever a classic
+// call came in between): bit 0 = batch step0 + 1 has been drawn, bit 1 = the speculative tile minima of step0 are in `work`.
+// The kernels take ONE set of launch parameters (what to draw, whether the tile minima are speculative, whether the step
+// reassigns); problems whose parameters agree at a step share its launches, the others get launches of their own at that step.
+// Two problems differ only around their reassigning steps (every 10 k / 1000 steps), so nearly every step is two launches for
+// the whole batch.
+int rhccq_mbk_steps_batch(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, int64_t step0, int32_t n_steps,
+                          const uint32_t* words, int64_t n_words, double* centres, double* weights, double* state, void* work,
+                          int64_t work_bytes, int32_t estep_split, uint32_t fast_mask, uint32_t classic_mask, int32_t classic_no_reassign,
+                          const int64_t* since0, int32_t* carry) {
+  if (!ctx || !keys || !probs || !words || !centres || !weights || !state || !work || !carry || !since0 || n_steps < 0 || n_words <= 0 || step0 < 0)
+    return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: bad argument");
+  if (n_prob < 1 || n_prob > 32) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: 1 .. 32 problems");
+  const uint32_t all = n_prob == 32 ? 0xffffffffu : ((1u << n_prob) - 1u);
+  if ((fast_mask & classic_mask) != 0u || ((fast_mask | classic_mask) & ~all) != 0u)
+    return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: a problem is on one schedule, and there are n_prob of them");
+  for (int p = 0; p < n_prob; ++p)
+    if (((fast_mask >> p) & 1u) && (since0[p] < 0 || (carry[p] & ~3) != 0)) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: bad since0 / carry");
   if (estep_split != 0 && estep_split != 1 && estep_split != 2 && estep_split != 4 && estep_split != 8)
-    return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_overlapped: estep_split must be 0, 1, 2, 4 or 8");
+    return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: estep_split must be 0, 1, 2, 4 or 8");
   WorkView v;
   long long blocks;
   int max_tiles;
-  if (step0 == 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_overlapped: the first steps of a problem are rhccq_mbk_steps'");
+  if (step0 == 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_batch: the first steps of a problem are rhccq_mbk_steps'");
   if (int e = layout_work(ctx, probs, n_prob, work, work_bytes, &v, &blocks, &max_tiles, false)) return e;
-  const long long k = probs[0].k, bs = probs[0].n < 1000 ? probs[0].n : 1000;
   const int SS = estep_split == 0 ? 1 : estep_split;
-  const int spec_tiles = (int)((k + kTileS - 1) / kTileS);
-  // which steps of this call reassign (sklearn _random_reassign with no zero-weight centre left)
-  std::vector<char> R((size_t)n_steps + 2, 0);
-  {
-    long long since = since0;
-    for (int s = 0; s < n_steps + 2; ++s) {
-      since += bs;
-      R[s] = since >= 10 * k;
-      if (R[s]) since = 0;
-    }
-  }
-  long long drawn = step0 + ((*carry & 1) ? 1 : 0);        // newest batch in the ring
-  bool have_spec = (*carry & 2) != 0;
+  // ---- the fast problems' schedules (mbk_schedule.h): which launches a step needs and which problems share them
+  std::vector<long long> sk((size_t)n_prob), sn((size_t)n_prob);
+  for (int p = 0; p < n_prob; ++p) { sk[(size_t)p] = probs[p].k; sn[(size_t)p] = probs[p].n; }
+  rhccq_sched::BatchSchedule sched(n_prob, sk.data(), sn.data(), fast_mask, step0, n_steps, since0, carry, kTileS);
+  std::vector<rhccq_sched::Launch> launches;
   UpdDraws dr{{v.bkeys[0], v.bkeys[1], v.bkeys[2], v.bkeys[3]}, 0, 0, 0, 0, n_prob, ctx->opt_reassign_lds, v.resel,
-              ctx->opt_reassign_order == 1 ? v.qs_e : nullptr, v.qs_l, v.qs_r, v.qs_mask};
+              ctx->opt_reassign_order == 1 ? v.qs_e : nullptr, v.qs_l, v.qs_r, v.qs_mask, 0u};
+  auto estep = [&](long long step, const uint32_t* bk, const double* pprev, unsigned mask) {
+#define RHCCQ_ESTEP_LAUNCH(S_)                                                                                                             \
+  hipLaunchKernelGGL(mbk_batch_estep_kernel<S_>, dim3(max_tiles * kPtChunks * S_ + 1, n_prob), dim3(256), 0, ctx->stream, keys, v.probs, centres, \
+                     state, step, bk, v.pdist, v.pidx, v.part_off, pprev, mask)
+    switch (SS) {
+      case 8: RHCCQ_ESTEP_LAUNCH(8); break;
+      case 4: RHCCQ_ESTEP_LAUNCH(4); break;
+      case 2: RHCCQ_ESTEP_LAUNCH(2); break;
+      default: RHCCQ_ESTEP_LAUNCH(1); break;
+    }
+#undef RHCCQ_ESTEP_LAUNCH
+  };
   for (int s = 0; s < n_steps; ++s) {
     const long long step = step0 + s;
     const uint32_t* bk = v.bkeys[step & 3];
-    if (!have_spec) {
-#define RHCCQ_ESTEP_LAUNCH(S_)                                                                                                             \
-  hipLaunchKernelGGL(mbk_batch_estep_kernel<S_>, dim3(max_tiles * kPtChunks * S_ + 1, n_prob), dim3(256), 0, ctx->stream, keys, v.probs, centres, \
-                     state, step, bk, v.pdist, v.pidx, v.part_off, (const double*)nullptr)
-      switch (SS) {
-        case 8: RHCCQ_ESTEP_LAUNCH(8); break;
-        case 4: RHCCQ_ESTEP_LAUNCH(4); break;
-        case 2: RHCCQ_ESTEP_LAUNCH(2); break;
-        default: RHCCQ_ESTEP_LAUNCH(1); break;
-      }
-#undef RHCCQ_ESTEP_LAUNCH
-    }
-    hipLaunchKernelGGL(mbk_fix_kernel, dim3((1000 + kFixPts - 1) / kFixPts, n_prob), dim3(256), 0, ctx->stream, v.probs, (const double*)state, step,
-                       (const double*)centres, bk, (const double*)v.pdist, (const int32_t*)v.pidx, v.part_off, v.pper[step & 1],
-                       have_spec ? (const int32_t*)v.lab[(step - 1) & 1] : (const int32_t*)nullptr, v.lab[step & 1],
-                       have_spec ? kTileS : kTileC);
-    dr.expect_reassign = R[s];
-    dr.draw_first = drawn + 1;
-    dr.draw_count = 0;
-    dr.reassign_draws = 0;
-    if (R[s]) {
-      // a reassigning step: the classic update (it draws the batches behind its choice() itself), the inertia in a launch of its own
-      if (drawn != step) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "mbk_steps_overlapped: a batch was drawn past a reassignment (internal error)");
-      dr.reassign_draws = R[s + 1] ? 1 : 2;
-      drawn = step + dr.reassign_draws;
+    // ---- the classic problems: E-step (the previous step's inertia rides along), fold, update, reassignment
+    if (classic_mask) {
+      estep(step, bk, s > 0 ? (const double*)v.pper[(step - 1) & 1] : (const double*)nullptr, classic_mask);
+      hipLaunchKernelGGL(mbk_fold_tiles_kernel, dim3((1000 + 15) / 16, n_prob), dim3(64), 0, ctx->stream, v.probs, (const double*)state, step,
+                         (const double*)centres, bk, v.pdist, v.pidx, v.part_off, v.pper[step & 1], 1, classic_mask);
+      const UpdDraws dc{{v.bkeys[0], v.bkeys[1], v.bkeys[2], v.bkeys[3]}, step + 1, 1, 1, classic_no_reassign ? 0 : -1, n_prob, ctx->opt_reassign_lds,
+                        v.resel, ctx->opt_reassign_order == 1 ? v.qs_e : nullptr, v.qs_l, v.qs_r, v.qs_mask, classic_mask};
       hipLaunchKernelGGL(mbk_update_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state, step,
-                         words, (long long)n_words, bk, dr, (const int32_t*)v.pidx, v.part_off, (const int32_t*)v.lab[step & 1]);
-      hipLaunchKernelGGL(mbk_reassign_apply_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state,
-                         step, words, (long long)n_words, bk, dr);
-      hipLaunchKernelGGL(mbk_inertia_kernel, dim3(n_prob), dim3(64), 0, ctx->stream, v.probs, state, step, (const double*)v.pper[step & 1]);
-      have_spec = false;
-      continue;
+                         words, (long long)n_words, bk, dc, (const int32_t*)v.pidx, v.part_off, (const int32_t*)nullptr);
+      if (!classic_no_reassign)
+        hipLaunchKernelGGL(mbk_reassign_apply_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state,
+                           step, words, (long long)n_words, bk, dc);
     }
-    // the speculative E-step of step + 1 needs its batch before this launch starts
-    const bool spec_next = drawn >= step + 1;
-    const long long target = R[s + 1] ? step + 1 : step + 2;
-    if (target > drawn) { dr.draw_count = (int)(target - drawn); drawn = target; }
-    hipLaunchKernelGGL(mbk_pipe_kernel, dim3(kPipeRoles + (spec_next ? spec_tiles * kSpecChunks : 0), n_prob), dim3(kPipeThreads), 0, ctx->stream,
-                       keys, v.probs, centres, weights, state, step, words, (long long)n_words, bk, dr, (const int32_t*)v.lab[step & 1],
-                       (const double*)v.pper[step & 1], (const uint32_t*)v.bkeys[(step + 1) & 3], v.pdist, v.pidx, v.part_off);
-    have_spec = spec_next;
+    // ---- the fast problems
+    if (!sched.step(s, launches)) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "mbk_steps_batch: a batch was drawn past a reassignment (internal error)");
+    for (const rhccq_sched::Launch& l : launches) {
+      switch (l.kind) {
+        case rhccq_sched::kEstep:
+          estep(step, bk, nullptr, l.mask);
+          break;
+        case rhccq_sched::kFixPlain:
+        case rhccq_sched::kFixSpec: {
+          const bool spec = l.kind == rhccq_sched::kFixSpec;
+          hipLaunchKernelGGL(mbk_fix_kernel, dim3((1000 + kFixPts - 1) / kFixPts, n_prob), dim3(256), 0, ctx->stream, v.probs, (const double*)state, step,
+                             (const double*)centres, bk, (const double*)v.pdist, (const int32_t*)v.pidx, v.part_off, v.pper[step & 1],
+                             spec ? (const int32_t*)v.lab[(step - 1) & 1] : (const int32_t*)nullptr, v.lab[step & 1], spec ? kTileS : kTileC, l.mask);
+          break;
+        }
+        default:
+          dr.pmask = l.mask;
+          dr.expect_reassign = l.kind == rhccq_sched::kReassign ? 1 : 0;
+          dr.draw_first = l.draw_first;
+          dr.draw_count = l.draw_count;
+          dr.reassign_draws = l.reassign_draws;
+          if (l.kind == rhccq_sched::kReassign) {
+            // a reassigning step: the classic update (it draws the batches behind its choice() itself), the inertia in a launch of its own
+            hipLaunchKernelGGL(mbk_update_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state, step,
+                               words, (long long)n_words, bk, dr, (const int32_t*)v.pidx, v.part_off, (const int32_t*)v.lab[step & 1]);
+            hipLaunchKernelGGL(mbk_reassign_apply_kernel, dim3(n_prob, 2), dim3(kUpdThreads), 0, ctx->stream, keys, v.probs, centres, weights, state,
+                               step, words, (long long)n_words, bk, dr);
+            hipLaunchKernelGGL(mbk_inertia_kernel, dim3(n_prob), dim3(64), 0, ctx->stream, v.probs, state, step, (const double*)v.pper[step & 1], l.mask);
+          } else {
+            hipLaunchKernelGGL(mbk_pipe_kernel, dim3(kPipeRoles + (l.spec_next ? l.spec_tiles * kSpecChunks : 0), n_prob), dim3(kPipeThreads), 0,
+                               ctx->stream, keys, v.probs, centres, weights, state, step, words, (long long)n_words, bk, dr,
+                               (const int32_t*)v.lab[step & 1], (const double*)v.pper[step & 1], (const uint32_t*)v.bkeys[(step + 1) & 3], v.pdist, v.pidx,
+                               v.part_off);
+          }
+      }
+    }
   }
-  *carry = (drawn > step0 + n_steps ? 1 : 0) | (have_spec ? 2 : 0);
+  if (classic_mask && n_steps > 0)
+    hipLaunchKernelGGL(mbk_inertia_kernel, dim3(n_prob), dim3(64), 0, ctx->stream, v.probs, state, step0 + n_steps - 1,
+                       (const double*)v.pper[(step0 + n_steps - 1) & 1], classic_mask);
+  for (int p = 0; p < n_prob; ++p)
+    if ((fast_mask >> p) & 1u) carry[p] = sched.carry(p);
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
+}
+
+// rhccq_mbk_steps_batch for ONE problem on the overlapped schedule
+int rhccq_mbk_steps_overlapped(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, int64_t step0,
+                               int32_t n_steps, const uint32_t* words, int64_t n_words, double* centres, double* weights, double* state,
+                               void* work, int64_t work_bytes, int32_t estep_split, int64_t since0, int32_t* carry) {
+  if (n_prob != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_steps_overlapped: exactly one problem");
+  return rhccq_mbk_steps_batch(ctx, keys, probs, 1, step0, n_steps, words, n_words, centres, weights, state, work, work_bytes, estep_split, 1u, 0u, 0,
+                               &since0, carry);
 }
 
 int rhccq_mbk_assign(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, const double* centres,

@@ -1,4 +1,6 @@
-// Overlapped mini-batch steps for ONE straggler problem (included by k8_minibatch.hip behind the update kernel).
+// Overlapped mini-batch steps for a straggler problem, or a small batch of them (included by k8_minibatch.hip behind the update kernel).
+// The kernels index everything by problem (blockIdx.y) and a launch names the problems it is for in a bit mask (mbk_masked): the
+// host gives problems whose launch parameters agree at a step one launch (mbk_schedule.h, rhccq_mbk_steps_batch).
 //
 // A 4K frame's critical path ends in one MiniBatchKMeans problem that runs its full 100 * n / 1000 steps (~2 000) while every
 // other problem has converged: three dependent launches per step (E-step over all k centres, fold, update), ~30 us, of which the
@@ -235,6 +237,7 @@ __global__ __launch_bounds__(kPipeThreads) void mbk_pipe_kernel(const uint32_t* 
                                                                 int32_t* __restrict__ pidx, const long long* __restrict__ part_off) {
   __shared__ __align__(16) unsigned char smem[kPipeLds];
   const int p = blockIdx.y, tid = threadIdx.x;
+  if (mbk_masked(dr.pmask, p)) return;
 #ifdef RHCCQ_STAMPS
   const unsigned long long _t_pipe = clock64();
 #endif
@@ -281,10 +284,12 @@ __global__ __launch_bounds__(256) void mbk_fix_kernel(const MbkP* __restrict__ p
                                                       const double* __restrict__ centres, const uint32_t* __restrict__ bkeys,
                                                       const double* __restrict__ pdist, const int32_t* __restrict__ pidx,
                                                       const long long* __restrict__ part_off, double* __restrict__ pper,
-                                                      const int32_t* __restrict__ lab_prev, int32_t* __restrict__ lab_out, int tile_c) {
+                                                      const int32_t* __restrict__ lab_prev, int32_t* __restrict__ lab_out, int tile_c,
+                                                      unsigned pmask) {
   __shared__ double s_d[4][kFixPts], s_p[4][kFixPts];
   __shared__ int s_j[4][kFixPts];
   const int p = blockIdx.y;
+  if (mbk_masked(pmask, p)) return;
   const MbkP P = probs[p];
   const long long po = part_off[p];
   if (mbk_stopped(state + p * 16, step, P.n)) return;

@@ -27,6 +27,7 @@ struct rhccq_ctx {
   void (*frame_state_free)(void*) = nullptr;
   int opt_init_shards = 1;   // workgroups per problem of the second-generation chain: 1 = one (default), 2 / 4 / 8 = at most that many
   int opt_frame_chains = 1;  // rhccq_encode_frame: the level-1 k-means++ chains of a frame in one launch (1, default) or one per problem lane (0)
+  int opt_frame_level2 = 1;  // rhccq_encode_frame: the level-2 palettes of all classes in one batch on one lane (1, default) or per class lane (0)
   int compute_units = 0;     // of `device`, asked once by the first launch that sizes its grid by it (csrc/palette_remap.hip)
 };
 

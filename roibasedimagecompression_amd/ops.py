@@ -223,6 +223,7 @@ class Rhccq:
     OPT_INIT_LDS_BLOCKS, OPT_INIT_MAX_ITEMS, OPT_INIT_KERNEL, OPT_INIT_SHARDS, OPT_INIT_CANDS_PER_WAVE, OPT_REASSIGN_LDS = 1, 2, 3, 4, 5, 6
     OPT_REASSIGN_ORDER = 7           # 1 (default): numpy's scalar-quicksort tie order of the capped reassignment; 0: stable (rounds 1-3)
     OPT_FRAME_CHAINS = 8             # rhccq_encode_frame: 1 (default) one launch for the frame's level-1 k-means++ chains; 0: one per problem lane
+    OPT_FRAME_LEVEL2 = 9             # rhccq_encode_frame: 1 (default) the level-2 palettes of all classes as one batch on one lane; 0: one per class lane
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""

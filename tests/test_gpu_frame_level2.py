@@ -1,0 +1,190 @@
+"""RHCCQ_OPT_FRAME_LEVEL2: the level-2 palettes of all classes of a frame clustered in ONE call on one lane, their MiniBatchKMeans problems as
+one batch (default), against one level-2 clustering per class lane.  Both must give the same frame bit for bit, and both the frame of
+FrameEncoder.encode -- palette, index map, unique-colour counts, window and level-3 quality.  GPU only.
+
+The frames are uniform-random RGB in horizontal bands, one class and one segment per band, so that nearly every pixel is a colour of its
+own: a band of P colours at level-1 quality q leaves P q / 1000 entries (MiniBatchKMeans, no cluster above max_colors for q <= 50), and
+the class's level 2 takes the MiniBatchKMeans path from 10 000 entries on.  At q = 50 that is ~205 000 pixels per class; k = n / 10 at
+level 2 (quality 100) then just passes the 1 024 centres the overlapped step schedule asks for."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rh():
+    from roibasedimagecompression_amd.ops import Rhccq
+    r = Rhccq(0)
+    yield r
+    r.set_option(Rhccq.OPT_FRAME_LEVEL2, 1)
+
+
+def _bands(rh, img, rows, quals, empty=()):
+    """one class per band of `rows` rows (one region, one segment); classes in `empty` get a label map without pixels"""
+    import torch
+    from roibasedimagecompression_amd.frame import ClassSpec
+    H, W = img.shape[:2]
+    specs, r = [], 0
+    for ci, (h, q) in enumerate(zip(rows, quals)):
+        lab = np.zeros((H, W), np.int32)
+        if ci not in empty:
+            lab[r:r + h] = 1
+        specs.append(ClassSpec(torch.from_numpy(lab).to(rh.device), np.zeros(1, np.int64), [(r, 0, r + h, W)], q))
+        r += h
+    assert r == H
+    return torch.from_numpy(img).to(rh.device), specs
+
+
+def _random_frame(H, W, seed):
+    return np.random.RandomState(seed).randint(0, 256, (H, W, 3)).astype(np.uint8)
+
+
+def _same(a, b):
+    import torch
+    assert np.array_equal(a["palette"], b["palette"])
+    assert a["indices_dtype"] == b["indices_dtype"] and torch.equal(a["indices"], b["indices"])
+    assert np.array_equal(a["n_unique"], b["n_unique"])
+    assert tuple(a["shape"]) == tuple(b["shape"]) and tuple(a["top_left"]) == tuple(b["top_left"]) and a["quality3"] == b["quality3"]
+
+
+def _fits(rh):
+    """the level-2 MiniBatchKMeans fits of the last native frame: rows of (class, points, k, steps, schedule, overlapped_from)"""
+    info = np.zeros((8, 6), np.int64)
+    n = rh._raw.rhccq_encode_frame_level2_info(rh.ctx, 8, info.ctypes.data)
+    assert 0 <= n <= 8
+    return info[:n]
+
+
+def _three_ways(rh, rgb, specs):
+    """switch 1 == switch 0 == FrameEncoder.encode; returns the result, the level-2 fits of the joined stage and its per-class clocks"""
+    from roibasedimagecompression_amd.frame import FrameEncoder
+    from roibasedimagecompression_amd.ops import Rhccq
+    enc = FrameEncoder(rh)
+    out, fits, clocks = {}, None, None
+    for opt in (1, 0, 1):                     # the joined stage twice: warm lanes and reused arenas must not matter
+        rh.set_option(Rhccq.OPT_FRAME_LEVEL2, opt)
+        r = enc.encode_native(rgb, specs)
+        if opt == 1:
+            f = _fits(rh)
+            assert fits is None or np.array_equal(f, fits)
+            fits = f
+            clocks = enc.class_timings
+            cn = ("level1_cluster", "first_positions_merge", "level2_cluster", "level2_finish")
+            assert all(tuple(tm) == cn for tm in clocks.values())
+        else:
+            assert len(_fits(rh)) == 0       # (the per-class path reports none)
+        if opt in out:
+            _same(out[opt], r)
+        out[opt] = r
+    rh.set_option(Rhccq.OPT_FRAME_LEVEL2, 1)
+    _same(out[0], out[1])
+    _same(enc.encode(rgb, specs), out[1])
+    return out[1], fits, clocks
+
+
+def test_two_classes_one_batch_different_step_counts(rh):
+    """both classes on the batched path with different n and k: both on the overlapped schedule from step 16, and the one that converges
+    first is masked out while the other runs on"""
+    rgb, specs = _bands(rh, _random_frame(700, 700, 1), (385, 315), (50, 50))
+    _, fits, clocks = _three_ways(rh, rgb, specs)
+    assert len(fits) == 2 and fits[:, 0].tolist() == [0, 1]
+    assert (fits[:, 1] >= 10000).all() and (fits[:, 2] >= 1024).all()                 # MiniBatchKMeans path, k fit for the overlapped schedule
+    assert fits[0, 1] != fits[1, 1] and fits[0, 2] != fits[1, 2]
+    assert (fits[:, 4] == 2).all() and (fits[:, 5] == 16).all()                       # in the batch, overlapped after the first 16 steps
+    assert fits[0, 3] != fits[1, 3] and (fits[:, 3] > 16 + 64).any()                  # one stops chunks before the other
+    # the joined stage's clock is level2_cluster of both classes
+    assert clocks[0]["level2_cluster"] == clocks[1]["level2_cluster"] > 0.0
+
+
+def test_one_class_batched_one_below_threshold(rh):
+    """the second class's merged palette (~3 200 entries) stays below the MiniBatchKMeans threshold: DBSCAN path, in the same clustering call"""
+    rgb, specs = _bands(rh, _random_frame(450, 640, 1), (350, 100), (50, 50))
+    out, fits, _ = _three_ways(rh, rgb, specs)
+    assert out["n_unique"][1] * 50 // 1000 < 10000
+    assert len(fits) == 1 and fits[0, 0] == 0 and fits[0, 1] >= 10000 and fits[0, 4] == 0     # a lone problem: its own fit
+
+
+def test_one_class_without_component(rh):
+    """the second class has no pixel: it hands nothing to the level-2 stage and adds only its share of the level-3 quality"""
+    rgb, specs = _bands(rh, _random_frame(700, 640, 1), (350, 350), (50, 50), empty=(1,))
+    out, fits, clocks = _three_ways(rh, rgb, specs)
+    assert out["n_unique"][1] == 0 and out["quality3"] == 100
+    assert len(fits) == 1 and fits[0, 0] == 0 and fits[0, 1] >= 10000
+    assert clocks[0]["level2_cluster"] > 0.0 and clocks[1]["level2_cluster"] == 0.0 and clocks[1]["level2_finish"] == 0.0
+
+
+def test_three_classes_two_batched(rh):
+    rgb, specs = _bands(rh, _random_frame(760, 700, 1), (340, 320, 100), (50, 50, 50))
+    _, fits, clocks = _three_ways(rh, rgb, specs)
+    assert len(fits) == 2 and fits[:, 0].tolist() == [0, 1] and (fits[:, 1] >= 10000).all() and (fits[:, 4] == 2).all()
+    assert fits[0, 3] != fits[1, 3]
+    t = [clocks[ci]["level2_cluster"] for ci in range(3)]
+    assert t[0] == t[1] == t[2] > 0.0                                                   # all three were served by the one call
+
+
+def test_quality_zero_still_refused(rh):
+    """a class quality of 0 is refused by rhccq_params inside the class thread, before anything reaches the level-2 stage: RHCCQ_E_ARG"""
+    from roibasedimagecompression_amd.frame import FrameEncoder
+    from roibasedimagecompression_amd.ops import Rhccq, RhccqError
+    img = _random_frame(96, 96, 2)
+    rgb, specs = _bands(rh, img, (48, 48), (50, 0))
+    enc = FrameEncoder(rh)
+    for opt in (1, 0):
+        rh.set_option(Rhccq.OPT_FRAME_LEVEL2, opt)
+        with pytest.raises(RhccqError, match=r"\(-1\).*rhccq_params"):
+            enc.encode_native(rgb, specs)
+    rh.set_option(Rhccq.OPT_FRAME_LEVEL2, 1)
+    # ... and the context still works afterwards
+    rgb, specs = _bands(rh, img, (48, 48), (50, 50))
+    _same(enc.encode(rgb, specs), enc.encode_native(rgb, specs))
+
+
+def _level2_points(enc, rgb, specs):
+    """the non-black colours of every class's level-2 palette, in palette order (what MiniBatchKMeans draws from), and their k"""
+    from oracle import rhccq_oracle as O
+    S = enc.prepare(rgb, specs)
+    _, _, jobs2 = enc.level2_jobs(S, enc.level1(S))
+    out = []
+    for jb in jobs2:
+        keys = np.asarray(jb["keys"])
+        keys = keys[keys != 0]
+        out.append((O.unpack_rgb(keys), int(np.ceil(len(keys) * jb["quality"] / 100 / 10))))
+    return out
+
+
+def test_problem_with_zero_weight_centres_beside_an_overlapped_one(rh):
+    """One problem of the batch never gets weight on all its centres while the other goes to the overlapped schedule.
+
+    What the schedules allow: a problem enters the overlapped schedule only once no centre has zero weight, and sklearn's update never
+    takes weight away (a reassigned centre gets the smallest weight of the centres that stay), so a problem cannot LOSE the condition
+    later; the device still checks it every step (state 5).  What does happen is a problem that has not reached it.  Here class 0
+    (45 500 colours at quality 100, k = 4 549) sees 1 000 of its points per step: more than 500 centres are without weight at every
+    step, each step moves the capped 500 of them, and the fit ends by the early-stopping rule after a dozen steps with centres still
+    unweighted; class 1 (12 000 colours, k = 1 200) is overlapped from step 16 and runs ~70 steps.  The CPU oracle confirms both on the
+    palettes themselves: class 0 reassigns 500 centres at EVERY one of its steps (which, 10 k samples not being reached, only a
+    zero-weight centre makes it do), class 1 reassigns nothing at step 17."""
+    from oracle import rhccq_oracle as O
+    rgb, specs = _bands(rh, _random_frame(240, 240, 1), (190, 50), (100, 100))
+    from roibasedimagecompression_amd.frame import FrameEncoder
+    _, fits, _ = _three_ways(rh, rgb, specs)
+    assert len(fits) == 2 and (fits[:, 1] >= 10000).all()
+    (p0, k0), (p1, k1) = _level2_points(FrameEncoder(rh), rgb, specs)
+    assert (len(p0), k0, len(p1), k1) == (fits[0, 1], fits[0, 2], fits[1, 1], fits[1, 2])
+    o0 = O.minibatch_kmeans_native(p0, k0, want_labels=False)[1]
+    assert o0["n_steps"] < 16 and 16000 < 10 * k0 and o0["n_reassigned"] == 500 * o0["n_steps"]      # zero-weight centres to its last step
+    o16, o17 = (O.minibatch_kmeans_native(p1, k1, max_steps=s, want_labels=False)[1] for s in (16, 17))
+    assert o17["n_steps"] == 17 and o17["n_reassigned"] == o16["n_reassigned"]                       # no centre without weight after 16 steps
+    assert fits[0, 3] == o0["n_steps"] and fits[0, 4] == 1 and fits[0, 5] == -1                      # classic steps only, in the batch
+    assert fits[1, 4] == 2 and fits[1, 5] == 16 and fits[1, 3] > 16                                # overlapped for the rest of its steps
+
+
+def test_classic_and_overlapped_problems_share_chunks(rh):
+    """A problem below the 1 024 centres the overlapped schedule asks for (class 1: quality 40, level 2 at 80: k = 0.08 n) keeps the classic
+    sequence for all its steps while the other problem of the batch runs overlapped: every chunk launches both schedules side by side."""
+    rgb, specs = _bands(rh, _random_frame(745, 700, 4), (315, 430), (50, 40))
+    _, fits, _ = _three_ways(rh, rgb, specs)
+    assert len(fits) == 2 and (fits[:, 1] >= 10000).all()
+    assert fits[0, 2] >= 1024 and fits[0, 4] == 2 and fits[0, 5] == 16
+    assert fits[1, 2] < 1024 and fits[1, 4] == 1 and fits[1, 5] == -1
+    assert (fits[:, 3] > 16).all()                                                      # both ran on behind the first 16 steps, in the same chunks
