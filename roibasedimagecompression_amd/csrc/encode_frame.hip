@@ -34,6 +34,7 @@
 
 #include "frame_level2_host.h"
 #include "host_raii.h"
+#include "mbk_fit_host.h"
 #include "rhccq_common.h"
 
 namespace {
@@ -229,9 +230,7 @@ struct Lane {
   Arena arena;
   Stream stream;
   Ctx ctx;
-  Pinned<double> pinned;                               // 3 x 16 doubles: landing buffers of the asynchronous state polls
-  Pinned<double> pinned_batch;                         // 3 x n_prob x 16 doubles: the same for a batch of problems (mbk_fit_batch), kept between frames
-  size_t pinned_batch_n = 0;
+  Pinned<double> pinned;                               // 3 x 32 x 16 doubles: landing buffers of the asynchronous state polls of a fit (mbk_fit)
   Event ev[3];
   std::vector<std::unique_ptr<Lane>> sub;              // further siblings (the MiniBatchKMeans problems of a class)
 
@@ -239,7 +238,7 @@ struct Lane {
     EF_HIP(hipSetDevice(dev));
     stream = make_stream();
     ctx = make_ctx(dev, stream.get());
-    pinned = make_pinned<double>(3 * 16);
+    pinned = make_pinned<double>(3 * rhccq_fit::kMaxProblems * rhccq_fit::kStateDoubles);
     for (auto& e : ev) e = make_event();
   }
   Lane& sublane(size_t i) {
@@ -285,13 +284,6 @@ struct Lane {
     EF_HIP(hipStreamSynchronize(stream.get()));
   }
   void sync() { EF_HIP(hipStreamSynchronize(stream.get())); }
-  double* batch_landing(size_t n_prob) {               // (grown while nothing of this lane is in flight: the caller has synchronised)
-    if (pinned_batch_n < n_prob) {
-      pinned_batch = make_pinned<double>(3 * 16 * n_prob);
-      pinned_batch_n = n_prob;
-    }
-    return pinned_batch.get();
-  }
 };
 
 struct Level2Fit {                                       // one MiniBatchKMeans fit of the frame's level-2 stage
@@ -307,43 +299,31 @@ struct FrameState {
 };
 void free_frame_state(void* p) { delete (FrameState*)p; }
 
-// ---- MiniBatchKMeans(k, batch_size=1000, random_state=42, n_init='auto').fit_predict of ONE palette resident on the device
-// (ops.py::minibatch_kmeans for one problem; reference call site clustering.py:207-218) --------------------------------------
+// ---- MiniBatchKMeans(k, batch_size=1000, random_state=42, n_init='auto').fit_predict of 1 .. 32 palettes resident on the device
+// (ops.py::minibatch_kmeans; reference call site clustering.py:207-218).  What the host decides on the way is mbk_fit_host.h ------------
 // The draws of one fit ahead of its k-means++ chain (sklearn _init_centroids with init_size, then kmeans_plusplus): host only
 struct MbkDraws {
-  int64_t init_size = 0;
+  rhccq_fit::Problem c;
   std::vector<int32_t> init_idx;
-  int32_t first = 0;
-  int T = 0;
-  int64_t pos = 0;                                     // raw MT19937 word of the first k-means++ uniform
-  int64_t nu = 0;                                      // uniforms of the chain
-  int64_t cursor0 = 0;                                 // stream position behind the k-means++ uniforms
 };
 
 MbkDraws mbk_draws(int64_t n, int64_t k) {
   MtTable& mt = MtTable::get();
   MbkDraws d;
-  const int64_t bs = std::min<int64_t>(1000, n);
-  d.init_size = 3 * bs;
-  if (d.init_size < k) d.init_size = 3 * k;
-  d.init_size = std::min(d.init_size, n);
+  d.c = rhccq_fit::problem(n, k);
+  const int64_t init_size = d.c.init_size;
   int64_t pos = 0;
-  pos += mt.randint(pos, n, d.init_size, nullptr);                       // validation_indices: stream position only
-  d.init_idx.resize((size_t)d.init_size);
-  if (d.init_size < n) pos += mt.randint(pos, n, d.init_size, d.init_idx.data());
+  pos += mt.randint(pos, n, init_size, nullptr);                         // validation_indices: stream position only
+  d.init_idx.resize((size_t)init_size);
+  if (init_size < n) pos += mt.randint(pos, n, init_size, d.init_idx.data());
   else for (int64_t i = 0; i < n; ++i) d.init_idx[(size_t)i] = (int32_t)i;
-  d.first = first_centre_index(d.init_size, mt.dbl(pos));
-  pos += 2;
-  d.T = 2 + (int)std::log((double)k);
-  d.nu = std::max<int64_t>((k - 1) * d.T, 1);
-  d.pos = pos;
-  d.cursor0 = pos + 2 * (k - 1) * d.T;
+  const int32_t first = first_centre_index(init_size, mt.dbl(pos));
+  rhccq_fit::chain_at(d.c, pos + 2, first);
   return d;
 }
 
 // A chain run ahead for one fit (RHCCQ_OPT_FRAME_CHAINS): its centres once `done` has fired
 struct PreChain {
-  int64_t n = 0, k = 0;
   MbkDraws draws;
   double* centres = nullptr;                           // [k][4], written by the chain, then the fit's own
   hipEvent_t done = nullptr;
@@ -353,327 +333,165 @@ struct PreChain {
 // moves a problem to another generation of the chain than the one it gets alone
 constexpr int64_t kFrameChainMaxInit = 98304;
 
-// `steps_out`: the steps the fit ran
-void mbk_fit(Lane& L, const uint32_t* keys, int64_t n, int64_t k, int32_t* labels_out, const PreChain* pre = nullptr, int64_t* steps_out = nullptr) {
-  rhccq_ctx* c = L.ctx.get();
-  MtTable& mt = MtTable::get();
-  const bool tr = trace_on();
-  double tt[6] = {now_ms(), 0, 0, 0, 0, 0};
-  double ts[4] = {0, 0, 0, 0};                                           // (trace) set-up: host draws, word table, uniforms + upload
-  const int64_t bs = std::min<int64_t>(1000, n);
-  MbkDraws own;
-  if (!pre) own = mbk_draws(n, k);
-  else if (pre->n != n || pre->k != k) throw Err{RHCCQ_E_ARG, "mbk_fit: the frame's chain was run for another problem"};
-  const MbkDraws& dr = pre ? pre->draws : own;
-  const int64_t init_size = dr.init_size, cursor0 = dr.cursor0;
-  rhccq_mbk_problem prob;
-  prob.off = 0; prob.n = n; prob.k = k; prob.koff = 0; prob.init_off = 0; prob.init_n = init_size; prob.rand_off = 0;
-  prob.first = dr.first; prob.T = dr.T;
+// (RHCCQ_TRACE) the clocks of a chain set-up, taken behind the stream's work up to there (sync) or as host time only
+struct ChainClocks {
+  bool sync = true;
+  double words = 0, uploaded = 0, ordered = 0, chained = 0;
+};
+
+// The k-means++ chains of `probs` (off / n / k the caller's, the rest laid out: rhccq_fit::Totals) as ONE launch on c's stream: every
+// problem's uniforms from its own MT19937 word, the init samples in one upload, one Morton order, zeroed centres and `chosen`,
+// rhccq_mbk_init with a workgroup per problem (the kernels treat the problems of a batch independently).  Returns the centres [ktot][4].
+double* mbk_chains(rhccq_ctx* c, Arena& A, const uint32_t* keys, const std::vector<rhccq_mbk_problem>& probs, const std::vector<const MbkDraws*>& draws,
+                   const rhccq_fit::Totals& tot, ChainClocks* clk) {
+  const hipStream_t stream = c->stream;
+  auto mark = [&](double ChainClocks::*t, bool sync) {
+    if (!clk) return;
+    if (sync && clk->sync) EF_HIP(hipStreamSynchronize(stream));
+    clk->*t = now_ms();
+  };
+  const int32_t N = (int32_t)probs.size();
   const uint32_t* words;
   int64_t n_words;
-  double* centres;
-  if (pre) {                                                             // the frame's launch ran the chain: wait for it on this lane
-    EF_HIP(hipStreamWaitEvent(L.stream.get(), pre->done, 0));
-    centres = pre->centres;
-    if (tr) { tt[1] = now_ms(); L.sync(); tt[2] = now_ms(); }
-  } else {
-    if (tr) ts[0] = now_ms();
-    mt.device(L.device, dr.pos + 2 * dr.nu, &words, &n_words);
-    if (tr) ts[1] = now_ms();
-    double* d_rand = L.dalloc<double>((size_t)dr.nu);
-    EF_RC(c, rhccq_mt_uniforms(c, words, dr.pos, dr.nu, d_rand));
-    int32_t* d_init = L.upload(dr.init_idx.data(), (size_t)init_size);
-    if (tr) { L.sync(); ts[2] = now_ms(); }
-    const int64_t obytes = rhccq_mbk_order_bytes(init_size);
-    void* otmp = L.arena.alloc((size_t)obytes);
-    int32_t* d_perm = L.dalloc<int32_t>((size_t)init_size);
-    EF_RC(c, rhccq_mbk_order(c, keys, &prob, 1, d_init, d_perm, otmp, obytes));
-    centres = L.dzeros<double>((size_t)k * 4);
-    int32_t* chosen = L.dzeros<int32_t>((size_t)k);
-    if (tr) { L.sync(); tt[1] = now_ms(); }
-    EF_RC(c, rhccq_mbk_init(c, keys, &prob, 1, d_init, d_perm, d_rand, centres, chosen));
-    if (tr) { L.sync(); tt[2] = now_ms(); }
+  MtTable::get().device(c->device, tot.words, &words, &n_words);
+  mark(&ChainClocks::words, false);
+  double* d_rand = (double*)A.alloc((size_t)tot.utot * 8);
+  std::vector<int32_t> init_idx;
+  init_idx.reserve((size_t)tot.itot);
+  for (int32_t p = 0; p < N; ++p) {
+    const MbkDraws& d = *draws[(size_t)p];
+    EF_RC(c, rhccq_mt_uniforms(c, words, d.c.pos, d.c.n_uniforms, d_rand + probs[(size_t)p].rand_off));
+    init_idx.insert(init_idx.end(), d.init_idx.begin(), d.init_idx.end());
   }
-  double* weights = L.dzeros<double>((size_t)k);
-  double st[16] = {0};
-  st[8] = (double)k;                                                     // every centre starts with zero weight
-  st[9] = (double)cursor0;                                               // MT19937 words consumed so far
-  double* state = L.upload(st, 16);
-  int64_t cur_max = cursor0;
-  const int64_t WORDS_PER_STEP = 16384;                                  // kWordsMargin of mbk_update_kernel
-  const int64_t wbytes = rhccq_mbk_work_bytes(&prob, 1);
-  void* work = L.arena.alloc((size_t)std::max<int64_t>(wbytes, 8));
-  const int64_t limit = (100 * n) / bs;
-  int64_t step = 0;
-  bool running = true;
-  auto check = [&](const double* s) {
-    if (s[4] == 3.0) throw Err{RHCCQ_E_LIMIT, "mini-batch steps ran past the end of the MT19937 word table (internal sizing error)"};
-    if (s[4] == 4.0) throw Err{RHCCQ_E_LIMIT, "the sharded k-means++ chain gave up waiting for a partner workgroup"};
-    if (s[4] == 5.0) throw Err{RHCCQ_E_LIMIT, "the overlapped mini-batch schedule and the device state disagree about a reassignment"};
-  };
-  const int tiles_mode = k >= 200000 ? RHCCQ_ESTEP_GRID : RHCCQ_ESTEP_TILES;
-  int split = 8;
-  for (int sp : {1, 2, 4, 8})
-    if (((k + 511) / 512) * 2 * sp >= 1536) { split = sp; break; }
-  while (running) {
-    const int par = (int)(step & 1);
-    // a lone problem whose centres all carry weight: the next E-step starts beside the update (rhccq_mbk_steps_overlapped)
-    if (step > 0 && tiles_mode == RHCCQ_ESTEP_TILES && k >= 1024 && st[par ? 13 : 8] == 0.0) {
-      int64_t since = (int64_t)st[par ? 12 : 3];
-      int32_t carry = 0;
-      const int chunk = 64;
-      int64_t cur_known = cur_max, steps_known = step;
-      struct Pending { int slot; };
-      std::vector<Pending> pending;
-      int n_chunk = 0;
-      bool stop = false;
-      while (!stop) {
-        if (step < limit) {
-          const int ns = (int)std::min<int64_t>(chunk, limit - step);
-          mt.device(L.device, cur_known + (step - steps_known + ns + 4) * 4200 + 8 * WORDS_PER_STEP, &words, &n_words);
-          EF_RC(c, rhccq_mbk_steps_overlapped(c, keys, &prob, 1, step, ns, words, n_words, centres, weights, state, work, wbytes, split, since,
-                                               &carry));
-          for (int i = 0; i < ns; ++i) {                                  // the schedule's own arithmetic (sklearn _random_reassign)
-            since += bs;
-            if (since >= 10 * k) since = 0;
-          }
-          step += ns;
-          const int slot = n_chunk % 3;
-          ++n_chunk;
-          EF_HIP(hipMemcpyAsync(L.pinned.get() + 16 * slot, state, 16 * sizeof(double), hipMemcpyDeviceToHost, L.stream.get()));
-          EF_HIP(hipEventRecord(L.ev[slot].get(), L.stream.get()));
-          pending.push_back(Pending{slot});
-        }
-        if (pending.size() >= 2 || step >= limit) {
-          const int slot = pending.front().slot;
-          pending.erase(pending.begin());
-          EF_HIP(hipEventSynchronize(L.ev[slot].get()));
-          std::memcpy(st, L.pinned.get() + 16 * slot, sizeof(st));
-          cur_known = (int64_t)std::max(st[9], st[14]);
-          steps_known = (int64_t)st[5];
-          if (st[4] >= 3.0 || st[11] != 0.0 || st[5] >= (double)limit) stop = true;
-          else if (pending.empty() && step >= limit) stop = true;
-        }
-      }
-      if (!pending.empty()) {                                             // launches queued behind the stop: they return at once
-        EF_HIP(hipEventSynchronize(L.ev[pending.back().slot].get()));
-        std::memcpy(st, L.pinned.get() + 16 * pending.back().slot, sizeof(st));
-      }
-      check(st);
-      break;
-    }
-    // most problems converge within a dozen steps: look early once
-    const int ns = (int)std::min<int64_t>(step ? 64 : 16, std::max<int64_t>(1, limit - step));
-    mt.device(L.device, cur_max + (ns + 3) * WORDS_PER_STEP, &words, &n_words);
-    int mode = tiles_mode;
-    if (step > 0 && st[par ? 13 : 8] == 0.0 && st[par ? 12 : 3] + (double)(ns * bs) < (double)(10 * k)) mode |= RHCCQ_STEPS_NO_REASSIGN;
-    EF_RC(c, rhccq_mbk_steps(c, keys, &prob, 1, step, ns, words, n_words, centres, weights, state, work, wbytes, mode, split));
-    step += ns;
-    L.download(st, state, 16);
-    cur_max = (int64_t)std::max(st[9], st[14]);
-    check(st);
-    running = st[11] == 0.0 && st[5] < (double)limit;
-  }
-  if (tr) { L.sync(); tt[3] = now_ms(); }
-  if (steps_out) *steps_out = (int64_t)st[5];
-  EF_RC(c, rhccq_mbk_assign(c, keys, &prob, 1, centres, work, wbytes, labels_out));
-  if (tr) {
-    L.sync();
-    tt[4] = now_ms();
-    if (pre)
-      fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: chain in the frame's launch, waited %.2f ms for it, %lld steps %.2f ms, assign %.2f ms\n", (long long)n,
-              (long long)k, tt[2] - tt[0], (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
-    else
-      fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms (host draws %.2f, word table %.2f, uniforms+upload %.2f, order %.2f), chain %.2f ms "
-              "(%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", (long long)n, (long long)k, tt[1] - tt[0], ts[0] - tt[0], ts[1] - ts[0],
-              ts[2] - ts[1], tt[1] - ts[2], tt[2] - tt[1], (tt[2] - tt[1]) * 1e3 / (double)k, (long long)st[5], tt[3] - tt[2], tt[4] - tt[3]);
-  }
+  int32_t* d_init = (int32_t*)A.alloc((size_t)tot.itot * 4);
+  EF_HIP(hipMemcpyAsync(d_init, init_idx.data(), (size_t)tot.itot * 4, hipMemcpyHostToDevice, stream));   // pageable: staged on return
+  mark(&ChainClocks::uploaded, true);
+  const int64_t obytes = rhccq_mbk_order_bytes(tot.itot);
+  void* otmp = A.alloc((size_t)obytes);
+  int32_t* d_perm = (int32_t*)A.alloc((size_t)tot.itot * 4);
+  EF_RC(c, rhccq_mbk_order(c, keys, probs.data(), N, d_init, d_perm, otmp, obytes));
+  double* centres = (double*)A.alloc((size_t)tot.ktot * 4 * 8);
+  int32_t* chosen = (int32_t*)A.alloc((size_t)tot.ktot * 4);
+  EF_HIP(hipMemsetAsync(centres, 0, (size_t)tot.ktot * 4 * 8, stream));
+  EF_HIP(hipMemsetAsync(chosen, 0, (size_t)tot.ktot * 4, stream));
+  mark(&ChainClocks::ordered, true);
+  EF_RC(c, rhccq_mbk_init(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen));
+  mark(&ChainClocks::chained, true);
+  return centres;
 }
 
-// ---- the same fit for a BATCH of problems on one lane and one stream (the frame's level-2 stage, RHCCQ_OPT_FRAME_LEVEL2) ----------
-// Every problem keeps what mbk_fit makes for it alone: its MT19937 positions, draws, init samples, T, first centre, step count and
-// stopping rule.  The kernels take (probs, n_prob) and treat the problems of a batch independently; what the batch shares is the
-// launches: one ordering, one chain launch with a workgroup per problem, one step sequence (rhccq_mbk_steps_batch: a problem is on
-// the overlapped schedule from the chunk at which mbk_fit would put it there, on the classic one until then, and masked out once it
-// has stopped), one assignment.  probs: off / n / k set by the caller (key offsets into `keys`); labels_out at the key offsets.
 struct BatchFit {
   int64_t steps = 0;                                   // out: steps the problem ran
   int64_t overlapped_from = -1;                        // out: the step at which it went to the overlapped schedule (-1: never)
 };
 
-void mbk_fit_batch(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& probs, int32_t* labels_out, std::vector<BatchFit>& fits) {
+// The fit of 1 .. 32 problems on one lane and one stream.  probs: off / n / k set by the caller (key offsets into `keys`); labels_out at
+// the key offsets.  Every problem keeps its own MT19937 positions, draws, init samples, T, first centre, step count and stopping rule;
+// what a batch shares is the launches: one ordering, one chain launch, one step sequence (rhccq_fit::Plan: the first 16 steps classic,
+// then chunks of 64 with every problem on the schedule its state asks for, masked out once it has stopped), one assignment.
+// pre (one problem only): its chain ran in the frame's launch.  Nothing between the chain and the first steps waits on the host.
+void mbk_fit(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& probs, int32_t* labels_out, std::vector<BatchFit>* fits = nullptr,
+             const PreChain* pre = nullptr) {
   rhccq_ctx* c = L.ctx.get();
-  MtTable& mt = MtTable::get();
   const int N = (int)probs.size();
-  if (N < 1 || N > 32) throw Err{RHCCQ_E_ARG, "mbk_fit_batch: 1 .. 32 problems"};
+  if (N < 1 || N > rhccq_fit::kMaxProblems) throw Err{RHCCQ_E_ARG, "mbk_fit: 1 .. 32 problems"};
+  if (pre && (N != 1 || pre->draws.c.n != probs[0].n || pre->draws.c.k != probs[0].k))
+    throw Err{RHCCQ_E_ARG, "mbk_fit: the frame's chain was run for another problem"};
   const bool tr = trace_on();
-  double tt[5] = {now_ms(), 0, 0, 0, 0};
-  fits.assign((size_t)N, BatchFit());
-  // ---- draws (host), uniforms, Morton order, chains: as frame_chains
-  std::vector<MbkDraws> draws((size_t)N);
-  int64_t ktot = 0, itot = 0, utot = 0, need_words = 1, cur_max = 0, k_max = 0, tiles = 0;
+  const double t0 = now_ms();
+  std::vector<MbkDraws> own(pre ? 0 : (size_t)N);
+  std::vector<const MbkDraws*> draws((size_t)N);
+  std::vector<rhccq_fit::Problem> cs((size_t)N);
+  rhccq_fit::Totals tot;
   for (int p = 0; p < N; ++p) {
-    rhccq_mbk_problem& q = probs[(size_t)p];
-    draws[(size_t)p] = mbk_draws(q.n, q.k);
-    const MbkDraws& d = draws[(size_t)p];
-    q.koff = ktot; q.init_off = itot; q.init_n = d.init_size; q.rand_off = utot; q.first = d.first; q.T = d.T;
-    ktot += q.k;
-    itot += d.init_size;
-    utot += d.nu;
-    need_words = std::max<int64_t>(need_words, d.pos + 2 * d.nu);
-    cur_max = std::max(cur_max, d.cursor0);
-    k_max = std::max(k_max, q.k);
-    tiles += (q.k + 511) / 512;
+    if (!pre) own[(size_t)p] = mbk_draws(probs[(size_t)p].n, probs[(size_t)p].k);
+    draws[(size_t)p] = pre ? &pre->draws : &own[(size_t)p];
+    cs[(size_t)p] = draws[(size_t)p]->c;
+    tot.add(probs[(size_t)p], cs[(size_t)p]);
   }
-  const uint32_t* words;
-  int64_t n_words;
-  mt.device(L.device, need_words, &words, &n_words);
-  double* d_rand = L.dalloc<double>((size_t)utot);
-  std::vector<int32_t> init_idx;
-  init_idx.reserve((size_t)itot);
-  for (int p = 0; p < N; ++p) {
-    const MbkDraws& d = draws[(size_t)p];
-    EF_RC(c, rhccq_mt_uniforms(c, words, d.pos, d.nu, d_rand + probs[(size_t)p].rand_off));   // (a problem's uniforms start at its own word)
-    init_idx.insert(init_idx.end(), d.init_idx.begin(), d.init_idx.end());
+  const double t_draws = now_ms();
+  ChainClocks clk;
+  double* centres;
+  if (pre) {                                                             // the frame's launch ran the chain: wait for it on this lane
+    EF_HIP(hipStreamWaitEvent(L.stream.get(), pre->done, 0));
+    centres = pre->centres;
+    if (tr) { L.sync(); clk.chained = now_ms(); }
+  } else {
+    centres = mbk_chains(c, L.arena, keys, probs, draws, tot, tr ? &clk : nullptr);
   }
-  int32_t* d_init = L.upload(init_idx.data(), (size_t)itot);
-  const int64_t obytes = rhccq_mbk_order_bytes(itot);
-  void* otmp = L.arena.alloc((size_t)obytes);
-  int32_t* d_perm = L.dalloc<int32_t>((size_t)itot);
-  EF_RC(c, rhccq_mbk_order(c, keys, probs.data(), N, d_init, d_perm, otmp, obytes));
-  double* centres = L.dzeros<double>((size_t)ktot * 4);
-  int32_t* chosen = L.dzeros<int32_t>((size_t)ktot);
-  if (tr) { L.sync(); tt[1] = now_ms(); }
-  EF_RC(c, rhccq_mbk_init(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen));
-  if (tr) { L.sync(); tt[2] = now_ms(); }
   // ---- steps
-  double* weights = L.dzeros<double>((size_t)ktot);
-  std::vector<double> st((size_t)N * 16, 0.0);
-  std::vector<int64_t> limit((size_t)N), bs((size_t)N);
-  int64_t limit_max = 0;
-  for (int p = 0; p < N; ++p) {
-    st[(size_t)p * 16 + 8] = (double)probs[(size_t)p].k;                  // every centre starts with zero weight
-    st[(size_t)p * 16 + 9] = (double)draws[(size_t)p].cursor0;            // MT19937 words consumed so far
-    bs[(size_t)p] = std::min<int64_t>(1000, probs[(size_t)p].n);
-    limit[(size_t)p] = (100 * probs[(size_t)p].n) / bs[(size_t)p];
-    limit_max = std::max(limit_max, limit[(size_t)p]);
-  }
-  double* state = L.upload(st.data(), st.size());
-  const int64_t WORDS_PER_STEP = 16384;                                  // kWordsMargin of mbk_update_kernel
+  double* weights = L.dzeros<double>((size_t)tot.ktot);
+  rhccq_fit::Plan plan(cs, tot.tiled());
+  double* state = L.upload(plan.st.data(), plan.st.size());
   const int64_t wbytes = rhccq_mbk_work_bytes(probs.data(), N);
   void* work = L.arena.alloc((size_t)std::max<int64_t>(wbytes, 8));
-  const bool tiled = k_max < 200000;                                     // (mbk_fit's rule for a lone problem; same results either way)
-  int split = 8;
-  for (int sp : {1, 2, 4, 8})
-    if (tiles * 2 * sp >= 1536) { split = sp; break; }
-  L.sync();                                                              // (`st` and `init_idx` are staged; the landing buffer may be regrown)
-  double* landing = L.batch_landing((size_t)N);
-  auto check = [&](const double* s) {
-    if (s[4] == 3.0) throw Err{RHCCQ_E_LIMIT, "mini-batch steps ran past the end of the MT19937 word table (internal sizing error)"};
-    if (s[4] == 4.0) throw Err{RHCCQ_E_LIMIT, "the sharded k-means++ chain gave up waiting for a partner workgroup"};
-    if (s[4] == 5.0) throw Err{RHCCQ_E_LIMIT, "the overlapped mini-batch schedule and the device state disagree about a reassignment"};
-  };
-  // the first steps: classic, all problems (most problems converge within a dozen steps: look early once)
-  int64_t step = 16;
-  mt.device(L.device, cur_max + (16 + 3) * WORDS_PER_STEP, &words, &n_words);
-  EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, 0, 16, words, n_words, centres, weights, state, work, wbytes, tiled ? RHCCQ_ESTEP_TILES : RHCCQ_ESTEP_GRID,
-                           split));
-  L.download(st.data(), state, st.size());
-  std::vector<char> running((size_t)N), fast((size_t)N, 0);
-  std::vector<int64_t> since((size_t)N, 0), cur_known((size_t)N), steps_known((size_t)N);
-  std::vector<int32_t> carry((size_t)N, 0);
-  auto take = [&](const double* snap) {                                  // a state snapshot of all problems
-    std::memcpy(st.data(), snap, st.size() * sizeof(double));
-    for (int p = 0; p < N; ++p) {
-      const double* s = &st[(size_t)p * 16];
-      cur_known[(size_t)p] = (int64_t)std::max(s[9], s[14]);
-      steps_known[(size_t)p] = (int64_t)s[5];
-      running[(size_t)p] = !(s[4] >= 3.0 || s[11] != 0.0 || s[5] >= (double)limit[(size_t)p]);
-    }
-  };
-  take(st.data());
-  for (int p = 0; p < N; ++p) check(&st[(size_t)p * 16]);
+  const int split = tot.split();
+  const size_t snap = plan.st.size();
+  double* landing = L.pinned.get();
   std::vector<int> pending;                                              // landing slots of the snapshots in flight
   int n_chunk = 0;
+  int64_t step = 0;
   while (true) {
-    const int par = (int)(step & 1);
-    uint32_t fast_mask = 0u, classic_mask = 0u;
-    bool no_reassign = true;
-    int64_t need = 0, left = 0;
-    for (int p = 0; p < N; ++p) {
-      if (!running[(size_t)p]) continue;
-      const double* s = &st[(size_t)p * 16];
-      const int64_t k = probs[(size_t)p].k;
-      // a problem whose centres all carry weight goes to the overlapped schedule for the rest of its steps (mbk_fit's rule; a classic
-      // problem's state is always the one of `step`: the loop waits for it below)
-      if (!fast[(size_t)p] && tiled && k >= 1024 && s[par ? 13 : 8] == 0.0) {
-        fast[(size_t)p] = 1;
-        fits[(size_t)p].overlapped_from = step;
-        since[(size_t)p] = (int64_t)s[par ? 12 : 3];
-        carry[(size_t)p] = 0;
-      }
-      left = std::max(left, limit[(size_t)p] - step);
-    }
-    const int ns = (int)std::min<int64_t>(64, left);
-    for (int p = 0; p < N && ns > 0; ++p) {
-      if (!running[(size_t)p]) continue;
-      const double* s = &st[(size_t)p * 16];
-      if (fast[(size_t)p]) {
-        fast_mask |= 1u << p;
-        need = std::max(need, cur_known[(size_t)p] + (step - steps_known[(size_t)p] + ns + 4) * 4200 + 8 * WORDS_PER_STEP);
-      } else {
-        classic_mask |= 1u << p;
-        need = std::max(need, cur_known[(size_t)p] + (ns + 3) * WORDS_PER_STEP);
-        no_reassign = no_reassign && s[par ? 13 : 8] == 0.0 && s[par ? 12 : 3] + (double)(ns * bs[(size_t)p]) < (double)(10 * probs[(size_t)p].k);
-      }
-    }
-    if ((fast_mask | classic_mask) == 0u && pending.empty()) break;
-    if (fast_mask | classic_mask) {
-      mt.device(L.device, need, &words, &n_words);
-      if (tiled)
-        EF_RC(c, rhccq_mbk_steps_batch(c, keys, probs.data(), N, step, ns, words, n_words, centres, weights, state, work, wbytes, split, fast_mask,
-                                       classic_mask, classic_mask && no_reassign ? 1 : 0, since.data(), carry.data()));
-      else                                                               // (the grid E-step: nobody is on the overlapped schedule)
-        EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, step, ns, words, n_words, centres, weights, state, work, wbytes, RHCCQ_ESTEP_GRID, split));
-      for (int p = 0; p < N; ++p)
-        if ((fast_mask >> p) & 1u)
-          for (int i = 0; i < ns; ++i) {                                  // the schedule's own arithmetic (sklearn _random_reassign)
-            since[(size_t)p] += bs[(size_t)p];
-            if (since[(size_t)p] >= 10 * probs[(size_t)p].k) since[(size_t)p] = 0;
-          }
-      step += ns;
+    const rhccq_fit::Chunk ch = plan.next(step);
+    if (!ch.any() && pending.empty()) break;
+    if (ch.any()) {
+      const uint32_t* words;
+      int64_t n_words;
+      MtTable::get().device(L.device, ch.need, &words, &n_words);
+      if (step == 0 || !plan.tiled)                                      // (the first call writes the problem tables; the grid E-step: nobody is overlapped)
+        EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, step, ch.ns, words, n_words, centres, weights, state, work, wbytes,
+                                 (plan.tiled ? RHCCQ_ESTEP_TILES : RHCCQ_ESTEP_GRID) | (ch.no_reassign ? RHCCQ_STEPS_NO_REASSIGN : 0), split));
+      else
+        EF_RC(c, rhccq_mbk_steps_batch(c, keys, probs.data(), N, step, ch.ns, words, n_words, centres, weights, state, work, wbytes, split, ch.fast_mask,
+                                       ch.classic_mask, ch.no_reassign ? 1 : 0, plan.since.data(), plan.carry.data()));
+      plan.advance(ch);
+      step += ch.ns;
       const int slot = n_chunk % 3;
       ++n_chunk;
-      EF_HIP(hipMemcpyAsync(landing + (size_t)slot * 16 * N, state, (size_t)16 * N * sizeof(double), hipMemcpyDeviceToHost, L.stream.get()));
+      EF_HIP(hipMemcpyAsync(landing + (size_t)slot * snap, state, snap * sizeof(double), hipMemcpyDeviceToHost, L.stream.get()));
       EF_HIP(hipEventRecord(L.ev[slot].get(), L.stream.get()));
       pending.push_back(slot);
     }
-    if (classic_mask || !tiled) {                                        // a classic problem's next chunk depends on its state: wait for the newest
+    if (ch.classic_mask) {                                               // a classic problem's next chunk depends on its state: wait for the newest
       EF_HIP(hipEventSynchronize(L.ev[pending.back()].get()));
-      take(landing + (size_t)pending.back() * 16 * N);
+      plan.take(landing + (size_t)pending.back() * snap);
       pending.clear();
-    } else if (pending.size() >= 2 || (fast_mask | classic_mask) == 0u) {  // overlapped problems only: the state two chunks behind
+    } else if (pending.size() >= 2 || !ch.any()) {                       // overlapped problems only: the state two chunks behind
       EF_HIP(hipEventSynchronize(L.ev[pending.front()].get()));
-      take(landing + (size_t)pending.front() * 16 * N);
+      plan.take(landing + (size_t)pending.front() * snap);
       pending.erase(pending.begin());
     }
-    for (int p = 0; p < N; ++p) check(&st[(size_t)p * 16]);
+    if (const char* e = plan.error()) throw Err{RHCCQ_E_LIMIT, e};
   }
-  for (int p = 0; p < N; ++p) fits[(size_t)p].steps = (int64_t)st[(size_t)p * 16 + 5];
-  if (tr) { L.sync(); tt[3] = now_ms(); }
+  if (fits) {
+    fits->assign((size_t)N, BatchFit());
+    for (int p = 0; p < N; ++p) (*fits)[(size_t)p] = BatchFit{plan.view(p).steps_done(), plan.overlapped_from[(size_t)p]};
+  }
+  double t_steps = 0;
+  if (tr) { L.sync(); t_steps = now_ms(); }
   EF_RC(c, rhccq_mbk_assign(c, keys, probs.data(), N, centres, work, wbytes, labels_out));
-  if (tr) {
-    L.sync();
-    tt[4] = now_ms();
+  if (!tr) return;
+  L.sync();
+  const double t_assign = now_ms();
+  const long long n0 = (long long)probs[0].n, k0 = (long long)probs[0].k, steps0 = (long long)plan.view(0).steps_done();
+  if (pre) {
+    fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: chain in the frame's launch, waited %.2f ms for it, %lld steps %.2f ms, assign %.2f ms\n", n0, k0,
+            clk.chained - t0, steps0, t_steps - clk.chained, t_assign - t_steps);
+  } else if (N == 1) {
+    fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms (host draws %.2f, word table %.2f, uniforms+upload %.2f, order %.2f), chain %.2f ms "
+            "(%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", n0, k0, clk.ordered - t0, t_draws - t0, clk.words - t_draws, clk.uploaded - clk.words,
+            clk.ordered - clk.uploaded, clk.chained - clk.ordered, (clk.chained - clk.ordered) * 1e3 / (double)k0, steps0, t_steps - clk.chained,
+            t_assign - t_steps);
+  } else {
     std::string names;
     for (int p = 0; p < N; ++p) {
       char buf[96];
       snprintf(buf, sizeof(buf), "%s n=%lld k=%lld %lld steps%s", p ? "," : "", (long long)probs[(size_t)p].n, (long long)probs[(size_t)p].k,
-               (long long)fits[(size_t)p].steps, fits[(size_t)p].overlapped_from >= 0 ? " (overlapped)" : "");
+               (long long)plan.view(p).steps_done(), plan.overlapped_from[(size_t)p] >= 0 ? " (overlapped)" : "");
       names += buf;
     }
     fprintf(stderr, "[rhccq] mbk batch of %d:%s: draws+order %.2f ms, chains %.2f ms, steps %.2f ms (%d chunks), assign %.2f ms\n", N, names.c_str(),
-            tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2], n_chunk, tt[4] - tt[3]);
+            clk.ordered - t0, clk.chained - clk.ordered, t_steps - clk.chained, n_chunk, t_assign - t_steps);
   }
 }
 
@@ -761,14 +579,16 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
             n = (int64_t)nbk.size();
           }
           jb.labels_dev = S.dalloc<int32_t>((size_t)n);
-          mbk_fit(S, keys, n, jb.k, jb.labels_dev, jb.pre);
+          std::vector<rhccq_mbk_problem> prob(1);
+          prob[0].off = 0; prob[0].n = n; prob[0].k = jb.k;
+          mbk_fit(S, keys, prob, jb.labels_dev, nullptr, jb.pre);
         }
         S.sync();
       },
       [&](size_t g) { (void)hipStreamSynchronize(L.sub[g]->stream.get()); });
 }
 
-// The MiniBatchKMeans problems of `tasks` as batches of at most 32 on L's own stream (mbk_fit_batch); a lone problem takes mbk_fit.
+// The MiniBatchKMeans problems of `tasks` as batches of at most 32 on L's own stream (mbk_fit); a batch of one reports as a lone fit.
 // Host palettes only (the level-2 stage's): their non-black keys go to the device in one copy.
 void run_mbk_batch(Lane& L, std::vector<Job*>& tasks) {
   for (size_t lo = 0; lo < tasks.size(); lo += 32) {
@@ -786,21 +606,15 @@ void run_mbk_batch(Lane& L, std::vector<Job*>& tasks) {
     const uint32_t* keys = L.upload(cat.data(), cat.size());
     L.sync();                                           // (`cat` is staged)
     int32_t* labels = L.dalloc<int32_t>(cat.size());
-    if (probs.size() == 1) {
-      Job& jb = *tasks[lo];
-      mbk_fit(L, keys, probs[0].n, probs[0].k, labels, nullptr, &jb.mbk_steps);
-      jb.mbk_schedule = 0;
-      jb.labels_dev = labels;
-    } else {
-      std::vector<BatchFit> fits;
-      mbk_fit_batch(L, keys, probs, labels, fits);
-      for (size_t i = lo; i < hi; ++i) {
-        Job& jb = *tasks[i];
-        jb.labels_dev = labels + probs[i - lo].off;
-        jb.mbk_steps = fits[i - lo].steps;
-        jb.mbk_schedule = fits[i - lo].overlapped_from >= 0 ? 2 : 1;
-        jb.mbk_overlapped_from = fits[i - lo].overlapped_from;
-      }
+    std::vector<BatchFit> fits;
+    mbk_fit(L, keys, probs, labels, &fits);
+    const bool lone = probs.size() == 1;
+    for (size_t i = lo; i < hi; ++i) {
+      Job& jb = *tasks[i];
+      jb.labels_dev = labels + probs[i - lo].off;
+      jb.mbk_steps = fits[i - lo].steps;
+      jb.mbk_schedule = lone ? 0 : fits[i - lo].overlapped_from >= 0 ? 2 : 1;
+      jb.mbk_overlapped_from = lone ? -1 : fits[i - lo].overlapped_from;
     }
     L.sync();
   }
@@ -1356,17 +1170,16 @@ void class_pipeline(FrameCtx& F, int ci, Lane& L, std::vector<ClassOut>& outs, b
 // caller's stream (one workgroup per problem, as a batch), before the class pipelines start.  The lanes' streams share the
 // runtime's few hardware queues; a chain on a queue holds up every other stream mapped there for its whole length (a 106 ms chain
 // of one class delayed the other class's set-up or steps by as much).  Nothing after the chains can start before they end, so
-// one launch costs no time and leaves no chain to block another stream.  The draws, uniforms and Morton order are the ones
-// mbk_fit makes for a lone problem (mbk_draws; rhccq_mbk_order / rhccq_mbk_init treat the problems of a batch independently).
+// one launch costs no time and leaves no chain to block another stream.  Draws and chain set-up are the fit's own (mbk_draws, mbk_chains).
 void frame_chains(FrameCtx& F, hipStream_t stream) {
   rhccq_ctx* c = F.root;
   FrameState& FS = *(FrameState*)c->frame_state;
-  Arena& A = FS.root_arena;
   const bool tr = trace_on();
   const double t0 = now_ms();
   std::vector<int> ids;
   std::vector<rhccq_mbk_problem> probs;
-  int64_t ktot = 0, itot = 0, utot = 0, need_words = 1;
+  std::vector<const MbkDraws*> draws;
+  rhccq_fit::Totals tot;
   for (int ci = 0; ci < F.n_classes; ++ci)
     for (int j = F.job_base[(size_t)ci]; j < F.job_base[(size_t)ci + 1]; ++j) {
       const int64_t hb = F.has_black[(size_t)j] ? 1 : 0;
@@ -1375,45 +1188,20 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
       const int64_t k = mbk_k(n, F.classes[ci].quality);
       if (k < 1) continue;                              // (a quality rhccq_params refuses: the class's own pipeline reports it)
       PreChain pc;
-      pc.n = n;
-      pc.k = k;
       pc.draws = mbk_draws(n, k);
-      if (pc.draws.init_size > kFrameChainMaxInit) continue;
+      if (pc.draws.c.init_size > kFrameChainMaxInit) continue;
       rhccq_mbk_problem q;
-      q.off = F.pal_off[(size_t)j] + hb; q.n = n; q.k = k; q.koff = ktot; q.init_off = itot; q.init_n = pc.draws.init_size; q.rand_off = utot;
-      q.first = pc.draws.first; q.T = pc.draws.T;
+      q.off = F.pal_off[(size_t)j] + hb; q.n = n; q.k = k;
+      tot.add(q, pc.draws.c);
       probs.push_back(q);
       ids.push_back(j);
-      ktot += k;
-      itot += pc.draws.init_size;
-      utot += pc.draws.nu;
-      need_words = std::max<int64_t>(need_words, pc.draws.pos + 2 * pc.draws.nu);
       F.pre[j] = std::move(pc);
+      draws.push_back(&F.pre[j].draws);
     }
   if (probs.empty()) return;
-  const uint32_t* words;
-  int64_t n_words;
-  MtTable::get().device(c->device, need_words, &words, &n_words);
-  double* d_rand = (double*)A.alloc((size_t)utot * 8);
-  std::vector<int32_t> init_idx;
-  init_idx.reserve((size_t)itot);
-  for (size_t i = 0; i < probs.size(); ++i) {
-    const MbkDraws& d = F.pre[ids[i]].draws;
-    EF_RC(c, rhccq_mt_uniforms(c, words, d.pos, d.nu, d_rand + probs[i].rand_off));
-    init_idx.insert(init_idx.end(), d.init_idx.begin(), d.init_idx.end());
-  }
-  int32_t* d_init = (int32_t*)A.alloc((size_t)itot * 4);
-  EF_HIP(hipMemcpyAsync(d_init, init_idx.data(), (size_t)itot * 4, hipMemcpyHostToDevice, stream));   // pageable: staged on return
-  const int64_t obytes = rhccq_mbk_order_bytes(itot);
-  void* otmp = A.alloc((size_t)obytes);
-  int32_t* d_perm = (int32_t*)A.alloc((size_t)itot * 4);
-  EF_RC(c, rhccq_mbk_order(c, F.keys_dev, probs.data(), (int32_t)probs.size(), d_init, d_perm, otmp, obytes));
-  double* centres = (double*)A.alloc((size_t)ktot * 4 * 8);
-  int32_t* chosen = (int32_t*)A.alloc((size_t)ktot * 4);
-  EF_HIP(hipMemsetAsync(centres, 0, (size_t)ktot * 4 * 8, stream));
-  EF_HIP(hipMemsetAsync(chosen, 0, (size_t)ktot * 4, stream));
-  const double t1 = now_ms();
-  EF_RC(c, rhccq_mbk_init(c, F.keys_dev, probs.data(), (int32_t)probs.size(), d_init, d_perm, d_rand, centres, chosen));
+  ChainClocks clk;
+  clk.sync = false;
+  double* centres = mbk_chains(c, FS.root_arena, F.keys_dev, probs, draws, tot, tr ? &clk : nullptr);
   F.chains_done = make_event();
   EF_HIP(hipEventRecord(F.chains_done.get(), stream));
   for (size_t i = 0; i < probs.size(); ++i) {
@@ -1422,7 +1210,7 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
     pc.done = F.chains_done.get();
   }
   if (tr) fprintf(stderr, "[rhccq] frame chains: %zu problems, %lld init samples, set-up %.2f ms (host), launched after %.2f ms\n", probs.size(),
-                  (long long)itot, t1 - t0, now_ms() - t0);
+                  (long long)tot.itot, clk.ordered - t0, now_ms() - t0);
 }
 
 int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const rhccq_class_desc* classes, int32_t n_classes, uint8_t* palette_out,
