@@ -1203,6 +1203,32 @@ def sk_lbp_uniform_8_1(gray):
     return np.where(changes <= 2, bits.sum(0), 9)
 
 
+def split_stats(region_image, mask=None):
+    """The masked statistics calculate_split_score reduces its scores from, in the order of csrc/split_score.hip:
+    (sums[12] = count, sum L, L^2, A, A^2, B, B^2, gm, sg, sg^2, g, g^2; lbp_hist int64[10]; gray_hist int64[32]; abs_sums[12]).
+    gm = the summed Lab gradient magnitude of split_score.py:47-50, sg = sobel(gray), g = gray; mask=None -> gray > 0.01.  Per-pixel
+    terms in float64 from sk_rgb2gray / sk_rgb2lab / sk_sobel / sk_lbp_uniform_8_1, the sums in np.longdouble (rounded to float64
+    once), so that they carry no summation-order error; abs_sums[q] = the sum of |term_q|, the scale of a summation error."""
+    gray = sk_rgb2gray(region_image)
+    if mask is None:
+        mask = gray > 0.01
+    mask = np.asarray(mask, bool)
+    lab = sk_rgb2lab(region_image)
+    gm = 0
+    for c in range(3):
+        s = sk_sobel(lab[:, :, c])
+        gm = gm + np.sqrt(s ** 2 + s ** 2)
+    sg = sk_sobel(gray)
+    L, A, B = (lab[..., c][mask] for c in range(3))
+    g, gm, sg = gray[mask], np.broadcast_to(gm, gray.shape)[mask], sg[mask]
+    terms = [np.ones(len(g)), L, L * L, A, A * A, B, B * B, gm, sg, sg * sg, g, g * g]
+    sums = np.array([np.sum(t.astype(np.longdouble)) for t in terms]).astype(np.float64)
+    abs_sums = np.array([np.sum(np.abs(t).astype(np.longdouble)) for t in terms]).astype(np.float64)
+    lbp_hist = np.bincount(sk_lbp_uniform_8_1(gray)[mask], minlength=10).astype(np.int64)
+    gray_hist = np.histogram(g, bins=32, range=(0, 1))[0].astype(np.int64)
+    return sums, lbp_hist, gray_hist, abs_sums
+
+
 def split_score(region_image, mask=None):
     """calculate_split_score (split_score.py:15-142): (overall, colour, texture) in [0, 1]"""
     gray = sk_rgb2gray(region_image)

@@ -63,6 +63,16 @@ def _gaussian_weights(sigma, radius):
     return np.ascontiguousarray(phi[radius:])
 
 
+def _antialias_sigma_radius(n_in, n_out):
+    """skimage.transform.resize's anti-aliasing sigma of one axis, (factor - 1) / 2, and scipy's kernel radius int(4 sigma + 0.5).  An
+    axis resized to 0 samples has factor = sigma = inf, on which scipy.ndimage.gaussian_filter raises OverflowError (int(inf)); so
+    does this, by the same arithmetic."""
+    with np.errstate(divide="ignore"):
+        factor = float(np.float64(n_in) / np.float64(n_out))
+    sigma = max(0.0, (factor - 1) / 2)
+    return sigma, int(4.0 * sigma + 0.5)
+
+
 def _resize(image, out_hw, order, anti_aliasing):
     """skimage.transform.resize(image, out_hw, order, mode='reflect', preserve_range=True, anti_aliasing=...) on the device:
     scipy.ndimage.gaussian_filter (sigma = (factor - 1) / 2 per resized axis, mode 'mirror', truncate 4) and scipy.ndimage.zoom
@@ -73,6 +83,7 @@ def _resize(image, out_hw, order, anti_aliasing):
     H, W = img.shape[:2]
     oh, ow = int(out_hw[0]), int(out_hw[1])
     C3 = int(np.prod(img.shape[2:])) if img.ndim > 2 else 1
+    blur = [_antialias_sigma_radius(n_in, n_out) for n_in, n_out in ((H, oh), (W, ow))] if order > 0 and anti_aliasing else []
     cy, cx = _zoom_coordinates(H, oh), _zoom_coordinates(W, ow)
     if order == 0:
         src = img.astype(np.uint8) if img.dtype == bool else img
@@ -87,12 +98,8 @@ def _resize(image, out_hw, order, anti_aliasing):
                   "zoom_nearest")
         return out.cpu().numpy()
     work = torch.from_numpy(np.array(img, order="C")).to(rh.device).to(torch.float64)
-    if anti_aliasing:
-        for axis, (n_in, n_out) in enumerate(((H, oh), (W, ow))):
-            sigma = max(0.0, (n_in / n_out - 1) / 2)
-            if sigma <= 1e-15:
-                continue
-            radius = int(4.0 * sigma + 0.5)
+    for axis, (sigma, radius) in enumerate(blur):
+        if sigma > 1e-15:
             outer, length, inner = (1, H, W * C3) if axis == 0 else (H, W, C3)
             nxt = torch.empty_like(work)
             d_w = rh.dev(_gaussian_weights(sigma, radius))

@@ -23,7 +23,7 @@ import torch
 
 from .api import roi_chain
 from .api.roi import min_region_size
-from .api.slic import _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
+from .api.slic import _antialias_sigma_radius, _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
 from .api.split_score import normalize_result, scores_from_stats
 from .frame import ClassSpec, FrameEncoder
 from .ops import default_context, psnr_from_sse
@@ -196,10 +196,9 @@ class ImageEncoder:
         work = crop_u8.to(torch.float64)
         keep = []
         for axis, (n_in, n_out) in enumerate(((H, oh), (W, ow))):
-            sigma = max(0.0, (n_in / n_out - 1) / 2)
+            sigma, radius = _antialias_sigma_radius(n_in, n_out)
             if sigma <= 1e-15:
                 continue
-            radius = int(4.0 * sigma + 0.5)
             outer, length, inner = (1, H, W * 3) if axis == 0 else (H, W, 3)
             nxt = torch.empty_like(work)
             d_w = rh.dev(_gaussian_weights(sigma, radius))

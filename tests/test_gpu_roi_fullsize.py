@@ -297,7 +297,20 @@ def test_quality_metrics_and_split_score_fullsize():
     m = np.zeros((H, W), bool)
     m[H // 8:H - H // 6, W // 7:W - W // 5] = True
     m &= rng.random((H, W)) > 0.1
-    for mask in (None, m):
-        got, want = c.run("device", calculate_split_score, a, mask), c.run("oracle", O.split_score, a, mask)
-        assert np.allclose(got, want, rtol=0, atol=1e-9), (got, want)
+    # the raw statistics behind the scores too (the colour score of this photo is clipped to 1.0, which hides its seven sums): what
+    # calculate_split_score's own launch returned, by the rule of tests/test_gpu_subregion_shapes.py
+    from roibasedimagecompression_amd.ops import default_context
+    from test_gpu_subregion_shapes import check_stats
+    rh, raw = default_context(), []
+    launch = rh.split_stats
+    rh.split_stats = lambda *args: raw.append(launch(*args)) or raw[-1]
+    try:
+        for mask in (None, m):
+            got, want = c.run("device", calculate_split_score, a, mask), c.run("oracle", O.split_score, a, mask)
+            assert np.allclose(got, want, rtol=0, atol=1e-9), (got, want)
+            assert len(raw) == 1
+            ratio = check_stats(raw.pop(), c.run("oracle", O.split_stats, a, mask), "4K raw statistics")
+            print(f"4K split_stats, mask {'given' if mask is not None else 'None'}: largest error / bound = {ratio:.3g}")
+    finally:
+        del rh.split_stats
     c.report("metrics and split score")
