@@ -91,6 +91,13 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              its own lane.  Same results.  Why: two host threads and two streams that queue ~700 launches each
  *                              on the same few hardware queues ran their steps at twice the period of either alone. */
 #define RHCCQ_OPT_FRAME_LEVEL2 9
+/*   RHCCQ_OPT_REFINE_LDS_ROWS  rhccq_palette_refine: palettes of at most this many rows keep their accumulators in LDS per workgroup,
+ *                              larger ones add to the workspace in global memory (0 .. rhccq_palette_refine_lds_rows(), default that
+ *                              maximum; 0 = always global memory).  Same results: integer sums in any order;
+ *   RHCCQ_OPT_REFINE_MAX_BLOCKS  rhccq_palette_refine: 0 (default) = 8 workgroups per CU, never more than there are chunks of 2048
+ *                              pixels; 1..65535 = at most that many workgroups, so that one workgroup takes many chunks.  Same results. */
+#define RHCCQ_OPT_REFINE_LDS_ROWS 10
+#define RHCCQ_OPT_REFINE_MAX_BLOCKS 11
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -722,6 +729,31 @@ int rhccq_palette_remap_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t
                              int32_t n_classes, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
 /* host only: the palette entries the kernel stages at a time; the winner is carried from one such tile to the next */
 int32_t rhccq_palette_remap_tile(void);
+
+/* ---- EXTENSION: refinement of a given palette, exact integer Lloyd iterations (no reference counterpart; csrc/palette_refine.hip) ----
+ * A pixel's weight is weights[cls[p]] when cls[p] < n_classes and weights[n_classes] otherwise (and for every pixel when cls == NULL);
+ * weights are 0..255 with at least one > 0, NULL = all ones.  Iteration i: (1) a(p) = rhccq_palette_remap's index of p (nearest row in
+ * exact integers, ties to the lowest row: a later duplicate never receives a pixel); (2) per row j, over the pixels with a(p) = j, in
+ * 64-bit integers N_j = sum w(p), S_j = sum w(p) p per channel, and E = sum w(p) |p - palette[a(p)]|^2 over all pixels; (3) a row with
+ * N_j > 0 becomes floor((2 S_j + N_j) / (2 N_j)) per channel (the weighted mean rounded to nearest, halves up), a row with N_j == 0 stays;
+ * history[i] = {E, rows whose three bytes changed}.  The refinement stops after the first iteration that changes no row or after
+ * max_iter; *n_iter = iterations that ran; history rows from n_iter on are zero.  E never increases from one iteration to the next.
+ * palette (K x 3, IN/OUT), rgb and cls are uint8 of any alignment; history is uint64[max_iter][2], n_iter one int32, both zeroed by the call.
+ * RHCCQ_E_ARG: a null rgb, palette, history, n_iter or work; K < 1; n_pixels < 0; n_classes outside 0..16 (or not 0 with cls == NULL);
+ * max_iter outside 1..64; a weight outside 0..255 or all weights 0; a misaligned history (8), n_iter (4) or work (8); work_bytes below
+ * rhccq_palette_refine_bytes(K).  RHCCQ_E_LIMIT: K > 65536.  n_pixels == 0 succeeds with *n_iter = 0, a zero history, the palette untouched.
+ * Device form: every pointer but weights_host is device memory; async on the context stream (two launches per iteration, later
+ * iterations return at once after convergence), no host synchronisation, nothing allocated.  history is control state as well as
+ * output while the call's launches are in flight: iteration i runs iff history[i - 1][1] != 0, so no other work on the stream or on
+ * another stream may write history (or palette, n_iter, work) before those launches have finished; a foreign write there would change
+ * how many iterations run.  Host form: the same functions run serially. */
+int32_t rhccq_palette_refine_lds_rows(void);            /* host only: the largest K whose accumulators live in LDS */
+int64_t rhccq_palette_refine_bytes(int32_t K);          /* host only: workspace bytes */
+int rhccq_palette_refine(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, uint8_t* palette, int32_t K, const uint8_t* cls,
+                         int32_t n_classes, const int32_t* weights_host, int32_t max_iter, void* work, int64_t work_bytes,
+                         uint64_t* history, int32_t* n_iter);
+int rhccq_palette_refine_host(const uint8_t* rgb, int64_t n_pixels, uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
+                              const int32_t* weights, int32_t max_iter, uint64_t* history, int32_t* n_iter);
 
 #ifdef __cplusplus
 }

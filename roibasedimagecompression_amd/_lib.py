@@ -176,6 +176,11 @@ PROTOTYPES = {
     "rhccq_palette_remap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_remap_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_remap_tile": (c_int32, []),
+    "rhccq_palette_refine_lds_rows": (c_int32, []),
+    "rhccq_palette_refine_bytes": (c_int64, [c_int32]),
+    "rhccq_palette_refine": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
+                                       c_void_p, c_void_p]),
+    "rhccq_palette_refine_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
 }
 
 

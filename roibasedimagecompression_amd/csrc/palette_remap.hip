@@ -14,48 +14,10 @@
 // 2.5 vector integer operations an evaluation, with the two entries read from LDS by all lanes at one address (a broadcast: no
 // bank conflict).
 // The host form runs the same pack / evaluate / carry functions serially.
-#include "rhccq_common.h"
+// The pack / evaluate / carry functions themselves are in palette_remap.h (the palette refinement assigns with them too).
+#include "palette_remap.h"
 
 namespace rhccq {
-
-constexpr int kRemapBlock = 256;      // lanes of a workgroup
-constexpr int kRemapPx = 8;           // pixels a lane keeps in registers: one LDS read of two entries feeds 16 evaluations
-constexpr int kRemapTile = 1024;      // palette entries staged in LDS at a time (8 KiB); <= 4096 (12 index bits)
-constexpr int kRemapIdxBits = 12;
-constexpr int kRemapMaxClasses = 16;
-constexpr int kRemapMaxK = 65536;     // the bound of the reference's uint16 mapping array (clustering.py:373)
-static_assert(kRemapTile <= (1 << kRemapIdxBits) && kRemapTile % 2 == 0, "tile-local index must fit its 12 bits");
-
-struct RemapEntry { uint32_t inv, w; };
-
-__host__ __device__ __forceinline__ uint32_t remap_dot(uint32_t a, uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_udot4(a, b, 0u, false);
-#else
-  return (a & 255u) * (b & 255u) + ((a >> 8) & 255u) * ((b >> 8) & 255u) + ((a >> 16) & 255u) * ((b >> 16) & 255u);
-#endif
-}
-__host__ __device__ __forceinline__ uint32_t remap_pack_px(const uint8_t* p) { return ((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | p[2]; }
-// entry `local` of a tile from its three bytes
-__host__ __device__ __forceinline__ RemapEntry remap_pack_entry(const uint8_t* c, int local) {
-  const uint32_t k = remap_pack_px(c);
-  return {0x00FFFFFFu - k, (remap_dot(k, k) << kRemapIdxBits) | (uint32_t)local};
-}
-// (key << 12 | local index) of pixel p against one entry
-__host__ __device__ __forceinline__ uint32_t remap_eval(uint32_t p, RemapEntry e) { return (remap_dot(p, e.inv) << (kRemapIdxBits + 1)) + e.w; }
-// a tile's winner against the winner so far: strict <, so an equal key of a later tile never replaces an earlier index
-__host__ __device__ __forceinline__ void remap_carry(uint32_t tile_best, int tile_base, uint32_t& key, uint32_t& idx) {
-  const uint32_t k = tile_best >> kRemapIdxBits;
-  if (k < key) {
-    key = k;
-    idx = (uint32_t)tile_base + (tile_best & ((1u << kRemapIdxBits) - 1u));
-  }
-}
-// the squared distance from the winning key
-__host__ __device__ __forceinline__ uint32_t remap_dist(uint32_t p, uint32_t key) {
-  const int s = (int)((p & 255u) + ((p >> 8) & 255u) + ((p >> 16) & 255u));
-  return (uint32_t)((int)key + (int)remap_dot(p, p) - 510 * s);
-}
 
 // A workgroup takes chunks of 256 x 8 pixels (lane l: pixels base + l + 256 q, so index stores coalesce) grid-stride, and walks the
 // palette tile by tile through LDS for each.  A palette of one tile is staged once.  The last tile is padded to an even length

@@ -29,6 +29,8 @@ struct rhccq_ctx {
   int opt_frame_chains = 1;  // rhccq_encode_frame: the level-1 k-means++ chains of a frame in one launch (1, default) or one per problem lane (0)
   int opt_frame_level2 = 1;  // rhccq_encode_frame: the level-2 palettes of all classes in one batch on one lane (1, default) or per class lane (0)
   int compute_units = 0;     // of `device`, asked once by the first launch that sizes its grid by it (csrc/palette_remap.hip)
+  int opt_refine_lds_rows = -1;    // rhccq_palette_refine: palettes of more rows accumulate in global memory (-1: rhccq_palette_refine_lds_rows())
+  int opt_refine_max_blocks = 0;   // rhccq_palette_refine: at most this many workgroups (0: 8 per CU)
 };
 
 #define RHCCQ_HIP(ctx, expr)                                                        \

@@ -467,15 +467,26 @@ class ImageEncoder:
         return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
-    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False):
+    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
         lowest row), plus `stats`.  One pass over the pixels: no region, SLIC or clustering stage runs.
         stats["remap"]["all"] = {pixels, sse, mse, psnr} of the result against the image (the kernel's by-product); with roi_mask
         (as encode takes it) also "roi" and "nonroi", inside and outside the mask.  report: stats["quality"] as encode fills it
-        (regions() for the region map, then quality()).  out_path: container.write_frame(exact=exact)."""
+        (regions() for the region map, then quality()).  out_path: container.write_frame(exact=exact).
+        refine = N > 0: the palette is first refined with up to N exact Lloyd iterations over the image (Rhccq.palette_refine: rows
+        move to the mean of their pixels, K stays), then the remap runs onto the refined palette, which is the result's "palette".
+        With roi_mask a pixel inside the mask weighs roi_weight (1..255) and one outside 1 in the refinement; without a mask
+        roi_weight must be 1.  stats["refine"] = {iterations, converged, sse: [...], changed: [...]} (the weighted sums of the
+        iterations that ran); stats["remap"] stays the unweighted figures of the final remap.  Rows that receive no pixel never
+        move, so a palette far from the image collapses onto a few rows: refinement follows drift, it does not replace encode."""
         rh = self.rh
+        refine, roi_weight = int(refine), int(roi_weight)
+        if refine < 0 or refine > 64:
+            raise ValueError("ImageEncoder.encode_with_palette: refine must be 0..64")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not refine)):
+            raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0")
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -498,8 +509,14 @@ class ImageEncoder:
             from .api.roi import region_map_from_mask
             cls = region_map_from_mask(rgb, roi_mask, rh)                     # 0 / 1: quality()'s rows
             lap("mask")
+        if refine:
+            pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
         idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
-        sums = rh.to_host(sums)
+        if refine:
+            sums, hist, nit = rh.to_host(sums, hist, nit)                     # one read for both
+            nit = int(nit[0])
+        else:
+            sums = rh.to_host(sums)
         lap("remap")
         remap = {"all": self._remap_row(*sums[-1])}
         if cls is not None:
@@ -507,6 +524,9 @@ class ImageEncoder:
         res = {"palette": rh.to_host(pal), "indices": idx, "indices_dtype": "uint8" if idx.dtype == torch.uint8 else "uint16",
                "shape": (H, W), "top_left": (0, 0)}
         stats = {"remap": remap}
+        if refine:
+            stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
+                               "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
         if out_path:
             from . import container
             container.write_frame(res, out_path, rh, exact=exact)
@@ -521,7 +541,7 @@ class ImageEncoder:
         res["stats"] = stats
         return res
 
-    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False):
+    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -530,8 +550,18 @@ class ImageEncoder:
         sums, over the whole picture when the key covers it and else over that rectangle (the remap then runs with the rectangle
         as its roi_mask, and its stats["remap"] has the "roi" / "nonroi" rows too).  A frame of another size than its key's is
         compared over the whole picture.  Every result has stats["key_frame"] (bool), stats["key_index"] (the frame whose
-        palette it uses) and stats["psnr"]; a remap also stats["key_psnr"].  out_paths: one file per frame (entries may be None)."""
+        palette it uses) and stats["psnr"]; a remap also stats["key_psnr"].  out_paths: one file per frame (entries may be None).
+        refine = N > 0: a frame whose plain remap falls below the bound is next tried as encode_with_palette(image, current palette,
+        refine=N) (with the key's rectangle as roi_mask and roi_weight inside it when the key covers a rectangle) and kept iff that
+        reaches the bound: stats["key_frame"] = False, stats["refined"] = True, key_index and key_psnr stay the key frame's, and the
+        refined palette is the one later frames are remapped onto.  Otherwise the frame is encoded in full as before.  Every
+        result that is not a key frame has stats["refined"] (bool; always False with refine = 0)."""
         rh = self.rh
+        refine, roi_weight = int(refine), int(roi_weight)
+        if refine < 0 or refine > 64:
+            raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
+            raise ValueError("ImageEncoder.encode_sequence: roi_weight must be 1..255, and 1 without refine")
         key_pal = key_psnr = key_window = key_frame_shape = None
         key_index = -1
         for n, image in enumerate(images):
@@ -540,11 +570,20 @@ class ImageEncoder:
                 window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
                 res = self.encode_with_palette(image, key_pal, roi_mask=window)
                 row = res["stats"]["remap"]["all" if window is None else "roi"]
-                if row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db:
+                kept = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
+                refined = False
+                if not kept and refine:
+                    res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1)
+                    row = res["stats"]["remap"]["all" if window is None else "roi"]
+                    kept = refined = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
+                if kept:
                     if path:
                         from . import container
                         container.write_frame(res, path, rh, exact=exact)
                     res["stats"].update(key_frame=False, key_index=key_index, psnr=row["psnr"], key_psnr=key_psnr)
+                    res["stats"]["refined"] = refined
+                    if refined:
+                        key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
                     yield res
                     continue
             res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact)

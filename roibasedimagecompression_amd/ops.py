@@ -110,6 +110,11 @@ def palette_remap_tile():
     return int(_lib.load().rhccq_palette_remap_tile())
 
 
+def palette_refine_lds_rows():
+    """the largest palette whose accumulators Rhccq.palette_refine's kernel keeps in LDS (larger ones add to global memory)"""
+    return int(_lib.load().rhccq_palette_refine_lds_rows())
+
+
 def psnr_from_sse(sse, n_pixels):
     """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
     10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
@@ -224,6 +229,8 @@ class Rhccq:
     OPT_REASSIGN_ORDER = 7           # 1 (default): numpy's scalar-quicksort tie order of the capped reassignment; 0: stable (rounds 1-3)
     OPT_FRAME_CHAINS = 8             # rhccq_encode_frame: 1 (default) one launch for the frame's level-1 k-means++ chains; 0: one per problem lane
     OPT_FRAME_LEVEL2 = 9             # rhccq_encode_frame: 1 (default) the level-2 palettes of all classes as one batch on one lane; 0: one per class lane
+    OPT_REFINE_LDS_ROWS = 10         # palette_refine: palettes of more rows accumulate in global memory (0 .. palette_refine_lds_rows(), default that)
+    OPT_REFINE_MAX_BLOCKS = 11       # palette_refine: at most this many workgroups (0, default: 8 per CU)
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""
@@ -1028,6 +1035,52 @@ class Rhccq:
         self._check(self.lib.rhccq_palette_remap(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), int(n_classes), self._p(idx),
                                                  idx.element_size(), self._p(sums)), "palette_remap")
         return idx, sums
+
+    # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------
+    def palette_refine(self, rgb, palette, class_map=None, weights=None, max_iter=8):
+        """rgb uint8[..., 3], palette uint8[K, 3] (numpy or device), class_map uint8 / bool, one element per pixel, or None;
+        weights: n_classes + 1 ints 0..255 (a pixel of class c < n_classes weighs weights[c], every other pixel weights[-1]),
+        None = all ones and no classes -> (palette: a NEW device uint8[K, 3], the argument is not modified; history device int64
+        [max_iter, 2]: row i = {weighted sum of squared errors the iteration's assignment found, rows it changed}, zero from
+        n_iter on; n_iter device int32[1]).  Each iteration assigns every pixel as palette_remap does and moves every row that
+        received pixels to their weighted mean rounded to nearest; it stops after the first iteration that changes no row."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_refine: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
+        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError("palette_refine: rgb [..., 3] and palette [K, 3] are expected")
+        n, K, max_iter = rgb.numel() // 3, int(palette.shape[0]), int(max_iter)
+        w = None if weights is None else [int(v) for v in weights]
+        if w is not None and len(w) < 1:
+            raise ValueError("palette_refine: weights must have n_classes + 1 entries")
+        n_classes = 0 if w is None else len(w) - 1
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != n:
+                raise ValueError("palette_refine: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_refine: class weights without a class map")
+        out = palette.clone()
+        history = self.empty((max(max_iter, 0), 2), torch.int64)
+        n_iter = self.empty((1,), torch.int32)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            if not 0 <= n_classes <= 16 or K < 1 or K > 65536 or not 1 <= max_iter <= 64 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+                raise RhccqError("palette_refine: K must be 1..65536, max_iter 1..64, weights 0..255 (n_classes + 1 <= 17 of them, one > 0)")
+            return out, history.zero_(), n_iter.zero_()
+        wbytes = int(self._raw.rhccq_palette_refine_bytes(K)) if K >= 1 else 0
+        work = self.empty((max(wbytes // 8, 1),), torch.int64)
+        warr = None if w is None else (C.c_int32 * len(w))(*w)
+        self._check(self.lib.rhccq_palette_refine(self.ctx, self._p(rgb), n, self._p(out), K, self._p(cls), n_classes,
+                                                  C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), max_iter, self._p(work),
+                                                  wbytes, self._p(history), self._p(n_iter)), "palette_refine")
+        return out, history, n_iter
 
     # -- split score (split_score.py:15-142) ----------------------------------------------------------
     def split_stats(self, rgb, mask=None):

@@ -1,0 +1,384 @@
+"""The palette refinement on the device (csrc/palette_refine.hip, Rhccq.palette_refine, ImageEncoder.encode_with_palette(refine=N) /
+encode_sequence(refine=N)) against the numpy reference of tests/refine_cases.py, bit for bit (palette, history, n_iter), on both
+accumulator paths (LDS per workgroup, global memory), and what is built on it: the refined remap, the container round trip, the
+middle step of a sequence.  GPU only."""
+import contextlib
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import refine_cases as RF
+import remap_cases as RM
+import roimask_cases as RC
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rh():
+    from roibasedimagecompression_amd.ops import default_context
+    return default_context()
+
+
+@pytest.fixture(scope="module")
+def enc(rh):
+    from roibasedimagecompression_amd.image import ImageEncoder
+    return ImageEncoder(rh)
+
+
+@contextlib.contextmanager
+def options(rh, lds_rows=None, max_blocks=None):
+    """the two tuning knobs of the refinement, restored to their defaults afterwards"""
+    try:
+        if lds_rows is not None:
+            rh.set_option(rh.OPT_REFINE_LDS_ROWS, lds_rows)
+        if max_blocks is not None:
+            rh.set_option(rh.OPT_REFINE_MAX_BLOCKS, max_blocks)
+        yield
+    finally:
+        rh.set_option(rh.OPT_REFINE_LDS_ROWS, RF.L)
+        rh.set_option(rh.OPT_REFINE_MAX_BLOCKS, 0)
+
+
+def _raw_refine(rh, rgb, pal, cls, weights, max_iter):
+    """rhccq_palette_refine itself; output buffers and the workspace pre-filled so that unwritten elements show"""
+    import torch
+    d_rgb = rh.dev(np.ascontiguousarray(rgb).reshape(-1, 3))
+    d_pal = rh.dev(np.array(np.asarray(pal).reshape(-1, 3)))                   # IN/OUT: a copy
+    d_cls = None if cls is None else rh.dev(np.ascontiguousarray(cls).reshape(-1))
+    n, K = d_rgb.shape[0], d_pal.shape[0]
+    if n == 0:                                           # (an empty tensor has a null pointer: the C entry wants real buffers)
+        d_rgb = rh.zeros((1, 3), torch.uint8)
+    hist = torch.full((max_iter, 2), 0x5555, dtype=torch.int64, device=rh.device)
+    nit = torch.full((1,), -7, dtype=torch.int32, device=rh.device)
+    wbytes = int(rh._raw.rhccq_palette_refine_bytes(K))
+    work = torch.full((wbytes // 8,), 0x3333, dtype=torch.int64, device=rh.device)
+    w = None if weights is None else (C.c_int32 * len(weights))(*weights)
+    rc = rh.lib.rhccq_palette_refine(rh.ctx, rh._p(d_rgb), n, rh._p(d_pal), K, rh._p(d_cls), 0 if weights is None else len(weights) - 1,
+                                     C.cast(w, C.c_void_p) if w is not None else C.c_void_p(0), max_iter, rh._p(work), wbytes, rh._p(hist),
+                                     rh._p(nit))
+    return rc, d_pal.cpu().numpy(), hist.cpu().numpy(), int(nit.item())
+
+
+def _check(rh, c, want, what):
+    want_pal, want_hist, want_n = want
+    rc, pal, hist, n = _raw_refine(rh, c["rgb"], c["pal"], c["cls"], c["weights"], c["max_iter"])
+    assert rc == 0, what
+    assert n == want_n and np.array_equal(hist, want_hist), (what, n, want_n, hist.tolist(), want_hist.tolist())
+    assert np.array_equal(pal, want_pal), what
+
+
+@pytest.mark.parametrize("name", RF.names())
+def test_device_equals_reference(rh, name):
+    c, want = RF.case(name), RF.reference(name)
+    K = len(c["pal"])
+    _check(rh, c, want, (name, "default"))
+    with options(rh, lds_rows=0):                                              # the global-memory accumulators at every size
+        _check(rh, c, want, (name, "lds_rows=0"))
+    if K in (RF.L - 1, RF.L, RF.L + 1):                                        # the threshold moved by one: L-1 stays in LDS, L and L+1 do not
+        with options(rh, lds_rows=RF.L - 1):
+            _check(rh, c, want, (name, "lds_rows=L-1"))
+    dup = RF.later_duplicates(c["pal"])
+    if len(dup) and len(c["rgb"].reshape(-1, 3)):                              # unchanged by the first iteration (refine_cases.reference)
+        rc, one, _, _ = _raw_refine(rh, c["rgb"], c["pal"], c["cls"], c["weights"], 1)
+        assert rc == 0 and np.array_equal(one[dup], c["pal"][dup]), name
+
+
+@pytest.mark.parametrize("name", RF.GRID_CASES)
+def test_more_chunks_than_workgroups(rh, name):
+    """4.5 M pixels: more chunks of 2048 pixels than the default grid has workgroups, so a workgroup's accumulators live through
+    several chunks, and every workgroup flushes into the same rows"""
+    import torch
+    c, want = RF.grid_case(name)
+    assert -(-c["rgb"].shape[0] * c["rgb"].shape[1] // RF.CHUNK) > 8 * torch.cuda.get_device_properties(rh.device).multi_processor_count
+    _check(rh, c, want, (name, "default"))
+    with options(rh, lds_rows=0):
+        _check(rh, c, want, (name, "lds_rows=0"))
+
+
+def test_one_workgroup_many_chunks(rh):
+    """OPT_REFINE_MAX_BLOCKS = 1: one workgroup takes all 40 chunks and its own sums pass 2^32, in LDS and in global memory"""
+    c, want = RF.one_workgroup_case()
+    with options(rh, max_blocks=1):
+        _check(rh, c, want, "lds")
+    with options(rh, lds_rows=0, max_blocks=1):
+        _check(rh, c, want, "global")
+    with options(rh, max_blocks=3):                                            # 40 chunks over 3 workgroups: 14, 13, 13
+        _check(rh, c, want, "three workgroups")
+
+
+def test_early_stop(rh):
+    c = RF.case("early_stop")
+    want_pal, want_hist, want_n = RF.reference("early_stop")
+    assert want_n < c["max_iter"] and (want_hist[want_n:] == 0).all()
+    rc, pal, hist, n = _raw_refine(rh, c["rgb"], c["pal"], None, None, c["max_iter"])
+    assert rc == 0 and n == want_n and (hist[n:] == 0).all() and hist[n - 1, 1] == 0
+    rc, pal2, hist2, n2 = _raw_refine(rh, c["rgb"], c["pal"], None, None, want_n)   # max_iter = n_iter: the same palette
+    assert rc == 0 and n2 == want_n and np.array_equal(pal2, pal) and np.array_equal(pal, want_pal) and np.array_equal(hist2, want_hist[:want_n])
+
+
+def test_options_are_checked(rh):
+    from roibasedimagecompression_amd import RhccqError
+    for opt, bad in ((rh.OPT_REFINE_LDS_ROWS, -1), (rh.OPT_REFINE_LDS_ROWS, RF.L + 1), (rh.OPT_REFINE_MAX_BLOCKS, -1), (rh.OPT_REFINE_MAX_BLOCKS, 65536)):
+        with pytest.raises(RhccqError):
+            rh.set_option(opt, bad)
+    with options(rh, lds_rows=RF.L, max_blocks=65535):
+        pass
+
+
+@pytest.mark.parametrize("what,over,code", [e[:3] for e in RF.ERRORS], ids=[e[0] for e in RF.ERRORS])
+def test_device_argument_errors(rh, what, over, code):
+    import torch
+    t = {"rgb": rh.zeros((4, 3), torch.uint8), "palette": rh.zeros((max(over.get("K", 3), 3), 3), torch.uint8),
+         "history": rh.zeros((65, 2), torch.int64), "n_iter": rh.zeros((2,), torch.int32), "work": rh.zeros((65537 * 4 + 1,), torch.int64)}
+    t.update({k: v for k, v in over.items() if k in t})
+    cls = rh.zeros((4,), torch.uint8) if over.get("cls") else None
+    K = over.get("K", 3)
+    off = {k: 0 for k in t}
+    if "misalign" in over:
+        off[over["misalign"]] = 2 if over["misalign"] == "n_iter" else 1
+
+    def p(k):
+        return C.c_void_p(t[k].data_ptr() + off[k]) if t[k] is not None else C.c_void_p(0)
+    w = over.get("weights")
+    warr = None if w is None else (C.c_int32 * len(w))(*w)
+    wbytes = int(rh._raw.rhccq_palette_refine_bytes(K)) - (1 if over.get("work_short") else 0)
+    rc = rh.lib.rhccq_palette_refine(rh.ctx, p("rgb"), over.get("n_pixels", 4), p("palette"), K, rh._p(cls), over.get("n_classes", 0),
+                                     C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), over.get("max_iter", 2), p("work"), wbytes,
+                                     p("history"), p("n_iter"))
+    assert rc == code, what
+    assert rh._raw.rhccq_last_error(rh.ctx).decode().startswith("palette_refine:")
+
+
+def test_zero_pixels(rh):
+    pal0 = np.array([[1, 2, 3], [4, 5, 6]], np.uint8)
+    rc, pal, hist, n = _raw_refine(rh, np.zeros((0, 3), np.uint8), pal0, None, None, 5)
+    assert rc == 0 and n == 0 and not hist.any() and np.array_equal(pal, pal0)
+    out, hist, nit = rh.palette_refine(np.zeros((0, 3), np.uint8), pal0, max_iter=5)
+    assert np.array_equal(out.cpu().numpy(), pal0) and not hist.cpu().numpy().any() and int(nit.item()) == 0 and tuple(hist.shape) == (5, 2)
+
+
+def test_python_surface(rh):
+    import torch
+    c = RF.case("classes2")
+    want_pal, want_hist, want_n = RF.reference("classes2")
+    d_pal = rh.dev(c["pal"])
+    keep = d_pal.clone()
+    pal, hist, nit = rh.palette_refine(rh.dev(c["rgb"]), d_pal, rh.dev(c["cls"]), c["weights"], max_iter=c["max_iter"])
+    assert torch.equal(d_pal, keep) and pal.data_ptr() != d_pal.data_ptr()     # the argument is not modified
+    assert pal.dtype == torch.uint8 and tuple(pal.shape) == tuple(c["pal"].shape) and pal.is_cuda
+    assert hist.dtype == torch.int64 and tuple(hist.shape) == (c["max_iter"], 2) and hist.is_cuda
+    assert nit.dtype == torch.int32 and tuple(nit.shape) == (1,) and nit.is_cuda
+    assert np.array_equal(pal.cpu().numpy(), want_pal) and np.array_equal(hist.cpu().numpy(), want_hist) and int(nit.item()) == want_n
+    pal2, hist2, nit2 = rh.palette_refine(c["rgb"], c["pal"], c["cls"], c["weights"], max_iter=c["max_iter"])      # numpy arguments
+    assert torch.equal(pal2, pal) and torch.equal(hist2, hist) and torch.equal(nit2, nit)
+    pal3, hist3, _ = rh.palette_refine(c["rgb"], c["pal"])                      # no classes, all ones, max_iter = 8
+    want3 = RF.refine_reference(c["rgb"], c["pal"])
+    assert tuple(hist3.shape) == (8, 2) and np.array_equal(pal3.cpu().numpy(), want3[0]) and np.array_equal(hist3.cpu().numpy(), want3[1])
+    with pytest.raises(ValueError):
+        rh.palette_refine(c["rgb"], c["pal"], None, [1, 2, 3])
+    with pytest.raises(ValueError):
+        rh.palette_refine(c["rgb"], c["pal"], c["cls"][:-1], [1, 2, 3])
+    with pytest.raises(TypeError):
+        rh.palette_refine(c["rgb"].astype(np.int32), c["pal"])
+
+
+# ---- a result of the encoder as the palette ---------------------------------------------------------------------------------------
+def _idx64(t):
+    a = t.cpu().numpy()
+    if a.dtype == np.int16:
+        a = a.view(np.uint16)
+    return a.reshape(-1).astype(np.int64)
+
+
+@pytest.fixture(scope="module")
+def encoded(enc):
+    """photo96 (96 x 128, synth.photo) encoded once: (image, the palette, the mask of the case)"""
+    (q1, q2), img, m = RC.case("photo96")
+    res = enc.encode(img, q1, q2)
+    return img, np.asarray(res["palette"], np.uint8).reshape(-1, 3), m
+
+
+@pytest.mark.parametrize("n", [1, 4])
+def test_encode_with_palette_refine(rh, enc, encoded, n):
+    img, pal, _ = encoded
+    plain = enc.encode_with_palette(img, pal)
+    out = enc.encode_with_palette(img, pal, refine=n)
+    r_pal, r_hist, r_n = rh.palette_refine(img, pal, max_iter=n)
+    idx, sums = rh.palette_remap(img, r_pal)
+    want_pal, want_hist, want_n = RF.refine_reference(img, pal, max_iter=n)
+    assert np.array_equal(out["palette"], want_pal) and np.array_equal(r_pal.cpu().numpy(), want_pal)
+    assert np.array_equal(_idx64(out["indices"]), _idx64(idx)) and out["indices"].dtype == idx.dtype
+    sums = sums.cpu().numpy()
+    assert list(out["stats"]["remap"]) == ["all"]
+    assert (out["stats"]["remap"]["all"]["pixels"], out["stats"]["remap"]["all"]["sse"]) == (int(sums[-1, 0]), int(sums[-1, 1]))
+    ref = out["stats"]["refine"]
+    assert ref["iterations"] == want_n == int(r_n.item()) and ref["sse"] == want_hist[:want_n, 0].tolist()
+    assert ref["changed"] == want_hist[:want_n, 1].tolist() and ref["converged"] == (want_hist[want_n - 1, 1] == 0)
+    assert ref["sse"][0] == plain["stats"]["remap"]["all"]["sse"]               # all weights one: the first assignment is the plain remap
+    assert out["stats"]["remap"]["all"]["sse"] <= plain["stats"]["remap"]["all"]["sse"]
+    assert "refine" not in plain["stats"] and np.array_equal(plain["palette"], pal)
+    with pytest.raises(ValueError):
+        enc.encode_with_palette(img, pal, refine=2, roi_weight=8)              # a weight needs a mask
+    with pytest.raises(ValueError):
+        enc.encode_with_palette(img, pal, refine=-1)
+
+
+def test_encode_with_palette_refine_roi_weight(rh, enc, encoded):
+    """the ROI weight reaches the kernel: equality with the reference run under the same weights (a larger weight does not
+    guarantee a smaller ROI error, so nothing of that kind is asserted)"""
+    img, pal, m = encoded
+    cls = m.astype(np.uint8)
+    for weight in (1, 8):
+        out = enc.encode_with_palette(img, pal, roi_mask=m, refine=3, roi_weight=weight)
+        want_pal, want_hist, want_n = RF.refine_reference(img, pal, cls, [1, weight, 1], max_iter=3)
+        _, want_sums = RM.remap_reference(img, want_pal, cls, 2)
+        assert np.array_equal(out["palette"], want_pal), weight
+        assert out["stats"]["refine"]["sse"] == want_hist[:want_n, 0].tolist() and out["stats"]["refine"]["iterations"] == want_n
+        for key, row in (("nonroi", want_sums[0]), ("roi", want_sums[1]), ("all", want_sums[2])):
+            assert (out["stats"]["remap"][key]["pixels"], out["stats"]["remap"][key]["sse"]) == (int(row[0]), int(row[1])), (weight, key)
+
+
+def test_container_round_trip(rh, enc, encoded, tmp_path):
+    from roibasedimagecompression_amd import container
+    img, pal, _ = encoded
+    path = str(tmp_path / "refined.rhccq")
+    out = enc.encode_with_palette(img, pal, out_path=path, exact=True, refine=4)
+    back = container.read_frame(path, rh)
+    assert np.array_equal(back["palette"].cpu().numpy(), out["palette"]) and np.array_equal(_idx64(back["indices"]), _idx64(out["indices"]))
+    assert np.array_equal(back["image"].cpu().numpy(), out["palette"][_idx64(out["indices"])].reshape(img.shape))
+    assert not np.array_equal(out["palette"], pal) and len(out["palette"]) == len(pal)
+
+
+# ---- sequences ----------------------------------------------------------------------------------------------------------------------
+def _same_result(a, b):
+    return (np.array_equal(np.asarray(a["palette"]), np.asarray(b["palette"])) and a["indices"].dtype == b["indices"].dtype
+            and np.array_equal(a["indices"].cpu().numpy(), b["indices"].cpu().numpy()) and tuple(a["shape"]) == tuple(b["shape"])
+            and tuple(a["top_left"]) == tuple(b["top_left"]) and a["indices_dtype"] == b["indices_dtype"])
+
+
+def test_encode_sequence_without_refine_is_unchanged(enc):
+    frames = RM.sequence_frames()
+    q1, q2 = RM.SEQ_QUALITIES
+    plain = list(enc.encode_sequence(frames, q1, q2, RM.SEQ_MAX_DROP_DB))
+    again = list(enc.encode_sequence(frames, q1, q2, RM.SEQ_MAX_DROP_DB, refine=0, roi_weight=1))
+    assert [r["stats"]["key_frame"] for r in plain] == [True, False, True, False] and [r["stats"]["key_index"] for r in plain] == [0, 0, 2, 2]
+    for a, b in zip(plain, again):
+        assert _same_result(a, b) and a["stats"]["key_frame"] == b["stats"]["key_frame"] and a["stats"]["psnr"] == b["stats"]["psnr"]
+        assert a["stats"].get("refined", False) is False
+    # these frames share nothing: a refinement of A's palette onto B does not reach the bound either, and B still re-keys
+    refined = list(enc.encode_sequence(frames, q1, q2, RM.SEQ_MAX_DROP_DB, refine=8))
+    assert [r["stats"]["key_frame"] for r in refined] == [True, False, True, False]
+    assert all(_same_result(a, b) for a, b in zip(plain, refined))
+
+
+def _key_psnr(rh, img, res):
+    import torch
+    every = rh.zeros(img.shape[:2], torch.uint8)
+    row = rh.class_error_sums_indexed(rh.dev(img), res["indices"].reshape(-1), rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3)),
+                                      every, 1)[0]
+    assert int(row[5]) == img.shape[0] * img.shape[1]
+    return RM.psnr(int(row[0]) + int(row[1]) + int(row[2]), int(row[5]))
+
+
+def test_encode_sequence_refines_a_drifting_frame(rh, enc):
+    """Frames [A, A', B] of refine_cases.drift_frames (A red only, A' = A + 20 in red, B green and blue only), qualities (20, 10),
+    max_drop_db = 3, refine = 8.  The figures below were computed with oracle.rhccq_oracle.script_flow and the numpy reference on
+    the CPU before the inputs were fixed; the device encoder is bit-exact to that oracle, so they are the values this test prints
+    on the GPU too (it asserts their order, not the digits): encode(A) has 65
+    colours and 53.09 dB, so the bound is 50.09 dB; the plain remap of A' onto that palette gives 46.45 dB (below the bound), the
+    palette refined with up to 8 iterations (7 run) gives 53.80 dB (above it): a shift of 20 separates the two, so the larger
+    shifts 30 (40.57 / 50.57 dB) and 40 (35.72 / 46.14 dB) are not needed.  B shares nothing with A and re-keys."""
+    A, A2, B = RF.drift_frames()
+    q1, q2 = RM.SEQ_QUALITIES
+    drop = RM.SEQ_MAX_DROP_DB
+    results = list(enc.encode_sequence([A, A2, B], q1, q2, drop, refine=8))
+    key, r1, r2 = results
+    assert key["stats"]["key_frame"] is True and _same_result(key, enc.encode(A, q1, q2))
+    key_pal = np.asarray(key["palette"], np.uint8).reshape(-1, 3)
+    key_psnr = _key_psnr(rh, A, key)
+    # the reference's view of frame 1: the plain remap misses the bound, the refined one reaches it
+    _, sums = RM.remap_reference(A2, key_pal)
+    plain_psnr = RM.psnr(int(sums[-1, 1]), int(sums[-1, 0]))
+    want_pal, want_hist, want_n = RF.refine_reference(A2, key_pal, max_iter=8)
+    want_idx, sums = RM.remap_reference(A2, want_pal)
+    refined_psnr = RM.psnr(int(sums[-1, 1]), int(sums[-1, 0]))
+    print(f"key {key_psnr:.4f} dB, bound {key_psnr - drop:.4f} dB, plain remap {plain_psnr:.4f} dB, refined {refined_psnr:.4f} dB, {want_n} iterations")
+    assert plain_psnr < key_psnr - drop <= refined_psnr
+    st = r1["stats"]
+    assert st["key_frame"] is False and st["refined"] is True and st["key_index"] == 0
+    assert abs(st["psnr"] - refined_psnr) < 1e-9 and abs(st["key_psnr"] - key_psnr) < 1e-9
+    assert np.array_equal(r1["palette"], want_pal) and np.array_equal(_idx64(r1["indices"]), want_idx)
+    direct = enc.encode_with_palette(A2, key_pal, refine=8)
+    assert _same_result(r1, direct) and st["refine"] == direct["stats"]["refine"] and st["remap"] == direct["stats"]["remap"]
+    assert st["refine"]["iterations"] == want_n and st["refine"]["sse"] == want_hist[:want_n, 0].tolist()
+    # frame 2 is encoded in full
+    assert r2["stats"]["key_frame"] is True and r2["stats"]["key_index"] == 2 and "refined" not in r2["stats"]
+    assert _same_result(r2, enc.encode(B, q1, q2))
+    # without the middle step frame 1 re-keys
+    plain = list(enc.encode_sequence([A, A2], q1, q2, drop))
+    assert [r["stats"]["key_frame"] for r in plain] == [True, True]
+
+
+def test_frame_after_a_refined_one_uses_the_refined_palette(rh, enc):
+    A, A2, _ = RF.drift_frames()
+    q1, q2 = RM.SEQ_QUALITIES
+    r0, r1, r2 = list(enc.encode_sequence([A, A2, A2], q1, q2, RM.SEQ_MAX_DROP_DB, refine=8))
+    assert r1["stats"]["refined"] is True and r2["stats"]["key_frame"] is False and r2["stats"]["refined"] is False
+    assert r2["stats"]["key_index"] == 0 and r2["stats"]["key_psnr"] == r1["stats"]["key_psnr"]
+    assert np.array_equal(r2["palette"], r1["palette"]) and not np.array_equal(r1["palette"], r0["palette"])
+    want_idx, sums = RM.remap_reference(A2, r1["palette"])
+    assert np.array_equal(_idx64(r2["indices"]), want_idx) and r2["stats"]["remap"]["all"]["sse"] == int(sums[-1, 1])
+    assert np.array_equal(_idx64(r2["indices"]), _idx64(r1["indices"]))        # the same frame on the same palette
+
+
+def test_encode_sequence_checks_its_arguments(enc):
+    A, A2, _ = RF.drift_frames()
+    q1, q2 = RM.SEQ_QUALITIES
+    for kw in ({"refine": 8, "roi_weight": 0}, {"refine": 8, "roi_weight": 256}, {"refine": 0, "roi_weight": 4}, {"refine": -1}, {"refine": 65}):
+        with pytest.raises(ValueError):
+            next(enc.encode_sequence([A, A2], q1, q2, RM.SEQ_MAX_DROP_DB, **kw))
+
+
+def test_encode_sequence_refines_inside_a_key_rectangle(rh):
+    """A key frame whose result covers a rectangle of the picture: the rectangle is the roi_mask of the later frames, its "roi" row
+    decides, and the refinement weighs the pixels inside it with roi_weight.  The rectangle comes from an encoder whose encode()
+    encodes rows 8..88, columns 16..112 only and reports that window, which is what a result with top_left != (0, 0) looks like.
+    With oracle.rhccq_oracle.script_flow on the CPU (bit-exact to the device encoder): the window of A has 58 colours and 52.99 dB,
+    so the bound is 49.99 dB; inside the window the plain remap of A' gives 47.49 dB and the refined one 53.82 dB with either
+    weight, while the palettes of weight 1 and weight 4 differ (8 iterations against 7), so the weight is seen to arrive."""
+    from roibasedimagecompression_amd.image import ImageEncoder
+    t, l, h, w = 8, 16, 80, 96
+
+    class Windowed(ImageEncoder):
+        def encode(self, image, q1, q2, **kw):
+            res = ImageEncoder.encode(self, np.ascontiguousarray(np.asarray(image)[t:t + h, l:l + w]), q1, q2, **kw)
+            assert tuple(res["top_left"]) == (0, 0) and tuple(res["shape"]) == (h, w)
+            res["top_left"] = (t, l)
+            return res
+    enc = Windowed(rh)
+    A, A2, _ = RF.drift_frames()
+    q1, q2 = RM.SEQ_QUALITIES
+    drop = RM.SEQ_MAX_DROP_DB
+    cls = np.zeros(A.shape[:2], np.uint8)
+    cls[t:t + h, l:l + w] = 1
+    palettes = {}
+    for weight in (1, 4):
+        key, r1 = list(enc.encode_sequence([A, A2], q1, q2, drop, refine=8, roi_weight=weight))
+        key_pal = np.asarray(key["palette"], np.uint8).reshape(-1, 3)
+        key_psnr = _key_psnr(rh, A[t:t + h, l:l + w], key)
+        _, sums = RM.remap_reference(A2, key_pal, cls, 2)
+        plain_psnr = RM.psnr(int(sums[1, 1]), int(sums[1, 0]))
+        want_pal, want_hist, want_n = RF.refine_reference(A2, key_pal, cls, [1, weight, 1], max_iter=8)
+        want_idx, sums = RM.remap_reference(A2, want_pal, cls, 2)
+        refined_psnr = RM.psnr(int(sums[1, 1]), int(sums[1, 0]))
+        print(f"weight {weight}: key {key_psnr:.4f} dB, plain remap {plain_psnr:.4f} dB, refined {refined_psnr:.4f} dB in the window, {want_n} iterations")
+        assert plain_psnr < key_psnr - drop <= refined_psnr
+        st = r1["stats"]
+        assert st["key_frame"] is False and st["refined"] is True and abs(st["psnr"] - refined_psnr) < 1e-9
+        assert np.array_equal(r1["palette"], want_pal) and np.array_equal(_idx64(r1["indices"]), want_idx)
+        assert st["refine"]["sse"] == want_hist[:want_n, 0].tolist() and sorted(st["remap"]) == ["all", "nonroi", "roi"]
+        assert _same_result(r1, enc.encode_with_palette(A2, key_pal, roi_mask=cls, refine=8, roi_weight=weight))
+        palettes[weight] = want_pal
+    assert not np.array_equal(palettes[1], palettes[4])                       # (known from the reference: the weight changes the result)
