@@ -98,6 +98,14 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              pixels; 1..65535 = at most that many workgroups, so that one workgroup takes many chunks.  Same results. */
 #define RHCCQ_OPT_REFINE_LDS_ROWS 10
 #define RHCCQ_OPT_REFINE_MAX_BLOCKS 11
+/*   RHCCQ_OPT_CHAIN_RELEASE    rhccq_encode_frame with RHCCQ_OPT_FRAME_CHAINS = 1 (no effect with 0): 1 (default) = every level-1 problem goes
+ *                              on the moment ITS chain has ended inside the frame's chain launch (rhccq_mbk_init_released: the kernel
+ *                              publishes a flag per problem; the problem's lane waits for it on the host and queues nothing before) -- a
+ *                              class with shorter chains runs its steps, assignments and merges beside the longest chain instead of
+ *                              behind it; 0 = every lane waits for the event behind the whole launch.  A chain kernel that publishes
+ *                              nothing (RHCCQ_OPT_INIT_KERNEL other than the third generation) is waited for by that event either way.
+ *                              Same results. */
+#define RHCCQ_OPT_CHAIN_RELEASE 12
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -282,6 +290,21 @@ int rhccq_mt_uniforms(rhccq_ctx* ctx, const uint32_t* words, int64_t pos, int64_
 int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs_host,
                    int32_t n_prob, const int32_t* init_idx, const int32_t* perm, const double* rand,
                    double* centres, int32_t* chosen);
+/* The same launch, publishing every problem the moment ITS chain has ended (the launch goes on for the longer chains of the other
+ * problems): flags_dev[16 p] (a 64-byte line per problem, device address of mapped host memory: rhccq_release_flags_alloc) receives
+ * `tag` (non-zero; use a new one per launch, then a flag never has to be cleared and a stale value never matches) once problem p's slice
+ * of `centres` is complete and released at system scope -- a later launch on ANOTHER stream may then read and rewrite that slice while
+ * this launch still runs, provided the slices of two problems share no 128-byte line of `centres` (koff a multiple of 4) or of `chosen`,
+ * which the launch writes too (koff a multiple of 32: what rhccq_encode_frame lays out).  *published_host
+ * = 1 when the kernel chosen publishes (the third-generation chain), 0 when it does not (any other generation or option setting: the
+ * flags stay untouched and only the end of the launch says that the centres are there).  Otherwise as rhccq_mbk_init. */
+int rhccq_mbk_init_released(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs_host,
+                            int32_t n_prob, const int32_t* init_idx, const int32_t* perm, const double* rand,
+                            double* centres, int32_t* chosen, uint32_t* flags_dev, uint32_t tag, int32_t* published_host);
+/* n_prob release flags, zeroed, in page-locked host memory mapped to the current device: *flags_host for the host's reads (volatile /
+ * atomic loads of flags_host[16 p]), *flags_dev for rhccq_mbk_init_released.  rhccq_release_flags_free(flags_host) once no launch uses them. */
+int rhccq_release_flags_alloc(int32_t n_prob, uint32_t** flags_host, uint32_t** flags_dev);
+void rhccq_release_flags_free(uint32_t* flags_host);
 /* np.argsort(w)[:cap] AS A SET under numpy's scalar sort kernel (numpy/_core/src/npysort/quicksort.cpp aquicksort_<double>,
  * heapsort.cpp behind its depth limit) -- the selection inside a capped reassignment of rhccq_mbk_steps, exposed for tests.
  * w: double[k] on the device, non-negative integers < 2^32; 0 < cap < k; depth0 < 0 = numpy's depth limit 2 floor(log2 k)

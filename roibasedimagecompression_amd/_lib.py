@@ -73,6 +73,10 @@ PROTOTYPES = {
     "rhccq_cluster_means": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_kmeans": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rhccq_mbk_init": (c_int32, [c_void_p, c_void_p, C.POINTER(MbkProblem), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_mbk_init_released": (c_int32, [c_void_p, c_void_p, C.POINTER(MbkProblem), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, C.c_uint32, C.POINTER(c_int32)]),
+    "rhccq_release_flags_alloc": (c_int32, [c_int32, C.POINTER(c_void_p), C.POINTER(c_void_p)]),
+    "rhccq_release_flags_free": (None, [c_void_p]),
     "rhccq_encode_frame": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, C.POINTER(ClassDesc), c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                      C.POINTER(FrameResult)]),
     "rhccq_encode_frame_level2_info": (c_int32, [c_void_p, c_int32, c_void_p]),

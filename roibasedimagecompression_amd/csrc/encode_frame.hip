@@ -30,8 +30,10 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <thread>
 #include <vector>
 
+#include "chain_release_host.h"
 #include "frame_level2_host.h"
 #include "host_raii.h"
 #include "mbk_fit_host.h"
@@ -286,6 +288,11 @@ struct Lane {
   void sync() { EF_HIP(hipStreamSynchronize(stream.get())); }
 };
 
+struct FreeReleaseFlags {
+  void operator()(uint32_t* host) const { rhccq_release_flags_free(host); }
+};
+using ReleaseFlags = std::unique_ptr<uint32_t, FreeReleaseFlags>;
+
 struct Level2Fit {                                       // one MiniBatchKMeans fit of the frame's level-2 stage
   int32_t cls = 0;
   int64_t n = 0, k = 0, steps = 0;
@@ -296,6 +303,12 @@ struct FrameState {
   std::vector<std::unique_ptr<Lane>> classes;
   Arena root_arena;                                    // the per-pixel tables of a frame (allocated and used on the caller's stream)
   std::vector<Level2Fit> level2_fits;                  // the last frame's level-2 MiniBatchKMeans fits (rhccq_encode_frame_level2_info)
+  // RHCCQ_OPT_CHAIN_RELEASE: one flag per problem of the frame's chain launch (mapped host memory, a 64-byte line each), the tag of the
+  // last launch.  Never cleared: a launch's tag is new, so what an earlier frame left never matches.
+  ReleaseFlags release_flags;
+  uint32_t* release_flags_dev = nullptr;               // their device address
+  int32_t release_cap = 0;                             // problems the flags have room for
+  uint32_t release_tag = 0;
 };
 void free_frame_state(void* p) { delete (FrameState*)p; }
 
@@ -322,12 +335,33 @@ MbkDraws mbk_draws(int64_t n, int64_t k) {
   return d;
 }
 
-// A chain run ahead for one fit (RHCCQ_OPT_FRAME_CHAINS): its centres once `done` has fired
+// A chain run ahead for one fit (RHCCQ_OPT_FRAME_CHAINS): its centres once `done` has fired, or, with RHCCQ_OPT_CHAIN_RELEASE, once
+// *flag shows `tag` (chain_release_host.h); tag 0: the kernel publishes nothing, the event alone
 struct PreChain {
   MbkDraws draws;
   double* centres = nullptr;                           // [k][4], written by the chain, then the fit's own
   hipEvent_t done = nullptr;
+  const uint32_t* flag = nullptr;                      // host address of the problem's release flag
+  uint32_t tag = 0;
+  bool host_wait = false;                              // the lane waits on the host (flag or event) and queues nothing before
 };
+
+// The lane's wait for its chain on the host: nothing is queued on the lane's stream until the chain has ended
+rhccq_release::Released wait_for_chain(const PreChain& pre) {
+  const rhccq_release::Released how = rhccq_release::wait_released(
+      pre.tag, [&] { return __atomic_load_n(pre.flag, __ATOMIC_ACQUIRE); },
+      [&]() -> int {
+        const hipError_t e = hipEventQuery(pre.done);
+        if (e == hipSuccess) return rhccq_release::kComplete;
+        if (e == hipErrorNotReady) return rhccq_release::kNotReady;
+        (void)hipGetLastError();
+        return 2 + (int)e;
+      },
+      [] { std::this_thread::sleep_for(std::chrono::microseconds(30)); },
+      [](int code) { throw Err{RHCCQ_E_HIP, std::string("the frame's chain launch: hipEventQuery: ") + hipGetErrorString((hipError_t)(code - 2))}; });
+  (void)hipGetLastError();                             // ("not ready" is an answer, not an error the next launch check of this thread should find)
+  return how;
+}
 
 // the third-generation chain's LDS limit (k8_init3.h): problems above it are left to their lanes, so that a frame's launch never
 // moves a problem to another generation of the chain than the one it gets alone
@@ -342,8 +376,9 @@ struct ChainClocks {
 // The k-means++ chains of `probs` (off / n / k the caller's, the rest laid out: rhccq_fit::Totals) as ONE launch on c's stream: every
 // problem's uniforms from its own MT19937 word, the init samples in one upload, one Morton order, zeroed centres and `chosen`,
 // rhccq_mbk_init with a workgroup per problem (the kernels treat the problems of a batch independently).  Returns the centres [ktot][4].
+// flags / tag / published (frame_chains, RHCCQ_OPT_CHAIN_RELEASE): the launch publishes every problem when its own chain has ended.
 double* mbk_chains(rhccq_ctx* c, Arena& A, const uint32_t* keys, const std::vector<rhccq_mbk_problem>& probs, const std::vector<const MbkDraws*>& draws,
-                   const rhccq_fit::Totals& tot, ChainClocks* clk) {
+                   const rhccq_fit::Totals& tot, ChainClocks* clk, uint32_t* flags = nullptr, uint32_t tag = 0, int32_t* published = nullptr) {
   const hipStream_t stream = c->stream;
   auto mark = [&](double ChainClocks::*t, bool sync) {
     if (!clk) return;
@@ -375,7 +410,8 @@ double* mbk_chains(rhccq_ctx* c, Arena& A, const uint32_t* keys, const std::vect
   EF_HIP(hipMemsetAsync(centres, 0, (size_t)tot.ktot * 4 * 8, stream));
   EF_HIP(hipMemsetAsync(chosen, 0, (size_t)tot.ktot * 4, stream));
   mark(&ChainClocks::ordered, true);
-  EF_RC(c, rhccq_mbk_init(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen));
+  if (flags) EF_RC(c, rhccq_mbk_init_released(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen, flags, tag, published));
+  else EF_RC(c, rhccq_mbk_init(c, keys, probs.data(), N, d_init, d_perm, d_rand, centres, chosen));
   mark(&ChainClocks::chained, true);
   return centres;
 }
@@ -412,8 +448,12 @@ void mbk_fit(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& prob
   const double t_draws = now_ms();
   ChainClocks clk;
   double* centres;
-  if (pre) {                                                             // the frame's launch ran the chain: wait for it on this lane
-    EF_HIP(hipStreamWaitEvent(L.stream.get(), pre->done, 0));
+  bool by_flag = false;
+  if (pre) {                                                             // the frame's launch ran the chain: wait for it
+    // RHCCQ_OPT_CHAIN_RELEASE: on the host, for this problem's flag or the launch's event, and queue nothing before -- a wait in the
+    // stream would sit in a hardware queue that other lanes share until the LONGEST chain has ended.  Otherwise: the event, in the stream.
+    if (pre->host_wait) by_flag = wait_for_chain(*pre) == rhccq_release::kByFlag;
+    else EF_HIP(hipStreamWaitEvent(L.stream.get(), pre->done, 0));
     centres = pre->centres;
     if (tr) { L.sync(); clk.chained = now_ms(); }
   } else {
@@ -475,8 +515,8 @@ void mbk_fit(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& prob
   const double t_assign = now_ms();
   const long long n0 = (long long)probs[0].n, k0 = (long long)probs[0].k, steps0 = (long long)plan.view(0).steps_done();
   if (pre) {
-    fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: chain in the frame's launch, waited %.2f ms for it, %lld steps %.2f ms, assign %.2f ms\n", n0, k0,
-            clk.chained - t0, steps0, t_steps - clk.chained, t_assign - t_steps);
+    fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: chain in the frame's launch, waited %.2f ms for it (%s), %lld steps %.2f ms, assign %.2f ms\n", n0, k0,
+            clk.chained - t0, by_flag ? "its own flag" : "the launch's event", steps0, t_steps - clk.chained, t_assign - t_steps);
   } else if (N == 1) {
     fprintf(stderr, "[rhccq] mbk n=%lld k=%lld: draws+order %.2f ms (host draws %.2f, word table %.2f, uniforms+upload %.2f, order %.2f), chain %.2f ms "
             "(%.2f us/pick), %lld steps %.2f ms, assign %.2f ms\n", n0, k0, clk.ordered - t0, t_draws - t0, clk.words - t_draws, clk.uploaded - clk.words,
@@ -558,6 +598,14 @@ void run_mbk_tasks(Lane& L, std::vector<Job*>& tasks) {
     groups[g].push_back(i);
     load[g] += tasks[i]->k;
   }
+  // RHCCQ_OPT_CHAIN_RELEASE: a lane takes its problems of the frame's chain launch as their chains end, shortest chain first, and behind
+  // them the problems that run their own chain on the lane (nothing holds those up).  Same results: the problems are independent.
+  for (auto& grp : groups)
+    std::stable_sort(grp.begin(), grp.end(), [&](size_t a, size_t b) {
+      const bool ra = tasks[a]->pre && tasks[a]->pre->host_wait, rb = tasks[b]->pre && tasks[b]->pre->host_wait;
+      if (ra != rb) return ra;
+      return ra && tasks[a]->k < tasks[b]->k;
+    });
   run_lanes(
       n_lanes,
       [&](size_t g) {
@@ -1193,6 +1241,9 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
       rhccq_mbk_problem q;
       q.off = F.pal_off[(size_t)j] + hb; q.n = n; q.k = k;
       tot.add(q, pc.draws.c);
+      // (a released problem's steps rewrite its centres while a neighbour's chain has yet to write its own: no 128-byte line -- 4 centres,
+      // 32 entries of `chosen` -- belongs to two problems.  The lanes' own fits lay their problems out themselves: nothing else moves.)
+      tot.ktot = (tot.ktot + 31) & ~(int64_t)31;
       probs.push_back(q);
       ids.push_back(j);
       F.pre[j] = std::move(pc);
@@ -1201,16 +1252,38 @@ void frame_chains(FrameCtx& F, hipStream_t stream) {
   if (probs.empty()) return;
   ChainClocks clk;
   clk.sync = false;
-  double* centres = mbk_chains(c, FS.root_arena, F.keys_dev, probs, draws, tot, tr ? &clk : nullptr);
+  // RHCCQ_OPT_CHAIN_RELEASE: a flag per problem and a tag no earlier launch used
+  const bool release = c->opt_chain_release != 0;
+  uint32_t* flags_dev = nullptr;
+  if (release) {
+    if (FS.release_cap < (int32_t)probs.size()) {       // (between frames: no launch uses the old flags)
+      uint32_t *h = nullptr, *d = nullptr;
+      const int32_t cap = std::max<int32_t>((int32_t)probs.size(), 64);
+      if (rhccq_release_flags_alloc(cap, &h, &d)) throw Err{RHCCQ_E_HIP, "rhccq_release_flags_alloc failed"};
+      FS.release_flags.reset(h);
+      FS.release_flags_dev = d;
+      FS.release_cap = cap;
+    }
+    flags_dev = FS.release_flags_dev;
+    FS.release_tag = rhccq_release::next_tag(FS.release_tag);
+  }
+  int32_t published = 0;
+  double* centres = mbk_chains(c, FS.root_arena, F.keys_dev, probs, draws, tot, tr ? &clk : nullptr, flags_dev, FS.release_tag, &published);
   F.chains_done = make_event();
   EF_HIP(hipEventRecord(F.chains_done.get(), stream));
   for (size_t i = 0; i < probs.size(); ++i) {
     PreChain& pc = F.pre[ids[i]];
     pc.centres = centres + 4 * probs[i].koff;
     pc.done = F.chains_done.get();
+    pc.host_wait = release;
+    if (release && published) {
+      pc.flag = FS.release_flags.get() + i * (size_t)rhccq_release::kFlagStrideWords;
+      pc.tag = FS.release_tag;
+    }
   }
-  if (tr) fprintf(stderr, "[rhccq] frame chains: %zu problems, %lld init samples, set-up %.2f ms (host), launched after %.2f ms\n", probs.size(),
-                  (long long)tot.itot, clk.ordered - t0, now_ms() - t0);
+  if (tr) fprintf(stderr, "[rhccq] frame chains: %zu problems, %lld init samples, set-up %.2f ms (host), launched after %.2f ms, %s\n", probs.size(),
+                  (long long)tot.itot, clk.ordered - t0, now_ms() - t0,
+                  !release ? "lanes wait for the launch" : published ? "every problem released by its own flag" : "this chain kernel publishes nothing: lanes wait for the launch on the host");
 }
 
 int encode_frame(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const rhccq_class_desc* classes, int32_t n_classes, uint8_t* palette_out,

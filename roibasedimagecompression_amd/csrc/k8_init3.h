@@ -176,6 +176,15 @@ __device__ __forceinline__ void g3_commit_quad(bool on, int b, uint32_t ck, int 
 // up to kG3LdsSamples (every problem with k <= 1 900: the level-2 palettes of a frame, the segments of a many-segment frame).  A pick
 // then makes no L2 round trip at all: 3.5 us alone on the chip either way, but INSIDE a frame, beside another problem's step
 // kernels, the global-memory version of a level-2 chain ran at 6.9 us per pick (its two dependent L2 reads waited behind their traffic).
+// byte offset of release_flags in mbk_init3_kernel's argument segment, release_tag 8 bytes behind it: the LDS-sample variant reads both from the segment (see the kernel's
+// end).  G3KernelArgs restates the signature; whoever changes one changes the other, and the static_assert beside the launches (k8_minibatch.hip) holds the offset to it.
+struct G3KernelArgs {
+  const uint32_t* keys; const void* probs; const int32_t* init_idx; const int32_t* perm; const double* rand; double* centres; int32_t* chosen; uint32_t* scratch;
+  const long long* scratch_off; int max_items; uint32_t* release_flags; uint32_t release_tag;
+};
+constexpr int kG3ArgReleaseFlags = 80;
+constexpr int kG3RecordPairs = 16;   // uint2 slots (one 128-byte line, so that both sample arrays keep their line alignment) between a problem's two sample arrays in global memory: the release record
+constexpr int kG3FlagStride = 16;    // 32-bit words between two problems' release flags: a 64-byte line each (chain_release_host.h)
 constexpr int kG3LdsSamples = 5760;   // 17 / 16 x padded samples <= kG3MaxLeaves table entries
 // kIW (round 4, kCW == 1 only): EVALUATION INSIDE THE CANDIDATE'S OWN WAVE.  The wave that found candidate t and its leaves keeps them in a list of
 // its own (no shared list, no atomic on a shared counter), loads their samples and sums its candidate's improvement itself -- no barrier between
@@ -188,7 +197,8 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
                                                                const int32_t* __restrict__ init_idx, const int32_t* __restrict__ perm,
                                                                const double* __restrict__ rand, double* __restrict__ centres,
                                                                int32_t* __restrict__ chosen, uint32_t* scratch,
-                                                               const long long* __restrict__ scratch_off, int max_items) {
+                                                               const long long* __restrict__ scratch_off, int max_items,
+                                                               uint32_t* /* release_flags */, uint32_t /* release_tag */) {
   __shared__ G3Shared sh;
   __shared__ uint4 blk[kG3MaxLeaves];                    // per leaf: box (3 pairs), max closest
   __shared__ uint4 sup[kG3MaxSup];                       // per super: box, max of the leaves' max (may lag high)
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
   const int nd = (n + 63) >> 6, np = nd << 6;                     // 64-draw blocks; padded sample count
   const int nb = np >> 4, nsb = (nb + 15) >> 4, ntop = (nd + 63) >> 6, nhyp = (nsb + 15) >> 4;
   uint2* samp = kLdsS ? reinterpret_cast<uint2*>(&blk[nb]) : reinterpret_cast<uint2*>(scratch + scratch_off[blockIdx.x]);
-  uint2* dsamp = samp + np;
+  uint2* dsamp = samp + np + (kLdsS ? 0 : kG3RecordPairs);     // (global memory: the launcher's release record lies in front of it)
   int32_t* cho = chosen + P.koff;
   const int rq = lane >> 4, rj = lane & 15;
   const int quad = lane >> 2, qj = lane & 3;
@@ -945,5 +955,40 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
     const double c0 = (double)key_r(kk), c1 = (double)key_g(kk), c2 = (double)key_b(kk);
     double* C = centres + (P.koff + j) * 4;
     C[0] = c0; C[1] = c1; C[2] = c2; C[3] = km64_csq(c0, c1, c2);
+  }
+  // ---- publish THIS problem (rhccq_mbk_init_released): its centres are complete although other workgroups of the launch still run.
+  // Every wave drains its own stores, the workgroup meets, one lane releases at system scope (write-back of this XCD's L2: the readers
+  // are later launches on other streams, anywhere on the chip) and only then stores the tag -- as an atomic store at system scope to
+  // the problem's own 64-byte line of mapped host memory; a plain store behind a fence is not seen outside this XCD.  The second wait
+  // is inline assembly because the compiler drops a wait it can prove empty and the flag could then overtake the write-back.
+  // Where and what to publish must cost the pick loop no register (its allocation is measured, DESIGN.md section 8: named in the body,
+  // the two arguments are loaded in the kernel's first lines and stay live to this point).  Samples in global memory: the launcher
+  // wrote a record {the problem's flag address, tag} into the 128-byte line in front of dsamp, a pointer that is live here anyway.
+  // Samples in LDS: the arguments are read from the kernel's argument segment here and nowhere else.
+  uint32_t* flag;
+  uint32_t tag;
+  if constexpr (kLdsS) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const char* const kargs = reinterpret_cast<const char*>(__builtin_amdgcn_kernarg_segment_ptr());
+    uint32_t* const flags = *reinterpret_cast<uint32_t* const*>(kargs + kG3ArgReleaseFlags);
+    flag = flags ? flags + (size_t)blockIdx.x * kG3FlagStride : nullptr;
+    tag = *reinterpret_cast<const uint32_t*>(kargs + kG3ArgReleaseFlags + 8);
+#else
+    flag = nullptr;                                      // (the host pass only parses this)
+    tag = 0u;
+#endif
+  } else {
+    const unsigned long long* const rec = reinterpret_cast<const unsigned long long*>(dsamp - kG3RecordPairs);
+    flag = reinterpret_cast<uint32_t*>(rec[0]);
+    tag = (uint32_t)rec[1];
+  }
+  if (flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(flag, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
   }
 }

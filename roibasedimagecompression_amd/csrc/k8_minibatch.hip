@@ -26,9 +26,11 @@
 //          exact) tiled through LDS; float64 VALU bound (K = 3 is not an MFMA shape).
 #include <hipcub/hipcub.hpp>
 
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
+#include "chain_release_host.h"
 #include "mbk_schedule.h"
 #include "rhccq_common.h"
 
@@ -2876,8 +2878,11 @@ int rhccq_mt_uniforms(rhccq_ctx* ctx, const uint32_t* words, int64_t pos, int64_
   return 0;
 }
 
-int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, const int32_t* init_idx,
-                   const int32_t* perm, const double* rand, double* centres, int32_t* chosen) {
+// rhccq_mbk_init and rhccq_mbk_init_released.  flags / tag: where and what a kernel that can publishes per problem (NULL: nothing);
+// *published: whether the kernel chosen does (the third generation only)
+static int mbk_init_launch(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, const int32_t* init_idx,
+                           const int32_t* perm, const double* rand, double* centres, int32_t* chosen, uint32_t* flags, uint32_t tag, int32_t* published) {
+  if (published) *published = 0;
   if (!ctx || !keys || !probs || !init_idx || !perm || !rand || !centres || !chosen || n_prob <= 0)
     return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_init: bad argument");
   // scratch: [MbkP table][scratch_off table][per problem sample arrays]
@@ -2959,6 +2964,35 @@ int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem
   uint32_t* dscr = (uint32_t*)(base + head);
   if (int e = put(ctx, dp, hp, sizeof(MbkP) * n_prob)) return e;
   if (int e = put(ctx, dof, ho, 8 * (size_t)n_wg)) return e;
+  // third generation, samples in global memory: the release record of every problem, in the 128-byte line between its two sample arrays
+  // (k8_init3.h; zeros = publish nothing).  The arrays take 4 of the 5 words per padded sample laid out above.  The variant with the
+  // samples in LDS (every problem of a level-2 batch or of a many-segment frame) never reads a record
+  // and gets none, so what is left is one 16-byte copy for each of the few large problems of a launch.
+  static_assert(offsetof(G3KernelArgs, release_flags) == kG3ArgReleaseFlags && offsetof(G3KernelArgs, release_tag) == kG3ArgReleaseFlags + 8,
+                "mbk_init3_kernel<*, true> reads release_flags / release_tag from its argument segment at this offset");
+  // the third generation's variant, decided ONCE for the records here and the launch below: candidates per search wave, and whether every
+  // problem's samples fit the LDS tail of the leaf table
+  int g3_cw = ctx->opt_init_cands_per_wave;
+  bool g3_lds_s = false;
+  if (gen3 && !flat) {
+    bool t16 = false;                                      // (more than 12 trials cannot occur below 98 304 samples; a fourth candidate per wave is not built)
+    for (int i = 0; i < n_prob; ++i) t16 = t16 || probs[i].T > 12;
+    if (t16) g3_cw = 1;
+    g3_lds_s = g3_cw == 1;
+    for (int i = 0; i < n_prob && g3_lds_s; ++i) g3_lds_s = probs[i].init_n <= kG3LdsSamples;
+  }
+  std::vector<unsigned long long> recs;                    // (lives until the synchronisation below, as `stage` does)
+  if (gen3 && !flat && !g3_lds_s) {
+    recs.assign(2 * (size_t)n_prob, 0ull);
+    for (int i = 0; i < n_prob; ++i) {
+      if (flags) {
+        recs[2 * (size_t)i] = (unsigned long long)(uintptr_t)(flags + (size_t)i * kG3FlagStride);
+        recs[2 * (size_t)i + 1] = tag;
+      }
+      const size_t np = (size_t)((probs[i].init_n + 63) / 64) * 64;
+      if (int e = put(ctx, dscr + ho[i] + 2 * np, &recs[2 * (size_t)i], 16)) return e;
+    }
+  }
   if (nshard > 1) RHCCQ_HIP(ctx, hipMemsetAsync(xch, 0, xbytes, ctx->stream));
   RHCCQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (flat) {
@@ -2971,25 +3005,22 @@ int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem
 #undef RHCCQ_FLAT_LAUNCH
   } else if (gen3) {
     const int mi = max_items < kG3MaxItems ? max_items : kG3MaxItems;
-    int cw = ctx->opt_init_cands_per_wave;
-    bool t16 = false;                                      // (more than 12 trials cannot occur below 98 304 samples; a fourth candidate per wave is not built)
-    for (int i = 0; i < n_prob; ++i) t16 = t16 || probs[i].T > 12;
-    if (t16) cw = 1;
-    bool lds_s = cw == 1;
-    for (int i = 0; i < n_prob && lds_s; ++i) lds_s = probs[i].init_n <= kG3LdsSamples;
+    const int cw = g3_cw;
+    const bool lds_s = g3_lds_s;
+    if (published) *published = flags != nullptr;
     const bool in_wave = cw == 1 && ctx->opt_init_kernel == 5;      // RHCCQ_OPT_INIT_KERNEL = 5: evaluation inside the candidate's own wave (measured slower)
     if (lds_s && in_wave)
-      hipLaunchKernelGGL((mbk_init3_kernel<1, true, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL((mbk_init3_kernel<1, true, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
     else if (lds_s)
-      hipLaunchKernelGGL((mbk_init3_kernel<1, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL((mbk_init3_kernel<1, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
     else if (in_wave)
-      hipLaunchKernelGGL((mbk_init3_kernel<1, false, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL((mbk_init3_kernel<1, false, true>), dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
     else if (cw == 3)
-      hipLaunchKernelGGL(mbk_init3_kernel<3>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL(mbk_init3_kernel<3>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
     else if (cw == 2)
-      hipLaunchKernelGGL(mbk_init3_kernel<2>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL(mbk_init3_kernel<2>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
     else
-      hipLaunchKernelGGL(mbk_init3_kernel<1>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi);
+      hipLaunchKernelGGL(mbk_init3_kernel<1>, dim3(n_prob), dim3(kG3Threads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr, dof, mi, flags, tag);
   }
   else if (nshard > 1)
     hipLaunchKernelGGL(mbk_init2_kernel<true>, dim3(n_wg), dim3(kJThreads), 0, ctx->stream, keys, dp, init_idx, perm, rand, centres, chosen, dscr,
@@ -3002,6 +3033,39 @@ int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem
                        lds_blocks, max_items);
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
+}
+
+int rhccq_mbk_init(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, const int32_t* init_idx,
+                   const int32_t* perm, const double* rand, double* centres, int32_t* chosen) {
+  return mbk_init_launch(ctx, keys, probs, n_prob, init_idx, perm, rand, centres, chosen, nullptr, 0u, nullptr);
+}
+
+int rhccq_mbk_init_released(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_problem* probs, int32_t n_prob, const int32_t* init_idx,
+                            const int32_t* perm, const double* rand, double* centres, int32_t* chosen, uint32_t* flags, uint32_t tag,
+                            int32_t* published_host) {
+  if (!flags || !tag || !published_host) return rhccq_fail(ctx, RHCCQ_E_ARG, "mbk_init_released: flags, a non-zero tag and published_host are needed");
+  return mbk_init_launch(ctx, keys, probs, n_prob, init_idx, perm, rand, centres, chosen, flags, tag, published_host);
+}
+
+int rhccq_release_flags_alloc(int32_t n_prob, uint32_t** flags_host, uint32_t** flags_dev) {
+  static_assert(kG3FlagStride == rhccq_release::kFlagStrideWords, "one flag layout for the kernel and the host wait");
+  if (n_prob <= 0 || !flags_host || !flags_dev) return RHCCQ_E_ARG;
+  void* h = nullptr;
+  void* d = nullptr;
+  const size_t bytes = (size_t)n_prob * kG3FlagStride * 4;
+  if (hipHostMalloc(&h, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return RHCCQ_E_HIP;
+  memset(h, 0, bytes);
+  if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+    (void)hipHostFree(h);
+    return RHCCQ_E_HIP;
+  }
+  *flags_host = (uint32_t*)h;
+  *flags_dev = (uint32_t*)d;
+  return 0;
+}
+
+void rhccq_release_flags_free(uint32_t* flags_host) {
+  if (flags_host) (void)hipHostFree(flags_host);
 }
 
 int rhccq_npysort_head(rhccq_ctx* ctx, const double* w, int32_t k, int32_t cap, int32_t depth0, int32_t use_lds, void* scratch, uint32_t* mask_out) {

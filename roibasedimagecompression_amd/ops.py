@@ -231,6 +231,7 @@ class Rhccq:
     OPT_FRAME_LEVEL2 = 9             # rhccq_encode_frame: 1 (default) the level-2 palettes of all classes as one batch on one lane; 0: one per class lane
     OPT_REFINE_LDS_ROWS = 10         # palette_refine: palettes of more rows accumulate in global memory (0 .. palette_refine_lds_rows(), default that)
     OPT_REFINE_MAX_BLOCKS = 11       # palette_refine: at most this many workgroups (0, default: 8 per CU)
+    OPT_CHAIN_RELEASE = 12           # rhccq_encode_frame: 1 (default) a level-1 problem goes on when its own chain of the frame's launch ends; 0: when the launch ends
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""
