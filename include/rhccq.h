@@ -778,6 +778,35 @@ int rhccq_palette_refine(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, u
 int rhccq_palette_refine_host(const uint8_t* rgb, int64_t n_pixels, uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
                               const int32_t* weights, int32_t max_iter, uint64_t* history, int32_t* n_iter);
 
+/* ---- EXTENSION: reduction of a given palette to K_target rows, exact pairwise merging (no reference counterpart; csrc/palette_reduce.hip) ----
+ * Pairwise-nearest-neighbour reduction with Ward's criterion.  palette is uint8[K][3], counts uint64[K] the weight of every row (the
+ * histogram of an index map, say), 1 <= K_target <= K.  A live cluster has a weight n, per-channel sums S in 64-bit integers and an integer
+ * centre c; row j starts with n_j = counts[j], S_j = n_j * palette[j], c_j = palette[j]; a cluster's id is the lowest original row in it.
+ * (1) Rows with counts[j] == 0 are dropped first: they never merge and map to -1.  (2) The cost of the pair a < b is the exact rational
+ * n_a n_b D(c_a, c_b) / (n_a + n_b), D the squared distance of the integer centres (rhccq_palette_remap's arithmetic).  (3) While more
+ * than K_target clusters live, the pair of least cost merges; costs are compared exactly (cross-multiplied in 128 bits), ties go to the
+ * smallest a, then the smallest b (duplicate rows have D = 0 and merge first): n_a += n_b, S_a += S_b, c_a = floor((2 S_a + n_a) / (2 n_a))
+ * per channel (rhccq_palette_refine's rounding: nearest, halves up), b dies.  (4) The live clusters come out in ascending id order:
+ * *k_out = min(K_target, non-empty rows); palette_out uint8[K_target][3] and counts_out uint64[K_target], zero from row k_out on;
+ * map int32[K]: old row -> new row, -1 for an empty row; merges int32[K - 1][2] (may be NULL): the (a, b) of every step in order, -1 past
+ * the last step.  The centre is an integer because it is the row a decoder will use; with the sum of the counts at most 2^32 - 1,
+ * n_a n_b < 2^62, D < 2^18 and n_a + n_b < 2^32, so every cross product is below 2^112.
+ * RHCCQ_E_ARG: a null palette, counts, palette_out, counts_out, map, k_out (or work); K < 1; K_target outside 1..K; every count zero; a
+ * misaligned counts, counts_out, work (8), map, merges or k_out (4); work_bytes below rhccq_palette_reduce_bytes(K).  RHCCQ_E_LIMIT:
+ * K > 65536; the sum of the counts above 2^32 - 1; in the device form K > rhccq_palette_reduce_max_rows().
+ * Device form: every pointer is device memory; async on the context stream (three launches: row state, the table of nearest partners,
+ * then ONE resident workgroup that runs the merge chain with its per-row state in LDS), no host synchronisation, nothing allocated.  The
+ * two errors that only the counts show (all zero; sum above 2^32 - 1) cannot be returned without reading them: the call returns 0 and the
+ * kernel writes RHCCQ_E_ARG / RHCCQ_E_LIMIT to *k_out, zero palette_out and counts_out, and -1 throughout map and merges.
+ * Host form: the same key / compare / scan / merge functions run serially on host memory, for any K <= 65536. */
+int32_t rhccq_palette_reduce_max_rows(void);            /* host only: the largest K of the device form (the rows one workgroup's LDS holds) */
+int64_t rhccq_palette_reduce_bytes(int32_t K);          /* host only: workspace bytes */
+int rhccq_palette_reduce(rhccq_ctx* ctx, const uint8_t* palette, const uint64_t* counts, int32_t K, int32_t K_target, void* work,
+                         int64_t work_bytes, uint8_t* palette_out, uint64_t* counts_out, int32_t* map, int32_t* merges /* may be NULL */,
+                         int32_t* k_out);
+int rhccq_palette_reduce_host(const uint8_t* palette, const uint64_t* counts, int32_t K, int32_t K_target, uint8_t* palette_out,
+                              uint64_t* counts_out, int32_t* map, int32_t* merges, int32_t* k_out);
+
 #ifdef __cplusplus
 }
 #endif

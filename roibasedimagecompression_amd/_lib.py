@@ -185,6 +185,11 @@ PROTOTYPES = {
     "rhccq_palette_refine": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64,
                                        c_void_p, c_void_p]),
     "rhccq_palette_refine_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "rhccq_palette_reduce_max_rows": (c_int32, []),
+    "rhccq_palette_reduce_bytes": (c_int64, [c_int32]),
+    "rhccq_palette_reduce": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "rhccq_palette_reduce_host": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -144,3 +144,45 @@ def read_frame(path, rh=None):
         raise RhccqError("read_frame: empty palette")
     img = rh.decode(idx, pal).reshape(h, w, 3)
     return {"image": img, "palette": pal, "indices": idx, "shape": (h, w), "dtype": name}
+
+
+def index_histogram(indices, n_rows, rh=None, weights=None):
+    """how often every palette row is used: int64[n_rows] on the device from an index map (uint8, int16 holding uint16, int32 or
+    int64, any shape), by torch.bincount.  An index past the palette counts for row 0, the row a decoder shows for it.  weights:
+    an int64 tensor with one element per index, added instead of 1."""
+    rh = rh or default_context()
+    wide = indices.reshape(-1).to(torch.int64)
+    if indices.dtype == torch.int16:
+        wide = wide & 0xFFFF
+    wide = torch.where(wide < n_rows, wide, torch.zeros_like(wide))
+    if weights is None:
+        return torch.bincount(wide, minlength=n_rows)
+    # float64 weights: every partial sum is an integer below 2^53, so the sums are exact
+    return torch.bincount(wide, weights=weights.reshape(-1).to(torch.float64), minlength=n_rows).to(torch.int64)
+
+
+def reduce_frame(src, dst, colours, rh=None, exact=False):
+    """a .rhccq file to one of at most `colours` palette rows, without the source image: read_frame, the histogram of the indices,
+    Rhccq.palette_reduce (exact pairwise merging, include/rhccq.h), every index through the reduction's map (no pixel carries an
+    unused row, so no -1 is read), write_frame.  A file that has no more than `colours` used rows only loses its unused ones.
+    -> {"from": rows read, "to": rows written, "bytes": write_frame's value, "psnr": the new decode against the old decode (inf
+    when nothing merged)}.  The palette may have at most ops.palette_reduce_max_rows() rows (RhccqError)."""
+    from .ops import psnr_from_sse
+    rh = rh or default_context()
+    fr = read_frame(src, rh)
+    pal = fr["palette"].contiguous()
+    K = int(pal.shape[0])
+    if int(colours) < 1:
+        raise ValueError("reduce_frame: colours >= 1 is expected")
+    h, w = fr["shape"]
+    wide = fr["indices"].reshape(-1).to(torch.int32)
+    if fr["indices"].dtype == torch.int16:
+        wide = wide & 0xFFFF
+    wide = torch.where(wide < K, wide, torch.zeros_like(wide)).contiguous()
+    new_pal, _, map_, _ = rh.palette_reduce(pal, index_histogram(wide, K, rh), min(int(colours), K))
+    idx = rh.remap(wide, map_.contiguous())
+    res = {"palette": rh.to_host(new_pal), "indices": idx, "shape": (h, w)}
+    size = write_frame(res, dst, rh, exact=exact)
+    one_class = torch.zeros((h, w), dtype=torch.uint8, device=rh.device)
+    row = rh.class_error_sums_indexed(fr["image"].contiguous(), idx, new_pal.contiguous(), one_class, 1)[0]
+    return {"from": K, "to": int(new_pal.shape[0]), "bytes": size, "psnr": psnr_from_sse(int(row[0]) + int(row[1]) + int(row[2]), h * w)}

@@ -399,14 +399,18 @@ class ImageEncoder:
         return region_metrics_from_sums(sums, rh.class_ssim7(rgb, recon, region_map, len(names)), names)
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
-    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False):
+    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
         container.write_frame(exact=exact).
         roi_mask: a caller's ROI mask (bool / uint8 [H,W], numpy or device tensor) instead of the detector: stats["roi_source"] =
         "caller".  report: stats["quality"] = PSNR / SSIM / ... of the result inside ("roi"), outside ("nonroi") the region map and
-        over the picture ("all") (api.comparison.region_metrics_from_sums), computed on the device from the indices."""
+        over the picture ("all") (api.comparison.region_metrics_from_sums), computed on the device from the indices.
+        max_colours = N (EXTENSION, default None = off): a finished result of more than N palette rows is reduced to N by
+        Rhccq.palette_reduce (exact pairwise merging, weights = the histogram of the result's own index map), and the pixels of the
+        rectangle the result covers are remapped onto the reduced palette (Rhccq.palette_remap); stats["reduce"] = {from, to, empty,
+        steps}.  The file and the report are those of the reduced result."""
         rh = self.rh
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -448,6 +452,9 @@ class ImageEncoder:
         res = enc.finish(S, comps3, m3c, q3, res3)
         torch.cuda.current_stream(rh.device).synchronize()
         lap("levels23")
+        if max_colours is not None and len(res["palette"]) > int(max_colours):
+            stats["reduce"] = self._reduce_result(rgb, res, int(max_colours))
+            lap("reduce")
         if out_path:
             from . import container
             container.write_frame(res, out_path, rh, exact=exact)
@@ -461,13 +468,35 @@ class ImageEncoder:
         return res
 
     # ---- a given palette (EXTENSION, no reference counterpart) ------------------------------------------------------------------
+    def _reduce(self, pal, counts, colours):
+        """Rhccq.palette_reduce and its stats row -> (palette device uint8[k_out, 3], {from, to, empty, steps})"""
+        if colours < 1:
+            raise ValueError("ImageEncoder: the number of colours to reduce to must be >= 1")
+        K = int(pal.shape[0])
+        new_pal, _, _, merges = self.rh.palette_reduce(pal, counts, min(colours, K))
+        k, steps = int(new_pal.shape[0]), int(merges.shape[0])
+        return new_pal.contiguous(), {"from": K, "to": k, "empty": K - k - steps, "steps": steps}
+
+    def _reduce_result(self, rgb, res, colours):
+        """encode's max_colours: the finished result in place -> its stats row"""
+        from .container import index_histogram
+        rh = self.rh
+        (top, left), (h, w) = res["top_left"], res["shape"]
+        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+        new_pal, row = self._reduce(pal, index_histogram(res["indices"], int(pal.shape[0]), rh), colours)
+        window = rgb if (top, left, h, w) == (0, 0, int(rgb.shape[0]), int(rgb.shape[1])) else rgb[top:top + h, left:left + w].contiguous()
+        idx, _ = rh.palette_remap(window, new_pal)
+        res.update(palette=rh.to_host(new_pal), indices=idx.reshape(res["indices"].shape),                 # (the layout the result had)
+                   indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
+        return row
+
     @staticmethod
     def _remap_row(pixels, sse):
         pixels, sse = int(pixels), int(sse)
         return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
-    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1):
+    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -480,13 +509,18 @@ class ImageEncoder:
         With roi_mask a pixel inside the mask weighs roi_weight (1..255) and one outside 1 in the refinement; without a mask
         roi_weight must be 1.  stats["refine"] = {iterations, converged, sse: [...], changed: [...]} (the weighted sums of the
         iterations that ran); stats["remap"] stays the unweighted figures of the final remap.  Rows that receive no pixel never
-        move, so a palette far from the image collapses onto a few rows: refinement follows drift, it does not replace encode."""
+        move, so a palette far from the image collapses onto a few rows: refinement follows drift, it does not replace encode.
+        colours = N (default None = off): the palette is first reduced to at most N rows for this image: a remap onto the given
+        palette, the rows' counts (torch.bincount; with roi_mask a pixel inside the mask counts roi_weight, as it weighs in the
+        refinement, and roi_weight needs no refine then), Rhccq.palette_reduce (exact pairwise merging; rows no pixel uses are dropped),
+        then the refinement, if asked for, of the reduced palette, and the final remap.  stats["reduce"] = {from: K, to: rows kept,
+        empty: rows dropped unused, steps: merges}.  K may be at most ops.palette_reduce_max_rows() (RhccqError)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_with_palette: refine must be 0..64")
-        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not refine)):
-            raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None))):
+            raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0 or colours")
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -509,6 +543,13 @@ class ImageEncoder:
             from .api.roi import region_map_from_mask
             cls = region_map_from_mask(rgb, roi_mask, rh)                     # 0 / 1: quality()'s rows
             lap("mask")
+        reduce_row = None
+        if colours is not None:
+            from .container import index_histogram
+            first, _ = rh.palette_remap(rgb, pal)
+            weights = None if cls is None or roi_weight == 1 else 1 + (roi_weight - 1) * (cls == 1).to(torch.int64)
+            pal, reduce_row = self._reduce(pal, index_histogram(first, int(pal.shape[0]), rh, weights), int(colours))
+            lap("reduce")
         if refine:
             pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
         idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
@@ -524,6 +565,8 @@ class ImageEncoder:
         res = {"palette": rh.to_host(pal), "indices": idx, "indices_dtype": "uint8" if idx.dtype == torch.uint8 else "uint16",
                "shape": (H, W), "top_left": (0, 0)}
         stats = {"remap": remap}
+        if reduce_row is not None:
+            stats["reduce"] = reduce_row
         if refine:
             stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
                                "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
@@ -541,7 +584,7 @@ class ImageEncoder:
         res["stats"] = stats
         return res
 
-    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1):
+    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -555,7 +598,8 @@ class ImageEncoder:
         refine=N) (with the key's rectangle as roi_mask and roi_weight inside it when the key covers a rectangle) and kept iff that
         reaches the bound: stats["key_frame"] = False, stats["refined"] = True, key_index and key_psnr stay the key frame's, and the
         refined palette is the one later frames are remapped onto.  Otherwise the frame is encoded in full as before.  Every
-        result that is not a key frame has stats["refined"] (bool; always False with refine = 0)."""
+        result that is not a key frame has stats["refined"] (bool; always False with refine = 0).
+        max_colours: passed to the key frames' encode (default None = off)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         if refine < 0 or refine > 64:
@@ -586,7 +630,7 @@ class ImageEncoder:
                         key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
                     yield res
                     continue
-            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact)
+            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

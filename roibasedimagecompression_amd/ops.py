@@ -115,6 +115,11 @@ def palette_refine_lds_rows():
     return int(_lib.load().rhccq_palette_refine_lds_rows())
 
 
+def palette_reduce_max_rows():
+    """the largest palette Rhccq.palette_reduce takes: the rows whose state one workgroup's LDS holds"""
+    return int(_lib.load().rhccq_palette_reduce_max_rows())
+
+
 def psnr_from_sse(sse, n_pixels):
     """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
     10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
@@ -1082,6 +1087,50 @@ class Rhccq:
                                                   C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), max_iter, self._p(work),
                                                   wbytes, self._p(history), self._p(n_iter)), "palette_refine")
         return out, history, n_iter
+
+    # -- reduction of a given palette to N rows: exact pairwise merging (EXTENSION: csrc/palette_reduce.hip) ------------
+    def palette_reduce(self, palette, counts, colours):
+        """palette uint8[K, 3], counts [K] non-negative integers (numpy or device; the weight of every row, their sum at most
+        2^32 - 1), colours = K_target in 1..K -> (palette device uint8[k_out, 3], counts device int64[k_out], map device int32[K]:
+        old row -> new row, -1 for a row of count 0, merges device int32[n_steps, 2]: the (a, b) of every merge in order).
+        Pairwise-nearest-neighbour merging by Ward's criterion in exact integers (include/rhccq.h): the two clusters whose union
+        costs least merge, ties to the lowest rows, the merged centre is the weighted mean rounded to nearest.  k_out =
+        min(colours, rows of non-zero count) is read back once.  K above palette_reduce_max_rows() raises RhccqError."""
+        def on_device(a, dtype, what):
+            if not torch.is_tensor(a):
+                a = np.ascontiguousarray(a)
+                if dtype is torch.int64:
+                    if a.dtype.kind not in "iu":
+                        raise TypeError(f"palette_reduce: {what} must be integers, got {a.dtype}")
+                    a = a.astype(np.uint64).view(np.int64)
+                a = torch.from_numpy(a)
+            if a.dtype != dtype and not (dtype is torch.int64 and a.dtype in (torch.int32, torch.uint8, torch.int16)):
+                raise TypeError(f"palette_reduce: {what} must be {dtype}, got {a.dtype}")
+            return a.to(self.device).to(dtype).contiguous()
+        palette = on_device(palette, torch.uint8, "palette")
+        counts = on_device(counts, torch.int64, "counts")
+        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
+            raise ValueError("palette_reduce: palette [K, 3] and counts [K] are expected")
+        K, target = int(palette.shape[0]), int(colours)
+        cap = palette_reduce_max_rows()
+        if K > cap:
+            raise RhccqError(f"palette_reduce: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        if K < 1 or not 1 <= target <= K:
+            raise RhccqError("palette_reduce: K >= 1 and colours in 1..K are required")
+        wbytes = int(self._raw.rhccq_palette_reduce_bytes(K))
+        work = self.empty((wbytes // 8,), torch.int64)
+        pal_out = self.empty((target, 3), torch.uint8)
+        cnt_out = self.empty((target,), torch.int64)
+        map_ = self.empty((K,), torch.int32)
+        merges = self.empty((max(K - 1, 1), 2), torch.int32)
+        k_out = self.empty((1,), torch.int32)
+        self._check(self.lib.rhccq_palette_reduce(self.ctx, self._p(palette), self._p(counts), K, target, self._p(work), wbytes, self._p(pal_out),
+                                                  self._p(cnt_out), self._p(map_), self._p(merges), self._p(k_out)), "palette_reduce")
+        k, live = torch.cat([k_out, (counts != 0).sum().to(torch.int32).reshape(1)]).tolist()     # the one read
+        if k < 0:                                            # the errors only the counts show come back through k_out
+            raise RhccqError(f"palette_reduce failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
+        n_steps = live - k
+        return pal_out[:k], cnt_out[:k], map_, merges[:max(n_steps, 0)]
 
     # -- split score (split_score.py:15-142) ----------------------------------------------------------
     def split_stats(self, rgb, mask=None):
