@@ -807,6 +807,56 @@ int rhccq_palette_reduce(rhccq_ctx* ctx, const uint8_t* palette, const uint64_t*
 int rhccq_palette_reduce_host(const uint8_t* palette, const uint64_t* counts, int32_t K, int32_t K_target, uint8_t* palette_out,
                               uint64_t* counts_out, int32_t* map, int32_t* merges, int32_t* k_out);
 
+/* ---- EXTENSION: the palette ladder: moments, the error curve of every rung, any rung from the log (no reference counterpart;
+ * csrc/palette_ladder.hip) ----
+ * rhccq_palette_moments: one pass over the pixels.  a(p) is rhccq_palette_remap's index of p (exact integers, ties to the lowest row);
+ * idx_out (may be NULL; otherwise idx_elem_bytes 1, 2 or 4 per element as the remap takes it) receives it.  moments is
+ * uint64[n_classes + 1][K][5] = {N, Sr, Sg, Sb, Q}: table c sums the pixels with cls[p] == c, the last table every pixel (the remap's
+ * rule for cls == NULL and for values >= n_classes: those pixels are in the last table only); per row j = a(p), N counts the pixels,
+ * S adds the channel values and Q adds r^2 + g^2 + b^2.  The moments are unweighted.  The call zeroes the array; n_pixels == 0 leaves it
+ * zero.  Integer addition only: every order gives the same sums.
+ * RHCCQ_E_ARG: a null rgb, palette or moments; K < 1; n_pixels < 0; n_classes outside 0..16 (or not 0 with cls == NULL); with idx_out:
+ * idx_elem_bytes not 1, 2 or 4, a misaligned idx_out, K > 256 with 1-byte indices; a misaligned moments (8).  RHCCQ_E_LIMIT: K > 65536.
+ * Device form: async on the context stream, nothing allocated: a memset, the remap's chunk loop with the accumulators in LDS while
+ * K <= rhccq_palette_moments_lds_rows(n_classes) and in global memory above, and a finish launch that forms the last table.
+ *
+ * rhccq_palette_curve: the squared error of every rung of rhccq_palette_reduce's ladder, without a remap.  palette, counts (the weights
+ * the chain was run with) and merges (int32[K - 1][2] as rhccq_palette_reduce writes it, -1 behind the last step) define the replay:
+ * row state n_j = counts[j], S_j = n_j * palette[j], c_j = palette[j]; step s merges (a, b) as the reduction does (n and S add, c_a =
+ * floor((2 S + n) / (2 n)) per channel) and b's moments go into a's.  moments is uint64[n_tables][K][5] as rhccq_palette_moments writes
+ * it (n_tables = n_classes + 1, 1..17); curve is uint64[n_tables][K]: curve[t][0] = sum over rows of (Q - 2 c.S + N |c|^2) over table t,
+ * curve[t][s] the same sum over the clusters after s steps; entries behind the last step are 0.  A row of count 0 never merges and
+ * keeps contributing its own term.  The replay ends at the first entry that is not a merge of two live rows a < b < K.  curve[t][s] is
+ * the error of table t's pixels shown through the clusters their rows went into, so it bounds from above the error of the nearest-row
+ * remap onto the rung of (non-empty rows - s) rows.  Every term is below 2^51 (sum of the counts at most 2^32 - 1, unweighted N no larger).
+ * RHCCQ_E_ARG: a null argument; K < 1; n_tables outside 1..17; misaligned counts, moments, curve, work (8) or merges (4); work_bytes
+ * below rhccq_palette_curve_bytes(K, n_tables).  RHCCQ_E_LIMIT: K > 65536; in the device form K > rhccq_palette_reduce_max_rows().
+ * Device form: a copy of the moments, one launch for the row state and curve[t][0], then ONE wave that replays the log.
+ *
+ * rhccq_palette_rung: the rung of K_target rows from the log, without the chain: identical in every byte to what
+ * rhccq_palette_reduce(K_target) writes to palette_out, counts_out, map and k_out for the same palette and counts (clusters in
+ * ascending id order, empty rows -1, zero rows from k_out on).  Every row is resolved through the first (non-empty rows - K_target)
+ * steps, n and n * palette are added per cluster, and the centre is floor((2 S + n) / (2 n)).  A log that ends before K_target is
+ * reached gives the clusters it has: *k_out is their number, map holds their rows, and only the first K_target are written.
+ * The log is expected to name every b once, as rhccq_palette_reduce writes it (a row dies once); an entry that is not a < b < K ends it.
+ * A log that repeats a b stays in bounds, but the device form does not define which of its links wins (the host form keeps the last).
+ * Errors as rhccq_palette_reduce's (no workspace; merges must be given); the two that only the counts show come back through *k_out
+ * in the device form.  Host forms: the same functions run serially on host memory, for any K <= 65536. */
+int32_t rhccq_palette_moments_lds_rows(int32_t n_classes);   /* host only: the largest K whose accumulators live in LDS (0: bad n_classes) */
+int rhccq_palette_moments(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                          int32_t n_classes, void* idx_out /* may be NULL */, int32_t idx_elem_bytes, uint64_t* moments);
+int rhccq_palette_moments_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                               int32_t n_classes, void* idx_out, int32_t idx_elem_bytes, uint64_t* moments);
+int64_t rhccq_palette_curve_bytes(int32_t K, int32_t n_tables);   /* host only: workspace bytes */
+int rhccq_palette_curve(rhccq_ctx* ctx, const uint8_t* palette, const uint64_t* counts, int32_t K, const int32_t* merges,
+                        const uint64_t* moments, int32_t n_tables, void* work, int64_t work_bytes, uint64_t* curve);
+int rhccq_palette_curve_host(const uint8_t* palette, const uint64_t* counts, int32_t K, const int32_t* merges, const uint64_t* moments,
+                             int32_t n_tables, uint64_t* curve);
+int rhccq_palette_rung(rhccq_ctx* ctx, const uint8_t* palette, const uint64_t* counts, int32_t K, const int32_t* merges, int32_t K_target,
+                       uint8_t* palette_out, uint64_t* counts_out, int32_t* map, int32_t* k_out);
+int rhccq_palette_rung_host(const uint8_t* palette, const uint64_t* counts, int32_t K, const int32_t* merges, int32_t K_target,
+                            uint8_t* palette_out, uint64_t* counts_out, int32_t* map, int32_t* k_out);
+
 #ifdef __cplusplus
 }
 #endif

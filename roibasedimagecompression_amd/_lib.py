@@ -190,6 +190,14 @@ PROTOTYPES = {
     "rhccq_palette_reduce": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "rhccq_palette_reduce_host": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_moments_lds_rows": (c_int32, [c_int32]),
+    "rhccq_palette_moments": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_moments_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_curve_bytes": (c_int64, [c_int32, c_int32]),
+    "rhccq_palette_curve": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "rhccq_palette_curve_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_rung": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_rung_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

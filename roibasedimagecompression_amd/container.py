@@ -72,18 +72,31 @@ def lossless_compress_device(palette, indices, shape, rh=None, exact=False):
             "i": rh.zlib_compress(idx, exact=exact), "d": name}
 
 
-def save_compressed_device(compressed_data, filename, rh=None, exact=False):
-    """save_compressed with the outer zlib layer on the device: b"RHCCQ", <I length, zlib of the protocol-5 pickle;
-    returns what save_compressed returns (the body's length + 8).  exact=True: the file is byte-identical to
-    save_compressed's"""
+def package_bytes(compressed_data, rh=None, exact=False):
+    """the .rhccq file of a package (lossless_compress_device's dict) as bytes: b"RHCCQ", <I length, zlib of the protocol-5 pickle,
+    the outer zlib layer on the device.  exact=True: the bytes of save_compressed's file"""
     rh = rh or default_context()
     raw = np.frombuffer(pickle.dumps(compressed_data, protocol=5), dtype=np.uint8).copy()
     body = rh.zlib_compress(rh.dev(raw), exact=exact)
+    return b"RHCCQ" + struct.pack("<I", len(body)) + body
+
+
+def save_compressed_device(compressed_data, filename, rh=None, exact=False):
+    """save_compressed with the outer zlib layer on the device (package_bytes written to `filename`); returns what save_compressed
+    returns (the body's length + 8).  exact=True: the file is byte-identical to save_compressed's"""
+    data = package_bytes(compressed_data, rh, exact=exact)
     with open(filename, "wb") as f:
-        f.write(b"RHCCQ")
-        f.write(struct.pack("<I", len(body)))
-        f.write(body)
-    return len(body) + 8
+        f.write(data)
+    return len(data) - 1                                   # (save_compressed counts the body and 8 of the 9 framing bytes)
+
+
+def frame_bytes(result, rh=None, exact=False):
+    """the .rhccq file of a FrameEncoder result (palette, indices, shape) as bytes, built in memory: what write_frame writes.
+    exact=True: every layer through the level-9 encoder, so the bytes are those of the host path's file"""
+    if "palette" not in result or "indices" not in result or "shape" not in result:
+        raise RhccqError("write_frame: a FrameEncoder result (palette, indices, shape) is required")
+    pkg = lossless_compress_device(result["palette"], result["indices"], result["shape"], rh, exact=exact)
+    return package_bytes(pkg, rh, exact=exact)
 
 
 def write_frame(result, filename, rh=None, exact=False):

@@ -32,14 +32,11 @@
 
 namespace rhccq {
 
-// rows the resident workgroup holds: 4096 * 12 bytes = 48 KiB of LDS, which with the reduction scratch stays below the 64 KiB a
-// workgroup gets without asking; row ids also fit the uint16 partner slots (0xFFFF = none)
-constexpr int kReduceMaxRows = 4096;
+// kReduceMaxRows, kReduceMaxSum, reduce_clamp and refine_mean (the merged centre) are in palette_remap.h: the ladder shares them
 constexpr int kReduceBlock = 1024;                    // lanes of the resident workgroup at K >= 1024 (smaller palettes take fewer waves)
 constexpr int kReduceWaves = kReduceBlock / 64;
 constexpr uint32_t kReduceNoIdx = 0xFFFFFFFFu;
 constexpr uint16_t kReduceNoRow = 0xFFFFu;
-constexpr unsigned long long kReduceMaxSum = 0xFFFFFFFFull;
 static_assert(kReduceMaxRows < kReduceNoRow && kReduceMaxRows * 12 + 1024 <= 64 * 1024 && kReduceWaves == 16, "LDS layout of the chain kernel");
 
 typedef unsigned __int128 reduce_u128;
@@ -63,9 +60,6 @@ __host__ __device__ __forceinline__ bool reduce_less(const ReduceKey& x, const R
   return l < r || (l == r && x.idx < y.idx);
 }
 
-// the weighted mean rounded to nearest, halves up: the refinement's rule (n > 0, s <= 255 n)
-__host__ __device__ __forceinline__ uint32_t reduce_mean(unsigned long long s, unsigned long long n) { return (uint32_t)((2ull * s + n) / (2ull * n)); }
-
 // r's best partner among the live rows first, first + step, ... < K (first > r); ascending order and a strict comparison keep the lowest
 __host__ __device__ __forceinline__ ReduceKey reduce_scan(int r, int K, const uint32_t* n, const uint32_t* c, int first, int step) {
   ReduceKey best = reduce_no_key();
@@ -77,9 +71,6 @@ __host__ __device__ __forceinline__ ReduceKey reduce_scan(int r, int K, const ui
   }
   return best;
 }
-
-// a count as it enters the sum check: clamped so that 65536 of them cannot overflow
-__host__ __device__ __forceinline__ unsigned long long reduce_clamp(unsigned long long v) { return v > kReduceMaxSum ? kReduceMaxSum + 1ull : v; }
 
 __device__ __forceinline__ ReduceKey reduce_shfl_xor(const ReduceKey& k, int o) {
   ReduceKey t;
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(kReduceBlock) void palette_reduce_chain_kernel(cons
       if (lane < 3) {
         const unsigned long long s = w.S[(size_t)a * 3 + lane] + w.S[(size_t)b * 3 + lane];
         w.S[(size_t)a * 3 + lane] = s;
-        ch = reduce_mean(s, nn_);
+        ch = refine_mean(s, nn_);
       }
       const uint32_t c = (__shfl(ch, 0, 64) << 16) | (__shfl(ch, 1, 64) << 8) | __shfl(ch, 2, 64);
       if (lane == 0) {
@@ -357,7 +348,7 @@ int rhccq_palette_reduce_host(const uint8_t* palette, const uint64_t* counts, in
     uint32_t ch[3];
     for (int i = 0; i < 3; ++i) {
       S[(size_t)a * 3 + i] += S[(size_t)b * 3 + i];
-      ch[i] = reduce_mean(S[(size_t)a * 3 + i], n[a]);
+      ch[i] = refine_mean(S[(size_t)a * 3 + i], n[a]);
     }
     c[a] = (ch[0] << 16) | (ch[1] << 8) | ch[2];
     n[b] = 0u;

@@ -34,9 +34,6 @@ static_assert(64ull * 255 * 255 < (1ull << 32), "wave sums fit 32 bits");
 
 struct RefineWeights { uint32_t w[kRemapMaxClasses + 1]; };
 
-// the weighted mean rounded to nearest, halves up (n > 0; s <= 255 n)
-__host__ __device__ __forceinline__ uint32_t refine_mean(unsigned long long s, unsigned long long n) { return (uint32_t)((2ull * s + n) / (2ull * n)); }
-
 // one pixel's (or one wave's) contribution to an accumulator row, in LDS or in global memory
 __device__ __forceinline__ void refine_add(unsigned long long* row, uint32_t n, uint32_t r, uint32_t g, uint32_t b) {
   atomicAdd(row + 0, (unsigned long long)n);

@@ -1,5 +1,7 @@
 // The pack / evaluate / carry functions and constants of the nearest-colour remap, shared by its kernel (palette_remap.hip) and by the
-// palette refinement that assigns pixels with the same arithmetic (palette_refine.hip).  The derivation is in palette_remap.hip.
+// palette refinement that assigns pixels with the same arithmetic (palette_refine.hip) and by the ladder's moments pass
+// (palette_ladder.hip), with the rounded mean that the refinement, the reduction's merges and the ladder's rungs share, and the
+// reduction's row cap, sum limit and clamp that the ladder shares.  The derivation is in palette_remap.hip.
 #pragma once
 #include "rhccq_common.h"
 
@@ -38,6 +40,16 @@ __host__ __device__ __forceinline__ void remap_carry(uint32_t tile_best, int til
     idx = (uint32_t)tile_base + (tile_best & ((1u << kRemapIdxBits) - 1u));
   }
 }
+// ---- shared by the reduction (palette_reduce.hip) and the ladder built on its log (palette_ladder.hip) ----
+// rows the reduction's resident workgroup holds: 4096 * 12 bytes = 48 KiB of LDS, which with the reduction scratch stays below the 64 KiB a
+// workgroup gets without asking; row ids also fit uint16 slots (0xFFFF = none).  The device forms of the ladder's curve and rung share the
+// cap: the reduction is the only producer of a merges log in device memory.
+constexpr int kReduceMaxRows = 4096;
+constexpr unsigned long long kReduceMaxSum = 0xFFFFFFFFull;      // the counts of a chain add up to at most this
+// a count as it enters the sum check: clamped so that 65536 of them cannot overflow
+__host__ __device__ __forceinline__ unsigned long long reduce_clamp(unsigned long long v) { return v > kReduceMaxSum ? kReduceMaxSum + 1ull : v; }
+// the weighted mean rounded to nearest, halves up (n > 0; s <= 255 n): the rule of the refinement's update and of every merged centre
+__host__ __device__ __forceinline__ uint32_t refine_mean(unsigned long long s, unsigned long long n) { return (uint32_t)((2ull * s + n) / (2ull * n)); }
 // the squared distance from the winning key
 __host__ __device__ __forceinline__ uint32_t remap_dist(uint32_t p, uint32_t key) {
   const int s = (int)((p & 255u) + ((p >> 8) & 255u) + ((p >> 16) & 255u));

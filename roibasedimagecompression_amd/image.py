@@ -399,7 +399,8 @@ class ImageEncoder:
         return region_metrics_from_sums(sums, rh.class_ssim7(rgb, recon, region_map, len(names)), names)
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
-    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None):
+    def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
+               target_bytes=None, target_psnr=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -410,8 +411,19 @@ class ImageEncoder:
         max_colours = N (EXTENSION, default None = off): a finished result of more than N palette rows is reduced to N by
         Rhccq.palette_reduce (exact pairwise merging, weights = the histogram of the result's own index map), and the pixels of the
         rectangle the result covers are remapped onto the reduced palette (Rhccq.palette_remap); stats["reduce"] = {from, to, empty,
-        steps}.  The file and the report are those of the reduced result."""
+        steps}.  The file and the report are those of the reduced result.
+        target_bytes = B or target_psnr = P (EXTENSION; exclusive with each other and with max_colours): the finished result's
+        palette is searched for the rung that meets the target, as encode_with_palette(window, palette, target_...=) searches it,
+        over the rectangle the result covers, with the region map as the mask of a {"roi", "nonroi"} PSNR target and refine = 0.
+        This differs from max_colours: the weights of the merge chain come from the nearest-row assignment of the pixels, not from
+        the result's own index map, because the error bound needs the moments of that assignment; the result's indices become the
+        nearest rows of the rung (also at the top rung, where nothing merges).  stats["target"] and stats["reduce"] as
+        encode_with_palette fills them.  The palette may have at most ops.palette_reduce_max_rows() rows (RhccqError)."""
         rh = self.rh
+        searching = target_bytes is not None or target_psnr is not None
+        if searching and max_colours is not None:
+            raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
+        cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
         image = np.ascontiguousarray(image, dtype=np.uint8)
@@ -455,9 +467,17 @@ class ImageEncoder:
         if max_colours is not None and len(res["palette"]) > int(max_colours):
             stats["reduce"] = self._reduce_result(rgb, res, int(max_colours))
             lap("reduce")
+        data = None
+        if searching:
+            stats["reduce"], stats["target"], data = self._target_result(rgb, res, region_map, target_bytes, cons, exact)
+            lap("target")
         if out_path:
             from . import container
-            container.write_frame(res, out_path, rh, exact=exact)
+            if data is not None:                                                  # the probe's bytes are the file
+                with open(out_path, "wb") as f:
+                    f.write(data)
+            else:
+                container.write_frame(res, out_path, rh, exact=exact)
             lap("container")
         if report:
             stats["quality"] = self.quality(rgb, res, region_map)
@@ -490,13 +510,175 @@ class ImageEncoder:
                    indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
         return row
 
+    def _target_result(self, rgb, res, region_map, target_bytes, cons, exact):
+        """encode's target_bytes / target_psnr: the finished result in place -> (stats["reduce"], stats["target"], the file's bytes or None)"""
+        rh = self.rh
+        (top, left), (h, w) = res["top_left"], res["shape"]
+        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+        whole = (top, left, h, w) == (0, 0, int(rgb.shape[0]), int(rgb.shape[1]))
+        window = rgb if whole else rgb[top:top + h, left:left + w].contiguous()
+        cls = (region_map if whole else region_map[top:top + h, left:left + w]).contiguous()
+        if cls.dtype == torch.bool:
+            cls = cls.view(torch.uint8)
+        new_pal, idx, _, _, _, row, target, data = self._search(window, pal, cls, 1, 0, None, target_bytes, cons, exact)
+        res.update(palette=rh.to_host(new_pal), indices=idx.reshape(res["indices"].shape),                 # (the layout the result had)
+                   indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
+        return row, target, data
+
     @staticmethod
     def _remap_row(pixels, sse):
         pixels, sse = int(pixels), int(sse)
         return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
-    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None):
+    def _finish_palette(self, rgb, pal, cls, roi_weight, refine):
+        """the refinement, if asked for, and the final remap -> (palette device, indices, sums host, history host or None, iterations)"""
+        rh = self.rh
+        hist = nit = None
+        if refine:
+            pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
+        idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
+        if refine:
+            sums, hist, nit = rh.to_host(sums, hist, nit)                     # one read for both
+            nit = int(nit[0])
+        else:
+            sums = rh.to_host(sums)
+        return pal, idx, sums, hist, nit
+
+    # ---- the ladder of a given palette and the targets on it (EXTENSION, no reference counterpart) -------------------------------------
+    _TABLES = ("nonroi", "roi", "all")                                         # the moment tables of a masked picture, in order
+
+    @staticmethod
+    def _target_args(fn, target_bytes, target_psnr, masked):
+        """the two target keywords checked -> None for a byte target, {table: dB} for a PSNR target"""
+        if target_bytes is not None and target_psnr is not None:
+            raise ValueError(f"{fn}: target_bytes and target_psnr are exclusive")
+        if target_bytes is not None:
+            if int(target_bytes) < 1:
+                raise ValueError(f"{fn}: target_bytes must be >= 1")
+            return None
+        cons = dict(target_psnr) if isinstance(target_psnr, dict) else {"all": target_psnr}
+        if not cons or any(k not in ImageEncoder._TABLES for k in cons):
+            raise ValueError(f'{fn}: target_psnr is a number or a dict over "all", "roi", "nonroi"')
+        if not masked and any(k != "all" for k in cons):
+            raise ValueError(f'{fn}: a "roi" or "nonroi" target needs roi_mask')
+        return {k: float(v) for k, v in cons.items()}
+
+    def _ladder(self, rgb, pal, cls, roi_weight):
+        rh = self.rh
+        first, mom = rh.palette_moments(rgb, pal, cls, 2 if cls is not None else 0)
+        N = mom[:, :, 0]
+        counts = (N[-1] if cls is None or roi_weight == 1 else N[-1] + (roi_weight - 1) * N[1]).contiguous()
+        _, _, _, merges = rh.palette_reduce(pal, counts, 1)
+        curve = rh.palette_curve(pal, counts, merges, mom)
+        live = int(merges.shape[0]) + 1
+        names = ("all",) if cls is None else self._TABLES
+        host, merges_host = rh.to_host(torch.cat([curve[:, :live].reshape(-1), N.sum(dim=1)]), merges)      # the one read-back of the curve and the log
+        sse = {n: [int(v) for v in host[t * live:(t + 1) * live]] for t, n in enumerate(names)}
+        pixels = {n: int(host[len(names) * live + t]) for t, n in enumerate(names)}
+        bound = {n: [psnr_from_sse(v, pixels[n]) if pixels[n] else None for v in sse[n]] for n in names}
+        return {"colours": [live - s for s in range(live)], "sse": sse, "psnr_bound": bound, "pixels": pixels, "merges": merges_host,
+                "state": {"palette": pal, "counts": counts, "merges": merges, "moments": mom, "indices": first, "class_map": cls}}
+
+    def ladder(self, image, palette, roi_mask=None, roi_weight=1):
+        """the rate-distortion ladder of a palette over an image, without a single encode: image uint8[H,W,3], palette uint8[K,3]
+        (or a dict with "palette"), roi_mask and roi_weight as encode_with_palette takes them -> {"colours": [k of step s: rows in
+        use, ..., 1], "sse": {"all": [...]} and "psnr_bound": {"all": [...]} per step (with a mask also "roi" and "nonroi"),
+        "pixels": {table: pixels}, "merges": int32[steps, 2], "state": the device tensors a search reuses}.
+        One moments pass (Rhccq.palette_moments: nearest-row index map, histogram and per-row moments), the counts
+        sum over classes of weight x N with weights [1, roi_weight, 1] (those colours= computes), one merge chain to a single row
+        with its log (Rhccq.palette_reduce), and Rhccq.palette_curve.  sse[s] is the exact squared error of the image shown through
+        the clusters after s merges; the nearest-row remap onto that rung (what colours=k encodes) can only be better, so
+        psnr_bound[s] is a lower bound of colours=k's PSNR for k = colours[s], refine = 0.  The host waits for the device twice:
+        Rhccq.palette_reduce reads its row count (8 bytes), and one read-back fetches the curve, the pixel counts and the log
+        together.  K may be at most ops.palette_reduce_max_rows() (RhccqError)."""
+        rh = self.rh
+        roi_weight = int(roi_weight)
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and roi_mask is None):
+            raise ValueError("ImageEncoder.ladder: roi_weight (1..255) other than 1 needs roi_mask")
+        if isinstance(palette, dict):
+            palette = palette["palette"]
+        pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
+        if pal.dtype != torch.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
+            raise ValueError("ImageEncoder.ladder: a uint8 K x 3 palette, K >= 1, is expected")
+        rgb = image.to(rh.device).contiguous() if torch.is_tensor(image) else rh.dev(np.asarray(image))
+        if rgb.dtype != torch.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("ImageEncoder.ladder: a uint8 H x W x 3 image is expected")
+        cls = None
+        if roi_mask is not None:
+            from .api.roi import region_map_from_mask
+            cls = region_map_from_mask(rgb, roi_mask, rh)
+        return self._ladder(rgb, pal.contiguous(), cls, roi_weight)
+
+    def _search(self, rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons, exact):
+        """the target search of encode_with_palette on the ladder of `pal` -> (palette device, indices, sums host, history, iterations,
+        stats["reduce"], stats["target"], the file's bytes or None)"""
+        from . import container
+        rh = self.rh
+        if colours is not None and int(colours) < 1:
+            raise ValueError("ImageEncoder: the number of colours to reduce to must be >= 1")
+        L = self._ladder(rgb, pal, cls, roi_weight)
+        st = L["state"]
+        K, live = int(pal.shape[0]), len(L["colours"])
+        k0 = min(int(colours) if colours is not None else K, live)
+        names = ("all",) if cls is None else self._TABLES
+        table_row = {"all": -1, "nonroi": 0, "roi": 1}
+
+        def rung(k):
+            return rh.palette_rung(pal, st["counts"], st["merges"], k)[0].contiguous()
+
+        def bound(k):
+            return {n: L["psnr_bound"][n][live - k] for n in names}
+
+        def misses(figures):
+            """the constraints a {table: PSNR or None} misses"""
+            return {n for n, want in cons.items() if figures[n] is not None and not figures[n] >= want}
+
+        def achieved(sums):
+            return {n: (psnr_from_sse(int(sums[table_row[n]][1]), int(sums[table_row[n]][0])) if int(sums[table_row[n]][0]) else None) for n in names}
+
+        if target_bytes is None:
+            k = next((k for k in range(1, k0 + 1) if not misses(bound(k))), k0)
+            out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine)
+            dropped = False
+            if refine:
+                lost = misses(achieved(out[2]))
+                if lost:
+                    plain = self._finish_palette(rgb, rung(k), cls, roi_weight, 0)
+                    if lost - misses(achieved(plain[2])):                        # the unrefined rung meets one of them
+                        out, dropped = plain, True
+            target = {"kind": "psnr", "target": dict(cons), "met": not misses(achieved(out[2])), "colours": k, "probes": [], "bound_psnr": bound(k),
+                      "refine_dropped": dropped}
+            data = None
+        else:
+            B, probes, fits, first = int(target_bytes), [], None, None
+
+            def probe(k):
+                nonlocal fits, first
+                out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine)
+                res = {"palette": rh.to_host(out[0]), "indices": out[1], "shape": (int(rgb.shape[0]), int(rgb.shape[1]))}
+                data = container.frame_bytes(res, rh, exact=exact)
+                probes.append((k, len(data)))
+                if len(data) <= B:
+                    fits = (k, out, data)                                      # the best feasible probe: kept, not recomputed
+                elif k == 1:
+                    first = (k, out, data)
+                return len(data) <= B
+            if not probe(k0):
+                lo, hi = 0, k0
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    if probe(mid):
+                        lo = mid
+                    else:
+                        hi = mid
+            k, out, data = fits if fits is not None else first                   # (nothing fits: rung 1 was the last probe)
+            target = {"kind": "bytes", "target": B, "met": fits is not None, "colours": k, "probes": probes, "bound_psnr": bound(k), "refine_dropped": False}
+        row = {"from": K, "to": k, "empty": K - live, "steps": live - k}
+        return out + (row, target, data)
+
+    def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
+                            target_bytes=None, target_psnr=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -514,13 +696,31 @@ class ImageEncoder:
         palette, the rows' counts (torch.bincount; with roi_mask a pixel inside the mask counts roi_weight, as it weighs in the
         refinement, and roi_weight needs no refine then), Rhccq.palette_reduce (exact pairwise merging; rows no pixel uses are dropped),
         then the refinement, if asked for, of the reduced palette, and the final remap.  stats["reduce"] = {from: K, to: rows kept,
-        empty: rows dropped unused, steps: merges}.  K may be at most ops.palette_reduce_max_rows() (RhccqError)."""
+        empty: rows dropped unused, steps: merges}.  K may be at most ops.palette_reduce_max_rows() (RhccqError).
+        target_bytes = B or target_psnr = P (exclusive; default None = off): the number of colours is searched on the palette's
+        ladder (ladder(): one moments pass, one merge chain, the exact error bound of every rung) instead of given.  The rungs are
+        1..k0, k0 = min(colours or K, rows in use); rung k is the palette colours=k uses, and the result is what colours=k, refine=R
+        gives (stats["reduce"] and stats["remap"] as colours=k fills them).  stats["target"] = {kind: "bytes" / "psnr", target, met,
+        colours: k, probes: [(k, bytes), ...] in the order they ran ([] for a PSNR target), bound_psnr: {table: the bound of rung k},
+        refine_dropped}.
+        target_psnr: a number for the whole picture, or a dict over "all", "roi", "nonroi" (the last two need roi_mask).  k is the
+        smallest rung whose bound (ops.psnr_from_sse of the curve's sum, float64) is >= every constraint; a table without pixels
+        meets any; no rung meets them: k = k0.  No probe runs.  Without refine the achieved figures cannot fall below the bound;
+        with refine a class can lose to another, and when the final remap's own sums miss a constraint that the unrefined rung
+        meets, the unrefined result is returned and refine_dropped is set.  met: the result's own sums meet every constraint.
+        target_bytes: probe(k) = rung k, the refinement if asked for, the remap, the container built in memory
+        (container.frame_bytes(exact=exact)).  k0 is probed first and is the result when it fits; otherwise a bisection over
+        lo = 0 (virtual), hi = k0 with mid = (lo + hi) // 2 keeps lo at the last rung that fitted, and rung lo is the result (lo == 0:
+        rung 1 with met False).  File size need not fall monotonically with k: the search returns a rung it verified, not provably
+        the largest one that fits.  With out_path the probe's bytes are the file, so its length is the recorded size."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
+        searching = target_bytes is not None or target_psnr is not None
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_with_palette: refine must be 0..64")
-        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None))):
-            raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0 or colours")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None or searching))):
+            raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0, colours or a target")
+        cons = self._target_args("ImageEncoder.encode_with_palette", target_bytes, target_psnr, roi_mask is not None) if searching else None
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -543,22 +743,21 @@ class ImageEncoder:
             from .api.roi import region_map_from_mask
             cls = region_map_from_mask(rgb, roi_mask, rh)                     # 0 / 1: quality()'s rows
             lap("mask")
-        reduce_row = None
-        if colours is not None:
-            from .container import index_histogram
-            first, _ = rh.palette_remap(rgb, pal)
-            weights = None if cls is None or roi_weight == 1 else 1 + (roi_weight - 1) * (cls == 1).to(torch.int64)
-            pal, reduce_row = self._reduce(pal, index_histogram(first, int(pal.shape[0]), rh, weights), int(colours))
-            lap("reduce")
-        if refine:
-            pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
-        idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
-        if refine:
-            sums, hist, nit = rh.to_host(sums, hist, nit)                     # one read for both
-            nit = int(nit[0])
+        reduce_row = target = data = None
+        if searching:
+            pal, idx, sums, hist, nit, reduce_row, target, data = self._search(rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons, exact)
+            refined = hist is not None
+            lap("target")
         else:
-            sums = rh.to_host(sums)
-        lap("remap")
+            if colours is not None:
+                from .container import index_histogram
+                first, _ = rh.palette_remap(rgb, pal)
+                weights = None if cls is None or roi_weight == 1 else 1 + (roi_weight - 1) * (cls == 1).to(torch.int64)
+                pal, reduce_row = self._reduce(pal, index_histogram(first, int(pal.shape[0]), rh, weights), int(colours))
+                lap("reduce")
+            pal, idx, sums, hist, nit = self._finish_palette(rgb, pal, cls, roi_weight, refine)
+            refined = bool(refine)
+            lap("remap")
         remap = {"all": self._remap_row(*sums[-1])}
         if cls is not None:
             remap["nonroi"], remap["roi"] = self._remap_row(*sums[0]), self._remap_row(*sums[1])
@@ -567,12 +766,18 @@ class ImageEncoder:
         stats = {"remap": remap}
         if reduce_row is not None:
             stats["reduce"] = reduce_row
-        if refine:
+        if target is not None:
+            stats["target"] = target
+        if refined:
             stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
                                "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
         if out_path:
             from . import container
-            container.write_frame(res, out_path, rh, exact=exact)
+            if data is not None:                                                  # the probe's bytes are the file
+                with open(out_path, "wb") as f:
+                    f.write(data)
+            else:
+                container.write_frame(res, out_path, rh, exact=exact)
             lap("container")
         if report:
             host = image.cpu().numpy() if torch.is_tensor(image) else np.ascontiguousarray(image, dtype=np.uint8)
@@ -584,7 +789,8 @@ class ImageEncoder:
         res["stats"] = stats
         return res
 
-    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None):
+    def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
+                        target_bytes=None, target_psnr=None):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -599,9 +805,14 @@ class ImageEncoder:
         reaches the bound: stats["key_frame"] = False, stats["refined"] = True, key_index and key_psnr stay the key frame's, and the
         refined palette is the one later frames are remapped onto.  Otherwise the frame is encoded in full as before.  Every
         result that is not a key frame has stats["refined"] (bool; always False with refine = 0).
-        max_colours: passed to the key frames' encode (default None = off)."""
+        max_colours: passed to the key frames' encode (default None = off).  target_bytes / target_psnr: passed to the key
+        frames' encode too (exclusive with each other and with max_colours; see encode for how the search differs from max_colours)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
+        if target_bytes is not None or target_psnr is not None:
+            if max_colours is not None:
+                raise ValueError("ImageEncoder.encode_sequence: target_bytes / target_psnr and max_colours are exclusive")
+            self._target_args("ImageEncoder.encode_sequence", target_bytes, target_psnr, True)
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
@@ -630,7 +841,8 @@ class ImageEncoder:
                         key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
                     yield res
                     continue
-            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours)
+            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
+                              target_psnr=target_psnr)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

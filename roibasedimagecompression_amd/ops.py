@@ -120,6 +120,11 @@ def palette_reduce_max_rows():
     return int(_lib.load().rhccq_palette_reduce_max_rows())
 
 
+def palette_moments_lds_rows(n_classes=0):
+    """the largest palette whose moment tables (n_classes + 1 of them) Rhccq.palette_moments' kernel keeps in LDS"""
+    return int(_lib.load().rhccq_palette_moments_lds_rows(int(n_classes)))
+
+
 def psnr_from_sse(sse, n_pixels):
     """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
     10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
@@ -1131,6 +1136,119 @@ class Rhccq:
             raise RhccqError(f"palette_reduce failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
         n_steps = live - k
         return pal_out[:k], cnt_out[:k], map_, merges[:max(n_steps, 0)]
+
+    # -- the palette ladder: moments, the error curve of every rung, any rung from the log (EXTENSION: csrc/palette_ladder.hip) ----
+    def _ladder_arg(self, a, dtype, what, fn):
+        """palette / counts / merges as a contiguous device tensor of `dtype` (counts: any integers, as palette_reduce takes them)"""
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(a)
+            if dtype is torch.int64:
+                if a.dtype.kind not in "iu":
+                    raise TypeError(f"{fn}: {what} must be integers, got {a.dtype}")
+                a = a.astype(np.uint64).view(np.int64)
+            a = torch.from_numpy(a)
+        if a.dtype != dtype and not (dtype is torch.int64 and a.dtype in (torch.int32, torch.uint8, torch.int16)):
+            raise TypeError(f"{fn}: {what} must be {dtype}, got {a.dtype}")
+        return a.to(self.device).to(dtype).contiguous()
+
+    def _ladder_log(self, merges, K, fn):
+        """the merges of palette_reduce (device int32[n_steps, 2], any n_steps <= K - 1) as the int32[max(K - 1, 1), 2] the C entries read"""
+        merges = self._ladder_arg(merges, torch.int32, "merges", fn)
+        if merges.ndim != 2 or merges.shape[1] != 2 or merges.shape[0] > max(K - 1, 0):
+            raise ValueError(f"{fn}: merges [n_steps <= K - 1, 2] is expected")
+        full = torch.full((max(K - 1, 1), 2), -1, dtype=torch.int32, device=self.device)
+        full[:merges.shape[0]] = merges
+        return full
+
+    def palette_moments(self, rgb, palette, class_map=None, n_classes=0, want_indices=True):
+        """rgb uint8[..., 3], palette uint8[K, 3] (numpy or device), class_map uint8 / bool, one element per pixel, or None ->
+        (indices as palette_remap returns them, or None with want_indices=False; moments device int64[n_classes + 1, K, 5]: per
+        table and palette row {N, Sr, Sg, Sb, Q} of the pixels whose nearest row it is -- their number, their channel sums and
+        the sum of r^2 + g^2 + b^2; table c over the pixels of class c, the last table over every pixel).  One pass; unweighted."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_moments: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
+        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError("palette_moments: rgb [..., 3] and palette [K, 3] are expected")
+        n, K, n_classes = rgb.numel() // 3, int(palette.shape[0]), int(n_classes)
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != n:
+                raise ValueError("palette_moments: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_moments: n_classes without a class map")
+        if not 0 <= n_classes <= 16 or K < 1 or K > 65536:
+            raise RhccqError("palette_moments: K must be 1..65536 and n_classes 0..16")
+        idx = self.empty(tuple(rgb.shape[:-1]), torch.uint8 if K <= 256 else torch.int16) if want_indices else None
+        moments = self.empty((n_classes + 1, K, 5), torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return idx, moments.zero_()
+        self._check(self.lib.rhccq_palette_moments(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), n_classes, self._p(idx),
+                                                   idx.element_size() if idx is not None else 0, self._p(moments)), "palette_moments")
+        return idx, moments
+
+    def palette_curve(self, palette, counts, merges, moments):
+        """palette uint8[K, 3], counts [K] (the weights the chain was run with), merges int32[n_steps, 2] (palette_reduce's), moments
+        int64[T, K, 5] (palette_moments') -> curve device int64[T, K]: curve[t, s] = the squared error of table t's pixels shown through
+        the clusters after s merges, in exact integers; 0 behind the last step.  It bounds the error of the nearest-row remap onto
+        that rung from above.  K above palette_reduce_max_rows() raises RhccqError."""
+        palette = self._ladder_arg(palette, torch.uint8, "palette", "palette_curve")
+        counts = self._ladder_arg(counts, torch.int64, "counts", "palette_curve")
+        moments = self._ladder_arg(moments, torch.int64, "moments", "palette_curve")
+        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
+            raise ValueError("palette_curve: palette [K, 3] and counts [K] are expected")
+        K = int(palette.shape[0])
+        if moments.ndim != 3 or moments.shape[1] != K or moments.shape[2] != 5 or not 1 <= moments.shape[0] <= 17:
+            raise ValueError("palette_curve: moments [1..17, K, 5] are expected")
+        cap = palette_reduce_max_rows()
+        if K > cap:
+            raise RhccqError(f"palette_curve: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        if K < 1:
+            raise RhccqError("palette_curve: K >= 1 is required")
+        merges = self._ladder_log(merges, K, "palette_curve")
+        T = int(moments.shape[0])
+        wbytes = int(self._raw.rhccq_palette_curve_bytes(K, T))
+        work = self.empty((wbytes // 8,), torch.int64)
+        curve = self.empty((T, K), torch.int64)
+        self._check(self.lib.rhccq_palette_curve(self.ctx, self._p(palette), self._p(counts), K, self._p(merges), self._p(moments), T, self._p(work),
+                                                 wbytes, self._p(curve)), "palette_curve")
+        return curve
+
+    def palette_rung(self, palette, counts, merges, colours):
+        """palette uint8[K, 3], counts [K], merges int32[n_steps, 2] (palette_reduce's log of a run to fewer than `colours` rows),
+        colours = K_target in 1..K -> (palette device uint8[k_out, 3], counts device int64[k_out], map device int32[K]): what
+        palette_reduce(palette, counts, colours) returns, rebuilt from the log without the merge chain.  k_out is read back once.
+        A log that ends before `colours` is reached gives the clusters it has (map names them all, the palette has the first
+        `colours`).  K above palette_reduce_max_rows() raises RhccqError."""
+        palette = self._ladder_arg(palette, torch.uint8, "palette", "palette_rung")
+        counts = self._ladder_arg(counts, torch.int64, "counts", "palette_rung")
+        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
+            raise ValueError("palette_rung: palette [K, 3] and counts [K] are expected")
+        K, target = int(palette.shape[0]), int(colours)
+        cap = palette_reduce_max_rows()
+        if K > cap:
+            raise RhccqError(f"palette_rung: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        if K < 1 or not 1 <= target <= K:
+            raise RhccqError("palette_rung: K >= 1 and colours in 1..K are required")
+        merges = self._ladder_log(merges, K, "palette_rung")
+        pal_out = self.empty((target, 3), torch.uint8)
+        cnt_out = self.empty((target,), torch.int64)
+        map_ = self.empty((K,), torch.int32)
+        k_out = self.empty((1,), torch.int32)
+        self._check(self.lib.rhccq_palette_rung(self.ctx, self._p(palette), self._p(counts), K, self._p(merges), target, self._p(pal_out),
+                                                self._p(cnt_out), self._p(map_), self._p(k_out)), "palette_rung")
+        k = int(k_out.item())                                # the one read
+        if k < 0:
+            raise RhccqError(f"palette_rung failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
+        k = min(k, target)
+        return pal_out[:k], cnt_out[:k], map_
 
     # -- split score (split_score.py:15-142) ----------------------------------------------------------
     def split_stats(self, rgb, mask=None):
