@@ -106,6 +106,10 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              nothing (RHCCQ_OPT_INIT_KERNEL other than the third generation) is waited for by that event either way.
  *                              Same results. */
 #define RHCCQ_OPT_CHAIN_RELEASE 12
+/*   RHCCQ_OPT_RUNS_ROWS        rhccq_palette_runs: the image rows one workgroup (one wave, a lane per row) walks: 0 (default) =
+ *                              rhccq_palette_runs_rows(), or 2, 4 or 8.  Fewer rows put more workgroups on more CUs and leave more
+ *                              lanes of each wave idle in the walk.  Same results. */
+#define RHCCQ_OPT_RUNS_ROWS 13
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -856,6 +860,30 @@ int rhccq_palette_rung(rhccq_ctx* ctx, const uint8_t* palette, const uint64_t* c
                        uint8_t* palette_out, uint64_t* counts_out, int32_t* map, int32_t* k_out);
 int rhccq_palette_rung_host(const uint8_t* palette, const uint64_t* counts, int32_t K, const int32_t* merges, int32_t K_target,
                             uint8_t* palette_out, uint64_t* counts_out, int32_t* map, int32_t* k_out);
+
+/* ---- EXTENSION: run-carrying remap onto a given palette (no reference counterpart; csrc/palette_runs.hip) ----------------------------
+ * rgb uint8[H][W][3], palette uint8[K][3], cls uint8[H][W] or NULL, slack uint32[n_classes + 1], each entry 0..195075 (3 * 255^2).  A pixel's
+ * slack is slack[cls[p]] when cls[p] < n_classes and slack[n_classes] otherwise (and for every pixel when cls == NULL): the rule of
+ * rhccq_palette_refine's weights.  (1) b(y, x) is rhccq_palette_remap's index of the pixel (nearest row in exact integers, ties to the lowest
+ * row) and db(y, x) its squared distance.  (2) Every image row is independent: out(y, 0) = b(y, 0); for x >= 1, with c = out(y, x - 1),
+ * out(y, x) = c if |rgb(y, x) - palette[c]|^2 <= db(y, x) + slack(y, x), else b(y, x).  A carry never crosses from one image row to the
+ * next, and at an exact tie the carried row wins (so slack 0 keeps the remap's squared error but not always its indices).  (3) idx_out
+ * (idx_elem_bytes 1, 2 or 4 per element, as the remap takes it) receives out; sums is uint64[n_classes + 1][3], zeroed by the call: row c =
+ * {pixels, sum of |rgb - palette[out]|^2, carried} over the pixels with cls[p] == c, the last row over every pixel (the rows of the remap's
+ * sums); carried counts the pixels with out != b.  Per row, SSE(out) <= SSE(b) + the slack summed over its carried pixels.
+ * RHCCQ_E_ARG: as rhccq_palette_remap, and a null slack, H < 0, W < 0, a slack above 195075.  RHCCQ_E_LIMIT: K > 65536.  H * W == 0
+ * succeeds with zero sums.
+ * Device form: every pointer but slack_host (copied by value into the launch) is device memory; async on the context stream, no host
+ * synchronisation, nothing allocated: rhccq_palette_remap into idx_out, a memset, then one launch that walks the rows in place (every
+ * position reads b before it writes out), one wave per RHCCQ_OPT_RUNS_ROWS image rows, the picture staged through LDS in tiles of
+ * rows x rhccq_palette_runs_tile_cols() pixels.  palette[b] is gathered from a copy of the palette in LDS while K <= 4096 and from global
+ * memory above.  Host form: the same step functions (csrc/palette_runs.h) run serially on host memory. */
+int32_t rhccq_palette_runs_tile_cols(void);             /* host only: the columns of a staging tile */
+int32_t rhccq_palette_runs_rows(void);                  /* host only: the image rows of a workgroup by default */
+int rhccq_palette_runs(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                       int32_t n_classes, const uint32_t* slack_host, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_runs_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
+                            const uint32_t* slack, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
 
 #ifdef __cplusplus
 }

@@ -198,6 +198,10 @@ PROTOTYPES = {
     "rhccq_palette_curve_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_rung": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rhccq_palette_rung_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_runs_tile_cols": (c_int32, []),
+    "rhccq_palette_runs_rows": (c_int32, []),
+    "rhccq_palette_runs": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_runs_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
 }
 
 

@@ -88,6 +88,10 @@ int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value) {
       if (value < 0 || value > 65535) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_REFINE_MAX_BLOCKS: 0 .. 65535");
       ctx->opt_refine_max_blocks = (int)value;
       return 0;
+    case RHCCQ_OPT_RUNS_ROWS:
+      if (value != 0 && value != 2 && value != 4 && value != 8) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_RUNS_ROWS: 0, 2, 4 or 8");
+      ctx->opt_runs_rows = (int)value;
+      return 0;
     case RHCCQ_OPT_CHAIN_RELEASE:
       if (value != 0 && value != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_CHAIN_RELEASE: 0 or 1");
       ctx->opt_chain_release = (int)value;

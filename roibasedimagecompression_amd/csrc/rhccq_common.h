@@ -31,6 +31,7 @@ struct rhccq_ctx {
   int compute_units = 0;     // of `device`, asked once by the first launch that sizes its grid by it (csrc/palette_remap.hip)
   int opt_refine_lds_rows = -1;    // rhccq_palette_refine: palettes of more rows accumulate in global memory (-1: rhccq_palette_refine_lds_rows())
   int opt_refine_max_blocks = 0;   // rhccq_palette_refine: at most this many workgroups (0: 8 per CU)
+  int opt_runs_rows = 0;           // rhccq_palette_runs: image rows of a workgroup (0: kRunsRowsDefault; 2, 4 or 8)
   int opt_chain_release = 1; // rhccq_encode_frame: a level-1 problem goes on when its own chain of the frame's launch has ended (1, default) or when the launch has (0)
 };
 

@@ -400,7 +400,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None):
+               target_bytes=None, target_psnr=None, run_slack=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -418,11 +418,17 @@ class ImageEncoder:
         This differs from max_colours: the weights of the merge chain come from the nearest-row assignment of the pixels, not from
         the result's own index map, because the error bound needs the moments of that assignment; the result's indices become the
         nearest rows of the rung (also at the top rung, where nothing merges).  stats["target"] and stats["reduce"] as
-        encode_with_palette fills them.  The palette may have at most ops.palette_reduce_max_rows() rows (RhccqError)."""
+        encode_with_palette fills them.  The palette may have at most ops.palette_reduce_max_rows() rows (RhccqError).
+        run_slack = s or {"roi": a, "nonroi": b} (EXTENSION, default None = off; 0 is a value): the finished result's index map (after
+        max_colours, if given) is rewritten by the run-carrying rule over its own palette and the rectangle it covers
+        (Rhccq.palette_runs: a pixel keeps its left neighbour's index while that costs at most the slack more squared error than its
+        nearest row), the dict's entries applying inside and outside the region map; stats["runs"] as encode_with_palette fills it.
+        With a target every probe and the result run with the slack, as in encode_with_palette."""
         rh = self.rh
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
+        runs = self._run_slack_args("ImageEncoder.encode", run_slack, True)
         cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -469,8 +475,13 @@ class ImageEncoder:
             lap("reduce")
         data = None
         if searching:
-            stats["reduce"], stats["target"], data = self._target_result(rgb, res, region_map, target_bytes, cons, exact)
+            stats["reduce"], stats["target"], data, row = self._target_result(rgb, res, region_map, target_bytes, cons, exact, runs)
+            if row is not None:
+                stats["runs"] = row
             lap("target")
+        elif runs is not None:
+            stats["runs"] = self._runs_result(rgb, res, region_map, runs)
+            lap("runs")
         if out_path:
             from . import container
             if data is not None:                                                  # the probe's bytes are the file
@@ -510,20 +521,67 @@ class ImageEncoder:
                    indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
         return row
 
-    def _target_result(self, rgb, res, region_map, target_bytes, cons, exact):
-        """encode's target_bytes / target_psnr: the finished result in place -> (stats["reduce"], stats["target"], the file's bytes or None)"""
-        rh = self.rh
+    def _window(self, rgb, res, region_map):
+        """the pixels and the region map of the rectangle a finished result covers -> (window, class map uint8)"""
         (top, left), (h, w) = res["top_left"], res["shape"]
-        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
         whole = (top, left, h, w) == (0, 0, int(rgb.shape[0]), int(rgb.shape[1]))
         window = rgb if whole else rgb[top:top + h, left:left + w].contiguous()
         cls = (region_map if whole else region_map[top:top + h, left:left + w]).contiguous()
         if cls.dtype == torch.bool:
             cls = cls.view(torch.uint8)
-        new_pal, idx, _, _, _, row, target, data = self._search(window, pal, cls, 1, 0, None, target_bytes, cons, exact)
+        return window, cls
+
+    def _target_result(self, rgb, res, region_map, target_bytes, cons, exact, runs=None):
+        """encode's target_bytes / target_psnr: the finished result in place -> (stats["reduce"], stats["target"], the file's bytes or None,
+        stats["runs"] or None)"""
+        rh = self.rh
+        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+        window, cls = self._window(rgb, res, region_map)
+        new_pal, idx, _, _, _, runs_row, row, target, data = self._search(window, pal, cls, 1, 0, None, target_bytes, cons, exact, runs)
         res.update(palette=rh.to_host(new_pal), indices=idx.reshape(res["indices"].shape),                 # (the layout the result had)
                    indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
-        return row, target, data
+        return row, target, data, runs_row
+
+    def _runs_result(self, rgb, res, region_map, runs):
+        """encode's run_slack without a target: the finished result's index map in place -> stats["runs"]"""
+        rh = self.rh
+        pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+        window, cls = self._window(rgb, res, region_map)
+        idx, sums = rh.palette_runs(window, pal, self._slack_table(runs, True), cls, 2)
+        res.update(indices=idx.reshape(res["indices"].shape), indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
+        return self._runs_row(runs, rh.to_host(sums), True)
+
+    # ---- the run-carrying remap (EXTENSION, no reference counterpart) ------------------------------------------------------------------
+    @staticmethod
+    def _run_slack_args(fn, run_slack, masked):
+        """the run_slack keyword checked -> None (off), or {"slack": as given, "nonroi": s, "roi": s}"""
+        from .ops import RUN_SLACK_MAX
+        if run_slack is None:
+            return None
+        if isinstance(run_slack, dict):
+            if sorted(run_slack) != ["nonroi", "roi"]:
+                raise ValueError(f'{fn}: run_slack is a number or a dict over "roi" and "nonroi"')
+            if not masked:
+                raise ValueError(f"{fn}: a roi / nonroi run_slack needs roi_mask")
+            given = {k: int(v) for k, v in run_slack.items()}
+            out = {"slack": given, "nonroi": given["nonroi"], "roi": given["roi"]}
+        else:
+            out = {"slack": int(run_slack), "nonroi": int(run_slack), "roi": int(run_slack)}
+        if not (0 <= out["nonroi"] <= RUN_SLACK_MAX and 0 <= out["roi"] <= RUN_SLACK_MAX):
+            raise ValueError(f"{fn}: a run_slack must be 0..{RUN_SLACK_MAX}")
+        return out
+
+    @staticmethod
+    def _slack_table(runs, masked):
+        """Rhccq.palette_runs' table over the region map's classes (0 = outside, 1 = inside; a map holds no other value)"""
+        return [runs["nonroi"], runs["roi"], min(runs["nonroi"], runs["roi"])] if masked else [runs["nonroi"]]
+
+    @staticmethod
+    def _runs_row(runs, sums, masked):
+        carried = {"all": int(sums[-1][2])}
+        if masked:
+            carried["roi"], carried["nonroi"] = int(sums[1][2]), int(sums[0][2])
+        return {"slack": runs["slack"], "carried": carried, "pixels": int(sums[-1][0])}
 
     @staticmethod
     def _remap_row(pixels, sse):
@@ -531,19 +589,27 @@ class ImageEncoder:
         return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
-    def _finish_palette(self, rgb, pal, cls, roi_weight, refine):
-        """the refinement, if asked for, and the final remap -> (palette device, indices, sums host, history host or None, iterations)"""
+    def _finish_palette(self, rgb, pal, cls, roi_weight, refine, runs=None):
+        """the refinement, if asked for, and the final remap (the run-carrying one with `runs`) -> (palette device, indices, sums host
+        {pixels, sse} per row, history host or None, iterations, stats["runs"] or None)"""
         rh = self.rh
         hist = nit = None
         if refine:
             pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
-        idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
+        if runs is not None:
+            idx, sums = rh.palette_runs(rgb, pal, self._slack_table(runs, cls is not None), cls, 2 if cls is not None else 0)
+        else:
+            idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
         if refine:
             sums, hist, nit = rh.to_host(sums, hist, nit)                     # one read for both
             nit = int(nit[0])
         else:
             sums = rh.to_host(sums)
-        return pal, idx, sums, hist, nit
+        runs_row = None
+        if runs is not None:
+            runs_row = self._runs_row(runs, sums, cls is not None)
+            sums = sums[:, :2]
+        return pal, idx, sums, hist, nit, runs_row
 
     # ---- the ladder of a given palette and the targets on it (EXTENSION, no reference counterpart) -------------------------------------
     _TABLES = ("nonroi", "roi", "all")                                         # the moment tables of a masked picture, in order
@@ -610,9 +676,9 @@ class ImageEncoder:
             cls = region_map_from_mask(rgb, roi_mask, rh)
         return self._ladder(rgb, pal.contiguous(), cls, roi_weight)
 
-    def _search(self, rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons, exact):
+    def _search(self, rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons, exact, runs=None):
         """the target search of encode_with_palette on the ladder of `pal` -> (palette device, indices, sums host, history, iterations,
-        stats["reduce"], stats["target"], the file's bytes or None)"""
+        stats["runs"] or None, stats["reduce"], stats["target"], the file's bytes or None)"""
         from . import container
         rh = self.rh
         if colours is not None and int(colours) < 1:
@@ -627,8 +693,19 @@ class ImageEncoder:
         def rung(k):
             return rh.palette_rung(pal, st["counts"], st["merges"], k)[0].contiguous()
 
+        # with a run slack a pixel may lose at most its slack against the nearest row: the curve's sum plus slack x pixels per table
+        # bounds the run-carrying result's squared error (exact integers)
+        extra = None
+        if runs is not None:
+            px = L["pixels"]
+            extra = {"all": runs["nonroi"] * px["all"]} if cls is None else {"nonroi": runs["nonroi"] * px["nonroi"], "roi": runs["roi"] * px["roi"]}
+            if cls is not None:
+                extra["all"] = extra["nonroi"] + extra["roi"]
+
         def bound(k):
-            return {n: L["psnr_bound"][n][live - k] for n in names}
+            if extra is None:
+                return {n: L["psnr_bound"][n][live - k] for n in names}
+            return {n: (psnr_from_sse(L["sse"][n][live - k] + extra[n], L["pixels"][n]) if L["pixels"][n] else None) for n in names}
 
         def misses(figures):
             """the constraints a {table: PSNR or None} misses"""
@@ -639,12 +716,12 @@ class ImageEncoder:
 
         if target_bytes is None:
             k = next((k for k in range(1, k0 + 1) if not misses(bound(k))), k0)
-            out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine)
+            out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine, runs)
             dropped = False
             if refine:
                 lost = misses(achieved(out[2]))
                 if lost:
-                    plain = self._finish_palette(rgb, rung(k), cls, roi_weight, 0)
+                    plain = self._finish_palette(rgb, rung(k), cls, roi_weight, 0, runs)
                     if lost - misses(achieved(plain[2])):                        # the unrefined rung meets one of them
                         out, dropped = plain, True
             target = {"kind": "psnr", "target": dict(cons), "met": not misses(achieved(out[2])), "colours": k, "probes": [], "bound_psnr": bound(k),
@@ -655,7 +732,7 @@ class ImageEncoder:
 
             def probe(k):
                 nonlocal fits, first
-                out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine)
+                out = self._finish_palette(rgb, rung(k), cls, roi_weight, refine, runs)
                 res = {"palette": rh.to_host(out[0]), "indices": out[1], "shape": (int(rgb.shape[0]), int(rgb.shape[1]))}
                 data = container.frame_bytes(res, rh, exact=exact)
                 probes.append((k, len(data)))
@@ -678,7 +755,7 @@ class ImageEncoder:
         return out + (row, target, data)
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
-                            target_bytes=None, target_psnr=None):
+                            target_bytes=None, target_psnr=None, run_slack=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -712,7 +789,17 @@ class ImageEncoder:
         (container.frame_bytes(exact=exact)).  k0 is probed first and is the result when it fits; otherwise a bisection over
         lo = 0 (virtual), hi = k0 with mid = (lo + hi) // 2 keeps lo at the last rung that fitted, and rung lo is the result (lo == 0:
         rung 1 with met False).  File size need not fall monotonically with k: the search returns a rung it verified, not provably
-        the largest one that fits.  With out_path the probe's bytes are the file, so its length is the recorded size."""
+        the largest one that fits.  With out_path the probe's bytes are the file, so its length is the recorded size.
+        run_slack = s or {"roi": a, "nonroi": b} (the dict needs roi_mask; default None = off, and 0 is a value: at an exact tie the
+        left neighbour's row wins): the final remap, whatever came before it (refine, colours, a target's rungs and probes), is
+        the run-carrying one (Rhccq.palette_runs): along every image row a pixel keeps its left neighbour's index while that costs
+        at most the slack (0..195075, a squared distance) more squared error than its nearest row.  The index map gets repetitive,
+        which the container's zlib stage rewards; the file format does not change.  stats["remap"] stays the figures of the index
+        map returned; stats["runs"] = {slack: as given, carried: {all: pixels whose index is not the nearest row[, roi, nonroi]},
+        pixels}.  A PSNR target keeps its guarantee: a rung's bound is formed from the curve's sum plus slack x pixels per table
+        (exact integers, a valid bound of the run-carrying result's squared error), so rungs come out larger than without a slack,
+        and bound_psnr records the adjusted bound.  A byte target probes every rung with the given slack; slack and colours are not
+        searched jointly."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
@@ -721,6 +808,7 @@ class ImageEncoder:
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None or searching))):
             raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0, colours or a target")
         cons = self._target_args("ImageEncoder.encode_with_palette", target_bytes, target_psnr, roi_mask is not None) if searching else None
+        runs = self._run_slack_args("ImageEncoder.encode_with_palette", run_slack, roi_mask is not None)
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -745,7 +833,8 @@ class ImageEncoder:
             lap("mask")
         reduce_row = target = data = None
         if searching:
-            pal, idx, sums, hist, nit, reduce_row, target, data = self._search(rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons, exact)
+            pal, idx, sums, hist, nit, runs_row, reduce_row, target, data = self._search(rgb, pal, cls, roi_weight, refine, colours, target_bytes, cons,
+                                                                                         exact, runs)
             refined = hist is not None
             lap("target")
         else:
@@ -755,7 +844,7 @@ class ImageEncoder:
                 weights = None if cls is None or roi_weight == 1 else 1 + (roi_weight - 1) * (cls == 1).to(torch.int64)
                 pal, reduce_row = self._reduce(pal, index_histogram(first, int(pal.shape[0]), rh, weights), int(colours))
                 lap("reduce")
-            pal, idx, sums, hist, nit = self._finish_palette(rgb, pal, cls, roi_weight, refine)
+            pal, idx, sums, hist, nit, runs_row = self._finish_palette(rgb, pal, cls, roi_weight, refine, runs)
             refined = bool(refine)
             lap("remap")
         remap = {"all": self._remap_row(*sums[-1])}
@@ -768,6 +857,8 @@ class ImageEncoder:
             stats["reduce"] = reduce_row
         if target is not None:
             stats["target"] = target
+        if runs_row is not None:
+            stats["runs"] = runs_row
         if refined:
             stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
                                "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
@@ -790,7 +881,7 @@ class ImageEncoder:
         return res
 
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
-                        target_bytes=None, target_psnr=None):
+                        target_bytes=None, target_psnr=None, run_slack=None):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -806,13 +897,18 @@ class ImageEncoder:
         refined palette is the one later frames are remapped onto.  Otherwise the frame is encoded in full as before.  Every
         result that is not a key frame has stats["refined"] (bool; always False with refine = 0).
         max_colours: passed to the key frames' encode (default None = off).  target_bytes / target_psnr: passed to the key
-        frames' encode too (exclusive with each other and with max_colours; see encode for how the search differs from max_colours)."""
+        frames' encode too (exclusive with each other and with max_colours; see encode for how the search differs from max_colours).
+        run_slack: one number (default None = off), passed to the key frames' encode and to every remap (plain and refined), whose
+        PSNRs the key-frame rule then compares; a roi / nonroi dict raises ValueError, because a remapped frame has no region map."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         if target_bytes is not None or target_psnr is not None:
             if max_colours is not None:
                 raise ValueError("ImageEncoder.encode_sequence: target_bytes / target_psnr and max_colours are exclusive")
             self._target_args("ImageEncoder.encode_sequence", target_bytes, target_psnr, True)
+        if isinstance(run_slack, dict):
+            raise ValueError("ImageEncoder.encode_sequence: run_slack is one number (a remapped frame has no region map)")
+        self._run_slack_args("ImageEncoder.encode_sequence", run_slack, False)
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
@@ -823,12 +919,13 @@ class ImageEncoder:
             path = out_paths[n] if out_paths is not None else None
             if key_pal is not None:
                 window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
-                res = self.encode_with_palette(image, key_pal, roi_mask=window)
+                res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack)
                 row = res["stats"]["remap"]["all" if window is None else "roi"]
                 kept = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 refined = False
                 if not kept and refine:
-                    res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1)
+                    res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1,
+                                                   run_slack=run_slack)
                     row = res["stats"]["remap"]["all" if window is None else "roi"]
                     kept = refined = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 if kept:
@@ -842,7 +939,7 @@ class ImageEncoder:
                     yield res
                     continue
             res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
-                              target_psnr=target_psnr)
+                              target_psnr=target_psnr, run_slack=run_slack)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

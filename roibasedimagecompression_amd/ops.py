@@ -125,6 +125,15 @@ def palette_moments_lds_rows(n_classes=0):
     return int(_lib.load().rhccq_palette_moments_lds_rows(int(n_classes)))
 
 
+def palette_runs_tile():
+    """(image rows a workgroup of Rhccq.palette_runs walks by default, columns of the tile it stages through LDS)"""
+    lib = _lib.load()
+    return int(lib.rhccq_palette_runs_rows()), int(lib.rhccq_palette_runs_tile_cols())
+
+
+RUN_SLACK_MAX = 3 * 255 ** 2          # the largest slack Rhccq.palette_runs takes: no squared distance is larger
+
+
 def psnr_from_sse(sse, n_pixels):
     """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
     10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
@@ -241,6 +250,7 @@ class Rhccq:
     OPT_FRAME_LEVEL2 = 9             # rhccq_encode_frame: 1 (default) the level-2 palettes of all classes as one batch on one lane; 0: one per class lane
     OPT_REFINE_LDS_ROWS = 10         # palette_refine: palettes of more rows accumulate in global memory (0 .. palette_refine_lds_rows(), default that)
     OPT_REFINE_MAX_BLOCKS = 11       # palette_refine: at most this many workgroups (0, default: 8 per CU)
+    OPT_RUNS_ROWS = 13               # palette_runs: image rows of a workgroup (0, default: palette_runs_tile()[0]; 2, 4 or 8)
     OPT_CHAIN_RELEASE = 12           # rhccq_encode_frame: 1 (default) a level-1 problem goes on when its own chain of the frame's launch ends; 0: when the launch ends
 
     def _bind_stream(self):
@@ -1045,6 +1055,49 @@ class Rhccq:
             return idx, sums.zero_()
         self._check(self.lib.rhccq_palette_remap(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), int(n_classes), self._p(idx),
                                                  idx.element_size(), self._p(sums)), "palette_remap")
+        return idx, sums
+
+    # -- run-carrying remap onto a given palette (EXTENSION: csrc/palette_runs.hip) -------------------------------------
+    def palette_runs(self, rgb, palette, slack, class_map=None, n_classes=0):
+        """rgb uint8[H, W, 3], palette uint8[K, 3] (numpy or device), slack: one integer 0..RUN_SLACK_MAX for every pixel, or
+        n_classes + 1 of them (a pixel of class c < n_classes takes slack[c], every other pixel slack[-1]), class_map uint8 / bool
+        [H, W] or None -> (indices device [H, W], uint8 when K <= 256, else int16 holding uint16; sums device int64
+        [n_classes + 1, 3]: row c = {pixels, sum of squared errors, carried pixels} of class c, the last row over every pixel).
+        Along every image row a pixel keeps its left neighbour's index while that costs at most its slack more squared error
+        than its nearest row (palette_remap's); a tie keeps the neighbour's.  Exact integers."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_runs: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
+        if rgb.ndim != 3 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError("palette_runs: rgb [H, W, 3] and palette [K, 3] are expected")
+        H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
+        table = [int(slack)] * (max(n_classes, 0) + 1) if np.ndim(slack) == 0 else [int(v) for v in slack]
+        if len(table) != n_classes + 1:
+            raise ValueError("palette_runs: slack is one integer or n_classes + 1 of them")
+        if min(table) < 0 or max(table) > RUN_SLACK_MAX:
+            raise ValueError(f"palette_runs: a slack must be 0..{RUN_SLACK_MAX}")
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != H * W:
+                raise ValueError("palette_runs: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_runs: n_classes without a class map")
+        idx = self.empty((H, W), torch.uint8 if K <= 256 else torch.int16)
+        sums = self.empty((n_classes + 1, 3), torch.int64)
+        if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
+            if not 0 <= n_classes <= 16 or K < 1 or K > 65536:
+                raise RhccqError("palette_runs: K must be 1..65536 and n_classes 0..16")
+            return idx, sums.zero_()
+        tarr = (C.c_uint32 * len(table))(*table)
+        self._check(self.lib.rhccq_palette_runs(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes,
+                                                C.cast(tarr, C.c_void_p), self._p(idx), idx.element_size(), self._p(sums)), "palette_runs")
         return idx, sums
 
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------

@@ -1,0 +1,335 @@
+"""The run-carrying remap on the device (csrc/palette_runs.hip, Rhccq.palette_runs, the run_slack keyword of ImageEncoder.encode_with_palette /
+encode / encode_sequence) against the numpy reference of tests/runs_cases.py, bit for bit, and what the encoder builds on it: the
+statistics, the last-step rule, the container round trip, the targets.  GPU only."""
+import numpy as np
+import pytest
+
+import remap_cases as RM
+import roimask_cases as RC
+import runs_cases as RN
+
+pytestmark = pytest.mark.gpu
+
+_TDT = {1: "uint8", 2: "int16", 4: "int32"}
+
+
+@pytest.fixture(scope="module")
+def rh():
+    from roibasedimagecompression_amd.ops import default_context
+    return default_context()
+
+
+@pytest.fixture(scope="module")
+def enc(rh):
+    from roibasedimagecompression_amd.image import ImageEncoder
+    return ImageEncoder(rh)
+
+
+def _idx64(t):
+    a = t.cpu().numpy()
+    if a.dtype == np.int16:
+        a = a.view(np.uint16)
+    elif a.dtype == np.int32:
+        a = a.view(np.uint32)
+    return a.astype(np.int64)
+
+
+def _raw_runs(rh, rgb, pal, cls, n_classes, slack, elem_bytes):
+    """rhccq_palette_runs itself, in the element width asked for; buffers pre-filled so that unwritten elements show"""
+    import ctypes as C
+    import torch
+    H, W = rgb.shape[:2]
+    d_rgb, d_pal = rh.dev(np.ascontiguousarray(rgb)), rh.dev(np.ascontiguousarray(pal).reshape(-1, 3))
+    d_cls = None if cls is None else rh.dev(np.ascontiguousarray(cls).reshape(-1))
+    table = RN.slack_table(slack, n_classes)
+    tarr = (C.c_uint32 * len(table))(*table)
+    idx = torch.full((H, W), 0x2B, dtype=getattr(torch, _TDT[elem_bytes]), device=rh.device)
+    sums = torch.full((n_classes + 1, 3), 0x5555, dtype=torch.int64, device=rh.device)
+    rc = rh.lib.rhccq_palette_runs(rh.ctx, rh._p(d_rgb), H, W, rh._p(d_pal), d_pal.shape[0], rh._p(d_cls), n_classes, C.cast(tarr, C.c_void_p),
+                                   rh._p(idx), elem_bytes, rh._p(sums))
+    return rc, _idx64(idx), sums.cpu().numpy()
+
+
+@pytest.mark.parametrize("name", RN.names())
+def test_device_equals_reference(rh, name):
+    import torch
+    rgb, pal, cls, nc, slack, _ = RN.case(name)
+    want_out, want_sums, _ = RN.reference(name)
+    for eb in RN.index_bytes(len(pal)):
+        rc, out, sums = _raw_runs(rh, rgb, pal, cls, nc, slack, eb)
+        assert rc == 0, (name, eb)
+        assert np.array_equal(out, want_out), (name, eb)
+        assert np.array_equal(sums, want_sums), (name, eb)
+    # the Python surface: numpy arguments, the repository's index storage, the picture's shape kept
+    idx, sums = rh.palette_runs(rgb, pal, slack, cls, nc)
+    assert idx.dtype == (torch.uint8 if len(pal) <= 256 else torch.int16) and tuple(idx.shape) == tuple(rgb.shape[:2])
+    assert sums.dtype == torch.int64 and idx.is_cuda and sums.is_cuda
+    assert np.array_equal(_idx64(idx), want_out) and np.array_equal(sums.cpu().numpy(), want_sums), name
+
+
+@pytest.mark.parametrize("name", RN.GRID_CASES)
+def test_many_workgroups_and_ragged_tiles(rh, name):
+    """2200 x 2049: hundreds of workgroups and 33 staging tiles a row, the last one of 1 column; K = T + 1 gathers the palette from LDS
+    across the remap's tile boundary"""
+    rgb, pal, cls, nc, slack, want_out, want_sums = RN.grid_case(name)
+    assert rgb.shape[1] % RN.COLS and rgb.shape[0] // RN.ROWS > 100
+    for eb in RN.index_bytes(len(pal)):
+        rc, out, sums = _raw_runs(rh, rgb, pal, cls, nc, slack, eb)
+        assert rc == 0, (name, eb)
+        assert np.array_equal(out, want_out), (name, eb)
+        assert np.array_equal(sums, want_sums), (name, eb)
+    assert 0 < want_sums[-1, 2] < want_sums[-1, 0]
+
+
+@pytest.mark.parametrize("rows", [2, 4, 8])
+def test_rows_of_a_workgroup_do_not_change_results(rh, rows):
+    from roibasedimagecompression_amd.ops import RhccqError
+    try:
+        rh.set_option(rh.OPT_RUNS_ROWS, rows)
+        for name in ("classes2", "run_across_tiles", "break_at_tile", f"shape{RN.ROWS + 1}x{RN.COLS + 3}", "shape65x7", f"K{RN.T + 1}"):
+            rgb, pal, cls, nc, slack, _ = RN.case(name)
+            want_out, want_sums, _ = RN.reference(name)
+            idx, sums = rh.palette_runs(rgb, pal, slack, cls, nc)
+            assert np.array_equal(_idx64(idx), want_out) and np.array_equal(sums.cpu().numpy(), want_sums), (rows, name)
+        with pytest.raises(RhccqError):
+            rh.set_option(rh.OPT_RUNS_ROWS, 16)
+    finally:
+        rh.set_option(rh.OPT_RUNS_ROWS, 0)
+
+
+def test_palette_above_the_lds_copy(rh):
+    """K = 4097: palette[b] is gathered from global memory"""
+    rng = np.random.default_rng(3)
+    pal = RM._palette(rng, 4097)
+    rgb = RN._image(rng, pal, RN.ROWS + 1, RN.COLS + 9, spread=15)
+    want_out, want_sums, _ = RN.runs_reference(rgb, pal, 500)
+    idx, sums = rh.palette_runs(rgb, pal, 500)
+    assert np.array_equal(_idx64(idx), want_out) and np.array_equal(sums.cpu().numpy(), want_sums) and want_sums[-1, 2] > 0
+
+
+def test_python_surface_arguments(rh):
+    rgb, pal, cls, nc, slack, _ = RN.case("classes2")
+    want_out, want_sums, _ = RN.reference("classes2")
+    idx, sums = rh.palette_runs(rh.dev(rgb), rh.dev(pal), slack, rh.dev(cls), nc)
+    assert np.array_equal(_idx64(idx), want_out) and np.array_equal(sums.cpu().numpy(), want_sums)
+    idx, sums = rh.palette_runs(np.zeros((0, 5, 3), np.uint8), pal, 7)
+    assert tuple(idx.shape) == (0, 5) and sums.cpu().numpy().tolist() == [[0, 0, 0]]
+    for bad in (lambda: rh.palette_runs(rgb, pal, slack, None, 2), lambda: rh.palette_runs(rgb, pal, [1, 2], cls, 2),
+                lambda: rh.palette_runs(rgb, pal, RN.MAX_SLACK + 1), lambda: rh.palette_runs(rgb, pal, -1),
+                lambda: rh.palette_runs(rgb.reshape(-1, 3), pal, 0), lambda: rh.palette_runs(rgb, pal, slack, cls[:-1], 2)):
+        with pytest.raises(ValueError):
+            bad()
+    with pytest.raises(TypeError):
+        rh.palette_runs(rgb.astype(np.int32), pal, 0)
+
+
+@pytest.mark.parametrize("what,over,code", RN.ERRORS, ids=[e[0] for e in RN.ERRORS])
+def test_device_argument_errors(rh, what, over, code):
+    import ctypes as C
+    import torch
+    t = {"rgb": rh.zeros((4, 3), torch.uint8), "palette": rh.zeros((3, 3), torch.uint8), "idx_out": rh.zeros((4,), torch.int32),
+         "sums": rh.zeros((18, 3), torch.int64)}
+    t.update({k: v for k, v in over.items() if k in t})
+    cls = rh.zeros((4,), torch.uint8) if over.get("cls") else None
+    slack = over.get("slack", [5])
+    tarr = None if slack is None else (C.c_uint32 * len(slack))(*slack)
+    rc = rh.lib.rhccq_palette_runs(rh.ctx, rh._p(t["rgb"]), over.get("H", 2), over.get("W", 2), rh._p(t["palette"]), over.get("K", 3), rh._p(cls),
+                                   over.get("n_classes", 0), C.cast(tarr, C.c_void_p) if tarr is not None else C.c_void_p(0), rh._p(t["idx_out"]),
+                                   over.get("idx_elem_bytes", 2), rh._p(t["sums"]))
+    assert rc == code, what
+    assert rh._raw.rhccq_last_error(rh.ctx).decode().startswith("palette_runs:")
+
+
+# ---- ImageEncoder.encode_with_palette(run_slack=) -------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def photo():
+    """roimask_cases' photo96 (96 x 128), its mask, and 300 of its pixels as the palette (2-byte indices; colours=64 gives 1-byte ones)"""
+    _, img, mask = RC.case("photo96")
+    flat = img.reshape(-1, 3)
+    pal = flat[np.random.default_rng(9).choice(len(flat), 300, replace=False)].copy()
+    return img, mask, pal
+
+
+def _check_result(res, img, mask, run_slack):
+    """the result's indices and statistics against the reference over the RETURNED palette"""
+    pal = np.asarray(res["palette"], np.uint8).reshape(-1, 3)
+    if mask is None:
+        want_out, want_sums, _ = RN.runs_reference(img, pal, run_slack)
+        rows = {"all": want_sums[0]}
+    else:
+        table = [run_slack["nonroi"], run_slack["roi"], min(run_slack.values())] if isinstance(run_slack, dict) else [run_slack] * 3
+        want_out, want_sums, _ = RN.runs_reference(img, pal, table, mask.astype(np.uint8), 2)
+        rows = {"nonroi": want_sums[0], "roi": want_sums[1], "all": want_sums[2]}
+    assert np.array_equal(_idx64(res["indices"]), want_out)
+    assert res["indices_dtype"] == ("uint8" if len(pal) <= 256 else "uint16") and tuple(res["indices"].shape) == img.shape[:2]
+    st = res["stats"]
+    assert sorted(st["remap"]) == sorted(rows)
+    for n, row in rows.items():
+        assert (st["remap"][n]["pixels"], st["remap"][n]["sse"]) == (int(row[0]), int(row[1])), n
+        assert abs(st["remap"][n]["psnr"] - RM.psnr(int(row[1]), int(row[0]))) < 1e-9
+    assert st["runs"] == {"slack": run_slack, "carried": {n: int(row[2]) for n, row in rows.items()}, "pixels": img.shape[0] * img.shape[1]}
+    return want_out, want_sums
+
+
+@pytest.mark.parametrize("masked,run_slack", [(False, 150), (True, 150), (True, {"roi": 20, "nonroi": 900}), (False, 0)])
+def test_encode_with_palette_run_slack(enc, photo, masked, run_slack):
+    img, mask, pal = photo
+    mask = mask if masked else None
+    res = enc.encode_with_palette(img, pal, roi_mask=mask, run_slack=run_slack)
+    _, want_sums = _check_result(res, img, mask, run_slack)
+    assert np.array_equal(res["palette"], pal)
+    plain = enc.encode_with_palette(img, pal, roi_mask=mask)
+    assert "runs" not in plain["stats"] and plain["stats"]["remap"]["all"]["sse"] <= res["stats"]["remap"]["all"]["sse"]
+    if run_slack == 0:
+        assert plain["stats"]["remap"] == res["stats"]["remap"]                 # slack 0 keeps the squared error, ties aside the indices too
+    else:
+        assert want_sums[-1, 2] > 0 and not np.array_equal(_idx64(plain["indices"]), _idx64(res["indices"]))
+
+
+def test_run_slack_arguments(enc, photo):
+    img, mask, pal = photo
+    for kw in ({"run_slack": {"roi": 1, "nonroi": 2}}, {"run_slack": {"roi": 1}, "roi_mask": mask}, {"run_slack": -1}, {"run_slack": RN.MAX_SLACK + 1},
+               {"run_slack": {"roi": 1, "nonroi": RN.MAX_SLACK + 1}, "roi_mask": mask}):
+        with pytest.raises(ValueError):
+            enc.encode_with_palette(img, pal, **kw)
+    with pytest.raises(ValueError):
+        next(enc.encode_sequence([img, img], 20, 10, 3.0, run_slack={"roi": 1, "nonroi": 2}))
+
+
+def test_run_carrying_remap_is_the_last_step(enc, photo):
+    """colours= and refine= run first, on the nearest-row assignment; the palette and their statistics are those of the call without a slack"""
+    img, mask, pal = photo
+    slack = {"roi": 60, "nonroi": 600}
+    res = enc.encode_with_palette(img, pal, roi_mask=mask, roi_weight=3, colours=64, refine=2, run_slack=slack)
+    plain = enc.encode_with_palette(img, pal, roi_mask=mask, roi_weight=3, colours=64, refine=2)
+    assert np.array_equal(res["palette"], plain["palette"]) and len(res["palette"]) == 64
+    assert res["stats"]["reduce"] == plain["stats"]["reduce"] and res["stats"]["refine"] == plain["stats"]["refine"]
+    _check_result(res, img, mask, slack)
+
+
+def test_container_round_trip(rh, enc, photo, tmp_path):
+    from roibasedimagecompression_amd import container
+    img, mask, pal = photo
+    path = str(tmp_path / "runs.rhccq")
+    res = enc.encode_with_palette(img, pal, run_slack=200, out_path=path, exact=True)
+    want_out, _ = _check_result(res, img, None, 200)
+    back = container.read_frame(path, rh)
+    assert np.array_equal(_idx64(back["indices"]).reshape(want_out.shape), want_out) and np.array_equal(back["palette"].cpu().numpy(), pal)
+    assert np.array_equal(back["image"].cpu().numpy().reshape(img.shape), pal[want_out])
+    plain = str(tmp_path / "plain.rhccq")
+    enc.encode_with_palette(img, pal, out_path=plain, exact=True)
+    import os
+    print("bytes", os.path.getsize(plain), "->", os.path.getsize(path))
+    assert os.path.getsize(path) < os.path.getsize(plain)
+
+
+@pytest.mark.parametrize("masked,run_slack,target", [(False, 60, 30.0), (True, {"roi": 10, "nonroi": 200}, {"roi": 33.0, "nonroi": 27.0}),
+                                                      (True, 40, {"all": 29.0, "roi": 31.0})])
+def test_target_psnr_keeps_its_guarantee(enc, photo, masked, run_slack, target):
+    img, mask, pal = photo
+    mask = mask if masked else None
+    cons = target if isinstance(target, dict) else {"all": target}
+    L = enc.ladder(img, pal, roi_mask=mask)
+    live = len(L["colours"])
+    s = {"roi": run_slack["roi"], "nonroi": run_slack["nonroi"]} if isinstance(run_slack, dict) else {"roi": run_slack, "nonroi": run_slack}
+    px = L["pixels"]
+    extra = {"all": s["nonroi"] * px["all"]} if mask is None else {"roi": s["roi"] * px["roi"], "nonroi": s["nonroi"] * px["nonroi"],
+                                                                     "all": s["roi"] * px["roi"] + s["nonroi"] * px["nonroi"]}
+
+    def bound(k):
+        return {n: RM.psnr(L["sse"][n][live - k] + extra[n], px[n]) for n in L["sse"]}
+
+    def ok(k):
+        return all(bound(k)[n] >= v for n, v in cons.items())
+    res = enc.encode_with_palette(img, pal, roi_mask=mask, target_psnr=target, run_slack=run_slack)
+    tg = res["stats"]["target"]
+    k = tg["colours"]
+    print(masked, run_slack, target, tg, {n: res["stats"]["remap"][n]["psnr"] for n in L["sse"]})
+    assert tg["kind"] == "psnr" and tg["met"] is True and tg["probes"] == [] and tg["refine_dropped"] is False
+    assert 1 < k < live and ok(k) and all(not ok(j) for j in range(1, k))       # the smallest rung whose ADJUSTED bound meets the target
+    assert all(tg["bound_psnr"][n] == pytest.approx(bound(k)[n], rel=1e-12) for n in L["sse"])
+    for n in L["sse"]:                                                          # the achieved figures cannot fall below the bound used
+        assert res["stats"]["remap"][n]["psnr"] >= tg["bound_psnr"][n], n
+    for n, v in cons.items():
+        assert tg["bound_psnr"][n] >= v and res["stats"]["remap"][n]["psnr"] >= v
+    without = enc.encode_with_palette(img, pal, roi_mask=mask, target_psnr=target)
+    assert without["stats"]["target"]["colours"] <= k
+    _check_result(res, img, mask, run_slack)
+    same = enc.encode_with_palette(img, pal, roi_mask=mask, colours=k, run_slack=run_slack)
+    assert np.array_equal(same["palette"], res["palette"]) and np.array_equal(_idx64(same["indices"]), _idx64(res["indices"]))
+
+
+@pytest.mark.parametrize("exact", [True, False])
+def test_target_bytes_probes_run_with_the_slack(rh, enc, photo, tmp_path, exact):
+    from roibasedimagecompression_amd import container
+    img, _, pal = photo
+    slack = 120
+    full = len(container.frame_bytes(enc.encode_with_palette(img, pal, run_slack=slack), rh, exact=exact))
+    out = str(tmp_path / "t.rhccq")
+    res = enc.encode_with_palette(img, pal, target_bytes=int(full * 0.6), run_slack=slack, exact=exact, out_path=out)
+    tg = res["stats"]["target"]
+    assert tg["kind"] == "bytes" and tg["met"] is True and len(tg["probes"]) > 1
+    for k, size in tg["probes"]:
+        again = enc.encode_with_palette(img, pal, colours=k, run_slack=slack)
+        assert size == len(container.frame_bytes(again, rh, exact=exact)), k
+        if k == tg["colours"]:
+            assert np.array_equal(again["palette"], res["palette"]) and np.array_equal(_idx64(again["indices"]), _idx64(res["indices"]))
+            assert again["stats"]["runs"] == res["stats"]["runs"] and again["stats"]["remap"] == res["stats"]["remap"]
+    import os
+    assert os.path.getsize(out) == dict(tg["probes"])[tg["colours"]] <= int(full * 0.6)
+    _check_result(res, img, None, slack)
+
+
+# ---- ImageEncoder.encode(run_slack=) and encode_sequence ------------------------------------------------------------------------------
+def _same_result(a, b):
+    return (np.array_equal(np.asarray(a["palette"]), np.asarray(b["palette"])) and a["indices"].dtype == b["indices"].dtype
+            and np.array_equal(a["indices"].cpu().numpy(), b["indices"].cpu().numpy()) and tuple(a["shape"]) == tuple(b["shape"])
+            and tuple(a["top_left"]) == tuple(b["top_left"]) and a["indices_dtype"] == b["indices_dtype"])
+
+
+def test_encode_run_slack(rh, enc, tmp_path):
+    from roibasedimagecompression_amd import container
+    (q1, q2), img, mask = RC.case("photo96")
+    base = enc.encode(img, q1, q2, roi_mask=mask)
+    none = enc.encode(img, q1, q2, roi_mask=mask, run_slack=None)
+    assert _same_result(base, none) and "runs" not in none["stats"] and "runs" not in base["stats"]
+    assert tuple(base["top_left"]) == (0, 0) and tuple(base["shape"]) == img.shape[:2]
+    pal = np.asarray(base["palette"], np.uint8).reshape(-1, 3)
+    cls = enc.region_map.cpu().numpy().astype(np.uint8)                        # the map the encoder made of the mask: 1 inside, 0 outside
+    assert cls.shape == img.shape[:2] and set(np.unique(cls).tolist()) == {0, 1}
+    for run_slack in (90, {"roi": 10, "nonroi": 400}):
+        path = str(tmp_path / "e.rhccq")
+        res = enc.encode(img, q1, q2, roi_mask=mask, run_slack=run_slack, out_path=path, exact=True)
+        assert np.array_equal(np.asarray(res["palette"], np.uint8).reshape(-1, 3), pal)
+        table = [run_slack["nonroi"], run_slack["roi"], min(run_slack.values())] if isinstance(run_slack, dict) else [run_slack] * 3
+        want_out, want_sums, _ = RN.runs_reference(img, pal, table, cls, 2)
+        assert np.array_equal(_idx64(res["indices"]).reshape(want_out.shape), want_out)
+        assert tuple(res["indices"].shape) == tuple(base["indices"].shape) and res["indices"].dtype == base["indices"].dtype
+        assert res["stats"]["runs"] == {"slack": run_slack, "carried": {"all": int(want_sums[2, 2]), "roi": int(want_sums[1, 2]),
+                                                                        "nonroi": int(want_sums[0, 2])}, "pixels": img.shape[0] * img.shape[1]}
+        assert want_sums[2, 2] > 0
+        back = container.read_frame(path, rh)
+        assert np.array_equal(_idx64(back["indices"]).reshape(want_out.shape), want_out)
+
+
+def test_encode_sequence_forwards_the_slack(enc):
+    frames = RM.sequence_frames()[:2]                                          # a key frame and a frame that is remapped onto it
+    q1, q2 = RM.SEQ_QUALITIES
+    results = list(enc.encode_sequence(frames, q1, q2, RM.SEQ_MAX_DROP_DB, run_slack=50))
+    assert [r["stats"]["key_frame"] for r in results] == [True, False]
+    assert _same_result(results[0], enc.encode(frames[0], q1, q2, run_slack=50)) and results[0]["stats"]["runs"]["slack"] == 50
+    pal = np.asarray(results[0]["palette"], np.uint8).reshape(-1, 3)
+    want_out, want_sums, _ = RN.runs_reference(frames[1], pal, 50)
+    assert np.array_equal(_idx64(results[1]["indices"]), want_out)
+    assert results[1]["stats"]["runs"] == {"slack": 50, "carried": {"all": int(want_sums[0, 2])}, "pixels": 96 * 128}
+    plain = list(enc.encode_sequence(frames, q1, q2, RM.SEQ_MAX_DROP_DB))
+    assert all("runs" not in r["stats"] for r in plain)
+
+
+# ---- the value claim on the device path ---------------------------------------------------------------------------------------------------
+def test_kodak_22_equals_reference(rh):
+    """the device index map is the reference's, so the 80 % / 1.2 dB condition of tests/test_palette_runs_cpu.py holds for it"""
+    img, pal, b, out, sums = RN.kodak()
+    idx, got = rh.palette_runs(img, pal, RN.KODAK_SLACK)
+    assert np.array_equal(_idx64(idx), out) and np.array_equal(got.cpu().numpy(), sums)
+    assert RN.index_bytes_zlib9(_idx64(idx)) <= RN.KODAK_MAX_BYTES_RATIO * RN.index_bytes_zlib9(b)
