@@ -885,6 +885,40 @@ int rhccq_palette_runs(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W,
 int rhccq_palette_runs_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
                             const uint32_t* slack, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
 
+/* ---- EXTENSION: exact row segmentation onto a given palette (no reference counterpart; csrc/palette_segment.hip) ----------------------
+ * rgb, palette, cls, n_classes, idx_out and idx_elem_bytes as rhccq_palette_runs takes them; penalty uint32[n_classes + 1], each entry
+ * 0..16777215 (2^24 - 1).  pen(y, x) = penalty[cls[p]] when cls[p] < n_classes and penalty[n_classes] otherwise (and for every pixel when
+ * cls == NULL).  Image rows are independent.  With d(x, c) = |rgb(y, x) - palette[c]|^2, per image row the call returns the labelling that
+ * minimises   sum_x d(x, out(x))  +  sum over x >= 1 with out(x) != out(x - 1) of pen(x)   (the 1-D Potts segmentation), by this rule:
+ *   forward   C_0(c) = d(0, c).  For x >= 1: m = min_c C_{x-1}(c), a(x) the lowest c that attains it; stay(x, c) <=> C_{x-1}(c) <= m + pen(x)
+ *             (an exact tie stays); C_x(c) = d(x, c) + min(C_{x-1}(c), m + pen(x)).
+ *   backward  out(W - 1) = the lowest c that attains min C_{W-1};  out(x - 1) = out(x) if stay(x, out(x)), else a(x).
+ * Every comparison is between costs of one column, so the implementation subtracts m after every step and drops the part of d that all
+ * rows of a pixel share; every cost stays below 2^25 and the arithmetic is int32 for any W (csrc/palette_segment.h).  What follows:
+ * every pixel is within the penalties of its two boundaries of its nearest row, d(x, out(x)) <= db(x) + [x > 0] pen(x) + [x < W - 1] pen(x + 1);
+ * penalty 0 keeps the remap's squared error (the indices may differ at ties); a row with W * 195075 < penalty is constant.
+ * sums is uint64[n_classes + 1][4], zeroed by the call: row c = {pixels, sum of |rgb - palette[out]|^2, pixels with out != b
+ * (b = rhccq_palette_remap's index), breaks} over the pixels with cls[p] == c, the last row over every pixel; a break is an x >= 1 with
+ * out(x) != out(x - 1), counted in the class of pixel x.
+ * RHCCQ_E_ARG: as rhccq_palette_runs, and a null penalty, a penalty above 2^24 - 1; device form: a null workspace, one not aligned to 8, or
+ * work_bytes below rhccq_palette_segment_bytes(H, W, K).  RHCCQ_E_LIMIT: K > 65536; device form: K > rhccq_palette_segment_max_rows()
+ * (1024: a wave owns an image row and holds the K states in registers, 16 per lane at most); host form: its tables could not be
+ * allocated.  H * W == 0 succeeds with zero sums (and needs no workspace).
+ * Device form: every pointer but penalty_host (copied by value into the launch) is device memory; async on the context stream, no host
+ * synchronisation, nothing allocated: rhccq_palette_remap into idx_out (b), a memset, then ONE launch, a one-wave workgroup per image
+ * row, that runs the row's forward pass and behind it its backward pass.  The workspace is the FULL PLANE of decisions, not only the rows in
+ * flight: per image row and tile of rhccq_palette_segment_tile_cols() (32) columns, ceil(K / 64) x 64 dwords of stay bits and 32 uint16 a(x),
+ * i.e. H x ceil(W / 32) x (256 ceil(K / 64) + 64) bytes (282 MB for 3840 x 2160 at K = 230).  Its contents before and after the call mean nothing.
+ * Host form: the same step functions (csrc/palette_segment.h) run serially on host memory, for any K <= 65536. */
+int32_t rhccq_palette_segment_max_rows(void);                         /* host only: the largest K of the device form */
+int32_t rhccq_palette_segment_tile_cols(void);                        /* host only: the columns of a tile of the workspace */
+int64_t rhccq_palette_segment_bytes(int32_t H, int32_t W, int32_t K); /* host only: workspace bytes (0 for arguments the device form refuses) */
+int rhccq_palette_segment(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                          int32_t n_classes, const uint32_t* penalty_host, void* work, int64_t work_bytes, void* idx_out, int32_t idx_elem_bytes,
+                          uint64_t* sums);
+int rhccq_palette_segment_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
+                               const uint32_t* penalty, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,12 @@ PROTOTYPES = {
     "rhccq_palette_runs_rows": (c_int32, []),
     "rhccq_palette_runs": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_runs_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_segment_max_rows": (c_int32, []),
+    "rhccq_palette_segment_tile_cols": (c_int32, []),
+    "rhccq_palette_segment_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "rhccq_palette_segment": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
+                                        c_void_p]),
+    "rhccq_palette_segment_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
 }
 
 

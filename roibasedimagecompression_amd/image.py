@@ -400,7 +400,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -423,12 +423,15 @@ class ImageEncoder:
         max_colours, if given) is rewritten by the run-carrying rule over its own palette and the rectangle it covers
         (Rhccq.palette_runs: a pixel keeps its left neighbour's index while that costs at most the slack more squared error than its
         nearest row), the dict's entries applying inside and outside the region map; stats["runs"] as encode_with_palette fills it.
-        With a target every probe and the result run with the slack, as in encode_with_palette."""
+        With a target every probe and the result run with the slack, as in encode_with_palette.
+        run_penalty = p or {"roi": a, "nonroi": b} (EXTENSION, default None = off; 0 is a value; exclusive with run_slack and with
+        target_psnr): the same place and the same rules, with the exact row segmentation (Rhccq.palette_segment) instead of the
+        greedy rule; stats["runs"] as encode_with_palette fills it."""
         rh = self.rh
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
-        runs = self._run_slack_args("ImageEncoder.encode", run_slack, True)
+        runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr)
         cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -543,11 +546,11 @@ class ImageEncoder:
         return row, target, data, runs_row
 
     def _runs_result(self, rgb, res, region_map, runs):
-        """encode's run_slack without a target: the finished result's index map in place -> stats["runs"]"""
+        """encode's run_slack / run_penalty without a target: the finished result's index map in place -> stats["runs"]"""
         rh = self.rh
         pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
         window, cls = self._window(rgb, res, region_map)
-        idx, sums = rh.palette_runs(window, pal, self._slack_table(runs, True), cls, 2)
+        idx, sums = self._runs_call(window, pal, cls, runs)
         res.update(indices=idx.reshape(res["indices"].shape), indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
         return self._runs_row(runs, rh.to_host(sums), True)
 
@@ -572,6 +575,45 @@ class ImageEncoder:
         return out
 
     @staticmethod
+    def _run_penalty_args(fn, run_penalty, masked):
+        """the run_penalty keyword checked -> None (off), or {"penalty": as given, "nonroi": p, "roi": p}"""
+        from .ops import RUN_PENALTY_MAX
+        if run_penalty is None:
+            return None
+        if isinstance(run_penalty, dict):
+            if sorted(run_penalty) != ["nonroi", "roi"]:
+                raise ValueError(f'{fn}: run_penalty is a number or a dict over "roi" and "nonroi"')
+            if not masked:
+                raise ValueError(f"{fn}: a roi / nonroi run_penalty needs roi_mask")
+            given = {k: int(v) for k, v in run_penalty.items()}
+            out = {"penalty": given, "nonroi": given["nonroi"], "roi": given["roi"]}
+        else:
+            out = {"penalty": int(run_penalty), "nonroi": int(run_penalty), "roi": int(run_penalty)}
+        if not (0 <= out["nonroi"] <= RUN_PENALTY_MAX and 0 <= out["roi"] <= RUN_PENALTY_MAX):
+            raise ValueError(f"{fn}: a run_penalty must be 0..{RUN_PENALTY_MAX}")
+        return out
+
+    @staticmethod
+    def _runs_args(fn, run_slack, run_penalty, masked, target_psnr=None):
+        """run_slack and run_penalty checked together -> None (both off) or the dict of the one given (it has "slack" or "penalty")"""
+        if run_slack is not None and run_penalty is not None:
+            raise ValueError(f"{fn}: run_slack and run_penalty are exclusive")
+        if run_penalty is not None and target_psnr is not None:
+            # the only bound the segmentation gives a pixel is its two boundaries' penalties: too loose to choose a rung by
+            raise ValueError(f"{fn}: run_penalty cannot be combined with target_psnr")
+        if run_penalty is not None:
+            return ImageEncoder._run_penalty_args(fn, run_penalty, masked)
+        return ImageEncoder._run_slack_args(fn, run_slack, masked)
+
+    def _runs_call(self, rgb, pal, cls, runs):
+        """the final index map by the rule `runs` names: the greedy carry (Rhccq.palette_runs) or the exact row segmentation
+        (Rhccq.palette_segment) -> (indices, sums device)"""
+        table, nc = self._slack_table(runs, cls is not None), 2 if cls is not None else 0
+        if "penalty" in runs:
+            return self.rh.palette_segment(rgb, pal, table, cls, nc)
+        return self.rh.palette_runs(rgb, pal, table, cls, nc)
+
+    @staticmethod
     def _slack_table(runs, masked):
         """Rhccq.palette_runs' table over the region map's classes (0 = outside, 1 = inside; a map holds no other value)"""
         return [runs["nonroi"], runs["roi"], min(runs["nonroi"], runs["roi"])] if masked else [runs["nonroi"]]
@@ -581,6 +623,11 @@ class ImageEncoder:
         carried = {"all": int(sums[-1][2])}
         if masked:
             carried["roi"], carried["nonroi"] = int(sums[1][2]), int(sums[0][2])
+        if "penalty" in runs:
+            breaks = {"all": int(sums[-1][3])}
+            if masked:
+                breaks["roi"], breaks["nonroi"] = int(sums[1][3]), int(sums[0][3])
+            return {"penalty": runs["penalty"], "carried": carried, "breaks": breaks, "pixels": int(sums[-1][0])}
         return {"slack": runs["slack"], "carried": carried, "pixels": int(sums[-1][0])}
 
     @staticmethod
@@ -597,7 +644,7 @@ class ImageEncoder:
         if refine:
             pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
         if runs is not None:
-            idx, sums = rh.palette_runs(rgb, pal, self._slack_table(runs, cls is not None), cls, 2 if cls is not None else 0)
+            idx, sums = self._runs_call(rgb, pal, cls, runs)
         else:
             idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
         if refine:
@@ -694,11 +741,13 @@ class ImageEncoder:
             return rh.palette_rung(pal, st["counts"], st["merges"], k)[0].contiguous()
 
         # with a run slack a pixel may lose at most its slack against the nearest row: the curve's sum plus slack x pixels per table
-        # bounds the run-carrying result's squared error (exact integers)
+        # bounds the run-carrying result's squared error (exact integers).  With a run penalty a pixel may lose the penalties of its two
+        # boundaries, its own and its right neighbour's (of either class): own + largest per pixel (a byte target records this bound)
         extra = None
         if runs is not None:
             px = L["pixels"]
-            extra = {"all": runs["nonroi"] * px["all"]} if cls is None else {"nonroi": runs["nonroi"] * px["nonroi"], "roi": runs["roi"] * px["roi"]}
+            per = {n: runs[n] + (max(runs["nonroi"], runs["roi"]) if "penalty" in runs else 0) for n in ("nonroi", "roi")}
+            extra = {"all": per["nonroi"] * px["all"]} if cls is None else {"nonroi": per["nonroi"] * px["nonroi"], "roi": per["roi"] * px["roi"]}
             if cls is not None:
                 extra["all"] = extra["nonroi"] + extra["roi"]
 
@@ -755,7 +804,7 @@ class ImageEncoder:
         return out + (row, target, data)
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
-                            target_bytes=None, target_psnr=None, run_slack=None):
+                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -799,7 +848,18 @@ class ImageEncoder:
         pixels}.  A PSNR target keeps its guarantee: a rung's bound is formed from the curve's sum plus slack x pixels per table
         (exact integers, a valid bound of the run-carrying result's squared error), so rungs come out larger than without a slack,
         and bound_psnr records the adjusted bound.  A byte target probes every rung with the given slack; slack and colours are not
-        searched jointly."""
+        searched jointly.
+        run_penalty = p or {"roi": a, "nonroi": b} (the dict needs roi_mask; default None = off, and 0 is a value; exclusive with
+        run_slack: both given raise ValueError): the final remap, in the same place as run_slack's (behind refine, colours and in
+        every probe of target_bytes), is the exact row segmentation (Rhccq.palette_segment): per image row the index map that
+        minimises the squared error plus the penalty (0..16777215) of every pixel whose index differs from its left neighbour's,
+        the pixel's own class deciding its penalty.  The greedy slack approximates this; at equal value the exact map has fewer
+        bytes and no more error.  A pixel is at most the penalties of its two boundaries worse than its
+        nearest row.  stats["remap"] stays the figures of the index map returned; stats["runs"] = {penalty: as given, carried: {all:
+        pixels whose index is not the nearest row[, roi, nonroi]}, breaks: {all: pixels whose index differs from their left
+        neighbour's[, roi, nonroi]}, pixels}.  With target_psnr it raises ValueError: two penalties a pixel is the only valid bound
+        and too loose to choose a rung by.  A byte target's bound_psnr adds (own + largest penalty) x pixels per table.  The palette
+        may have at most ops.palette_segment_max_rows() rows (RhccqError)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
@@ -808,7 +868,7 @@ class ImageEncoder:
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None or searching))):
             raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0, colours or a target")
         cons = self._target_args("ImageEncoder.encode_with_palette", target_bytes, target_psnr, roi_mask is not None) if searching else None
-        runs = self._run_slack_args("ImageEncoder.encode_with_palette", run_slack, roi_mask is not None)
+        runs = self._runs_args("ImageEncoder.encode_with_palette", run_slack, run_penalty, roi_mask is not None, target_psnr)
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -881,7 +941,7 @@ class ImageEncoder:
         return res
 
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
-                        target_bytes=None, target_psnr=None, run_slack=None):
+                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -899,16 +959,17 @@ class ImageEncoder:
         max_colours: passed to the key frames' encode (default None = off).  target_bytes / target_psnr: passed to the key
         frames' encode too (exclusive with each other and with max_colours; see encode for how the search differs from max_colours).
         run_slack: one number (default None = off), passed to the key frames' encode and to every remap (plain and refined), whose
-        PSNRs the key-frame rule then compares; a roi / nonroi dict raises ValueError, because a remapped frame has no region map."""
+        PSNRs the key-frame rule then compares; a roi / nonroi dict raises ValueError, because a remapped frame has no region map.
+        run_penalty: one number (default None = off), by the same rules (exclusive with run_slack and with target_psnr)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         if target_bytes is not None or target_psnr is not None:
             if max_colours is not None:
                 raise ValueError("ImageEncoder.encode_sequence: target_bytes / target_psnr and max_colours are exclusive")
             self._target_args("ImageEncoder.encode_sequence", target_bytes, target_psnr, True)
-        if isinstance(run_slack, dict):
-            raise ValueError("ImageEncoder.encode_sequence: run_slack is one number (a remapped frame has no region map)")
-        self._run_slack_args("ImageEncoder.encode_sequence", run_slack, False)
+        if isinstance(run_slack, dict) or isinstance(run_penalty, dict):
+            raise ValueError("ImageEncoder.encode_sequence: run_slack / run_penalty is one number (a remapped frame has no region map)")
+        self._runs_args("ImageEncoder.encode_sequence", run_slack, run_penalty, False, target_psnr)
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
@@ -919,13 +980,13 @@ class ImageEncoder:
             path = out_paths[n] if out_paths is not None else None
             if key_pal is not None:
                 window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
-                res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack)
+                res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack, run_penalty=run_penalty)
                 row = res["stats"]["remap"]["all" if window is None else "roi"]
                 kept = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 refined = False
                 if not kept and refine:
                     res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1,
-                                                   run_slack=run_slack)
+                                                   run_slack=run_slack, run_penalty=run_penalty)
                     row = res["stats"]["remap"]["all" if window is None else "roi"]
                     kept = refined = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 if kept:
@@ -939,7 +1000,7 @@ class ImageEncoder:
                     yield res
                     continue
             res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
-                              target_psnr=target_psnr, run_slack=run_slack)
+                              target_psnr=target_psnr, run_slack=run_slack, run_penalty=run_penalty)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

@@ -132,6 +132,19 @@ def palette_runs_tile():
 
 
 RUN_SLACK_MAX = 3 * 255 ** 2          # the largest slack Rhccq.palette_runs takes: no squared distance is larger
+RUN_PENALTY_MAX = (1 << 24) - 1       # the largest penalty Rhccq.palette_segment takes
+
+
+def palette_segment_max_rows():
+    """the largest palette Rhccq.palette_segment takes on the device (a wave holds the K states of an image row in registers)"""
+    from . import _lib
+    return int(_lib.load().rhccq_palette_segment_max_rows())
+
+
+def palette_segment_tile():
+    """columns of a tile of Rhccq.palette_segment's workspace (a state's stay bits over a tile are one dword)"""
+    from . import _lib
+    return int(_lib.load().rhccq_palette_segment_tile_cols())
 
 
 def psnr_from_sse(sse, n_pixels):
@@ -1098,6 +1111,54 @@ class Rhccq:
         tarr = (C.c_uint32 * len(table))(*table)
         self._check(self.lib.rhccq_palette_runs(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes,
                                                 C.cast(tarr, C.c_void_p), self._p(idx), idx.element_size(), self._p(sums)), "palette_runs")
+        return idx, sums
+
+    # -- exact row segmentation onto a given palette (EXTENSION: csrc/palette_segment.hip) ---------------------------------
+    def palette_segment(self, rgb, palette, penalty, class_map=None, n_classes=0):
+        """rgb uint8[H, W, 3], palette uint8[K, 3] (numpy or device; K <= palette_segment_max_rows(), else RhccqError), penalty: one
+        integer 0..RUN_PENALTY_MAX for every pixel, or n_classes + 1 of them (a pixel of class c < n_classes takes penalty[c], every
+        other pixel penalty[-1]), class_map uint8 / bool [H, W] or None -> (indices device [H, W], uint8 when K <= 256, else int16
+        holding uint16; sums device int64 [n_classes + 1, 4]: row c = {pixels, sum of squared errors, pixels whose index is not the
+        nearest row, breaks} of class c, the last row over every pixel).  Per image row the index map minimises the squared error
+        plus the penalty of every pixel whose index differs from its left neighbour's (a break), exactly: the 1-D Potts
+        segmentation by its K-state dynamic programme in integers (include/rhccq.h pins ties).  The workspace (the full plane of
+        decisions, rhccq_palette_segment_bytes) is a torch allocation of this call."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_segment: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
+        if rgb.ndim != 3 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError("palette_segment: rgb [H, W, 3] and palette [K, 3] are expected")
+        H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
+        table = [int(penalty)] * (max(n_classes, 0) + 1) if np.ndim(penalty) == 0 else [int(v) for v in penalty]
+        if len(table) != n_classes + 1:
+            raise ValueError("palette_segment: penalty is one integer or n_classes + 1 of them")
+        if min(table) < 0 or max(table) > RUN_PENALTY_MAX:
+            raise ValueError(f"palette_segment: a penalty must be 0..{RUN_PENALTY_MAX}")
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != H * W:
+                raise ValueError("palette_segment: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_segment: n_classes without a class map")
+        if K < 1 or K > palette_segment_max_rows() or not 0 <= n_classes <= 16:
+            raise RhccqError(f"palette_segment: K must be 1..{palette_segment_max_rows()} on the device and n_classes 0..16")
+        idx = self.empty((H, W), torch.uint8 if K <= 256 else torch.int16)
+        sums = self.empty((n_classes + 1, 4), torch.int64)
+        if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
+            return idx, sums.zero_()
+        nbytes = int(self.lib.rhccq_palette_segment_bytes(H, W, K))
+        work = self.empty((nbytes // 8,), torch.int64)
+        tarr = (C.c_uint32 * len(table))(*table)
+        self._check(self.lib.rhccq_palette_segment(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes,
+                                                   C.cast(tarr, C.c_void_p), self._p(work), nbytes, self._p(idx), idx.element_size(),
+                                                   self._p(sums)), "palette_segment")
         return idx, sums
 
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------

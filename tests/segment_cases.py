@@ -1,0 +1,282 @@
+"""Shared cases of the exact row segmentation tests (tests/test_palette_segment_cpu.py, tests/test_gpu_palette_segment.py): a plain
+helper module, not a conftest.
+
+`segment_reference` is the numpy statement of rhccq_palette_segment's rule (include/rhccq.h): plain int64 costs that are never
+renormalised, vectorised over image rows and states, chunked over image rows.  Every case's reference is computed once per process
+and shared (do not modify what `case`, `reference` and `kodak` return); `reference` asserts once the properties the rule implies."""
+import functools
+import itertools
+import zlib
+
+import numpy as np
+
+import remap_cases as RM
+import runs_cases as RN
+from roibasedimagecompression_amd import ops
+
+COLS = ops.palette_segment_tile()          # columns of a tile of the kernel's workspace: the widths sit at its edges
+CAP = ops.palette_segment_max_rows()       # the largest palette of the device form
+MAX_PENALTY = (1 << 24) - 1
+MAX_D = 3 * 255 ** 2
+E_ARG, E_LIMIT = RM.E_ARG, RM.E_LIMIT
+GOLDEN = RN.GOLDEN
+
+
+def penalty_table(penalty, n_classes):
+    return [int(penalty)] * (n_classes + 1) if np.ndim(penalty) == 0 else [int(v) for v in penalty]
+
+
+def penalty_map(shape, penalty, cls=None, n_classes=0):
+    """-> (pen int64[H, W], class row int64[H, W]: the class below n_classes, else n_classes)"""
+    table = np.asarray(penalty_table(penalty, n_classes), np.int64)
+    assert len(table) == n_classes + 1 and table.min() >= 0 and table.max() <= MAX_PENALTY
+    c = np.full(shape, n_classes, np.int64) if cls is None else np.minimum(np.asarray(cls).reshape(shape).astype(np.int64), n_classes)
+    return table[c], c
+
+
+def segment_reference(rgb, palette, penalty, cls=None, n_classes=0, b=None, chunk_elems=1 << 24):
+    """-> (out int64[H, W], sums int64[n_classes + 1, 4]: row c = {pixels, squared error of out, pixels with out != b, breaks} over
+    cls == c, the last row over every pixel, b int64[H, W]).  `b`: the nearest-row map when the caller has it already."""
+    rgb = np.asarray(rgb, np.uint8)
+    H, W = rgb.shape[:2]
+    pal = np.asarray(palette, np.uint8).reshape(-1, 3).astype(np.int64)
+    K = len(pal)
+    pen, c = penalty_map((H, W), penalty, cls, n_classes)
+    if b is None:
+        b = RM.remap_reference(rgb, palette)[0]
+    b = np.asarray(b, np.int64).reshape(H, W)
+    out = np.zeros((H, W), np.int64)
+    step = max(1, chunk_elems // max(1, W * K))
+    for r0 in range(0, H if W else 0, step):
+        px = rgb[r0:r0 + step].astype(np.int64)
+        h = len(px)
+        ar = np.arange(h)
+
+        def d(x):
+            return ((px[:, x, None, :] - pal[None, :, :]) ** 2).sum(axis=2)
+        stay = np.zeros((h, W, K), bool)
+        a = np.zeros((h, W), np.int64)
+        C = d(0)
+        for x in range(1, W):
+            m = C.min(axis=1)
+            a[:, x] = C.argmin(axis=1)                                      # (the first, so the lowest, row that attains it)
+            lim = (m + pen[r0:r0 + h, x])[:, None]
+            stay[:, x] = C <= lim
+            C = d(x) + np.minimum(C, lim)
+        o = C.argmin(axis=1)
+        out[r0:r0 + h, W - 1] = o
+        for x in range(W - 1, 0, -1):
+            o = np.where(stay[ar, x, o], o, a[:, x])
+            out[r0:r0 + h, x - 1] = o
+    dist = ((rgb.astype(np.int64) - pal[out]) ** 2).sum(axis=2)
+    moved = out != b
+    brk = np.zeros((H, W), bool)
+    brk[:, 1:] = out[:, 1:] != out[:, :-1]
+    sums = np.zeros((n_classes + 1, 4), np.int64)
+    for k in range(n_classes):
+        sel = c == k
+        sums[k] = (sel.sum(), dist[sel].sum(), moved[sel].sum(), brk[sel].sum())
+    sums[n_classes] = (H * W, dist.sum(), moved.sum(), brk.sum())
+    return out, sums, b
+
+
+def objective(rgb, palette, out, pen):
+    """per image row: squared error of `out` plus the penalties of its breaks -> int64[H]"""
+    pal = np.asarray(palette, np.uint8).reshape(-1, 3).astype(np.int64)
+    out = np.asarray(out, np.int64)
+    dist = ((np.asarray(rgb).astype(np.int64) - pal[out]) ** 2).sum(axis=2)
+    brk = np.zeros(out.shape, bool)
+    brk[:, 1:] = out[:, 1:] != out[:, :-1]
+    return dist.sum(axis=1) + (pen * brk).sum(axis=1)
+
+
+def brute_force(rgb, palette, pen):
+    """the least objective of every image row over all K^W labellings (tiny rows only)"""
+    H, W = rgb.shape[:2]
+    K = len(palette)
+    assert K ** W <= 729
+    labels = np.array(list(itertools.product(range(K), repeat=W)), np.int64)
+    return np.array([min(int(objective(rgb[y:y + 1], palette, lab[None], pen[y:y + 1])[0]) for lab in labels) for y in range(H)], np.int64)
+
+
+def _build():
+    """name -> (rgb uint8[H, W, 3], palette uint8[K, 3], cls uint8[H, W] or None, n_classes, penalty (a number or a table),
+    expected out rows, "constant" or None)"""
+    rng = np.random.default_rng(20261020)
+    out = {}
+    pal37 = RM._palette(rng, 37)
+    # shape edges: one and two columns, the tile's width, one below and above it, twice it; one, a few and more than 64 image rows
+    for h in (1, 3, 70):
+        for w in (1, 2, COLS - 1, COLS, COLS + 1, 2 * COLS):
+            out[f"shape{h}x{w}"] = (RN._image(rng, pal37, h, w, spread=10), pal37, None, 0, 700, None)
+    # palette sizes at the edges of a lane's state slots (64 states a slot) and of the index widths; even sizes have duplicate rows
+    for K in (1, 2, 63, 64, 65, 128, 129, 256, 257, CAP):
+        pal = RM._palette(rng, K, levels=256 if K % 2 else 6)
+        out[f"K{K}"] = (RN._image(rng, pal, 5, 70, spread=12), pal, None, 0, 300, None)
+    # duplicate rows throughout (ties in stay, a(x) and the last column's minimum): 8 colours in 40 rows, pixels on and between them
+    pal = RM._palette(rng, 40, levels=2)
+    out["duplicates"] = (RN._image(rng, pal, 9, 2 * COLS + 7, spread=2), pal, None, 0, 3, None)
+    out["duplicates_pen0"] = (RN._image(rng, pal, 9, 2 * COLS + 7, spread=1), pal, None, 0, 0, None)
+    # hand-written.  Rows (0,0,0) and (2,0,0), pixels 0, 2, 2: C_0 = (0, 4); with penalty 4 row 1 sits exactly at m + pen in column 1
+    # and stays (staying and arriving cost 4 both); with penalty 3 it sits at m + pen + 1 and the labelling arrives from row 0
+    pal = np.array([[0, 0, 0], [2, 0, 0]], np.uint8)
+    img = np.array([[[0, 0, 0], [2, 0, 0], [2, 0, 0]]], np.uint8)
+    out["tie_stays"] = (img, pal, None, 0, 4, [[1, 1, 1]])
+    out["one_above_the_tie"] = (img, pal, None, 0, 3, [[0, 1, 1]])
+    out["one_below_the_tie"] = (img, pal, None, 0, 5, [[1, 1, 1]])
+    # the last column's minimum is attained twice: the lowest row is taken
+    out["last_column_tie"] = (np.array([[[1, 0, 0], [1, 0, 0]]], np.uint8), pal, None, 0, 1, [[0, 0]])
+    # tiny rows, checked against brute force over all K^W labellings in reference()
+    for i, (K, w, p) in enumerate([(2, 3, 2), (2, 6, 9), (3, 4, 1), (3, 5, 6), (3, 6, 30), (3, 6, 3)]):
+        pal = rng.integers(0, 6, (K, 3)).astype(np.uint8)
+        out[f"tiny{i}"] = (rng.integers(0, 6, (4, w, 3)).astype(np.uint8), pal, None, 0, p, None)
+    # class penalties: 2 classes with the values 2, 3 and 255 outside them, and 16 classes
+    pal = RM._palette(rng, 90)
+    img = RN._image(rng, pal, 11, COLS + 29, spread=20)
+    cls = rng.integers(0, 4, img.shape[:2]).astype(np.uint8)
+    cls[rng.random(img.shape[:2]) < 0.05] = 255
+    out["classes2"] = (img, pal, cls, 2, [0, 2500, 400], None)
+    out["classes2_blocks"] = (img, pal, np.repeat(rng.integers(0, 4, (img.shape[0], -(-img.shape[1] // 16))), 16, axis=1)[:, :img.shape[1]].astype(np.uint8),
+                              2, [MAX_PENALTY, 0, 77], None)
+    out["classes16"] = (img, pal, rng.integers(0, 18, img.shape[:2]).astype(np.uint8), 16, [53 * k for k in range(17)], None)
+    # penalty 0 and the largest penalty (W * 195075 < 2^24 - 1 holds up to W = 86: every image row is constant)
+    pal = RM._palette(rng, 60, levels=6)
+    img = RN._image(rng, pal, 7, 86, spread=30)
+    out["penalty0"] = (img, pal, None, 0, 0, None)
+    out["penalty_max"] = (img, pal, None, 0, MAX_PENALTY, "constant")
+    # a long row: white pixels (a few dark ones) against a near-black palette; the unrenormalised cost passes 2^32
+    img = np.full((2, 23000, 3), 255, np.uint8)
+    img[rng.random(img.shape[:2]) < 0.01] = (2, 1, 0)
+    out["long_row"] = (img, np.array([[0, 0, 0], [3, 2, 1]], np.uint8), None, 0, 50000, None)
+    # many workgroups
+    pal = RM._palette(rng, 100)
+    out["many_rows"] = (RN._image(rng, pal, 600, 200, spread=25), pal, None, 0, 400, None)
+    return out
+
+
+_CASES = None
+
+
+def names():
+    global _CASES
+    if _CASES is None:
+        _CASES = _build()
+        for rgb, pal, cls, _, _, _ in _CASES.values():
+            for a in (rgb, pal, cls):
+                if a is not None:
+                    a.setflags(write=False)
+    return list(_CASES)
+
+
+def case(name):
+    names()
+    return _CASES[name]
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """-> (out int64[H, W], sums int64[n_classes + 1, 4], b int64[H, W]); the properties the rule implies are asserted here once"""
+    rgb, pal, cls, nc, penalty, expect = case(name)
+    H, W = rgb.shape[:2]
+    out, sums, b = segment_reference(rgb, pal, penalty, cls, nc)
+    pen, _ = penalty_map((H, W), penalty, cls, nc)
+    p64, px = pal.astype(np.int64), rgb.astype(np.int64)
+    if expect == "constant":
+        total = ((px[:, :, None, :] - p64[None, None]) ** 2).sum(axis=3).sum(axis=1)          # [H, K]
+        assert (W * MAX_D < pen[:, 1:]).all() and (out == total.argmin(axis=1)[:, None]).all(), name
+    elif expect is not None:
+        assert out.tolist() == expect, name
+    # every pixel is within the penalties of its two boundaries of its nearest row
+    d_out, d_b = ((px - p64[out]) ** 2).sum(axis=2), ((px - p64[b]) ** 2).sum(axis=2)
+    bound = d_b.copy()
+    bound[:, 1:] += pen[:, 1:]
+    bound[:, :-1] += pen[:, 1:]
+    assert (d_out <= bound).all(), name
+    # the objective is no larger than the nearest-row map's and the greedy run-carrying map's at slack = penalty (any labelling bounds it)
+    obj = objective(rgb, pal, out, pen)
+    assert (obj <= objective(rgb, pal, b, pen)).all(), name
+    greedy = RN.runs_reference(rgb, pal, [min(v, RN.MAX_SLACK) for v in penalty_table(penalty, nc)], cls, nc, b=b)[0]
+    assert (obj <= objective(rgb, pal, greedy, pen)).all(), name
+    if len(pal) <= 3 and W <= 6:
+        assert np.array_equal(obj, brute_force(rgb, pal, pen)), name
+    if max(penalty_table(penalty, nc)) == 0:
+        assert sums[-1, 1] == int(d_b.sum()), name                                             # penalty 0 keeps the remap's squared error
+    if name == "long_row":
+        assert int(obj.max()) > 1 << 32
+    for a in (out, sums, b):
+        a.setflags(write=False)
+    return out, sums, b
+
+
+def check_monotone(segment, name="duplicates", penalties=(0, 1, 5, 40, 300, 5000, 200000, MAX_PENALTY)):
+    """with one penalty for the whole picture a larger penalty never gives more breaks nor a smaller squared error, per image row;
+    `segment(rgb, pal, penalty)` -> out"""
+    rgb, pal = case(name)[:2]
+    p64, px = pal.astype(np.int64), rgb.astype(np.int64)
+    last = None
+    for p in penalties:
+        out = np.asarray(segment(rgb, pal, p), np.int64)
+        brk = (out[:, 1:] != out[:, :-1]).sum(axis=1)
+        sse = ((px - p64[out]) ** 2).sum(axis=2).sum(axis=1)
+        if last is not None:
+            assert (brk <= last[0]).all() and (sse >= last[1]).all(), p
+        last = (brk, sse)
+    assert (last[0] == 0).all()                                                                # (the largest penalty: constant rows)
+
+
+def index_bytes(K):
+    return RM.index_bytes(K)
+
+
+# the argument errors of rhccq_palette_segment: (what, overrides of a valid call, return code).  A valid call: 2 x 2 pixels, K = 3, no
+# class map, n_classes = 0, penalty [5], 2-byte indices; "cls": True asks for a valid class map; "penalty": a table or None (NULL).
+ERRORS = [
+    ("null rgb", {"rgb": None}, E_ARG),
+    ("null palette", {"palette": None}, E_ARG),
+    ("null idx_out", {"idx_out": None}, E_ARG),
+    ("null sums", {"sums": None}, E_ARG),
+    ("null penalty", {"penalty": None}, E_ARG),
+    ("K = 0", {"K": 0}, E_ARG),
+    ("K < 0", {"K": -5}, E_ARG),
+    ("H < 0", {"H": -1}, E_ARG),
+    ("W < 0", {"W": -1}, E_ARG),
+    ("n_classes < 0", {"cls": True, "n_classes": -1}, E_ARG),
+    ("n_classes = 17", {"cls": True, "n_classes": 17, "penalty": [0] * 18}, E_ARG),
+    ("n_classes without a class map", {"n_classes": 1, "penalty": [0, 0]}, E_ARG),
+    ("idx_elem_bytes = 0", {"idx_elem_bytes": 0}, E_ARG),
+    ("idx_elem_bytes = 3", {"idx_elem_bytes": 3}, E_ARG),
+    ("idx_elem_bytes = 8", {"idx_elem_bytes": 8}, E_ARG),
+    ("K = 257 with 1-byte indices", {"K": 257, "idx_elem_bytes": 1}, E_ARG),
+    ("penalty 2^24", {"penalty": [MAX_PENALTY + 1]}, E_ARG),
+    ("a class penalty 2^24", {"cls": True, "n_classes": 2, "penalty": [0, MAX_PENALTY + 1, 0]}, E_ARG),
+    ("the last penalty 2^31", {"cls": True, "n_classes": 2, "penalty": [0, 0, 1 << 31]}, E_ARG),
+    ("K = 65537", {"K": 65537}, E_LIMIT),
+]
+# the device form's own: the workspace ("work": None = NULL, "odd" = off its alignment, "short" = one byte too few) and its row cap
+DEVICE_ERRORS = [
+    ("null workspace", {"work": None}, E_ARG),
+    ("misaligned workspace", {"work": "odd"}, E_ARG),
+    ("short workspace", {"work": "short"}, E_ARG),
+    ("K = cap + 1", {"K": CAP + 1}, E_LIMIT),
+]
+
+
+# ---- the value claim: kodak_22 and the palette of its shipped container ----------------------------------------------------------------
+KODAK_PENALTY = 128
+KODAK_MAX_BYTES_RATIO = 0.93          # the segmentation's zlib-9 index bytes against the greedy map's at slack 128
+
+
+@functools.lru_cache(maxsize=None)
+def kodak():
+    """-> (image uint8[512, 768, 3], palette uint8[139, 3], b, out at KODAK_PENALTY, sums of out, the greedy map at slack KODAK_PENALTY,
+    its sums)"""
+    img, pal, b, greedy, greedy_sums = RN.kodak()
+    assert RN.KODAK_SLACK == KODAK_PENALTY
+    out, sums, _ = segment_reference(img, pal, KODAK_PENALTY, b=b)
+    for a in (out, sums):
+        a.setflags(write=False)
+    return img, pal, b, out, sums, greedy, greedy_sums
+
+
+def index_bytes_zlib9(idx):
+    return len(zlib.compress(np.asarray(idx).astype(np.uint8).tobytes(), 9))
