@@ -919,6 +919,58 @@ int rhccq_palette_segment(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t
 int rhccq_palette_segment_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
                                const uint32_t* penalty, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
 
+/* ---- EXTENSION: a palette from the image, exact variance splits over a colour histogram (no reference counterpart; csrc/palette_build.hip) ----
+ * Greedy variance-minimising box splitting over a 32 x 32 x 32 histogram (Wu's quantiser) with exact rational comparisons: the top-down
+ * counterpart of rhccq_palette_reduce (the gain of a split is Ward's cost of merging the two halves back).
+ *
+ * rhccq_palette_cells: one pass over the pixels.  The cell of a pixel is (r >> 3, g >> 3, b >> 3).  cells is uint64[4][32][32][32] =
+ * planes {N, Sr, Sg, Sb}, indexed [r >> 3][g >> 3][b >> 3]: N adds the pixel's weight, S the weight x the full 8-bit channel value, so a
+ * box's mean is the exact mean of its pixels, not of cell centres.  Weights follow rhccq_palette_refine's rule: weights[cls[p]] when
+ * cls[p] < n_classes and weights[n_classes] otherwise (and for every pixel when cls == NULL); 0..255 with at least one > 0, NULL = all
+ * ones.  accumulate == 0: the call zeroes cells first; accumulate != 0: it adds to what is there, so the tables of several frames sum
+ * into one (a shared palette for a set of images).  Integer addition only: every order gives the same table.
+ * RHCCQ_E_ARG: a null rgb or cells; n_pixels < 0; n_classes outside 0..16 (or not 0 with cls == NULL); a weight outside 0..255 or all
+ * weights 0; cells not aligned to 8.  RHCCQ_E_LIMIT: n_pixels x the largest weight above 2^32 - 1.  n_pixels == 0 succeeds.
+ * Device form: every pointer but weights_host is device memory; rgb and cls of any alignment; async on the context stream (a memset
+ * unless accumulating, one launch), nothing allocated.  A workgroup takes rhccq_palette_cells_chunk() pixels at a time, a lane 8 of them
+ * rhccq_palette_cells_block() apart; a wave sums the pixels of equal cells, a workgroup collects them in a table of 1 024 cells in LDS, and
+ * what is left goes to global memory with 64-bit atomics.
+ *
+ * rhccq_palette_build: the split chain.  A box is a half-open range of cells [lo, hi) per axis (order r, g, b); box 0 is the whole cube;
+ * a box's N and S are the sums of its cells.  A cut of a box is (axis a, position t with lo_a < t < hi_a): the lower half [lo_a, t), the
+ * upper half [t, hi_a); it is valid iff both halves have N > 0.  With (N, S) the box and (N1, S1) the lower half its gain is the exact
+ * rational |N S1 - N1 S|^2 / (N N1 (N - N1)) (the squared norm over the three channels): the squared error the split removes.  A gain of
+ * 0 is a valid cut.  The best cut of a box is the valid cut of largest gain, ties to the lowest axis, then the lowest t.  One step: among
+ * the boxes that have a valid cut the one whose best cut has the largest gain is split, ties to the lowest box index; the box keeps its
+ * index and becomes the lower half, the upper half gets the next free index.  The chain ends at K_target boxes or when no box has a
+ * valid cut.  Gains are compared exactly by cross-multiplication: with the sum of N at most 2^32 - 1 and S <= 255 N per cell (the
+ * caller's duty for a table not made by rhccq_palette_cells) a numerator is below 2^146, a denominator below 2^96, a cross product below
+ * 2^242 (128 bits are not enough: a 512 x 768 picture needs 138).
+ * *k_out = the number of boxes; palette_out uint8[K_target][3]: row i = floor((2 S + N) / (2 N)) per channel of box i (the refinement's
+ * rounding), rows in creation order; counts_out uint64[K_target]: N of each box; boxes_out uint8[K_target][6] (may be NULL): lo then hi;
+ * splits int32[K_target - 1][3] (may be NULL): (box, axis, t) per step, -1 behind the last step; rows from k_out on are zero.
+ * Colours that share a cell are never separated (two colours in one cell give one row), and two boxes may round to the same row.
+ * RHCCQ_E_ARG: a null cells, palette_out, counts_out, k_out (or work); K_target < 1; N all zero; misaligned cells, counts_out, work (8),
+ * splits or k_out (4); work_bytes below rhccq_palette_build_bytes().  RHCCQ_E_LIMIT: K_target > 32768; the sum of N above 2^32 - 1; in
+ * the device form K_target > rhccq_palette_build_max_rows().
+ * Device form: every pointer is device memory; async on the context stream (three launches that form the 33^3 summed-volume tables of
+ * the four planes in the workspace, then ONE resident workgroup that runs the chain with boxes and cached best cuts in LDS), no host
+ * synchronisation, nothing allocated.  The two errors that only the table shows (N all zero; sum above 2^32 - 1) cannot be returned
+ * without reading it: the call returns 0 and the kernel writes RHCCQ_E_ARG / RHCCQ_E_LIMIT to *k_out, zero palette_out, counts_out and
+ * boxes_out, and -1 throughout splits.  Host form: the same functions (csrc/palette_build.h) run serially, for K_target <= 32768. */
+int32_t rhccq_palette_cells_block(void);                /* host only: pixels between two pixels of one lane (the lanes of a workgroup) */
+int32_t rhccq_palette_cells_chunk(void);                /* host only: pixels a workgroup takes at a time */
+int rhccq_palette_cells(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, const uint8_t* cls, int32_t n_classes, const int32_t* weights_host,
+                        int32_t accumulate, uint64_t* cells);
+int rhccq_palette_cells_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t* cls, int32_t n_classes, const int32_t* weights,
+                             int32_t accumulate, uint64_t* cells);
+int32_t rhccq_palette_build_max_rows(void);             /* host only: the largest K_target of the device form (the boxes one workgroup's LDS holds) */
+int64_t rhccq_palette_build_bytes(void);                /* host only: workspace bytes */
+int rhccq_palette_build(rhccq_ctx* ctx, const uint64_t* cells, int32_t K_target, void* work, int64_t work_bytes, uint8_t* palette_out,
+                        uint64_t* counts_out, uint8_t* boxes_out /* may be NULL */, int32_t* splits /* may be NULL */, int32_t* k_out);
+int rhccq_palette_build_host(const uint64_t* cells, int32_t K_target, uint8_t* palette_out, uint64_t* counts_out, uint8_t* boxes_out,
+                             int32_t* splits, int32_t* k_out);
+
 #ifdef __cplusplus
 }
 #endif

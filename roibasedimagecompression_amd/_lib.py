@@ -208,6 +208,14 @@ PROTOTYPES = {
     "rhccq_palette_segment": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                                         c_void_p]),
     "rhccq_palette_segment_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_cells_block": (c_int32, []),
+    "rhccq_palette_cells_chunk": (c_int32, []),
+    "rhccq_palette_cells": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_cells_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_build_max_rows": (c_int32, []),
+    "rhccq_palette_build_bytes": (c_int64, []),
+    "rhccq_palette_build": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_build_host": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

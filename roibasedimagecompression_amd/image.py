@@ -940,8 +940,81 @@ class ImageEncoder:
         res["stats"] = stats
         return res
 
+    def _frame_tensor(self, fn, image):
+        rh = self.rh
+        rgb = image.to(rh.device).contiguous() if torch.is_tensor(image) else rh.dev(np.asarray(image))
+        if rgb.dtype != torch.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"ImageEncoder.{fn}: a uint8 H x W x 3 image is expected")
+        return rgb
+
+    def _cells(self, fn, rgb, roi_mask, roi_weight, into=None):
+        """the frame's histogram table (Rhccq.palette_cells); with a mask a pixel inside it weighs roi_weight and one outside 1"""
+        rh = self.rh
+        if roi_mask is None:
+            return rh.palette_cells(rgb, into=into)
+        from .api.roi import region_map_from_mask
+        return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
+
+    def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
+                 target_psnr=None, run_slack=None, run_penalty=None):
+        """image: uint8[H,W,3] (numpy or device tensor), colours = N -> the result dict of encode_with_palette for a palette of at most N
+        rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
+        variance-minimising box splitting over it in exact integers (Rhccq.palette_build: the box whose best cut removes the most
+        squared error is split until N boxes exist; a row is the mean of its box's pixels), then exactly what
+        encode_with_palette(image, that palette, ...) does: out_path, exact, roi_mask, report, refine, target_bytes, target_psnr,
+        run_slack and run_penalty keep their meaning and validation.  No region, SLIC or clustering stage runs, and no palette is
+        needed to start from.  With roi_mask a pixel inside the mask weighs roi_weight (1..255) in the histogram, so roi_weight other
+        than 1 needs only the mask here (and weighs in the refinement too when refine > 0).  N may be at most
+        ops.palette_build_max_rows() (RhccqError).  Colours that share a cell of the histogram (equal in their upper five bits per
+        channel) are never separated, so fewer than N rows come back when fewer cells are occupied, and two boxes may round to the
+        same row.  stats["build"] = {asked: N, rows: rows built, cells: occupied cells, steps: splits}; everything else as
+        encode_with_palette fills it."""
+        rh = self.rh
+        colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
+        searching = target_bytes is not None or target_psnr is not None
+        if colours < 1:
+            raise ValueError("ImageEncoder.quantize: colours >= 1 is required")
+        if refine < 0 or refine > 64:
+            raise ValueError("ImageEncoder.quantize: refine must be 0..64")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and roi_mask is None):
+            raise ValueError("ImageEncoder.quantize: roi_weight (1..255) other than 1 needs roi_mask")
+        if searching:
+            self._target_args("ImageEncoder.quantize", target_bytes, target_psnr, roi_mask is not None)
+        self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr)
+        rgb = self._frame_tensor("quantize", image)
+        t0 = time.perf_counter()
+        cells = self._cells("quantize", rgb, roi_mask, roi_weight)
+        pal, _, splits, _ = rh.palette_build(cells, colours)
+        build = {"asked": colours, "rows": int(pal.shape[0]), "cells": int((cells[0] != 0).sum()), "steps": int(splits.shape[0])}
+        seconds = time.perf_counter() - t0
+        res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
+                                       roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
+                                       run_slack=run_slack, run_penalty=run_penalty)
+        res["stats"]["build"] = build
+        res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
+        return res
+
+    def shared_palette(self, images, colours, roi_masks=None, roi_weight=1):
+        """images: uint8[H,W,3] each (any sizes), colours = N -> one palette (device uint8[k, 3], k <= N) for all of them: the images'
+        histogram tables are summed into one (Rhccq.palette_cells(into=)) and the split chain runs once (Rhccq.palette_build), so the
+        result is the palette quantize would build for the pictures laid side by side.  roi_masks: one mask (or None) per image;
+        a pixel inside its mask weighs roi_weight (1..255).  The weights of all images together may add up to at most 2^32 - 1."""
+        colours, roi_weight = int(colours), int(roi_weight)
+        images = list(images)
+        masks = [None] * len(images) if roi_masks is None else list(roi_masks)
+        if not images or len(masks) != len(images):
+            raise ValueError("ImageEncoder.shared_palette: at least one image, and one mask (or None) per image, are expected")
+        if colours < 1:
+            raise ValueError("ImageEncoder.shared_palette: colours >= 1 is required")
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and all(m is None for m in masks)):
+            raise ValueError("ImageEncoder.shared_palette: roi_weight (1..255) other than 1 needs roi_masks")
+        cells = None
+        for image, mask in zip(images, masks):
+            cells = self._cells("shared_palette", self._frame_tensor("shared_palette", image), mask, roi_weight, into=cells)
+        return self.rh.palette_build(cells, colours)[0]
+
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
-                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
+                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -960,9 +1033,18 @@ class ImageEncoder:
         frames' encode too (exclusive with each other and with max_colours; see encode for how the search differs from max_colours).
         run_slack: one number (default None = off), passed to the key frames' encode and to every remap (plain and refined), whose
         PSNRs the key-frame rule then compares; a roi / nonroi dict raises ValueError, because a remapped frame has no region map.
-        run_penalty: one number (default None = off), by the same rules (exclusive with run_slack and with target_psnr)."""
+        run_penalty: one number (default None = off), by the same rules (exclusive with run_slack and with target_psnr).
+        key_colours = N (default None = off: key frames are encoded in full, as above): a key frame is made by
+        quantize(image, colours=N) instead of encode, in about the time of a few remaps; roi_quality and nonroi_quality are not used
+        then, max_colours is exclusive with it (ValueError), and target_bytes, target_psnr, run_slack and run_penalty go to quantize."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
+        if key_colours is not None:
+            key_colours = int(key_colours)
+            if max_colours is not None:
+                raise ValueError("ImageEncoder.encode_sequence: key_colours and max_colours are exclusive")
+            if key_colours < 1:
+                raise ValueError("ImageEncoder.encode_sequence: key_colours >= 1 is required")
         if target_bytes is not None or target_psnr is not None:
             if max_colours is not None:
                 raise ValueError("ImageEncoder.encode_sequence: target_bytes / target_psnr and max_colours are exclusive")
@@ -999,8 +1081,12 @@ class ImageEncoder:
                         key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
                     yield res
                     continue
-            res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
-                              target_psnr=target_psnr, run_slack=run_slack, run_penalty=run_penalty)
+            if key_colours is not None:
+                res = self.quantize(image, colours=key_colours, out_path=path, exact=exact, target_bytes=target_bytes, target_psnr=target_psnr,
+                                    run_slack=run_slack, run_penalty=run_penalty)
+            else:
+                res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
+                                  target_psnr=target_psnr, run_slack=run_slack, run_penalty=run_penalty)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

@@ -147,6 +147,20 @@ def palette_segment_tile():
     return int(_lib.load().rhccq_palette_segment_tile_cols())
 
 
+def palette_build_max_rows():
+    """the most colours Rhccq.palette_build returns on the device: the boxes whose state one workgroup's LDS holds"""
+    return int(_lib.load().rhccq_palette_build_max_rows())
+
+
+def palette_cells_granules():
+    """(pixels between two pixels of one lane of Rhccq.palette_cells' kernel, pixels a workgroup takes at a time)"""
+    lib = _lib.load()
+    return int(lib.rhccq_palette_cells_block()), int(lib.rhccq_palette_cells_chunk())
+
+
+PALETTE_CELLS_SHAPE = (4, 32, 32, 32)  # Rhccq.palette_cells' table: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3)
+
+
 def psnr_from_sse(sse, n_pixels):
     """calculate_quality_metrics' PSNR (comparison.py:33-37) from a sum of squared errors over n_pixels RGB pixels:
     10 log10(255^2 / (sse / (3 n_pixels))), inf at sse == 0"""
@@ -1250,6 +1264,85 @@ class Rhccq:
             raise RhccqError(f"palette_reduce failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
         n_steps = live - k
         return pal_out[:k], cnt_out[:k], map_, merges[:max(n_steps, 0)]
+
+    # -- a palette from the image: exact variance splits over a colour histogram (EXTENSION: csrc/palette_build.hip) ---------------
+    def palette_cells(self, rgb, cls=None, n_classes=0, weights=None, into=None):
+        """rgb uint8[..., 3] (numpy or device), cls uint8 / bool, one element per pixel, or None; weights: n_classes + 1 ints 0..255
+        (a pixel of class c < n_classes weighs weights[c], every other pixel weights[-1]; None = all ones) -> the device table
+        int64[4, 32, 32, 32]: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3), N the summed weights, S the summed
+        weight x channel value.  into: a table an earlier call returned; this call adds to it and returns it, so the tables of
+        several frames sum into one.  One pass over the pixels, no read back."""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"palette_cells: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb = on_device(rgb, "rgb")
+        if rgb.ndim < 1 or rgb.shape[-1] != 3:
+            raise ValueError("palette_cells: rgb [..., 3] is expected")
+        n, n_classes = rgb.numel() // 3, int(n_classes)
+        w = None if weights is None else [int(v) for v in weights]
+        if w is not None and len(w) != n_classes + 1:
+            raise ValueError("palette_cells: weights must have n_classes + 1 entries")
+        d_cls = None
+        if cls is not None:
+            d_cls = on_device(cls, "cls")
+            if d_cls.numel() != n:
+                raise ValueError("palette_cells: the class map must have one element per pixel")
+        elif n_classes:
+            raise ValueError("palette_cells: n_classes without a class map")
+        if not 0 <= n_classes <= 16 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+            raise RhccqError("palette_cells: n_classes must be 0..16 and weights 0..255 with one > 0")
+        if into is not None:
+            if not torch.is_tensor(into) or into.dtype != torch.int64 or tuple(into.shape) != PALETTE_CELLS_SHAPE or not into.is_contiguous() \
+                    or into.device != torch.device(self.device):
+                raise ValueError("palette_cells: into must be a table palette_cells returned (contiguous device int64[4, 32, 32, 32])")
+        cells = into if into is not None else self.empty(PALETTE_CELLS_SHAPE, torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return cells if into is not None else cells.zero_()
+        warr = None if w is None else (C.c_int32 * len(w))(*w)
+        self._check(self.lib.rhccq_palette_cells(self.ctx, self._p(rgb), n, self._p(d_cls), n_classes,
+                                                 C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), 1 if into is not None else 0,
+                                                 self._p(cells)), "palette_cells")
+        return cells
+
+    def palette_build(self, cells, colours):
+        """cells: the table of palette_cells (int64[4, 32, 32, 32], numpy or device; the sum of N at most 2^32 - 1), colours = K_target
+        in 1..palette_build_max_rows() -> (palette device uint8[k, 3], counts device int64[k], splits device int32[k - 1, 3]: the
+        (box, axis, t) of every split in order, boxes device uint8[k, 6]: lo then hi per box).  Greedy variance-minimising box
+        splitting in exact integers (include/rhccq.h): the box whose best cut removes the most squared error is split, ties to the
+        lowest box, axis and position; a row is the mean of its box's pixels rounded to nearest.  k <= colours is read back once."""
+        if not torch.is_tensor(cells):
+            a = np.ascontiguousarray(cells)
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"palette_build: cells must be integers, got {a.dtype}")
+            cells = torch.from_numpy(a.astype(np.uint64).view(np.int64))
+        if cells.dtype != torch.int64:
+            raise TypeError(f"palette_build: cells must be int64, got {cells.dtype}")
+        if tuple(cells.shape) != PALETTE_CELLS_SHAPE:
+            raise ValueError("palette_build: cells [4, 32, 32, 32] is expected")
+        cells = cells.to(self.device).contiguous()
+        target, cap = int(colours), palette_build_max_rows()
+        if target > cap:
+            raise RhccqError(f"palette_build: {target} colours, the device form returns at most {cap} (palette_build_max_rows())")
+        if target < 1:
+            raise RhccqError("palette_build: colours >= 1 is required")
+        wbytes = int(self._raw.rhccq_palette_build_bytes())
+        work = self.empty((wbytes // 8,), torch.int64)
+        pal_out = self.empty((target, 3), torch.uint8)
+        cnt_out = self.empty((target,), torch.int64)
+        boxes = self.empty((target, 6), torch.uint8)
+        splits = self.empty((max(target - 1, 1), 3), torch.int32)
+        k_out = self.empty((1,), torch.int32)
+        self._check(self.lib.rhccq_palette_build(self.ctx, self._p(cells), target, self._p(work), wbytes, self._p(pal_out), self._p(cnt_out),
+                                                 self._p(boxes), self._p(splits), self._p(k_out)), "palette_build")
+        k = int(k_out.item())                                # the one read
+        if k < 0:                                            # the errors only the table shows come back through k_out
+            raise RhccqError(f"palette_build failed ({k}): " + ("the table is empty" if k == -1 else "the table's N adds up to more than 2^32 - 1"))
+        return pal_out[:k], cnt_out[:k], splits[:k - 1], boxes[:k]
 
     # -- the palette ladder: moments, the error curve of every rung, any rung from the log (EXTENSION: csrc/palette_ladder.hip) ----
     def _ladder_arg(self, a, dtype, what, fn):
