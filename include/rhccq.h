@@ -971,6 +971,74 @@ int rhccq_palette_build(rhccq_ctx* ctx, const uint64_t* cells, int32_t K_target,
 int rhccq_palette_build_host(const uint64_t* cells, int32_t K_target, uint8_t* palette_out, uint64_t* counts_out, uint8_t* boxes_out,
                              int32_t* splits, int32_t* k_out);
 
+/* ---- EXTENSION: the palette build path for a batch of images (no reference counterpart; csrc/palette_batch.hip) ----
+ * rhccq_palette_cells, rhccq_palette_build, rhccq_palette_remap and rhccq_palette_refine over B images in one call each.  Every image's
+ * result is bit for bit what the single-image call gives for that image alone; nothing of one image enters another's.  The split chain of
+ * one image is one workgroup for milliseconds and the rest of the card idles: B chains run on B workgroups side by side, and no call here
+ * needs a host synchronisation before the next, so cells, build, refine and remap of a batch queue behind one another.
+ *
+ * Layout common to the four.  The B images lie back to back in one buffer: rgb is interleaved uint8 of any alignment, image b the pixels
+ * [px_off[b], px_off[b + 1]) of it.  px_off is int64[B + 1] with px_off[0] == 0, never decreasing; an image of 0 pixels is legal.  The
+ * device forms take it twice: px_off_host (host memory: checked, and it sizes the grid) and px_off_dev (the same values in device memory:
+ * what the kernels read).  KEEPING THE TWO EQUAL IS THE CALLER'S DUTY: the call cannot compare them without a synchronisation, and
+ * offsets in px_off_dev that reach outside the buffers make the kernels read and write out of bounds.  cls (may be NULL) is one uint8
+ * per pixel over the same concatenation; classes and weights follow the single calls' rules, one n_classes and one weight table for the
+ * batch.  Outputs per image are planes strided by image, as stated per entry.
+ * RHCCQ_E_ARG, beside the single calls' rules: B < 1; a null px_off_host, px_off_dev or k_rows; px_off_host[0] != 0 or a decreasing
+ * px_off_host; K_stride < 1; misaligned outputs, k_rows (4) or workspace (8); a short workspace.  RHCCQ_E_LIMIT: B > 65535 (slice the
+ * batch), and the single calls' limits.
+ * Device forms: every pointer but px_off_host and weights_host is device memory; async on the context stream, no host synchronisation,
+ * nothing allocated, nothing copied.  In every kernel a grid row (the chain: a workgroup) is one image, so a workgroup never holds pixels
+ * of two images and chunking restarts at every image boundary.  No workgroup waits for another (no flags, no spinning, no cooperative
+ * launch, no grid sized to what is resident): stream order between launches is the only synchronisation, and a batch larger than the
+ * card queues.  Host forms (px_off and k_rows in host memory, one px_off): a loop over the single-image host functions behind the same
+ * argument checks.
+ *
+ * rhccq_palette_cells_batch: cells is uint64[B][4][32][32][32]; the call zeroes it (there is no accumulate mode).  A memset and one
+ * launch.  RHCCQ_E_LIMIT (pixels x the largest weight above 2^32 - 1) applies per image.
+ *
+ * rhccq_palette_build_batch: one K_target for the batch, at most rhccq_palette_build_max_rows() in the device form.  palette_out uint8[B]
+ * [K_target][3], counts_out uint64[B][K_target], k_out int32[B], boxes_out uint8[B][K_target][6] (may be NULL), splits int32[B]
+ * [K_target - 1][3] (may be NULL).  The workspace is rhccq_palette_build_batch_bytes(B) = B x rhccq_palette_build_bytes().  Three prefix
+ * launches over all tables, then ONE launch of B workgroups, workgroup b the chain of table b.  A table whose N is all zero, or adds up
+ * to more than 2^32 - 1, gets RHCCQ_E_ARG / RHCCQ_E_LIMIT in its own k_out[b], zero rows and -1 throughout its splits; the call returns
+ * 0 and its neighbours are untouched.  The host form does the same (it does not return the table's error).
+ *
+ * rhccq_palette_remap_batch: palettes is uint8[B][K_stride][3], k_rows int32[B] the rows in use per image (device memory in the device
+ * form: rhccq_palette_build_batch's k_out goes in as it is).  Rows from k_rows[b] on are never read; a k_rows[b] above K_stride counts as
+ * K_stride.  An image with k_rows[b] < 1 (a build's error code included) gets index 0 throughout and zero sums.  idx_out is concatenated
+ * like rgb, idx_elem_bytes (1, 2 or 4) per element for the whole batch; 1 byte needs K_stride <= 256.  sums is uint64[B][n_classes + 1]
+ * [2], rows as rhccq_palette_remap's, zeroed by the call.  A memset and one launch.
+ *
+ * rhccq_palette_refine_batch: rhccq_palette_refine per image, in place in palettes (uint8[B][K_stride][3], rows from k_rows[b] on
+ * untouched), two launches per iteration for the whole batch.  history is uint64[B][max_iter][2], n_iter int32[B].  Image b runs
+ * iteration i > 0 iff its own history[b][i - 1][1] != 0: images stop independently.  As in the single call THE HISTORY IS CONTROL STATE
+ * while the call's launches are in flight: the kernels read it to decide whether to run, so it must not be written or reused before they
+ * have finished.  An image of 0 pixels or with k_rows[b] < 1 runs no iteration (n_iter[b] = 0, zero history).  The workspace is
+ * rhccq_palette_refine_batch_bytes(B, K_stride) = B x rhccq_palette_refine_bytes(K_stride).  The accumulators live in LDS when K_stride
+ * <= rhccq_palette_refine_lds_rows() (RHCCQ_OPT_REFINE_LDS_ROWS applies), else in the workspace FOR THE WHOLE BATCH: the choice goes by the
+ * stride, not by each image's rows.  Both give the same sums. */
+int64_t rhccq_palette_build_batch_bytes(int32_t B);                      /* host only: workspace bytes (0 for B < 1) */
+int64_t rhccq_palette_refine_batch_bytes(int32_t B, int32_t K_stride);   /* host only: workspace bytes (0 for B < 1 or K_stride < 1) */
+int rhccq_palette_cells_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t* px_off_host, const int64_t* px_off_dev, int32_t B, const uint8_t* cls,
+                              int32_t n_classes, const int32_t* weights_host, uint64_t* cells);
+int rhccq_palette_cells_batch_host(const uint8_t* rgb, const int64_t* px_off, int32_t B, const uint8_t* cls, int32_t n_classes, const int32_t* weights,
+                                   uint64_t* cells);
+int rhccq_palette_build_batch(rhccq_ctx* ctx, const uint64_t* cells, int32_t B, int32_t K_target, void* work, int64_t work_bytes, uint8_t* palette_out,
+                              uint64_t* counts_out, uint8_t* boxes_out /* may be NULL */, int32_t* splits /* may be NULL */, int32_t* k_out);
+int rhccq_palette_build_batch_host(const uint64_t* cells, int32_t B, int32_t K_target, uint8_t* palette_out, uint64_t* counts_out, uint8_t* boxes_out,
+                                   int32_t* splits, int32_t* k_out);
+int rhccq_palette_remap_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t* px_off_host, const int64_t* px_off_dev, int32_t B,
+                              const uint8_t* palettes, int32_t K_stride, const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, void* idx_out,
+                              int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_remap_batch_host(const uint8_t* rgb, const int64_t* px_off, int32_t B, const uint8_t* palettes, int32_t K_stride, const int32_t* k_rows,
+                                   const uint8_t* cls, int32_t n_classes, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_refine_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t* px_off_host, const int64_t* px_off_dev, int32_t B, uint8_t* palettes,
+                               int32_t K_stride, const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, const int32_t* weights_host,
+                               int32_t max_iter, void* work, int64_t work_bytes, uint64_t* history, int32_t* n_iter);
+int rhccq_palette_refine_batch_host(const uint8_t* rgb, const int64_t* px_off, int32_t B, uint8_t* palettes, int32_t K_stride, const int32_t* k_rows,
+                                    const uint8_t* cls, int32_t n_classes, const int32_t* weights, int32_t max_iter, uint64_t* history, int32_t* n_iter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,19 @@ PROTOTYPES = {
     "rhccq_palette_build_bytes": (c_int64, []),
     "rhccq_palette_build": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rhccq_palette_build_host": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_build_batch_bytes": (c_int64, [c_int32]),
+    "rhccq_palette_refine_batch_bytes": (c_int64, [c_int32, c_int32]),
+    "rhccq_palette_cells_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "rhccq_palette_cells_batch_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "rhccq_palette_build_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_build_batch_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_palette_remap_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                            c_int32, c_void_p]),
+    "rhccq_palette_remap_batch_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_refine_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                             c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_palette_refine_batch_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                                  c_void_p]),
 }
 
 

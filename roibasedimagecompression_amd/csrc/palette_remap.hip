@@ -19,117 +19,13 @@
 
 namespace rhccq {
 
-// A workgroup takes chunks of 256 x 8 pixels (lane l: pixels base + l + 256 q, so index stores coalesce) grid-stride, and walks the
-// palette tile by tile through LDS for each.  A palette of one tile is staged once.  The last tile is padded to an even length
-// with a copy of its last entry under the next local index: equal key, higher index, never the minimum.
+// The kernel's body (remap_body) and the argument check are in palette_remap.h: the batched form (palette_batch.hip) runs them per image.
 template <typename IdxT>
 __global__ __launch_bounds__(kRemapBlock) void palette_remap_kernel(const uint8_t* __restrict__ rgb, long long n_px,
                                                                     const uint8_t* __restrict__ pal, int K,
                                                                     const uint8_t* __restrict__ cls, int n_classes,
                                                                     IdxT* __restrict__ idx_out, unsigned long long* __restrict__ sums) {
-  __shared__ uint4 s_pal[kRemapTile / 2];                                             // two entries per 16-byte read
-  __shared__ unsigned long long s_sum[kRemapBlock / 64][kRemapMaxClasses + 1][2];     // per wave: rows {pixels, SSE}
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < (kRemapBlock / 64) * (kRemapMaxClasses + 1) * 2; i += kRemapBlock) (&s_sum[0][0][0])[i] = 0ull;
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  constexpr long long kChunk = (long long)kRemapBlock * kRemapPx;
-  const long long n_chunks = (n_px + kChunk - 1) / kChunk;
-  unsigned long long all_sse = 0ull;
-  bool staged = false;
-
-  for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {          // (block uniform: the barriers below are safe)
-    const long long base = chunk * kChunk + threadIdx.x;
-    uint32_t px[kRemapPx], bkey[kRemapPx], bidx[kRemapPx];
-#pragma unroll
-    for (int q = 0; q < kRemapPx; ++q) {
-      const long long p = base + (long long)q * kRemapBlock;
-      px[q] = p < n_px ? remap_pack_px(rgb + p * 3) : 0u;
-      bkey[q] = 0xFFFFFFFFu;
-      bidx[q] = 0u;
-    }
-    for (int t = 0; t < n_tiles; ++t) {
-      const int tile_base = t * kRemapTile, len = min(kRemapTile, K - tile_base), len2 = (len + 1) & ~1;
-      if (n_tiles > 1 || !staged) {
-        __syncthreads();                                                               // every wave is done with the previous tile
-        RemapEntry* s_e = reinterpret_cast<RemapEntry*>(s_pal);
-        for (int j = threadIdx.x; j < len2; j += kRemapBlock) s_e[j] = remap_pack_entry(pal + (long long)(tile_base + min(j, len - 1)) * 3, j);
-        __syncthreads();
-        staged = true;
-      }
-      uint32_t best[kRemapPx];
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) best[q] = 0xFFFFFFFFu;
-#pragma unroll 2
-      for (int j = 0; j < len2 / 2; ++j) {
-        const uint4 e = s_pal[j];                                                      // wave-uniform address: broadcast
-#pragma unroll
-        for (int q = 0; q < kRemapPx; ++q) {
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.x, e.y}));
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.z, e.w}));
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) remap_carry(best[q], tile_base, bkey[q], bidx[q]);
-    }
-    uint32_t dist[kRemapPx];
-#pragma unroll
-    for (int q = 0; q < kRemapPx; ++q) {
-      const long long p = base + (long long)q * kRemapBlock;
-      const bool in = p < n_px;
-      dist[q] = in ? remap_dist(px[q], bkey[q]) : 0u;
-      if (in) idx_out[p] = (IdxT)bidx[q];
-      all_sse += dist[q];
-    }
-    if (n_classes > 0) {                                                               // per class: lane sums in 64 bits, one wave reduction
-      unsigned c[kRemapPx];
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) {
-        const long long p = base + (long long)q * kRemapBlock;
-        c[q] = p < n_px ? (unsigned)cls[p] : 0xFFFFFFFFu;
-      }
-      for (int k = 0; k < n_classes; ++k) {
-        unsigned long long v = 0ull, n = 0ull;
-#pragma unroll
-        for (int q = 0; q < kRemapPx; ++q) {
-          v += c[q] == (unsigned)k ? dist[q] : 0u;
-          n += c[q] == (unsigned)k ? 1u : 0u;
-        }
-        v = wave_sum(v);
-        n = wave_sum(n);
-        if (lane == 0) { s_sum[wv][k][0] += n; s_sum[wv][k][1] += v; }               // this wave's table: no other writer
-      }
-    }
-  }
-  all_sse = wave_sum(all_sse);
-  if (lane == 0) s_sum[wv][kRemapMaxClasses][1] = all_sse;
-  __syncthreads();
-  if ((int)threadIdx.x < (n_classes + 1) * 2) {                                        // one atomic per workgroup, row and column
-    const int k = threadIdx.x >> 1, col = threadIdx.x & 1;
-    unsigned long long t = 0ull;
-    if (k < n_classes) {
-      for (int i = 0; i < kRemapBlock / 64; ++i) t += s_sum[i][k][col];
-    } else if (col == 1) {
-      for (int i = 0; i < kRemapBlock / 64; ++i) t += s_sum[i][kRemapMaxClasses][1];
-    } else {                                                                           // the pixels of this workgroup's chunks
-      for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) t += (unsigned long long)min(kChunk, n_px - chunk * kChunk);
-    }
-    if (t) atomicAdd(&sums[threadIdx.x], t);
-  }
-}
-
-static int remap_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels, const void* palette, int32_t K, const void* cls, int32_t n_classes,
-                       const void* idx_out, int32_t idx_elem_bytes, const void* sums) {
-  if (!rgb || !palette || !idx_out || !sums) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: null argument");
-  if (K < 1 || n_pixels < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: K >= 1 and n_pixels >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: n_classes must be 0 without a class map");
-  if (idx_elem_bytes != 1 && idx_elem_bytes != 2 && idx_elem_bytes != 4)
-    return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: idx_elem_bytes must be 1, 2 or 4");
-  if ((uintptr_t)idx_out & (uintptr_t)(idx_elem_bytes - 1)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: misaligned indices");
-  if ((uintptr_t)sums & 7) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: misaligned sums");
-  if (idx_elem_bytes == 1 && K > 256) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_remap: 1-byte indices hold at most 256 colours");
-  if (K > kRemapMaxK) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_remap: at most 65536 colours");
-  return 0;
+  remap_body<IdxT>(rgb, n_px, pal, K, cls, n_classes, idx_out, sums, blockIdx.x, gridDim.x);
 }
 
 template <typename IdxT>

@@ -26,7 +26,8 @@ from .api.roi import min_region_size
 from .api.slic import _antialias_sigma_radius, _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
 from .api.split_score import normalize_result, scores_from_stats
 from .frame import ClassSpec, FrameEncoder
-from .ops import default_context, psnr_from_sse
+from . import ops
+from .ops import RhccqError, default_context, psnr_from_sse
 from .palette import cluster_palettes
 
 __all__ = ["ImageEncoder", "Region"]
@@ -993,6 +994,115 @@ class ImageEncoder:
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         return res
+
+    # images of one slice of quantize_batch: a slice holds 1 MiB of histogram and 1.1 MiB of summed-volume table per image beside its
+    # pixels and indices (128 images: 275 MiB), and 128 chains are half the card's CUs, so two slices' chains already fill it
+    QUANTIZE_BATCH_SLICE = 128
+
+    def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False):
+        """images: a list of uint8[H,W,3] images of any sizes (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor
+        (a contiguous device tensor is used in place, nothing is concatenated) -> a list with one result dict per image: what
+        quantize(image, colours, refine=refine, roi_mask=mask, roi_weight=...) returns for that image alone, bit for bit (palette
+        trimmed to its rows, indices [H,W], stats["build"], stats["remap"], stats["refine"]); only stats["seconds"] differs
+        ({"batch": the whole call}).  roi_masks: one mask (or None) per image; a pixel inside its mask weighs roi_weight (1..255),
+        which other than 1 needs at least one mask; an image without a mask is quantised as with roi_weight = 1.
+        The images are laid back to back and every stage runs once for all of them (Rhccq.palette_cells_batch, palette_build_batch:
+        one split chain per image side by side, palette_refine_batch, palette_remap_batch); the rows each image got stay on the
+        device between the stages, and the host reads everything it needs (rows, sums, histories, iterations, occupied cells, the
+        palettes) ONCE, after the whole batch is queued.  The index width is chosen by `colours` (uint8 up to 256, else 16 bits);
+        an image that ends with 256 rows or fewer is narrowed to uint8 afterwards, as quantize returns it.  More than
+        QUANTIZE_BATCH_SLICE (128) images are queued in slices of that many, which bounds the workspace; the one read stays one.
+        out_paths: one file name (or None) per image, written afterwards with container.write_frame(exact=exact), one by one.
+        target_bytes, target_psnr, run_slack, run_penalty and report are not parameters: each needs a host decision per image;
+        quantize has them.  Validation and error types follow quantize; an image whose table is empty (no pixels) raises
+        RhccqError after the read, as quantize does for it."""
+        rh = self.rh
+        fn = "ImageEncoder.quantize_batch"
+        colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
+        if colours < 1:
+            raise ValueError(f"{fn}: colours >= 1 is required")
+        if refine < 0 or refine > 64:
+            raise ValueError(f"{fn}: refine must be 0..64")
+        stacked = None
+        if (torch.is_tensor(images) or isinstance(images, np.ndarray)) and images.ndim == 4:
+            stacked = images.to(rh.device).contiguous() if torch.is_tensor(images) else rh.dev(images)
+            if stacked.dtype != torch.uint8 or stacked.shape[3] != 3:
+                raise ValueError(f"{fn}: a uint8 B x H x W x 3 tensor is expected")
+            frames = list(stacked)                                               # views
+        else:
+            frames = [self._frame_tensor("quantize_batch", im) for im in images]
+        B = len(frames)
+        masks = [None] * B if roi_masks is None else list(roi_masks)
+        paths = [None] * B if out_paths is None else list(out_paths)
+        if B < 1 or len(masks) != B or len(paths) != B:
+            raise ValueError(f"{fn}: at least one image, and one mask and one path (or None) per image, are expected")
+        masked = any(m is not None for m in masks)
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not masked):
+            raise ValueError(f"{fn}: roi_weight (1..255) other than 1 needs roi_masks")
+        if colours > ops.palette_build_max_rows():
+            raise RhccqError(f"{fn}: {colours} colours, the device form returns at most {ops.palette_build_max_rows()} (palette_build_max_rows())")
+        t0 = time.perf_counter()
+        nc, weights = (2, [1, roi_weight, 1]) if masked else (0, None)
+        queued = []
+        for s0 in range(0, B, self.QUANTIZE_BATCH_SLICE):
+            part = frames[s0:s0 + self.QUANTIZE_BATCH_SLICE]
+            off = np.concatenate([[0], np.cumsum([int(f.shape[0]) * int(f.shape[1]) for f in part])]).astype(np.int64)
+            if stacked is not None:
+                rgb = stacked[s0:s0 + len(part)].reshape(-1, 3)
+            else:
+                rgb = part[0].reshape(-1, 3) if len(part) == 1 else torch.cat([f.reshape(-1, 3) for f in part])
+            cls = None
+            if masked:
+                # an image without a mask takes the class outside both (2): weight 1 everywhere, and no row of the class sums
+                from .api.roi import region_map_from_mask
+                maps = [torch.full((int(off[i + 1] - off[i]),), 2, dtype=torch.uint8, device=rh.device) if m is None
+                        else region_map_from_mask(f, m, rh).reshape(-1) for i, (f, m) in enumerate(zip(part, masks[s0:s0 + len(part)]))]
+                cls = maps[0] if len(maps) == 1 else torch.cat(maps)
+            off_dev = rh.dev(off)
+            cells = rh.palette_cells_batch(rgb, off, cls, nc, weights, px_off_dev=off_dev)
+            occupied = (cells[:, 0] != 0).sum(dim=(1, 2, 3))
+            pal, _, _, _, k = rh.palette_build_batch(cells, colours)
+            hist = nit = None
+            if refine:
+                pal, hist, nit = rh.palette_refine_batch(rgb, off, pal, k, cls, weights, max_iter=refine, px_off_dev=off_dev)
+            idx, sums = rh.palette_remap_batch(rgb, off, pal, k, cls, nc, px_off_dev=off_dev)
+            queued.append((off, idx, [k, occupied, sums, pal] + ([hist, nit] if refine else [])))
+        host = rh.to_host(*[t for _, _, ts in queued for t in ts])                 # the one read
+        out, at = [], 0
+        for s, (off, idx, ts) in enumerate(queued):
+            k, occupied, sums, pal = host[at:at + 4]
+            hist, nit = host[at + 4:at + 6] if refine else (None, None)
+            at += len(ts)
+            for b in range(len(off) - 1):
+                i = s * self.QUANTIZE_BATCH_SLICE + b
+                rows = int(k[b])
+                if rows < 0:                                                     # the errors only the table shows come back through k
+                    raise RhccqError(f"{fn}: image {i}: palette_build failed ({rows}): "
+                                     + ("the table is empty" if rows == -1 else "the table's N adds up to more than 2^32 - 1"))
+                H, W = int(frames[i].shape[0]), int(frames[i].shape[1])
+                ind = idx[int(off[b]):int(off[b + 1])].reshape(H, W)
+                if ind.dtype != torch.uint8 and rows <= 256:
+                    ind = ind.to(torch.uint8)
+                remap = {"all": self._remap_row(*sums[b][-1])}
+                if masks[i] is not None:
+                    remap["nonroi"], remap["roi"] = self._remap_row(*sums[b][0]), self._remap_row(*sums[b][1])
+                stats = {"remap": remap}
+                if refine:
+                    n = int(nit[b])
+                    stats["refine"] = {"iterations": n, "converged": n == 0 or int(hist[b][n - 1, 1]) == 0,
+                                       "sse": [int(v) for v in hist[b][:n, 0]], "changed": [int(v) for v in hist[b][:n, 1]]}
+                stats["build"] = {"asked": colours, "rows": rows, "cells": int(occupied[b]), "steps": rows - 1}
+                out.append({"palette": np.ascontiguousarray(pal[b][:rows]), "indices": ind, "indices_dtype": "uint8" if ind.dtype == torch.uint8 else "uint16",
+                            "shape": (H, W), "top_left": (0, 0), "stats": stats})
+        if any(p for p in paths):
+            from . import container
+            for res, p in zip(out, paths):
+                if p:
+                    container.write_frame(res, p, rh, exact=exact)
+        seconds = {"batch": round(time.perf_counter() - t0, 4)}
+        for res in out:
+            res["stats"]["seconds"] = dict(seconds)
+        return out
 
     def shared_palette(self, images, colours, roi_masks=None, roi_weight=1):
         """images: uint8[H,W,3] each (any sizes), colours = N -> one palette (device uint8[k, 3], k <= N) for all of them: the images'

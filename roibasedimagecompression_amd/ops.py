@@ -1344,6 +1344,160 @@ class Rhccq:
             raise RhccqError(f"palette_build failed ({k}): " + ("the table is empty" if k == -1 else "the table's N adds up to more than 2^32 - 1"))
         return pal_out[:k], cnt_out[:k], splits[:k - 1], boxes[:k]
 
+    # -- the palette build path for a batch of images (EXTENSION: csrc/palette_batch.hip) ----------------------------------------------
+    def _batch_pixels(self, fn, rgb, px_off, px_off_dev, class_map):
+        """the arguments the four batched calls share -> (rgb device uint8, px_off host int64[B + 1], its device copy, class map device
+        or None, pixels).  px_off_dev: a device int64 copy of px_off an earlier call of the family returned or the caller made (one
+        upload for the four calls); None: this call uploads one"""
+        def on_device(a, what):
+            if not torch.is_tensor(a):
+                a = torch.from_numpy(np.ascontiguousarray(a))
+            if a.dtype == torch.bool:
+                a = a.view(torch.uint8)
+            if a.dtype != torch.uint8:
+                raise TypeError(f"{fn}: {what} must be uint8, got {a.dtype}")
+            return a.to(self.device).contiguous()
+        rgb = on_device(rgb, "rgb")
+        if rgb.ndim < 1 or rgb.shape[-1] != 3:
+            raise ValueError(f"{fn}: rgb [..., 3] is expected")
+        n = rgb.numel() // 3
+        off = np.ascontiguousarray(np.asarray(px_off.cpu() if torch.is_tensor(px_off) else px_off), dtype=np.int64).reshape(-1)
+        if len(off) < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != n:
+            raise ValueError(f"{fn}: px_off must hold B + 1 >= 2 offsets that start at 0, never decrease and end at the number of pixels")
+        if px_off_dev is None:
+            px_off_dev = self.dev(off)
+        elif not torch.is_tensor(px_off_dev) or px_off_dev.dtype != torch.int64 or px_off_dev.numel() != len(off) or not px_off_dev.is_contiguous() \
+                or px_off_dev.device != torch.device(self.device):
+            raise ValueError(f"{fn}: px_off_dev must be a contiguous device int64 copy of px_off")
+        cls = None
+        if class_map is not None:
+            cls = on_device(class_map, "class_map")
+            if cls.numel() != n:
+                raise ValueError(f"{fn}: the class map must have one element per pixel")
+        return rgb, off, px_off_dev, cls, n
+
+    def _batch_palettes(self, fn, palettes, k_rows, B):
+        if not torch.is_tensor(palettes):
+            palettes = torch.from_numpy(np.ascontiguousarray(palettes))
+        if palettes.dtype != torch.uint8 or palettes.ndim != 3 or palettes.shape[0] != B or palettes.shape[2] != 3 or palettes.shape[1] < 1:
+            raise ValueError(f"{fn}: palettes uint8[B, K_stride >= 1, 3] is expected")
+        if not torch.is_tensor(k_rows):
+            k_rows = torch.from_numpy(np.ascontiguousarray(k_rows, dtype=np.int32))
+        if k_rows.dtype != torch.int32 or k_rows.numel() != B:
+            raise ValueError(f"{fn}: k_rows int32[B] is expected")
+        return palettes.to(self.device).contiguous(), k_rows.to(self.device).contiguous().reshape(-1)
+
+    def palette_cells_batch(self, rgb, px_off, cls=None, n_classes=0, weights=None, px_off_dev=None):
+        """palette_cells for B images that lie back to back in rgb (uint8[..., 3], numpy or device): image b is the pixels
+        px_off[b] .. px_off[b + 1] (B + 1 host integers from 0 to the number of pixels; an image may be empty); cls, n_classes and
+        weights as palette_cells takes them, cls over the same concatenation -> the device tables int64[B, 4, 32, 32, 32], table b
+        what palette_cells gives for image b alone.  One launch, no read back."""
+        rgb, off, off_dev, d_cls, n = self._batch_pixels("palette_cells_batch", rgb, px_off, px_off_dev, cls)
+        B, n_classes = len(off) - 1, int(n_classes)
+        w = None if weights is None else [int(v) for v in weights]
+        if w is not None and len(w) != n_classes + 1:
+            raise ValueError("palette_cells_batch: weights must have n_classes + 1 entries")
+        if d_cls is None and n_classes:
+            raise ValueError("palette_cells_batch: n_classes without a class map")
+        if not 0 <= n_classes <= 16 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+            raise RhccqError("palette_cells_batch: n_classes must be 0..16 and weights 0..255 with one > 0")
+        cells = self.empty((B,) + PALETTE_CELLS_SHAPE, torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return cells.zero_()
+        warr = None if w is None else (C.c_int32 * len(w))(*w)
+        self._check(self.lib.rhccq_palette_cells_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(d_cls), n_classes,
+                                                       C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), self._p(cells)),
+                    "palette_cells_batch")
+        return cells
+
+    def palette_build_batch(self, cells, colours):
+        """cells: the tables of palette_cells_batch (int64[B, 4, 32, 32, 32], numpy or device), colours = one K_target in
+        1..palette_build_max_rows() for all of them -> (palettes device uint8[B, colours, 3], counts device int64[B, colours], splits
+        device int32[B, colours - 1, 3], boxes device uint8[B, colours, 6], k device int32[B]): per image what palette_build gives,
+        NOT trimmed and not read back: k[b] is the rows image b has (zero rows behind them), or the negative code of a table that is
+        empty (-1) or adds up to more than 2^32 - 1 (-3), whose rows are all zero.  B chains run as B workgroups of one launch."""
+        if not torch.is_tensor(cells):
+            a = np.ascontiguousarray(cells)
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"palette_build_batch: cells must be integers, got {a.dtype}")
+            cells = torch.from_numpy(a.astype(np.uint64).view(np.int64))
+        if cells.dtype != torch.int64:
+            raise TypeError(f"palette_build_batch: cells must be int64, got {cells.dtype}")
+        if cells.ndim != 5 or tuple(cells.shape[1:]) != PALETTE_CELLS_SHAPE or cells.shape[0] < 1:
+            raise ValueError("palette_build_batch: cells [B >= 1, 4, 32, 32, 32] is expected")
+        cells = cells.to(self.device).contiguous()
+        B, target, cap = int(cells.shape[0]), int(colours), palette_build_max_rows()
+        if target > cap:
+            raise RhccqError(f"palette_build_batch: {target} colours, the device form returns at most {cap} (palette_build_max_rows())")
+        if target < 1:
+            raise RhccqError("palette_build_batch: colours >= 1 is required")
+        wbytes = int(self._raw.rhccq_palette_build_batch_bytes(B))
+        work = self.empty((wbytes // 8,), torch.int64)
+        pal_out = self.empty((B, target, 3), torch.uint8)
+        cnt_out = self.empty((B, target), torch.int64)
+        boxes = self.empty((B, target, 6), torch.uint8)
+        splits = self.empty((B, target - 1, 3), torch.int32)
+        k_out = self.empty((B,), torch.int32)
+        self._check(self.lib.rhccq_palette_build_batch(self.ctx, self._p(cells), B, target, self._p(work), wbytes, self._p(pal_out), self._p(cnt_out),
+                                                       self._p(boxes), self._p(splits) if target > 1 else C.c_void_p(0), self._p(k_out)),
+                    "palette_build_batch")
+        return pal_out, cnt_out, splits, boxes, k_out
+
+    def palette_remap_batch(self, rgb, px_off, palettes, k_rows, class_map=None, n_classes=0, px_off_dev=None):
+        """palette_remap for B images laid out as palette_cells_batch takes them.  palettes uint8[B, K_stride, 3] and k_rows int32[B]
+        (numpy or device; palette_build_batch's palettes and k go in as they are): image b is mapped onto rows 0 .. k_rows[b] - 1 of
+        palettes[b], the rows behind them are never read, and an image with k_rows[b] < 1 gets index 0 and zero sums -> (indices
+        device [pixels], concatenated like rgb: uint8 when K_stride <= 256, else int16 holding uint16; sums device int64
+        [B, n_classes + 1, 2], rows as palette_remap's).  k_rows is read on the device: no read back."""
+        rgb, off, off_dev, cls, n = self._batch_pixels("palette_remap_batch", rgb, px_off, px_off_dev, class_map)
+        B, n_classes = len(off) - 1, int(n_classes)
+        palettes, k_rows = self._batch_palettes("palette_remap_batch", palettes, k_rows, B)
+        K = int(palettes.shape[1])
+        if cls is None and n_classes:
+            raise ValueError("palette_remap_batch: n_classes without a class map")
+        if not 0 <= n_classes <= 16 or K > 65536:
+            raise RhccqError("palette_remap_batch: K_stride must be 1..65536 and n_classes 0..16")
+        idx = self.empty((n,), torch.uint8 if K <= 256 else torch.int16)
+        sums = self.empty((B, n_classes + 1, 2), torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return idx, sums.zero_()
+        self._check(self.lib.rhccq_palette_remap_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(palettes), K,
+                                                       self._p(k_rows), self._p(cls), n_classes, self._p(idx), idx.element_size(), self._p(sums)),
+                    "palette_remap_batch")
+        return idx, sums
+
+    def palette_refine_batch(self, rgb, px_off, palettes, k_rows, class_map=None, weights=None, max_iter=8, px_off_dev=None):
+        """palette_refine for B images laid out as palette_cells_batch takes them, palettes and k_rows as palette_remap_batch takes
+        them; class_map, weights and max_iter as palette_refine takes them, one table for the batch -> (palettes: a NEW device
+        uint8[B, K_stride, 3], rows from k_rows[b] on copied unchanged; history device int64[B, max_iter, 2]; n_iter device int32[B]):
+        per image what palette_refine gives for its k_rows[b] rows.  Images stop independently; an empty image, or one with
+        k_rows[b] < 1, runs no iteration.  Two launches per iteration for the whole batch, no read back."""
+        rgb, off, off_dev, cls, n = self._batch_pixels("palette_refine_batch", rgb, px_off, px_off_dev, class_map)
+        B, max_iter = len(off) - 1, int(max_iter)
+        palettes, k_rows = self._batch_palettes("palette_refine_batch", palettes, k_rows, B)
+        K = int(palettes.shape[1])
+        w = None if weights is None else [int(v) for v in weights]
+        if w is not None and len(w) < 1:
+            raise ValueError("palette_refine_batch: weights must have n_classes + 1 entries")
+        n_classes = 0 if w is None else len(w) - 1
+        if cls is None and n_classes:
+            raise ValueError("palette_refine_batch: class weights without a class map")
+        if not 0 <= n_classes <= 16 or K > 65536 or not 1 <= max_iter <= 64 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+            raise RhccqError("palette_refine_batch: K_stride must be 1..65536, max_iter 1..64, weights 0..255 (n_classes + 1 <= 17 of them, one > 0)")
+        out = palettes.clone()
+        history = self.empty((B, max_iter, 2), torch.int64)
+        n_iter = self.empty((B,), torch.int32)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return out, history.zero_(), n_iter.zero_()
+        wbytes = int(self._raw.rhccq_palette_refine_batch_bytes(B, K))
+        work = self.empty((wbytes // 8,), torch.int64)
+        warr = None if w is None else (C.c_int32 * len(w))(*w)
+        self._check(self.lib.rhccq_palette_refine_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(out), K,
+                                                        self._p(k_rows), self._p(cls), n_classes,
+                                                        C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), max_iter, self._p(work), wbytes,
+                                                        self._p(history), self._p(n_iter)), "palette_refine_batch")
+        return out, history, n_iter
+
     # -- the palette ladder: moments, the error curve of every rung, any rung from the log (EXTENSION: csrc/palette_ladder.hip) ----
     def _ladder_arg(self, a, dtype, what, fn):
         """palette / counts / merges as a contiguous device tensor of `dtype` (counts: any integers, as palette_reduce takes them)"""
