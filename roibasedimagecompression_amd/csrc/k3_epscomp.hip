@@ -415,7 +415,7 @@ __global__ __launch_bounds__(kEpsThreads) void eps_components_lds_kernel(const u
   __syncthreads();
   // K4 labelling: root = smallest member index; label = rank of the root among roots
   {
-    constexpr int kPer = (RHCCQ_EPS_LDS_MAX + kEpsThreads - 1) / kEpsThreads;   // 20 points per thread
+    constexpr int kPer = (RHCCQ_EPS_LDS_MAX + kEpsThreads - 1) / kEpsThreads;   // 10 points per thread
     uint32_t root[kPer];
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
