@@ -5,8 +5,9 @@
 // Why: the split chain is one workgroup for about 2 ms at 256 colours (7 to 8 us a step) and cannot be shortened, but B chains on B
 // workgroups take what one takes; and a loop of single calls pays every launch and every host synchronisation once per image.
 //
-// How.  Every kernel here is the single-image kernel's body (palette_build.h, palette_remap.h, palette_refine.h) called with the
-// pointers of one image: blockIdx.y (the chain: blockIdx.x) is the image, blockIdx.x the workgroup among the gridDim.x that share it.
+// How.  Every kernel here is the single-image kernel's body (palette_build.h, palette_remap.h, palette_refine.h; the remap and the
+// refinement both search through the one remap_search) called with the pointers of one image: blockIdx.y (the chain: blockIdx.x) is
+// the image, blockIdx.x the workgroup among the gridDim.x that share it.
 // An image's pixels are [px_off[b], px_off[b + 1]) of the concatenation and its chunks count from its own first pixel, so a workgroup
 // never holds pixels of two images and the sums of an image are formed by the same additions as in the single call (integers: any
 // order gives the same result anyway).  The grid's x extent is sized on the host by the largest image (px_off_host); the kernels read
@@ -73,12 +74,11 @@ __global__ __launch_bounds__(kRemapBlock) void palette_remap_batch_kernel(const 
   const int b = blockIdx.y;
   long long n_px;
   const long long first = batch_image(px_off, b, &n_px);
-  constexpr long long kChunk = (long long)kRemapBlock * kRemapPx;
-  if ((long long)blockIdx.x * kChunk >= n_px) return;                                  // (block uniform)
+  if ((long long)blockIdx.x * kRemapChunk >= n_px) return;                             // (block uniform)
   const int K = batch_rows(k_rows, b, K_stride);
   if (K < 1) {                                                                         // no palette (a build's error code): index 0, zero sums
-    for (long long c = (long long)blockIdx.x * kChunk; c < n_px; c += (long long)gridDim.x * kChunk)
-      for (long long p = c + threadIdx.x; p < min(c + kChunk, n_px); p += kRemapBlock) idx_out[first + p] = (IdxT)0;
+    for (long long c = (long long)blockIdx.x * kRemapChunk; c < n_px; c += (long long)gridDim.x * kRemapChunk)
+      for (long long p = c + threadIdx.x; p < min(c + kRemapChunk, n_px); p += kRemapBlock) idx_out[first + p] = (IdxT)0;
     return;
   }
   remap_body<IdxT>(rgb + first * 3, n_px, pal + (size_t)b * K_stride * 3, K, n_classes > 0 ? cls + first : nullptr, n_classes, idx_out + first,
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kRemapBlock) void palette_refine_assign_batch_kerne
   const int b = blockIdx.y;
   long long n_px;
   const long long first = batch_image(px_off, b, &n_px);
-  if ((long long)blockIdx.x * kRemapBlock * kRemapPx >= n_px) return;                  // (block uniform)
+  if ((long long)blockIdx.x * kRemapChunk >= n_px) return;                             // (block uniform)
   const int K = batch_rows(k_rows, b, K_stride);
   if (K < 1) return;
   refine_assign_body<kLds>(rgb + first * 3, n_px, pal + (size_t)b * K_stride * 3, K, n_classes > 0 ? cls + first : nullptr, n_classes, wt, iter,
@@ -144,11 +144,6 @@ static unsigned batch_grid_x(int64_t max_px, long long chunk, long long cap, int
   return (unsigned)(chunks < share ? chunks : share);
 }
 
-static int batch_units(rhccq_ctx* ctx) {
-  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  return 0;
-}
-
 static int build_batch_check(rhccq_ctx* ctx, const void* cells, int32_t B, int32_t K_target, const void* palette_out, const void* counts_out,
                              const void* splits, const void* k_out) {
   if (B < 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_build_batch: B >= 1 is required");
@@ -177,7 +172,7 @@ int rhccq_palette_cells_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t*
   if (const int rc = cells_check(ctx, rgb, max_px, cls, n_classes, weights_host, cells, &wt)) return rc;      // (the limit holds per image)
   RHCCQ_HIP(ctx, hipMemsetAsync(cells, 0, (size_t)B * kBuildCells * 4 * sizeof(uint64_t), ctx->stream));
   if (max_px == 0) return 0;
-  if (const int rc = batch_units(ctx)) return rc;
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
   const dim3 grid(batch_grid_x(max_px, kCellsChunk, (long long)ctx->compute_units * 4, B), (unsigned)B);
   hipLaunchKernelGGL(palette_cells_batch_kernel, grid, dim3(kCellsBlock), 0, ctx->stream, rgb, (const long long*)px_off_dev, cls, (int)n_classes, wt,
                      (unsigned long long*)cells);
@@ -253,23 +248,15 @@ int rhccq_palette_remap_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t*
   if (const int rc = remap_check(ctx, rgb, px_off_host[B], palettes, K_stride, cls, n_classes, idx_out, idx_elem_bytes, sums)) return rc;
   RHCCQ_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)B * (n_classes + 1) * 2 * sizeof(uint64_t), ctx->stream));
   if (max_px == 0) return 0;
-  if (const int rc = batch_units(ctx)) return rc;
-  const dim3 grid(batch_grid_x(max_px, (long long)kRemapBlock * kRemapPx, (long long)ctx->compute_units * 8, B), (unsigned)B), block(kRemapBlock);
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
+  const dim3 grid(batch_grid_x(max_px, kRemapChunk, (long long)ctx->compute_units * 8, B), (unsigned)B), block(kRemapBlock);
   const long long* off = (const long long*)px_off_dev;
   unsigned long long* s = (unsigned long long*)sums;
-  switch (idx_elem_bytes) {
-    case 1:
-      hipLaunchKernelGGL(palette_remap_batch_kernel<uint8_t>, grid, block, 0, ctx->stream, rgb, off, palettes, (int)K_stride, k_rows, cls, (int)n_classes,
-                         (uint8_t*)idx_out, s);
-      break;
-    case 2:
-      hipLaunchKernelGGL(palette_remap_batch_kernel<uint16_t>, grid, block, 0, ctx->stream, rgb, off, palettes, (int)K_stride, k_rows, cls, (int)n_classes,
-                         (uint16_t*)idx_out, s);
-      break;
-    default:
-      hipLaunchKernelGGL(palette_remap_batch_kernel<uint32_t>, grid, block, 0, ctx->stream, rgb, off, palettes, (int)K_stride, k_rows, cls, (int)n_classes,
-                         (uint32_t*)idx_out, s);
-  }
+  index_dispatch(idx_elem_bytes, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(palette_remap_batch_kernel<T>, grid, block, 0, ctx->stream, rgb, off, palettes, (int)K_stride, k_rows, cls, (int)n_classes,
+                       (T*)idx_out, s);
+  });
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -315,9 +302,9 @@ int rhccq_palette_refine_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t
   RHCCQ_HIP(ctx, hipMemsetAsync(n_iter, 0, (size_t)B * sizeof(int32_t), ctx->stream));
   if (max_px == 0) return 0;
   RHCCQ_HIP(ctx, hipMemsetAsync(work, 0, (size_t)need, ctx->stream));
-  if (const int rc = batch_units(ctx)) return rc;
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
   const long long cap = ctx->opt_refine_max_blocks > 0 ? ctx->opt_refine_max_blocks : (long long)ctx->compute_units * 8;
-  const dim3 grid(batch_grid_x(max_px, (long long)kRemapBlock * kRemapPx, cap, B), (unsigned)B), block(kRemapBlock);
+  const dim3 grid(batch_grid_x(max_px, kRemapChunk, cap, B), (unsigned)B), block(kRemapBlock);
   const dim3 ugrid((unsigned)((K_stride + 255) / 256), (unsigned)B);
   // one choice for the batch: accumulators in LDS when the stride (so every image's rows) fits, else in the workspace for every image
   const int lds_rows = ctx->opt_refine_lds_rows < 0 ? kRefineLdsRows : ctx->opt_refine_lds_rows;

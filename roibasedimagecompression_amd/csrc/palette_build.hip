@@ -72,7 +72,7 @@ int rhccq_palette_cells(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, co
   if (const int rc = cells_check(ctx, rgb, n_pixels, cls, n_classes, weights_host, cells, &wt)) return rc;
   if (!accumulate) RHCCQ_HIP(ctx, hipMemsetAsync(cells, 0, (size_t)kBuildCells * 4 * sizeof(uint64_t), ctx->stream));
   if (n_pixels == 0) return 0;
-  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
   const long long chunks = (n_pixels + kCellsChunk - 1) / kCellsChunk, cap = (long long)ctx->compute_units * 4;
   const long long blocks = chunks < cap ? chunks : cap;
   hipLaunchKernelGGL(palette_cells_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(kCellsBlock), 0, ctx->stream, rgb, (long long)n_pixels, cls,

@@ -14,9 +14,9 @@
 // Q - 2 c.S + N |c|^2 = sum |p - c|^2 is non-negative, so unsigned arithmetic (wrapping in between) gives the exact value.
 //
 // Device forms (async on the context stream, stream order the only synchronisation: no kernel waits for another workgroup):
-//   moments   memset | the remap's chunk loop (256 lanes x 8 pixels, palette tiles through LDS) with accumulators as the refinement's
-//             assign kernel keeps them: a copy per workgroup in (dynamic) LDS while (tables x K x 40 bytes) fits beside the tile in
-//             64 KiB, flushed with 64-bit atomics, global atomics above that | a finish launch that adds the class tables into the last
+//   moments   memset | remap_search (palette_remap.h: 256 lanes x 8 pixels, palette tiles through LDS) with accumulators as the
+//             refinement's assign kernel keeps them: a copy per workgroup in (dynamic) LDS while (tables x K x 40 bytes) fits beside the
+//             tile in 64 KiB, flushed with 64-bit atomics, global atomics above that | a finish launch that adds the class tables into the last
 //             one (during the pass it holds the pixels of no class, afterwards every pixel).
 //   curve     copy of the moments into the workspace | one thread per (table, row): row state and the initial sums | ONE wave that
 //             replays the log: lanes 0..2 own a channel of S, lane t owns table t; n and c live in LDS.  Latency bound, like the chain.
@@ -66,52 +66,14 @@ template <typename IdxT, bool kLds>
 __global__ __launch_bounds__(kRemapBlock) void palette_moments_kernel(const uint8_t* __restrict__ rgb, long long n_px, const uint8_t* __restrict__ pal,
                                                                       int K, const uint8_t* __restrict__ cls, int n_classes,
                                                                       IdxT* __restrict__ idx_out, unsigned long long* __restrict__ mom) {
-  __shared__ uint4 s_pal[kRemapTile / 2];
   extern __shared__ unsigned long long s_acc[];                                         // kLds: [n_classes + 1][K][5]
   const int lane = threadIdx.x & 63;
   const int n_acc = (n_classes + 1) * K * kLadderFields;
   if (kLds)
     for (int j = threadIdx.x; j < n_acc; j += kRemapBlock) s_acc[j] = 0ull;
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  constexpr long long kChunk = (long long)kRemapBlock * kRemapPx;
-  const long long n_chunks = (n_px + kChunk - 1) / kChunk;
-  bool staged = false;
   __syncthreads();
 
-  for (long long chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {          // (block uniform: the barriers below are safe)
-    const long long base = chunk * kChunk + threadIdx.x;
-    uint32_t px[kRemapPx], bkey[kRemapPx], bidx[kRemapPx];
-#pragma unroll
-    for (int q = 0; q < kRemapPx; ++q) {
-      const long long p = base + (long long)q * kRemapBlock;
-      px[q] = p < n_px ? remap_pack_px(rgb + p * 3) : 0u;
-      bkey[q] = 0xFFFFFFFFu;
-      bidx[q] = 0u;
-    }
-    for (int t = 0; t < n_tiles; ++t) {
-      const int tile_base = t * kRemapTile, len = min(kRemapTile, K - tile_base), len2 = (len + 1) & ~1;
-      if (n_tiles > 1 || !staged) {
-        __syncthreads();                                                               // every wave is done with the previous tile
-        RemapEntry* s_e = reinterpret_cast<RemapEntry*>(s_pal);
-        for (int j = threadIdx.x; j < len2; j += kRemapBlock) s_e[j] = remap_pack_entry(pal + (long long)(tile_base + min(j, len - 1)) * 3, j);
-        __syncthreads();
-        staged = true;
-      }
-      uint32_t best[kRemapPx];
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) best[q] = 0xFFFFFFFFu;
-#pragma unroll 2
-      for (int j = 0; j < len2 / 2; ++j) {
-        const uint4 e = s_pal[j];                                                      // wave-uniform address: broadcast
-#pragma unroll
-        for (int q = 0; q < kRemapPx; ++q) {
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.x, e.y}));
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.z, e.w}));
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) remap_carry(best[q], tile_base, bkey[q], bidx[q]);
-    }
+  remap_search(rgb, n_px, pal, K, blockIdx.x, gridDim.x, [&](long long base, auto& px, auto&, auto& bidx) {
     unsigned long long* tab = kLds ? s_acc : mom;
 #pragma unroll
     for (int q = 0; q < kRemapPx; ++q) {
@@ -137,7 +99,7 @@ __global__ __launch_bounds__(kRemapBlock) void palette_moments_kernel(const uint
         moments_add(tab + (size_t)slot * kLadderFields, 1u, r, g, b, qq);
       }
     }
-  }
+  });
   if (kLds) {
     __syncthreads();
     for (int j = threadIdx.x; j < n_acc; j += kRemapBlock) {
@@ -158,38 +120,23 @@ __global__ __launch_bounds__(256) void palette_moments_finish_kernel(unsigned lo
 
 static int moments_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels, const void* palette, int32_t K, const void* cls, int32_t n_classes,
                          const void* idx_out, int32_t idx_elem_bytes, const void* moments) {
-  if (!rgb || !palette || !moments) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: null argument");
-  if (K < 1 || n_pixels < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: K >= 1 and n_pixels >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: n_classes must be 0 without a class map");
+  const char* const what = "palette_moments";
+  if (const int rc = search_check(ctx, what, !rgb || !palette || !moments, n_pixels, K, cls, n_classes)) return rc;
   if (idx_out) {
-    if (idx_elem_bytes != 1 && idx_elem_bytes != 2 && idx_elem_bytes != 4)
-      return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: idx_elem_bytes must be 1, 2 or 4");
-    if ((uintptr_t)idx_out & (uintptr_t)(idx_elem_bytes - 1)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: misaligned indices");
-    if (idx_elem_bytes == 1 && K > 256) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: 1-byte indices hold at most 256 colours");
+    if (const int rc = index_check(ctx, what, idx_out, idx_elem_bytes)) return rc;
+    if (const int rc = index_rows_check(ctx, what, idx_elem_bytes, K)) return rc;
   }
   if ((uintptr_t)moments & 7) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_moments: misaligned moments");
-  if (K > kRemapMaxK) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_moments: at most 65536 colours");
-  return 0;
+  return search_limit(ctx, what, K);
 }
 
 template <typename IdxT>
 static void moments_host(const uint8_t* rgb, int64_t n_px, const uint8_t* pal, int K, const uint8_t* cls, int n_classes, IdxT* idx_out, uint64_t* mom) {
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  std::vector<RemapEntry> ent(K);
-  for (int j = 0; j < K; ++j) ent[j] = remap_pack_entry(pal + (int64_t)j * 3, j % kRemapTile);
+  const std::vector<RemapEntry> ent = remap_pack_palette(pal, K);
   for (int64_t p = 0; p < n_px; ++p) {
     const uint32_t px = remap_pack_px(rgb + p * 3);
-    uint32_t key = 0xFFFFFFFFu, idx = 0u;
-    for (int t = 0; t < n_tiles; ++t) {
-      const int tile_base = t * kRemapTile, len = K - tile_base < kRemapTile ? K - tile_base : kRemapTile;
-      uint32_t best = 0xFFFFFFFFu;
-      for (int j = 0; j < len; ++j) {
-        const uint32_t v = remap_eval(px, ent[tile_base + j]);
-        best = v < best ? v : best;
-      }
-      remap_carry(best, tile_base, key, idx);
-    }
+    uint32_t key;
+    const uint32_t idx = remap_search_host(px, ent, &key);
     if (idx_out) idx_out[p] = (IdxT)idx;
     const int t = n_classes > 0 && cls[p] < n_classes ? cls[p] : n_classes;
     uint64_t* row = mom + ((size_t)t * K + idx) * kLadderFields;
@@ -406,29 +353,19 @@ int rhccq_palette_moments(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, 
   const size_t n_acc = (size_t)(n_classes + 1) * K * kLadderFields;
   RHCCQ_HIP(ctx, hipMemsetAsync(moments, 0, n_acc * sizeof(uint64_t), ctx->stream));
   if (n_pixels == 0) return 0;
-  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const long long chunks = (n_pixels + (long long)kRemapBlock * kRemapPx - 1) / ((long long)kRemapBlock * kRemapPx);
-  const long long cap = (long long)ctx->compute_units * 8;
-  const long long blocks = chunks < cap ? chunks : cap;
-  const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks)), block(kRemapBlock);
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
+  const dim3 grid(remap_blocks(n_pixels, (long long)ctx->compute_units * 8)), block(kRemapBlock);
   const bool lds = K <= moments_lds_rows(n_classes);
-  const size_t shmem = lds ? n_acc * sizeof(uint64_t) : 0;
   unsigned long long* mom = (unsigned long long*)moments;
-#define RHCCQ_MOMENTS_LAUNCH(T)                                                                                                                   \
-  do {                                                                                                                                            \
-    if (lds)                                                                                                                                      \
-      hipLaunchKernelGGL((palette_moments_kernel<T, true>), grid, block, shmem, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls,     \
-                         (int)n_classes, (T*)idx_out, mom);                                                                                       \
-    else                                                                                                                                          \
-      hipLaunchKernelGGL((palette_moments_kernel<T, false>), grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls,        \
-                         (int)n_classes, (T*)idx_out, mom);                                                                                       \
-  } while (0)
-  switch (idx_out ? idx_elem_bytes : 4) {
-    case 1: RHCCQ_MOMENTS_LAUNCH(uint8_t); break;
-    case 2: RHCCQ_MOMENTS_LAUNCH(uint16_t); break;
-    default: RHCCQ_MOMENTS_LAUNCH(uint32_t);
-  }
-#undef RHCCQ_MOMENTS_LAUNCH
+  index_dispatch(idx_out ? idx_elem_bytes : 4, [&](auto* t) {                          // (no index buffer: the 4-byte instance)
+    using T = std::remove_pointer_t<decltype(t)>;
+    if (lds)
+      hipLaunchKernelGGL((palette_moments_kernel<T, true>), grid, block, n_acc * sizeof(uint64_t), ctx->stream, rgb, (long long)n_pixels, palette, (int)K,
+                         cls, (int)n_classes, (T*)idx_out, mom);
+    else
+      hipLaunchKernelGGL((palette_moments_kernel<T, false>), grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls, (int)n_classes,
+                         (T*)idx_out, mom);
+  });
   if (n_classes > 0)
     hipLaunchKernelGGL(palette_moments_finish_kernel, dim3((unsigned)((K * kLadderFields + 255) / 256)), dim3(256), 0, ctx->stream, mom, (int)K,
                        (int)n_classes);
@@ -440,11 +377,7 @@ int rhccq_palette_moments_host(const uint8_t* rgb, int64_t n_pixels, const uint8
                                void* idx_out, int32_t idx_elem_bytes, uint64_t* moments) {
   if (const int rc = moments_check(nullptr, rgb, n_pixels, palette, K, cls, n_classes, idx_out, idx_elem_bytes, moments)) return rc;
   for (size_t j = 0; j < (size_t)(n_classes + 1) * K * kLadderFields; ++j) moments[j] = 0;
-  switch (idx_out ? idx_elem_bytes : 4) {
-    case 1: moments_host<uint8_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint8_t*)idx_out, moments); break;
-    case 2: moments_host<uint16_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint16_t*)idx_out, moments); break;
-    default: moments_host<uint32_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint32_t*)idx_out, moments);
-  }
+  index_dispatch(idx_out ? idx_elem_bytes : 4, [&](auto* t) { moments_host(rgb, n_pixels, palette, K, cls, n_classes, (decltype(t))idx_out, moments); });
   return 0;
 }
 

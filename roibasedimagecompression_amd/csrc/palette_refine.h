@@ -1,6 +1,6 @@
 // The functions of the palette refinement (palette_refine.hip) that its kernels share with the batched form (palette_batch.hip): the
-// bodies of the assignment and of the update, the accumulator add and the argument check.  The rule is in include/rhccq.h; the device
-// form is described in palette_refine.hip.
+// bodies of the assignment (what it does with the winners of remap_search, palette_remap.h) and of the update, the accumulator add and
+// the argument check.  The rule is in include/rhccq.h; the device form is described in palette_refine.hip.
 #pragma once
 #include "palette_remap.h"
 
@@ -34,54 +34,16 @@ __device__ __forceinline__ void refine_assign_body(const uint8_t* __restrict__ r
                                                     unsigned long long* __restrict__ acc, unsigned long long* s_acc,
                                                     long long bid, long long nblk) {
   if (iter > 0 && history[(iter - 1) * 2 + 1] == 0ull) return;                          // the iteration before changed no row (or did not run)
-  __shared__ uint4 s_pal[kRemapTile / 2];
   __shared__ unsigned long long s_err[kRemapBlock / 64];
   __shared__ uint32_t s_w[kRemapMaxClasses + 1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if ((int)threadIdx.x <= n_classes) s_w[threadIdx.x] = wt.w[threadIdx.x];
   if (kLds)
     for (int j = threadIdx.x; j < K * 4; j += kRemapBlock) s_acc[j] = 0ull;
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  constexpr long long kChunk = (long long)kRemapBlock * kRemapPx;
-  const long long n_chunks = (n_px + kChunk - 1) / kChunk;
   unsigned long long err = 0ull;
-  bool staged = false;
   __syncthreads();
 
-  for (long long chunk = bid; chunk < n_chunks; chunk += nblk) {          // (block uniform: the barriers below are safe)
-    const long long base = chunk * kChunk + threadIdx.x;
-    uint32_t px[kRemapPx], bkey[kRemapPx], bidx[kRemapPx];
-#pragma unroll
-    for (int q = 0; q < kRemapPx; ++q) {
-      const long long p = base + (long long)q * kRemapBlock;
-      px[q] = p < n_px ? remap_pack_px(rgb + p * 3) : 0u;
-      bkey[q] = 0xFFFFFFFFu;
-      bidx[q] = 0u;
-    }
-    for (int t = 0; t < n_tiles; ++t) {
-      const int tile_base = t * kRemapTile, len = min(kRemapTile, K - tile_base), len2 = (len + 1) & ~1;
-      if (n_tiles > 1 || !staged) {
-        __syncthreads();                                                               // every wave is done with the previous tile
-        RemapEntry* s_e = reinterpret_cast<RemapEntry*>(s_pal);
-        for (int j = threadIdx.x; j < len2; j += kRemapBlock) s_e[j] = remap_pack_entry(pal + (long long)(tile_base + min(j, len - 1)) * 3, j);
-        __syncthreads();
-        staged = true;
-      }
-      uint32_t best[kRemapPx];
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) best[q] = 0xFFFFFFFFu;
-#pragma unroll 2
-      for (int j = 0; j < len2 / 2; ++j) {
-        const uint4 e = s_pal[j];                                                      // wave-uniform address: broadcast
-#pragma unroll
-        for (int q = 0; q < kRemapPx; ++q) {
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.x, e.y}));
-          best[q] = min(best[q], remap_eval(px[q], RemapEntry{e.z, e.w}));
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < kRemapPx; ++q) remap_carry(best[q], tile_base, bkey[q], bidx[q]);
-    }
+  remap_search(rgb, n_px, pal, K, bid, nblk, [&](long long base, auto& px, auto& bkey, auto& bidx) {
 #pragma unroll
     for (int q = 0; q < kRemapPx; ++q) {
       const long long p = base + (long long)q * kRemapBlock;
@@ -102,7 +64,7 @@ __device__ __forceinline__ void refine_assign_body(const uint8_t* __restrict__ r
         refine_add(tab + (size_t)bidx[q] * 4, w, wr, wg, wb);
       }
     }
-  }
+  });
   err = wave_sum(err);
   if (lane == 0) s_err[wv] = err;
   __syncthreads();
@@ -147,10 +109,7 @@ __device__ __forceinline__ void refine_update_body(uint8_t* __restrict__ pal, in
 
 static inline int refine_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels, const void* palette, int32_t K, const void* cls, int32_t n_classes,
                         const int32_t* weights, int32_t max_iter, const void* history, const void* n_iter, RefineWeights* wt) {
-  if (!rgb || !palette || !history || !n_iter) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: null argument");
-  if (K < 1 || n_pixels < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: K >= 1 and n_pixels >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: n_classes must be 0 without a class map");
+  if (const int rc = search_check(ctx, "palette_refine", !rgb || !palette || !history || !n_iter, n_pixels, K, cls, n_classes)) return rc;
   if (max_iter < 1 || max_iter > kRefineMaxIter) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: max_iter must be 1..64");
   bool any = false;
   for (int i = 0; i <= n_classes; ++i) {
@@ -161,8 +120,7 @@ static inline int refine_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels
   }
   if (!any) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: at least one weight must be > 0");
   if (((uintptr_t)history & 7) || ((uintptr_t)n_iter & 3)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: misaligned history or n_iter");
-  if (K > kRemapMaxK) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_refine: at most 65536 colours");
-  return 0;
+  return search_limit(ctx, "palette_refine", K);
 }
 
 }  // namespace rhccq

@@ -10,8 +10,8 @@
 // floor 10 with error 2 against 11 with error 1.)
 //
 // Device form: two launches per iteration, max_iter iterations queued on the stream, no host synchronisation.
-//   assign      the remap kernel's chunk loop (256 lanes x 8 pixels, palette tiles through LDS) that stores no index: it adds
-//               (w, w r, w g, w b) to the winner's accumulator row and w * dist to a per-lane 64-bit sum.
+//   assign      remap_search (palette_remap.h: 256 lanes x 8 pixels, palette tiles through LDS); after each chunk it adds
+//               (w, w r, w g, w b) to the winner's accumulator row and w * dist to a per-lane 64-bit sum.  It stores no index.
 //   update      one thread per row: new row, changed rows counted into history[i][1], accumulators cleared for the next iteration.
 // An iteration i > 0 runs iff history[i - 1][1] != 0: both kernels read that word first and return at once otherwise (the call zeroes
 // the history, so an iteration that did not run leaves 0 there and stops the ones behind it too).  Stream order between launches is
@@ -21,6 +21,8 @@
 // Integer addition: both forms give the same sums in any order.  Every field is 64-bit wherever it lives: a field grows by at most
 // 255 * 255 a pixel, so it cannot overflow below 2^64 / 65025 > 2^48 pixels (n_pixels is an int64 count of addressable bytes / 3).
 #include "palette_refine.h"
+
+#include <algorithm>
 
 namespace rhccq {
 
@@ -62,11 +64,9 @@ int rhccq_palette_refine(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, u
   RHCCQ_HIP(ctx, hipMemsetAsync(n_iter, 0, sizeof(int32_t), ctx->stream));
   if (n_pixels == 0) return 0;
   RHCCQ_HIP(ctx, hipMemsetAsync(work, 0, (size_t)rhccq_palette_refine_bytes(K), ctx->stream));
-  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const long long chunks = (n_pixels + (long long)kRemapBlock * kRemapPx - 1) / ((long long)kRemapBlock * kRemapPx);
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
   const long long cap = ctx->opt_refine_max_blocks > 0 ? ctx->opt_refine_max_blocks : (long long)ctx->compute_units * 8;
-  const long long blocks = chunks < cap ? chunks : cap;
-  const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks)), block(kRemapBlock), ugrid((unsigned)((K + 255) / 256));
+  const dim3 grid(remap_blocks(n_pixels, cap)), block(kRemapBlock), ugrid((unsigned)((K + 255) / 256));
   const int lds_rows = ctx->opt_refine_lds_rows < 0 ? kRefineLdsRows : ctx->opt_refine_lds_rows;
   const bool lds = K <= lds_rows;
   unsigned long long* acc = (unsigned long long*)work;
@@ -91,25 +91,15 @@ int rhccq_palette_refine_host(const uint8_t* rgb, int64_t n_pixels, uint8_t* pal
   for (int i = 0; i < max_iter * 2; ++i) history[i] = 0;
   *n_iter = 0;
   if (n_pixels == 0) return 0;
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  RemapEntry* ent = new RemapEntry[K];
-  uint64_t* acc = new uint64_t[(size_t)K * 4];
+  std::vector<uint64_t> acc((size_t)K * 4);
   for (int it = 0; it < max_iter; ++it) {
-    for (int j = 0; j < K; ++j) ent[j] = remap_pack_entry(palette + (int64_t)j * 3, j % kRemapTile);
-    for (size_t j = 0; j < (size_t)K * 4; ++j) acc[j] = 0;
+    const std::vector<RemapEntry> ent = remap_pack_palette(palette, K);
+    std::fill(acc.begin(), acc.end(), 0);
     uint64_t err = 0;
     for (int64_t p = 0; p < n_pixels; ++p) {
       const uint32_t px = remap_pack_px(rgb + p * 3);
-      uint32_t key = 0xFFFFFFFFu, idx = 0u;
-      for (int t = 0; t < n_tiles; ++t) {
-        const int tile_base = t * kRemapTile, len = K - tile_base < kRemapTile ? K - tile_base : kRemapTile;
-        uint32_t best = 0xFFFFFFFFu;
-        for (int j = 0; j < len; ++j) {
-          const uint32_t v = remap_eval(px, ent[tile_base + j]);
-          best = v < best ? v : best;
-        }
-        remap_carry(best, tile_base, key, idx);
-      }
+      uint32_t key;
+      const uint32_t idx = remap_search_host(px, ent, &key);
       const uint64_t w = wt.w[n_classes > 0 && cls[p] < n_classes ? cls[p] : n_classes];
       err += w * remap_dist(px, key);
       acc[idx * 4] += w;
@@ -131,8 +121,6 @@ int rhccq_palette_refine_host(const uint8_t* rgb, int64_t n_pixels, uint8_t* pal
     *n_iter = it + 1;
     if (!changed) break;
   }
-  delete[] acc;
-  delete[] ent;
   return 0;
 }
 

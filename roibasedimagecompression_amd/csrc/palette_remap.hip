@@ -13,13 +13,14 @@
 //     v_dot4_u32_u8 t = p . c'      v_lshl_add_u32 v = (t << 13) + w      (for each)      v_min3_u32 best = min(best, v0, v1)
 // 2.5 vector integer operations an evaluation, with the two entries read from LDS by all lanes at one address (a broadcast: no
 // bank conflict).
-// The host form runs the same pack / evaluate / carry functions serially.
-// The pack / evaluate / carry functions themselves are in palette_remap.h (the palette refinement assigns with them too).
+// The pack / evaluate / carry functions, the device loop that runs them (remap_search) and its serial host form (remap_search_host)
+// are in palette_remap.h: the palette refinement and the ladder's moments pass search with them too.
 #include "palette_remap.h"
 
 namespace rhccq {
 
-// The kernel's body (remap_body) and the argument check are in palette_remap.h: the batched form (palette_batch.hip) runs them per image.
+// The kernel's body (remap_body: remap_search and what follows a chunk) and the argument check are in palette_remap.h: the batched
+// form (palette_batch.hip) runs them per image.
 template <typename IdxT>
 __global__ __launch_bounds__(kRemapBlock) void palette_remap_kernel(const uint8_t* __restrict__ rgb, long long n_px,
                                                                     const uint8_t* __restrict__ pal, int K,
@@ -31,28 +32,17 @@ __global__ __launch_bounds__(kRemapBlock) void palette_remap_kernel(const uint8_
 template <typename IdxT>
 static void remap_host(const uint8_t* rgb, int64_t n_px, const uint8_t* pal, int K, const uint8_t* cls, int n_classes, IdxT* idx_out,
                        uint64_t* sums) {
-  const int n_tiles = (K + kRemapTile - 1) / kRemapTile;
-  RemapEntry* ent = new RemapEntry[K];
-  for (int j = 0; j < K; ++j) ent[j] = remap_pack_entry(pal + (int64_t)j * 3, j % kRemapTile);
+  const std::vector<RemapEntry> ent = remap_pack_palette(pal, K);
   for (int64_t p = 0; p < n_px; ++p) {
     const uint32_t px = remap_pack_px(rgb + p * 3);
-    uint32_t key = 0xFFFFFFFFu, idx = 0u;
-    for (int t = 0; t < n_tiles; ++t) {
-      const int tile_base = t * kRemapTile, len = K - tile_base < kRemapTile ? K - tile_base : kRemapTile;
-      uint32_t best = 0xFFFFFFFFu;
-      for (int j = 0; j < len; ++j) {
-        const uint32_t v = remap_eval(px, ent[tile_base + j]);
-        best = v < best ? v : best;
-      }
-      remap_carry(best, tile_base, key, idx);
-    }
+    uint32_t key;
+    const uint32_t idx = remap_search_host(px, ent, &key);
     const uint32_t d = remap_dist(px, key);
     idx_out[p] = (IdxT)idx;
     if (n_classes > 0 && cls[p] < n_classes) { sums[cls[p] * 2] += 1; sums[cls[p] * 2 + 1] += d; }
     sums[n_classes * 2] += 1;
     sums[n_classes * 2 + 1] += d;
   }
-  delete[] ent;
 }
 
 }  // namespace rhccq
@@ -69,25 +59,14 @@ int rhccq_palette_remap(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, co
   if (const int rc = remap_check(ctx, rgb, n_pixels, palette, K, cls, n_classes, idx_out, idx_elem_bytes, sums)) return rc;
   RHCCQ_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)(n_classes + 1) * 2 * sizeof(uint64_t), ctx->stream));
   if (n_pixels == 0) return 0;
-  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  const int cus = ctx->compute_units;
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
   // 8 workgroups of 4 waves per CU (the kernel needs 9280 bytes of LDS and at most 62 registers), never more than there are chunks
-  const long long chunks = (n_pixels + (long long)kRemapBlock * kRemapPx - 1) / ((long long)kRemapBlock * kRemapPx);
-  const long long blocks = chunks < (long long)cus * 8 ? chunks : (long long)cus * 8;
-  const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks)), block(kRemapBlock);
-  switch (idx_elem_bytes) {
-    case 1:
-      hipLaunchKernelGGL(palette_remap_kernel<uint8_t>, grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls,
-                         (int)n_classes, (uint8_t*)idx_out, (unsigned long long*)sums);
-      break;
-    case 2:
-      hipLaunchKernelGGL(palette_remap_kernel<uint16_t>, grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls,
-                         (int)n_classes, (uint16_t*)idx_out, (unsigned long long*)sums);
-      break;
-    default:
-      hipLaunchKernelGGL(palette_remap_kernel<uint32_t>, grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls,
-                         (int)n_classes, (uint32_t*)idx_out, (unsigned long long*)sums);
-  }
+  const dim3 grid(remap_blocks(n_pixels, (long long)ctx->compute_units * 8)), block(kRemapBlock);
+  index_dispatch(idx_elem_bytes, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(palette_remap_kernel<T>, grid, block, 0, ctx->stream, rgb, (long long)n_pixels, palette, (int)K, cls, (int)n_classes, (T*)idx_out,
+                       (unsigned long long*)sums);
+  });
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -96,11 +75,7 @@ int rhccq_palette_remap_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t
                              void* idx_out, int32_t idx_elem_bytes, uint64_t* sums) {
   if (const int rc = remap_check(nullptr, rgb, n_pixels, palette, K, cls, n_classes, idx_out, idx_elem_bytes, sums)) return rc;
   for (int i = 0; i < (n_classes + 1) * 2; ++i) sums[i] = 0;
-  switch (idx_elem_bytes) {
-    case 1: remap_host<uint8_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint8_t*)idx_out, sums); break;
-    case 2: remap_host<uint16_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint16_t*)idx_out, sums); break;
-    default: remap_host<uint32_t>(rgb, n_pixels, palette, K, cls, n_classes, (uint32_t*)idx_out, sums);
-  }
+  index_dispatch(idx_elem_bytes, [&](auto* t) { remap_host(rgb, n_pixels, palette, K, cls, n_classes, (decltype(t))idx_out, sums); });
   return 0;
 }
 

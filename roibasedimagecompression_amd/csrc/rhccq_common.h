@@ -28,7 +28,7 @@ struct rhccq_ctx {
   int opt_init_shards = 1;   // workgroups per problem of the second-generation chain: 1 = one (default), 2 / 4 / 8 = at most that many
   int opt_frame_chains = 1;  // rhccq_encode_frame: the level-1 k-means++ chains of a frame in one launch (1, default) or one per problem lane (0)
   int opt_frame_level2 = 1;  // rhccq_encode_frame: the level-2 palettes of all classes in one batch on one lane (1, default) or per class lane (0)
-  int compute_units = 0;     // of `device`, asked once by the first launch that sizes its grid by it (csrc/palette_remap.hip)
+  int compute_units = 0;     // of `device`, asked once by the first launch that sizes its grid by it (rhccq_compute_units)
   int opt_refine_lds_rows = -1;    // rhccq_palette_refine: palettes of more rows accumulate in global memory (-1: rhccq_palette_refine_lds_rows())
   int opt_refine_max_blocks = 0;   // rhccq_palette_refine: at most this many workgroups (0: 8 per CU)
   int opt_runs_rows = 0;           // rhccq_palette_runs: image rows of a workgroup (0: kRunsRowsDefault; 2, 4 or 8)
@@ -56,6 +56,12 @@ struct rhccq_ctx {
 static inline int rhccq_fail(rhccq_ctx* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
+}
+
+// ctx->compute_units, asked of the device on first use
+static inline int rhccq_compute_units(rhccq_ctx* ctx) {
+  if (ctx->compute_units <= 0) RHCCQ_HIP(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  return 0;
 }
 
 // copy a small host table into the context's device scratch (async on the stream; the host

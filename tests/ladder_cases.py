@@ -79,14 +79,31 @@ def _build():
     return out
 
 
+# The nearest-colour search's constructed ties (remap_cases), for the moments pass alone: equal distances inside a tile and across a
+# tile boundary, where the lowest row must win.  "expect" holds the indices.  Kept out of names(): no chain runs on them.
+TIE_NAMES = ["tie", "tie_reversed", "tie_duplicates", "boundary_tie", "boundary_tie_reversed", "boundary_duplicate", "boundary_nearer_looking",
+             "boundary_three_tiles", "boundary_later_strictly_nearer"]
+
+
+def _build_ties():
+    out = {}
+    for name in TIE_NAMES:
+        rgb, pal, cls, n_classes, expect = RM.case(name)
+        assert cls is None and n_classes == 0 and expect is not None and 1 <= len(rgb) <= 3 and len(pal) <= 2 * RM.T + 1
+        out[name] = {"rgb": rgb, "pal": pal, "cls": None, "n_classes": 0, "weights": [1], "expect": list(expect)}
+    return out
+
+
 _CASES = None
+_TIES = None
 
 
 def names(pixels=True):
     """pixels: only the cases that have any (a chain needs weight)"""
-    global _CASES
+    global _CASES, _TIES
     if _CASES is None:
-        _CASES = _build()
+        _CASES, _TIES = _build(), _build_ties()
+        assert not set(_CASES) & set(_TIES)
         for c in _CASES.values():
             for a in (c["rgb"], c["pal"], c["cls"]):
                 if a is not None:
@@ -95,8 +112,9 @@ def names(pixels=True):
 
 
 def case(name):
+    """a case of names() or of TIE_NAMES"""
     names()
-    return _CASES[name]
+    return _CASES[name] if name in _CASES else _TIES[name]
 
 
 def table_masks(c):
@@ -126,6 +144,7 @@ def reference(name):
     px = c["rgb"].reshape(-1, 3).astype(np.int64)
     K = len(c["pal"])
     idx, _ = RM.remap_reference(c["rgb"], c["pal"]) if len(px) else (np.zeros(0, np.int64), None)
+    assert "expect" not in c or idx.tolist() == c["expect"], name
     fields = np.concatenate([np.ones((len(px), 1), np.int64), px, (px * px).sum(axis=1, keepdims=True)], axis=1)
     masks = table_masks(c)
     mom = np.zeros((len(masks), K, 5), np.int64)

@@ -1,5 +1,5 @@
 """The host forms of the palette ladder (csrc/palette_ladder.hip: the device kernels' functions run serially) against numpy:
-rhccq_palette_moments_host against bincount sums over the remap reference's indices, rhccq_palette_curve_host against the error of
+rhccq_palette_moments_host against bincount sums over the remap reference's indices, also on the search's constructed ties, rhccq_palette_curve_host against the error of
 the pixels decoded through reduce_cases.reduce_reference's map and palette at every step, rhccq_palette_rung_host against
 rhccq_palette_reduce_host at every target, the bound the curve is for, and the argument errors.  No GPU."""
 import numpy as np
@@ -34,6 +34,19 @@ def test_moments_equal_bincount_sums(name):
     assert int(want_mom[-1, :, 0].sum()) == n and (n > 0 or not want_mom.any())
     if c["n_classes"] == 16:                                                    # values >= n_classes are in the last table alone
         assert int(want_mom[:-1, :, 0].sum()) < n
+
+
+@pytest.mark.parametrize("name", LD.TIE_NAMES)
+def test_moments_keep_the_lowest_row_on_a_tie(name):
+    """the search's constructed ties, inside a tile and across a tile boundary: every legal index width and no index buffer"""
+    c = LD.case(name)
+    want_idx, want_mom, _ = LD.reference(name)
+    assert want_idx.tolist() == c["expect"]
+    for width in (None,) + RM.index_bytes(len(c["pal"])):
+        rc, idx, mom = LD.host_moments(c["rgb"], c["pal"], None, 0, width)
+        assert rc == 0, (name, width)
+        assert np.array_equal(mom, want_mom), (name, width)
+        assert (idx is None) == (width is None) and (idx is None or idx.tolist() == c["expect"]), (name, width)
 
 
 def test_the_flat_cases_have_one_winner():
