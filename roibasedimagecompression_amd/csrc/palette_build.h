@@ -409,16 +409,9 @@ static inline int cells_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels,
                        CellsWeights* wt) {
   if (!rgb || !cells) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: null argument");
   if (n_pixels < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: n_pixels >= 0 is required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: n_classes must be 0 without a class map");
-  uint32_t top = 0u;
-  for (int i = 0; i <= n_classes; ++i) {
-    const int32_t w = weights ? weights[i] : 1;
-    if (w < 0 || w > 255) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: weights must be 0..255");
-    wt->w[i] = (uint32_t)w;
-    top = (uint32_t)w > top ? (uint32_t)w : top;
-  }
-  if (!top) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: at least one weight must be > 0");
+  if (const int rc = classes_check(ctx, "palette_cells", cls, n_classes)) return rc;
+  uint32_t top;
+  if (const int rc = weights_check(ctx, "palette_cells", weights, n_classes, wt->w, &top)) return rc;
   if ((uintptr_t)cells & 7) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_cells: misaligned cells (8)");
   if ((uint64_t)n_pixels > kCellsMaxSum / top) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_cells: n_pixels x the largest weight exceeds 2^32 - 1");
   return 0;

@@ -111,14 +111,8 @@ static inline int refine_check(rhccq_ctx* ctx, const void* rgb, int64_t n_pixels
                         const int32_t* weights, int32_t max_iter, const void* history, const void* n_iter, RefineWeights* wt) {
   if (const int rc = search_check(ctx, "palette_refine", !rgb || !palette || !history || !n_iter, n_pixels, K, cls, n_classes)) return rc;
   if (max_iter < 1 || max_iter > kRefineMaxIter) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: max_iter must be 1..64");
-  bool any = false;
-  for (int i = 0; i <= n_classes; ++i) {
-    const int32_t w = weights ? weights[i] : 1;
-    if (w < 0 || w > 255) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: weights must be 0..255");
-    wt->w[i] = (uint32_t)w;
-    any |= w > 0;
-  }
-  if (!any) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: at least one weight must be > 0");
+  uint32_t top;
+  if (const int rc = weights_check(ctx, "palette_refine", weights, n_classes, wt->w, &top)) return rc;
   if (((uintptr_t)history & 7) || ((uintptr_t)n_iter & 3)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_refine: misaligned history or n_iter");
   return search_limit(ctx, "palette_refine", K);
 }

@@ -142,13 +142,28 @@ static inline uint32_t remap_search_host(uint32_t px, const std::vector<RemapEnt
 
 // ---- argument checks, grid and index width shared by the remap, the refinement and the moments (`what`: the operation's name) ----
 static inline int remap_fail(rhccq_ctx* ctx, int code, const char* what, const char* msg) { return rhccq_fail(ctx, code, (std::string(what) + msg).c_str()); }
+// the class map and the number of classes (also of palette_runs.h's check and of the cells, palette_build.h)
+static inline int classes_check(rhccq_ctx* ctx, const char* what, const void* cls, int32_t n_classes) {
+  if (n_classes < 0 || n_classes > kRemapMaxClasses) return remap_fail(ctx, RHCCQ_E_ARG, what, ": n_classes must be 0..16");
+  if (!cls && n_classes != 0) return remap_fail(ctx, RHCCQ_E_ARG, what, ": n_classes must be 0 without a class map");
+  return 0;
+}
 // pixels, palette and class map; any_null: one of the operation's required pointers is null
 static inline int search_check(rhccq_ctx* ctx, const char* what, bool any_null, int64_t n_pixels, int32_t K, const void* cls, int32_t n_classes) {
   if (any_null) return remap_fail(ctx, RHCCQ_E_ARG, what, ": null argument");
   if (K < 1 || n_pixels < 0) return remap_fail(ctx, RHCCQ_E_ARG, what, ": K >= 1 and n_pixels >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return remap_fail(ctx, RHCCQ_E_ARG, what, ": n_classes must be 0..16");
-  if (!cls && n_classes != 0) return remap_fail(ctx, RHCCQ_E_ARG, what, ": n_classes must be 0 without a class map");
-  return 0;
+  return classes_check(ctx, what, cls, n_classes);
+}
+// the n_classes + 1 weights of the refinement and the cells (null: all ones) into the kernel's table; *top: the largest, which is > 0
+static inline int weights_check(rhccq_ctx* ctx, const char* what, const int32_t* weights, int32_t n_classes, uint32_t* table, uint32_t* top) {
+  *top = 0u;
+  for (int i = 0; i <= n_classes; ++i) {
+    const int32_t w = weights ? weights[i] : 1;
+    if (w < 0 || w > 255) return remap_fail(ctx, RHCCQ_E_ARG, what, ": weights must be 0..255");
+    table[i] = (uint32_t)w;
+    *top = (uint32_t)w > *top ? (uint32_t)w : *top;
+  }
+  return *top ? 0 : remap_fail(ctx, RHCCQ_E_ARG, what, ": at least one weight must be > 0");
 }
 // the last test of each: the one that is a limit and not an argument error
 static inline int search_limit(rhccq_ctx* ctx, const char* what, int32_t K) {

@@ -50,4 +50,24 @@ __host__ __device__ __forceinline__ uint32_t runs_class(const uint8_t* cls, long
   return c < (uint32_t)n_classes ? c : (uint32_t)n_classes;
 }
 
+// ---- shared by the host side of the run-carrying remap and of the row segmentation (palette_segment.hip), `what` the operation's name ----
+// the argument tests both have (`table`: the slack or the penalty of every class row); each appends its own last two in its own order
+static inline int rows_check(rhccq_ctx* ctx, const char* what, const void* rgb, int32_t H, int32_t W, const void* palette, int32_t K, const void* cls,
+                             int32_t n_classes, const uint32_t* table, const void* idx_out, int32_t idx_elem_bytes, const void* sums) {
+  if (!rgb || !palette || !idx_out || !sums || !table) return remap_fail(ctx, RHCCQ_E_ARG, what, ": null argument");
+  if (K < 1 || H < 0 || W < 0) return remap_fail(ctx, RHCCQ_E_ARG, what, ": K >= 1, H >= 0 and W >= 0 are required");
+  if (const int rc = classes_check(ctx, what, cls, n_classes)) return rc;
+  if (const int rc = index_check(ctx, what, idx_out, idx_elem_bytes)) return rc;
+  if ((uintptr_t)sums & 7) return remap_fail(ctx, RHCCQ_E_ARG, what, ": misaligned sums");
+  return index_rows_check(ctx, what, idx_elem_bytes, K);
+}
+// the host forms: one pixel's row of sums `v` added to its class row k (if it has one) and to the total, the last row
+template <int kCols>
+static inline void rows_add_host(uint64_t* sums, uint32_t k, int n_classes, const uint64_t (&v)[kCols]) {
+  for (int j = 0; j < kCols; ++j) {
+    if (k < (uint32_t)n_classes) sums[k * kCols + j] += v[j];
+    sums[n_classes * kCols + j] += v[j];
+  }
+}
+
 }  // namespace rhccq

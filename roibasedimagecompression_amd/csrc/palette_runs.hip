@@ -172,16 +172,8 @@ __global__ __launch_bounds__(kRunsLanes) void palette_runs_kernel(const uint8_t*
 
 static int runs_check(rhccq_ctx* ctx, const void* rgb, int32_t H, int32_t W, const void* palette, int32_t K, const void* cls, int32_t n_classes,
                       const uint32_t* slack, const void* idx_out, int32_t idx_elem_bytes, const void* sums) {
-  if (!rgb || !palette || !idx_out || !sums || !slack) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: null argument");
-  if (K < 1 || H < 0 || W < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: K >= 1, H >= 0 and W >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: n_classes must be 0 without a class map");
-  if (idx_elem_bytes != 1 && idx_elem_bytes != 2 && idx_elem_bytes != 4)
-    return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: idx_elem_bytes must be 1, 2 or 4");
-  if ((uintptr_t)idx_out & (uintptr_t)(idx_elem_bytes - 1)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: misaligned indices");
-  if ((uintptr_t)sums & 7) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: misaligned sums");
-  if (idx_elem_bytes == 1 && K > 256) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: 1-byte indices hold at most 256 colours");
-  if (K > kRemapMaxK) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_runs: at most 65536 colours");
+  if (const int rc = rows_check(ctx, "palette_runs", rgb, H, W, palette, K, cls, n_classes, slack, idx_out, idx_elem_bytes, sums)) return rc;
+  if (const int rc = search_limit(ctx, "palette_runs", K)) return rc;
   for (int i = 0; i <= n_classes; ++i)
     if (slack[i] > kRunsMaxSlack) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_runs: a slack is at most 195075");
   return 0;
@@ -196,12 +188,8 @@ static void runs_host(const uint8_t* rgb, int H, int W, const uint8_t* pal, cons
       const long long p = (long long)y * W + x;
       const uint32_t px = remap_pack_px(rgb + p * 3), b = (uint32_t)idx[p], pb = remap_pack_px(pal + (long long)b * 3);
       runs_step(st, px, runs_limit(px, pb, slack[runs_class(cls, p, n_classes)], x == 0), b, pb);
-      const uint32_t d = runs_dist(px, st.col), car = st.idx != b ? 1u : 0u;
       idx[p] = (IdxT)st.idx;
-      if (n_classes > 0 && cls[p] < n_classes) { sums[cls[p] * 3] += 1; sums[cls[p] * 3 + 1] += d; sums[cls[p] * 3 + 2] += car; }
-      sums[n_classes * 3] += 1;
-      sums[n_classes * 3 + 1] += d;
-      sums[n_classes * 3 + 2] += car;
+      rows_add_host(sums, runs_class(cls, p, n_classes), n_classes, {1, runs_dist(px, st.col), st.idx != b ? 1u : 0u});
     }
   }
 }
@@ -233,19 +221,11 @@ int rhccq_palette_runs(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W,
   const int rows = ctx->opt_runs_rows > 0 ? ctx->opt_runs_rows : kRunsRowsDefault;
   const dim3 grid((unsigned)((H + rows - 1) / rows)), block(kRunsLanes);
   const size_t lds = runs_lds_bytes(rows, K, n_classes);                               // at most 41 088 bytes: below the 64 KiB a launch gets unasked
-  switch (idx_elem_bytes) {
-    case 1:
-      hipLaunchKernelGGL(palette_runs_kernel<uint8_t>, grid, block, lds, ctx->stream, rgb, (int)H, (int)W, palette, (int)K, cls, (int)n_classes,
-                         slack, rows, (uint8_t*)idx_out, (unsigned long long*)sums);
-      break;
-    case 2:
-      hipLaunchKernelGGL(palette_runs_kernel<uint16_t>, grid, block, lds, ctx->stream, rgb, (int)H, (int)W, palette, (int)K, cls, (int)n_classes,
-                         slack, rows, (uint16_t*)idx_out, (unsigned long long*)sums);
-      break;
-    default:
-      hipLaunchKernelGGL(palette_runs_kernel<uint32_t>, grid, block, lds, ctx->stream, rgb, (int)H, (int)W, palette, (int)K, cls, (int)n_classes,
-                         slack, rows, (uint32_t*)idx_out, (unsigned long long*)sums);
-  }
+  index_dispatch(idx_elem_bytes, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    hipLaunchKernelGGL(palette_runs_kernel<T>, grid, block, lds, ctx->stream, rgb, (int)H, (int)W, palette, (int)K, cls, (int)n_classes, slack, rows,
+                       (T*)idx_out, (unsigned long long*)sums);
+  });
   RHCCQ_LAUNCH_CHECK(ctx);
   return 0;
 }
@@ -258,11 +238,7 @@ int rhccq_palette_runs_host(const uint8_t* rgb, int32_t H, int32_t W, const uint
   if (n == 0) return 0;
   uint64_t remap_sums[2];
   if (const int rc = rhccq_palette_remap_host(rgb, n, palette, K, nullptr, 0, idx_out, idx_elem_bytes, remap_sums)) return rc;
-  switch (idx_elem_bytes) {
-    case 1: runs_host<uint8_t>(rgb, H, W, palette, cls, n_classes, slack, (uint8_t*)idx_out, sums); break;
-    case 2: runs_host<uint16_t>(rgb, H, W, palette, cls, n_classes, slack, (uint16_t*)idx_out, sums); break;
-    default: runs_host<uint32_t>(rgb, H, W, palette, cls, n_classes, slack, (uint32_t*)idx_out, sums);
-  }
+  index_dispatch(idx_elem_bytes, [&](auto* t) { runs_host(rgb, H, W, palette, cls, n_classes, slack, (decltype(t))idx_out, sums); });
   return 0;
 }
 

@@ -235,19 +235,10 @@ __global__ __launch_bounds__(kSegLanes) void palette_segment_kernel(const uint8_
 
 static int seg_check(rhccq_ctx* ctx, const void* rgb, int32_t H, int32_t W, const void* palette, int32_t K, const void* cls, int32_t n_classes,
                      const uint32_t* penalty, const void* idx_out, int32_t idx_elem_bytes, const void* sums) {
-  if (!rgb || !palette || !idx_out || !sums || !penalty) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: null argument");
-  if (K < 1 || H < 0 || W < 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: K >= 1, H >= 0 and W >= 0 are required");
-  if (n_classes < 0 || n_classes > kRemapMaxClasses) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: n_classes must be 0..16");
-  if (!cls && n_classes != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: n_classes must be 0 without a class map");
-  if (idx_elem_bytes != 1 && idx_elem_bytes != 2 && idx_elem_bytes != 4)
-    return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: idx_elem_bytes must be 1, 2 or 4");
-  if ((uintptr_t)idx_out & (uintptr_t)(idx_elem_bytes - 1)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: misaligned indices");
-  if ((uintptr_t)sums & 7) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: misaligned sums");
-  if (idx_elem_bytes == 1 && K > 256) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: 1-byte indices hold at most 256 colours");
+  if (const int rc = rows_check(ctx, "palette_segment", rgb, H, W, palette, K, cls, n_classes, penalty, idx_out, idx_elem_bytes, sums)) return rc;
   for (int i = 0; i <= n_classes; ++i)
     if (penalty[i] > kSegMaxPenalty) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_segment: a penalty is at most 16777215");
-  if (K > kRemapMaxK) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_segment: at most 65536 colours");
-  return 0;
+  return search_limit(ctx, "palette_segment", K);
 }
 
 // the (packed, slot 0) cost of column x from that of column x - 1, and the column's a and stay bits (bit c % 64 of word c / 64 of `stay`)
@@ -302,11 +293,7 @@ static int seg_host(const uint8_t* rgb, int H, int W, const uint8_t* pal, int K,
       const uint64_t d = runs_dist(remap_pack_px(rgb + p * 3), remap_pack_px(pal + (long long)c * 3));
       const uint64_t mov = c != b ? 1 : 0, brk = x > 0 && c != left ? 1 : 0;
       idx[p] = (IdxT)c;
-      if (k < (uint32_t)n_classes) { sums[k * 4] += 1; sums[k * 4 + 1] += d; sums[k * 4 + 2] += mov; sums[k * 4 + 3] += brk; }
-      sums[n_classes * 4] += 1;
-      sums[n_classes * 4 + 1] += d;
-      sums[n_classes * 4 + 2] += mov;
-      sums[n_classes * 4 + 3] += brk;
+      rows_add_host(sums, k, n_classes, {1, d, mov, brk});
       c = left;
     }
   }
@@ -374,11 +361,9 @@ int rhccq_palette_segment_host(const uint8_t* rgb, int32_t H, int32_t W, const u
   if (n == 0) return 0;
   uint64_t remap_sums[2];
   if (const int rc = rhccq_palette_remap_host(rgb, n, palette, K, nullptr, 0, idx_out, idx_elem_bytes, remap_sums)) return rc;
-  switch (idx_elem_bytes) {
-    case 1: return seg_host<uint8_t>(rgb, H, W, palette, K, cls, n_classes, penalty, (uint8_t*)idx_out, sums);
-    case 2: return seg_host<uint16_t>(rgb, H, W, palette, K, cls, n_classes, penalty, (uint16_t*)idx_out, sums);
-    default: return seg_host<uint32_t>(rgb, H, W, palette, K, cls, n_classes, penalty, (uint32_t*)idx_out, sums);
-  }
+  int rc = 0;
+  index_dispatch(idx_elem_bytes, [&](auto* t) { rc = seg_host(rgb, H, W, palette, K, cls, n_classes, penalty, (decltype(t))idx_out, sums); });
+  return rc;
 }
 
 }  // extern "C"

@@ -557,41 +557,21 @@ class ImageEncoder:
 
     # ---- the run-carrying remap (EXTENSION, no reference counterpart) ------------------------------------------------------------------
     @staticmethod
-    def _run_slack_args(fn, run_slack, masked):
-        """the run_slack keyword checked -> None (off), or {"slack": as given, "nonroi": s, "roi": s}"""
-        from .ops import RUN_SLACK_MAX
-        if run_slack is None:
+    def _run_arg(fn, name, key, most, value, masked):
+        """the keyword `name` (run_slack, run_penalty) checked -> None (off), or {key: as given, "nonroi": v, "roi": v}, each v in 0..most"""
+        if value is None:
             return None
-        if isinstance(run_slack, dict):
-            if sorted(run_slack) != ["nonroi", "roi"]:
-                raise ValueError(f'{fn}: run_slack is a number or a dict over "roi" and "nonroi"')
+        if isinstance(value, dict):
+            if sorted(value) != ["nonroi", "roi"]:
+                raise ValueError(f'{fn}: {name} is a number or a dict over "roi" and "nonroi"')
             if not masked:
-                raise ValueError(f"{fn}: a roi / nonroi run_slack needs roi_mask")
-            given = {k: int(v) for k, v in run_slack.items()}
-            out = {"slack": given, "nonroi": given["nonroi"], "roi": given["roi"]}
+                raise ValueError(f"{fn}: a roi / nonroi {name} needs roi_mask")
+            given = {k: int(v) for k, v in value.items()}
+            out = {key: given, "nonroi": given["nonroi"], "roi": given["roi"]}
         else:
-            out = {"slack": int(run_slack), "nonroi": int(run_slack), "roi": int(run_slack)}
-        if not (0 <= out["nonroi"] <= RUN_SLACK_MAX and 0 <= out["roi"] <= RUN_SLACK_MAX):
-            raise ValueError(f"{fn}: a run_slack must be 0..{RUN_SLACK_MAX}")
-        return out
-
-    @staticmethod
-    def _run_penalty_args(fn, run_penalty, masked):
-        """the run_penalty keyword checked -> None (off), or {"penalty": as given, "nonroi": p, "roi": p}"""
-        from .ops import RUN_PENALTY_MAX
-        if run_penalty is None:
-            return None
-        if isinstance(run_penalty, dict):
-            if sorted(run_penalty) != ["nonroi", "roi"]:
-                raise ValueError(f'{fn}: run_penalty is a number or a dict over "roi" and "nonroi"')
-            if not masked:
-                raise ValueError(f"{fn}: a roi / nonroi run_penalty needs roi_mask")
-            given = {k: int(v) for k, v in run_penalty.items()}
-            out = {"penalty": given, "nonroi": given["nonroi"], "roi": given["roi"]}
-        else:
-            out = {"penalty": int(run_penalty), "nonroi": int(run_penalty), "roi": int(run_penalty)}
-        if not (0 <= out["nonroi"] <= RUN_PENALTY_MAX and 0 <= out["roi"] <= RUN_PENALTY_MAX):
-            raise ValueError(f"{fn}: a run_penalty must be 0..{RUN_PENALTY_MAX}")
+            out = {key: int(value), "nonroi": int(value), "roi": int(value)}
+        if not (0 <= out["nonroi"] <= most and 0 <= out["roi"] <= most):
+            raise ValueError(f"{fn}: a {name} must be 0..{most}")
         return out
 
     @staticmethod
@@ -603,8 +583,8 @@ class ImageEncoder:
             # the only bound the segmentation gives a pixel is its two boundaries' penalties: too loose to choose a rung by
             raise ValueError(f"{fn}: run_penalty cannot be combined with target_psnr")
         if run_penalty is not None:
-            return ImageEncoder._run_penalty_args(fn, run_penalty, masked)
-        return ImageEncoder._run_slack_args(fn, run_slack, masked)
+            return ImageEncoder._run_arg(fn, "run_penalty", "penalty", ops.RUN_PENALTY_MAX, run_penalty, masked)
+        return ImageEncoder._run_arg(fn, "run_slack", "slack", ops.RUN_SLACK_MAX, run_slack, masked)
 
     def _runs_call(self, rgb, pal, cls, runs):
         """the final index map by the rule `runs` names: the greedy carry (Rhccq.palette_runs) or the exact row segmentation

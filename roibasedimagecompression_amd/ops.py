@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _palette_args as A
 from ._lib import MbkProblem, RhccqError
 from .mt import MtWords
 
@@ -1055,26 +1056,10 @@ class Rhccq:
         (indices device tensor of rgb's leading shape: uint8 when K <= 256, else int16 holding uint16; sums device int64
         [n_classes + 1, 2]: row c = {pixels, sum of squared errors} of class c, the last row over every pixel).  Each index is the
         nearest palette row in exact integers, ties to the lowest row."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_remap: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
-        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
-            raise ValueError("palette_remap: rgb [..., 3] and palette [K, 3] are expected")
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_remap")
         n, K = rgb.numel() // 3, int(palette.shape[0])
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != n:
-                raise ValueError("palette_remap: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_remap: n_classes without a class map")
-        idx = self.empty(tuple(rgb.shape[:-1]), torch.uint8 if K <= 256 else torch.int16)
+        cls = A.class_map(class_map, n, n_classes, self.device, "palette_remap")
+        idx = self.empty(tuple(rgb.shape[:-1]), A.index_dtype(K))
         sums = self.empty((int(n_classes) + 1, 2), torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             if not 0 <= int(n_classes) <= 16 or K < 1 or K > 65536:
@@ -1092,39 +1077,18 @@ class Rhccq:
         [n_classes + 1, 3]: row c = {pixels, sum of squared errors, carried pixels} of class c, the last row over every pixel).
         Along every image row a pixel keeps its left neighbour's index while that costs at most its slack more squared error
         than its nearest row (palette_remap's); a tie keeps the neighbour's.  Exact integers."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_runs: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
-        if rgb.ndim != 3 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
-            raise ValueError("palette_runs: rgb [H, W, 3] and palette [K, 3] are expected")
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_runs", rows=True)
         H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
-        table = [int(slack)] * (max(n_classes, 0) + 1) if np.ndim(slack) == 0 else [int(v) for v in slack]
-        if len(table) != n_classes + 1:
-            raise ValueError("palette_runs: slack is one integer or n_classes + 1 of them")
-        if min(table) < 0 or max(table) > RUN_SLACK_MAX:
-            raise ValueError(f"palette_runs: a slack must be 0..{RUN_SLACK_MAX}")
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != H * W:
-                raise ValueError("palette_runs: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_runs: n_classes without a class map")
-        idx = self.empty((H, W), torch.uint8 if K <= 256 else torch.int16)
+        _, table = A.class_table(slack, n_classes, RUN_SLACK_MAX, "palette_runs", "slack")
+        cls = A.class_map(class_map, H * W, n_classes, self.device, "palette_runs")
+        idx = self.empty((H, W), A.index_dtype(K))
         sums = self.empty((n_classes + 1, 3), torch.int64)
         if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
             if not 0 <= n_classes <= 16 or K < 1 or K > 65536:
                 raise RhccqError("palette_runs: K must be 1..65536 and n_classes 0..16")
             return idx, sums.zero_()
-        tarr = (C.c_uint32 * len(table))(*table)
-        self._check(self.lib.rhccq_palette_runs(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes,
-                                                C.cast(tarr, C.c_void_p), self._p(idx), idx.element_size(), self._p(sums)), "palette_runs")
+        self._check(self.lib.rhccq_palette_runs(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table, self._p(idx),
+                                                idx.element_size(), self._p(sums)), "palette_runs")
         return idx, sums
 
     # -- exact row segmentation onto a given palette (EXTENSION: csrc/palette_segment.hip) ---------------------------------
@@ -1137,42 +1101,20 @@ class Rhccq:
         plus the penalty of every pixel whose index differs from its left neighbour's (a break), exactly: the 1-D Potts
         segmentation by its K-state dynamic programme in integers (include/rhccq.h pins ties).  The workspace (the full plane of
         decisions, rhccq_palette_segment_bytes) is a torch allocation of this call."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_segment: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
-        if rgb.ndim != 3 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
-            raise ValueError("palette_segment: rgb [H, W, 3] and palette [K, 3] are expected")
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_segment", rows=True)
         H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
-        table = [int(penalty)] * (max(n_classes, 0) + 1) if np.ndim(penalty) == 0 else [int(v) for v in penalty]
-        if len(table) != n_classes + 1:
-            raise ValueError("palette_segment: penalty is one integer or n_classes + 1 of them")
-        if min(table) < 0 or max(table) > RUN_PENALTY_MAX:
-            raise ValueError(f"palette_segment: a penalty must be 0..{RUN_PENALTY_MAX}")
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != H * W:
-                raise ValueError("palette_segment: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_segment: n_classes without a class map")
+        _, table = A.class_table(penalty, n_classes, RUN_PENALTY_MAX, "palette_segment", "penalty")
+        cls = A.class_map(class_map, H * W, n_classes, self.device, "palette_segment")
         if K < 1 or K > palette_segment_max_rows() or not 0 <= n_classes <= 16:
             raise RhccqError(f"palette_segment: K must be 1..{palette_segment_max_rows()} on the device and n_classes 0..16")
-        idx = self.empty((H, W), torch.uint8 if K <= 256 else torch.int16)
+        idx = self.empty((H, W), A.index_dtype(K))
         sums = self.empty((n_classes + 1, 4), torch.int64)
         if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
             return idx, sums.zero_()
         nbytes = int(self.lib.rhccq_palette_segment_bytes(H, W, K))
         work = self.empty((nbytes // 8,), torch.int64)
-        tarr = (C.c_uint32 * len(table))(*table)
-        self._check(self.lib.rhccq_palette_segment(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes,
-                                                   C.cast(tarr, C.c_void_p), self._p(work), nbytes, self._p(idx), idx.element_size(),
-                                                   self._p(sums)), "palette_segment")
+        self._check(self.lib.rhccq_palette_segment(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table,
+                                                   self._p(work), nbytes, self._p(idx), idx.element_size(), self._p(sums)), "palette_segment")
         return idx, sums
 
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------
@@ -1183,42 +1125,22 @@ class Rhccq:
         [max_iter, 2]: row i = {weighted sum of squared errors the iteration's assignment found, rows it changed}, zero from
         n_iter on; n_iter device int32[1]).  Each iteration assigns every pixel as palette_remap does and moves every row that
         received pixels to their weighted mean rounded to nearest; it stops after the first iteration that changes no row."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_refine: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
-        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
-            raise ValueError("palette_refine: rgb [..., 3] and palette [K, 3] are expected")
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_refine")
         n, K, max_iter = rgb.numel() // 3, int(palette.shape[0]), int(max_iter)
-        w = None if weights is None else [int(v) for v in weights]
-        if w is not None and len(w) < 1:
-            raise ValueError("palette_refine: weights must have n_classes + 1 entries")
+        w, warg = A.class_weights(weights, None, "palette_refine")
         n_classes = 0 if w is None else len(w) - 1
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != n:
-                raise ValueError("palette_refine: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_refine: class weights without a class map")
+        cls = A.class_map(class_map, n, n_classes, self.device, "palette_refine", without="class weights")
         out = palette.clone()
         history = self.empty((max(max_iter, 0), 2), torch.int64)
         n_iter = self.empty((1,), torch.int32)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
-            if not 0 <= n_classes <= 16 or K < 1 or K > 65536 or not 1 <= max_iter <= 64 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+            if not 0 <= n_classes <= 16 or K < 1 or K > 65536 or not 1 <= max_iter <= 64 or A.bad_weights(w):
                 raise RhccqError("palette_refine: K must be 1..65536, max_iter 1..64, weights 0..255 (n_classes + 1 <= 17 of them, one > 0)")
             return out, history.zero_(), n_iter.zero_()
         wbytes = int(self._raw.rhccq_palette_refine_bytes(K)) if K >= 1 else 0
         work = self.empty((max(wbytes // 8, 1),), torch.int64)
-        warr = None if w is None else (C.c_int32 * len(w))(*w)
-        self._check(self.lib.rhccq_palette_refine(self.ctx, self._p(rgb), n, self._p(out), K, self._p(cls), n_classes,
-                                                  C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), max_iter, self._p(work),
-                                                  wbytes, self._p(history), self._p(n_iter)), "palette_refine")
+        self._check(self.lib.rhccq_palette_refine(self.ctx, self._p(rgb), n, self._p(out), K, self._p(cls), n_classes, warg, max_iter,
+                                                  self._p(work), wbytes, self._p(history), self._p(n_iter)), "palette_refine")
         return out, history, n_iter
 
     # -- reduction of a given palette to N rows: exact pairwise merging (EXTENSION: csrc/palette_reduce.hip) ------------
@@ -1229,25 +1151,10 @@ class Rhccq:
         Pairwise-nearest-neighbour merging by Ward's criterion in exact integers (include/rhccq.h): the two clusters whose union
         costs least merge, ties to the lowest rows, the merged centre is the weighted mean rounded to nearest.  k_out =
         min(colours, rows of non-zero count) is read back once.  K above palette_reduce_max_rows() raises RhccqError."""
-        def on_device(a, dtype, what):
-            if not torch.is_tensor(a):
-                a = np.ascontiguousarray(a)
-                if dtype is torch.int64:
-                    if a.dtype.kind not in "iu":
-                        raise TypeError(f"palette_reduce: {what} must be integers, got {a.dtype}")
-                    a = a.astype(np.uint64).view(np.int64)
-                a = torch.from_numpy(a)
-            if a.dtype != dtype and not (dtype is torch.int64 and a.dtype in (torch.int32, torch.uint8, torch.int16)):
-                raise TypeError(f"palette_reduce: {what} must be {dtype}, got {a.dtype}")
-            return a.to(self.device).to(dtype).contiguous()
-        palette = on_device(palette, torch.uint8, "palette")
-        counts = on_device(counts, torch.int64, "counts")
-        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
-            raise ValueError("palette_reduce: palette [K, 3] and counts [K] are expected")
-        K, target = int(palette.shape[0]), int(colours)
-        cap = palette_reduce_max_rows()
-        if K > cap:
-            raise RhccqError(f"palette_reduce: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        palette = A.as_dtype(palette, torch.uint8, self.device, "palette_reduce", "palette")
+        counts = A.as_dtype(counts, torch.int64, self.device, "palette_reduce", "counts")
+        K, target = A.counted_rows(palette, counts, "palette_reduce"), int(colours)
+        A.rows_cap(K, palette_reduce_max_rows(), "palette_reduce")
         if K < 1 or not 1 <= target <= K:
             raise RhccqError("palette_reduce: K >= 1 and colours in 1..K are required")
         wbytes = int(self._raw.rhccq_palette_reduce_bytes(K))
@@ -1260,9 +1167,7 @@ class Rhccq:
         self._check(self.lib.rhccq_palette_reduce(self.ctx, self._p(palette), self._p(counts), K, target, self._p(work), wbytes, self._p(pal_out),
                                                   self._p(cnt_out), self._p(map_), self._p(merges), self._p(k_out)), "palette_reduce")
         k, live = torch.cat([k_out, (counts != 0).sum().to(torch.int32).reshape(1)]).tolist()     # the one read
-        if k < 0:                                            # the errors only the counts show come back through k_out
-            raise RhccqError(f"palette_reduce failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
-        n_steps = live - k
+        n_steps = live - A.k_out_rows(k, "palette_reduce")   # the errors only the counts show come back through k_out
         return pal_out[:k], cnt_out[:k], map_, merges[:max(n_steps, 0)]
 
     # -- a palette from the image: exact variance splits over a colour histogram (EXTENSION: csrc/palette_build.hip) ---------------
@@ -1272,29 +1177,11 @@ class Rhccq:
         int64[4, 32, 32, 32]: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3), N the summed weights, S the summed
         weight x channel value.  into: a table an earlier call returned; this call adds to it and returns it, so the tables of
         several frames sum into one.  One pass over the pixels, no read back."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_cells: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb = on_device(rgb, "rgb")
-        if rgb.ndim < 1 or rgb.shape[-1] != 3:
-            raise ValueError("palette_cells: rgb [..., 3] is expected")
+        rgb, _ = A.pixels(rgb, None, self.device, "palette_cells")
         n, n_classes = rgb.numel() // 3, int(n_classes)
-        w = None if weights is None else [int(v) for v in weights]
-        if w is not None and len(w) != n_classes + 1:
-            raise ValueError("palette_cells: weights must have n_classes + 1 entries")
-        d_cls = None
-        if cls is not None:
-            d_cls = on_device(cls, "cls")
-            if d_cls.numel() != n:
-                raise ValueError("palette_cells: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_cells: n_classes without a class map")
-        if not 0 <= n_classes <= 16 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+        w, warg = A.class_weights(weights, n_classes, "palette_cells")
+        d_cls = A.class_map(cls, n, n_classes, self.device, "palette_cells", what="cls")
+        if not 0 <= n_classes <= 16 or A.bad_weights(w):
             raise RhccqError("palette_cells: n_classes must be 0..16 and weights 0..255 with one > 0")
         if into is not None:
             if not torch.is_tensor(into) or into.dtype != torch.int64 or tuple(into.shape) != PALETTE_CELLS_SHAPE or not into.is_contiguous() \
@@ -1303,9 +1190,7 @@ class Rhccq:
         cells = into if into is not None else self.empty(PALETTE_CELLS_SHAPE, torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             return cells if into is not None else cells.zero_()
-        warr = None if w is None else (C.c_int32 * len(w))(*w)
-        self._check(self.lib.rhccq_palette_cells(self.ctx, self._p(rgb), n, self._p(d_cls), n_classes,
-                                                 C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), 1 if into is not None else 0,
+        self._check(self.lib.rhccq_palette_cells(self.ctx, self._p(rgb), n, self._p(d_cls), n_classes, warg, 1 if into is not None else 0,
                                                  self._p(cells)), "palette_cells")
         return cells
 
@@ -1315,13 +1200,7 @@ class Rhccq:
         (box, axis, t) of every split in order, boxes device uint8[k, 6]: lo then hi per box).  Greedy variance-minimising box
         splitting in exact integers (include/rhccq.h): the box whose best cut removes the most squared error is split, ties to the
         lowest box, axis and position; a row is the mean of its box's pixels rounded to nearest.  k <= colours is read back once."""
-        if not torch.is_tensor(cells):
-            a = np.ascontiguousarray(cells)
-            if a.dtype.kind not in "iu":
-                raise TypeError(f"palette_build: cells must be integers, got {a.dtype}")
-            cells = torch.from_numpy(a.astype(np.uint64).view(np.int64))
-        if cells.dtype != torch.int64:
-            raise TypeError(f"palette_build: cells must be int64, got {cells.dtype}")
+        cells = A.cells_table(cells, "palette_build")
         if tuple(cells.shape) != PALETTE_CELLS_SHAPE:
             raise ValueError("palette_build: cells [4, 32, 32, 32] is expected")
         cells = cells.to(self.device).contiguous()
@@ -1339,9 +1218,8 @@ class Rhccq:
         k_out = self.empty((1,), torch.int32)
         self._check(self.lib.rhccq_palette_build(self.ctx, self._p(cells), target, self._p(work), wbytes, self._p(pal_out), self._p(cnt_out),
                                                  self._p(boxes), self._p(splits), self._p(k_out)), "palette_build")
-        k = int(k_out.item())                                # the one read
-        if k < 0:                                            # the errors only the table shows come back through k_out
-            raise RhccqError(f"palette_build failed ({k}): " + ("the table is empty" if k == -1 else "the table's N adds up to more than 2^32 - 1"))
+        # the one read; the errors only the table shows come back through k_out
+        k = A.k_out_rows(int(k_out.item()), "palette_build", "the table is empty", "the table's N adds up to more than 2^32 - 1")
         return pal_out[:k], cnt_out[:k], splits[:k - 1], boxes[:k]
 
     # -- the palette build path for a batch of images (EXTENSION: csrc/palette_batch.hip) ----------------------------------------------
@@ -1349,17 +1227,7 @@ class Rhccq:
         """the arguments the four batched calls share -> (rgb device uint8, px_off host int64[B + 1], its device copy, class map device
         or None, pixels).  px_off_dev: a device int64 copy of px_off an earlier call of the family returned or the caller made (one
         upload for the four calls); None: this call uploads one"""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"{fn}: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb = on_device(rgb, "rgb")
-        if rgb.ndim < 1 or rgb.shape[-1] != 3:
-            raise ValueError(f"{fn}: rgb [..., 3] is expected")
+        rgb, _ = A.pixels(rgb, None, self.device, fn)
         n = rgb.numel() // 3
         off = np.ascontiguousarray(np.asarray(px_off.cpu() if torch.is_tensor(px_off) else px_off), dtype=np.int64).reshape(-1)
         if len(off) < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != n:
@@ -1369,11 +1237,7 @@ class Rhccq:
         elif not torch.is_tensor(px_off_dev) or px_off_dev.dtype != torch.int64 or px_off_dev.numel() != len(off) or not px_off_dev.is_contiguous() \
                 or px_off_dev.device != torch.device(self.device):
             raise ValueError(f"{fn}: px_off_dev must be a contiguous device int64 copy of px_off")
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != n:
-                raise ValueError(f"{fn}: the class map must have one element per pixel")
+        cls = A.class_map(class_map, n, 0, self.device, fn)          # (n_classes: each call tests it where its other arguments are done)
         return rgb, off, px_off_dev, cls, n
 
     def _batch_palettes(self, fn, palettes, k_rows, B):
@@ -1394,20 +1258,15 @@ class Rhccq:
         what palette_cells gives for image b alone.  One launch, no read back."""
         rgb, off, off_dev, d_cls, n = self._batch_pixels("palette_cells_batch", rgb, px_off, px_off_dev, cls)
         B, n_classes = len(off) - 1, int(n_classes)
-        w = None if weights is None else [int(v) for v in weights]
-        if w is not None and len(w) != n_classes + 1:
-            raise ValueError("palette_cells_batch: weights must have n_classes + 1 entries")
-        if d_cls is None and n_classes:
-            raise ValueError("palette_cells_batch: n_classes without a class map")
-        if not 0 <= n_classes <= 16 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+        w, warg = A.class_weights(weights, n_classes, "palette_cells_batch")
+        A.class_map(d_cls, n, n_classes, self.device, "palette_cells_batch")
+        if not 0 <= n_classes <= 16 or A.bad_weights(w):
             raise RhccqError("palette_cells_batch: n_classes must be 0..16 and weights 0..255 with one > 0")
         cells = self.empty((B,) + PALETTE_CELLS_SHAPE, torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             return cells.zero_()
-        warr = None if w is None else (C.c_int32 * len(w))(*w)
         self._check(self.lib.rhccq_palette_cells_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(d_cls), n_classes,
-                                                       C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), self._p(cells)),
-                    "palette_cells_batch")
+                                                       warg, self._p(cells)), "palette_cells_batch")
         return cells
 
     def palette_build_batch(self, cells, colours):
@@ -1416,13 +1275,7 @@ class Rhccq:
         device int32[B, colours - 1, 3], boxes device uint8[B, colours, 6], k device int32[B]): per image what palette_build gives,
         NOT trimmed and not read back: k[b] is the rows image b has (zero rows behind them), or the negative code of a table that is
         empty (-1) or adds up to more than 2^32 - 1 (-3), whose rows are all zero.  B chains run as B workgroups of one launch."""
-        if not torch.is_tensor(cells):
-            a = np.ascontiguousarray(cells)
-            if a.dtype.kind not in "iu":
-                raise TypeError(f"palette_build_batch: cells must be integers, got {a.dtype}")
-            cells = torch.from_numpy(a.astype(np.uint64).view(np.int64))
-        if cells.dtype != torch.int64:
-            raise TypeError(f"palette_build_batch: cells must be int64, got {cells.dtype}")
+        cells = A.cells_table(cells, "palette_build_batch")
         if cells.ndim != 5 or tuple(cells.shape[1:]) != PALETTE_CELLS_SHAPE or cells.shape[0] < 1:
             raise ValueError("palette_build_batch: cells [B >= 1, 4, 32, 32, 32] is expected")
         cells = cells.to(self.device).contiguous()
@@ -1453,11 +1306,10 @@ class Rhccq:
         B, n_classes = len(off) - 1, int(n_classes)
         palettes, k_rows = self._batch_palettes("palette_remap_batch", palettes, k_rows, B)
         K = int(palettes.shape[1])
-        if cls is None and n_classes:
-            raise ValueError("palette_remap_batch: n_classes without a class map")
+        A.class_map(cls, n, n_classes, self.device, "palette_remap_batch")
         if not 0 <= n_classes <= 16 or K > 65536:
             raise RhccqError("palette_remap_batch: K_stride must be 1..65536 and n_classes 0..16")
-        idx = self.empty((n,), torch.uint8 if K <= 256 else torch.int16)
+        idx = self.empty((n,), A.index_dtype(K))
         sums = self.empty((B, n_classes + 1, 2), torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             return idx, sums.zero_()
@@ -1476,13 +1328,10 @@ class Rhccq:
         B, max_iter = len(off) - 1, int(max_iter)
         palettes, k_rows = self._batch_palettes("palette_refine_batch", palettes, k_rows, B)
         K = int(palettes.shape[1])
-        w = None if weights is None else [int(v) for v in weights]
-        if w is not None and len(w) < 1:
-            raise ValueError("palette_refine_batch: weights must have n_classes + 1 entries")
+        w, warg = A.class_weights(weights, None, "palette_refine_batch")
         n_classes = 0 if w is None else len(w) - 1
-        if cls is None and n_classes:
-            raise ValueError("palette_refine_batch: class weights without a class map")
-        if not 0 <= n_classes <= 16 or K > 65536 or not 1 <= max_iter <= 64 or (w is not None and (min(w) < 0 or max(w) > 255 or not any(w))):
+        A.class_map(cls, n, n_classes, self.device, "palette_refine_batch", without="class weights")
+        if not 0 <= n_classes <= 16 or K > 65536 or not 1 <= max_iter <= 64 or A.bad_weights(w):
             raise RhccqError("palette_refine_batch: K_stride must be 1..65536, max_iter 1..64, weights 0..255 (n_classes + 1 <= 17 of them, one > 0)")
         out = palettes.clone()
         history = self.empty((B, max_iter, 2), torch.int64)
@@ -1491,30 +1340,15 @@ class Rhccq:
             return out, history.zero_(), n_iter.zero_()
         wbytes = int(self._raw.rhccq_palette_refine_batch_bytes(B, K))
         work = self.empty((wbytes // 8,), torch.int64)
-        warr = None if w is None else (C.c_int32 * len(w))(*w)
         self._check(self.lib.rhccq_palette_refine_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(out), K,
-                                                        self._p(k_rows), self._p(cls), n_classes,
-                                                        C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), max_iter, self._p(work), wbytes,
+                                                        self._p(k_rows), self._p(cls), n_classes, warg, max_iter, self._p(work), wbytes,
                                                         self._p(history), self._p(n_iter)), "palette_refine_batch")
         return out, history, n_iter
 
     # -- the palette ladder: moments, the error curve of every rung, any rung from the log (EXTENSION: csrc/palette_ladder.hip) ----
-    def _ladder_arg(self, a, dtype, what, fn):
-        """palette / counts / merges as a contiguous device tensor of `dtype` (counts: any integers, as palette_reduce takes them)"""
-        if not torch.is_tensor(a):
-            a = np.ascontiguousarray(a)
-            if dtype is torch.int64:
-                if a.dtype.kind not in "iu":
-                    raise TypeError(f"{fn}: {what} must be integers, got {a.dtype}")
-                a = a.astype(np.uint64).view(np.int64)
-            a = torch.from_numpy(a)
-        if a.dtype != dtype and not (dtype is torch.int64 and a.dtype in (torch.int32, torch.uint8, torch.int16)):
-            raise TypeError(f"{fn}: {what} must be {dtype}, got {a.dtype}")
-        return a.to(self.device).to(dtype).contiguous()
-
     def _ladder_log(self, merges, K, fn):
         """the merges of palette_reduce (device int32[n_steps, 2], any n_steps <= K - 1) as the int32[max(K - 1, 1), 2] the C entries read"""
-        merges = self._ladder_arg(merges, torch.int32, "merges", fn)
+        merges = A.as_dtype(merges, torch.int32, self.device, fn, "merges")
         if merges.ndim != 2 or merges.shape[1] != 2 or merges.shape[0] > max(K - 1, 0):
             raise ValueError(f"{fn}: merges [n_steps <= K - 1, 2] is expected")
         full = torch.full((max(K - 1, 1), 2), -1, dtype=torch.int32, device=self.device)
@@ -1526,28 +1360,12 @@ class Rhccq:
         (indices as palette_remap returns them, or None with want_indices=False; moments device int64[n_classes + 1, K, 5]: per
         table and palette row {N, Sr, Sg, Sb, Q} of the pixels whose nearest row it is -- their number, their channel sums and
         the sum of r^2 + g^2 + b^2; table c over the pixels of class c, the last table over every pixel).  One pass; unweighted."""
-        def on_device(a, what):
-            if not torch.is_tensor(a):
-                a = torch.from_numpy(np.ascontiguousarray(a))
-            if a.dtype == torch.bool:
-                a = a.view(torch.uint8)
-            if a.dtype != torch.uint8:
-                raise TypeError(f"palette_moments: {what} must be uint8, got {a.dtype}")
-            return a.to(self.device).contiguous()
-        rgb, palette = on_device(rgb, "rgb"), on_device(palette, "palette")
-        if rgb.ndim < 1 or rgb.shape[-1] != 3 or palette.ndim != 2 or palette.shape[1] != 3:
-            raise ValueError("palette_moments: rgb [..., 3] and palette [K, 3] are expected")
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_moments")
         n, K, n_classes = rgb.numel() // 3, int(palette.shape[0]), int(n_classes)
-        cls = None
-        if class_map is not None:
-            cls = on_device(class_map, "class_map")
-            if cls.numel() != n:
-                raise ValueError("palette_moments: the class map must have one element per pixel")
-        elif n_classes:
-            raise ValueError("palette_moments: n_classes without a class map")
+        cls = A.class_map(class_map, n, n_classes, self.device, "palette_moments")
         if not 0 <= n_classes <= 16 or K < 1 or K > 65536:
             raise RhccqError("palette_moments: K must be 1..65536 and n_classes 0..16")
-        idx = self.empty(tuple(rgb.shape[:-1]), torch.uint8 if K <= 256 else torch.int16) if want_indices else None
+        idx = self.empty(tuple(rgb.shape[:-1]), A.index_dtype(K)) if want_indices else None
         moments = self.empty((n_classes + 1, K, 5), torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             return idx, moments.zero_()
@@ -1560,17 +1378,13 @@ class Rhccq:
         int64[T, K, 5] (palette_moments') -> curve device int64[T, K]: curve[t, s] = the squared error of table t's pixels shown through
         the clusters after s merges, in exact integers; 0 behind the last step.  It bounds the error of the nearest-row remap onto
         that rung from above.  K above palette_reduce_max_rows() raises RhccqError."""
-        palette = self._ladder_arg(palette, torch.uint8, "palette", "palette_curve")
-        counts = self._ladder_arg(counts, torch.int64, "counts", "palette_curve")
-        moments = self._ladder_arg(moments, torch.int64, "moments", "palette_curve")
-        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
-            raise ValueError("palette_curve: palette [K, 3] and counts [K] are expected")
-        K = int(palette.shape[0])
+        palette = A.as_dtype(palette, torch.uint8, self.device, "palette_curve", "palette")
+        counts = A.as_dtype(counts, torch.int64, self.device, "palette_curve", "counts")
+        moments = A.as_dtype(moments, torch.int64, self.device, "palette_curve", "moments")
+        K = A.counted_rows(palette, counts, "palette_curve")
         if moments.ndim != 3 or moments.shape[1] != K or moments.shape[2] != 5 or not 1 <= moments.shape[0] <= 17:
             raise ValueError("palette_curve: moments [1..17, K, 5] are expected")
-        cap = palette_reduce_max_rows()
-        if K > cap:
-            raise RhccqError(f"palette_curve: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        A.rows_cap(K, palette_reduce_max_rows(), "palette_curve")
         if K < 1:
             raise RhccqError("palette_curve: K >= 1 is required")
         merges = self._ladder_log(merges, K, "palette_curve")
@@ -1588,14 +1402,10 @@ class Rhccq:
         palette_reduce(palette, counts, colours) returns, rebuilt from the log without the merge chain.  k_out is read back once.
         A log that ends before `colours` is reached gives the clusters it has (map names them all, the palette has the first
         `colours`).  K above palette_reduce_max_rows() raises RhccqError."""
-        palette = self._ladder_arg(palette, torch.uint8, "palette", "palette_rung")
-        counts = self._ladder_arg(counts, torch.int64, "counts", "palette_rung")
-        if palette.ndim != 2 or palette.shape[1] != 3 or counts.ndim != 1 or counts.shape[0] != palette.shape[0]:
-            raise ValueError("palette_rung: palette [K, 3] and counts [K] are expected")
-        K, target = int(palette.shape[0]), int(colours)
-        cap = palette_reduce_max_rows()
-        if K > cap:
-            raise RhccqError(f"palette_rung: {K} rows, the device form takes at most {cap} (palette_reduce_max_rows())")
+        palette = A.as_dtype(palette, torch.uint8, self.device, "palette_rung", "palette")
+        counts = A.as_dtype(counts, torch.int64, self.device, "palette_rung", "counts")
+        K, target = A.counted_rows(palette, counts, "palette_rung"), int(colours)
+        A.rows_cap(K, palette_reduce_max_rows(), "palette_rung")
         if K < 1 or not 1 <= target <= K:
             raise RhccqError("palette_rung: K >= 1 and colours in 1..K are required")
         merges = self._ladder_log(merges, K, "palette_rung")
@@ -1605,10 +1415,7 @@ class Rhccq:
         k_out = self.empty((1,), torch.int32)
         self._check(self.lib.rhccq_palette_rung(self.ctx, self._p(palette), self._p(counts), K, self._p(merges), target, self._p(pal_out),
                                                 self._p(cnt_out), self._p(map_), self._p(k_out)), "palette_rung")
-        k = int(k_out.item())                                # the one read
-        if k < 0:
-            raise RhccqError(f"palette_rung failed ({k}): " + ("every count is zero" if k == -1 else "the counts add up to more than 2^32 - 1"))
-        k = min(k, target)
+        k = min(A.k_out_rows(int(k_out.item()), "palette_rung"), target)       # the one read
         return pal_out[:k], cnt_out[:k], map_
 
     # -- split score (split_score.py:15-142) ----------------------------------------------------------

@@ -314,6 +314,7 @@ CELLS_ERRORS = [
     ("all weights zero", {"cls": True, "n_classes": 1, "weights": [0, 0]}, E_ARG),
     ("2^32 pixels", {"n_pixels": 1 << 32}, E_LIMIT),
     ("2^24 + 65794 pixels of weight 255", {"n_pixels": (1 << 24) + 65794, "weights": [255]}, E_LIMIT),      # 255 n = 2^32 + 254
+    ("a weight of 256 on 2^32 pixels", {"n_pixels": 1 << 32, "weights": [256]}, E_ARG),                   # the weights are tested before the limit
 ]
 # of rhccq_palette_build.  A valid call: K_target = 4 on a table of three pixels; "splits": None and "boxes": None are valid (optional)
 BUILD_ERRORS = [

@@ -232,7 +232,10 @@ ERRORS = [
     ("misaligned work", {"misalign": "work"}, E_ARG, True),
     ("short workspace", {"work_short": True}, E_ARG, True),
     ("K = 65537", {"K": 65537}, E_LIMIT, False),
+    ("max_iter = 0 with a weight of 256", {"max_iter": 0, "cls": True, "n_classes": 1, "weights": [256, 1]}, E_ARG, False),
 ]
+# max_iter is tested before the weights: both give E_ARG, so the device test tells them apart by the case's message
+ERROR_MESSAGES = {"max_iter = 0 with a weight of 256": "palette_refine: max_iter must be 1..64"}
 
 
 # ---- the frames of the encode_sequence test -------------------------------------------------------------------------------------------

@@ -196,6 +196,7 @@ ERRORS = [
     ("a class slack above 3 * 255^2", {"cls": True, "n_classes": 2, "slack": [0, MAX_SLACK + 1, 0]}, E_ARG),
     ("the last slack above 3 * 255^2", {"cls": True, "n_classes": 2, "slack": [0, 0, 1 << 31]}, E_ARG),
     ("K = 65537", {"K": 65537}, E_LIMIT),
+    ("K = 65537 with a slack above 3 * 255^2", {"K": 65537, "slack": [MAX_SLACK + 1]}, E_LIMIT),      # the colours are tested before the slack
 ]
 
 

@@ -251,6 +251,7 @@ ERRORS = [
     ("a class penalty 2^24", {"cls": True, "n_classes": 2, "penalty": [0, MAX_PENALTY + 1, 0]}, E_ARG),
     ("the last penalty 2^31", {"cls": True, "n_classes": 2, "penalty": [0, 0, 1 << 31]}, E_ARG),
     ("K = 65537", {"K": 65537}, E_LIMIT),
+    ("K = 65537 with penalty 2^24", {"K": 65537, "penalty": [MAX_PENALTY + 1]}, E_ARG),               # the penalty is tested before the colours
 ]
 # the device form's own: the workspace ("work": None = NULL, "odd" = off its alignment, "short" = one byte too few) and its row cap
 DEVICE_ERRORS = [

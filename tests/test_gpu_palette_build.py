@@ -116,11 +116,14 @@ def test_cells_python_surface_arguments(rh):
     rgb, cls, nc, weights = BC.pixel_case("classes_0_3_2")
     got = rh.palette_cells(rh.dev(rgb), rh.dev(cls), nc, weights)
     assert np.array_equal(got.cpu().numpy(), BC.pixel_reference("classes_0_3_2"))
-    for bad in (lambda: rh.palette_cells(rgb, None, 2, weights), lambda: rh.palette_cells(rgb, cls, 2, [1, 2]), lambda: rh.palette_cells(rgb, cls[:-1], nc, weights),
-                lambda: rh.palette_cells(rgb.reshape(-1), None), lambda: rh.palette_cells(rgb, into=np.zeros(BC.SHAPE, np.int64))):
-        with pytest.raises(ValueError):
+    for bad, msg in ((lambda: rh.palette_cells(rgb, None, 2, weights), "n_classes without a class map"),
+                     (lambda: rh.palette_cells(rgb, cls, 2, [1, 2]), r"weights must have n_classes \+ 1 entries"),
+                     (lambda: rh.palette_cells(rgb, cls[:-1], nc, weights), "the class map must have one element per pixel"),
+                     (lambda: rh.palette_cells(rgb.reshape(-1), None), r"rgb \[\.\.\., 3\] is expected"),
+                     (lambda: rh.palette_cells(rgb, into=np.zeros(BC.SHAPE, np.int64)), "into must be a table palette_cells returned")):
+        with pytest.raises(ValueError, match="palette_cells: " + msg):
             bad()
-    with pytest.raises(TypeError):
+    with pytest.raises(TypeError, match=r"palette_cells: rgb must be uint8, got torch\.int32"):
         rh.palette_cells(rgb.astype(np.int32))
     for bad in (lambda: rh.palette_cells(rgb, cls, 2, [0, 0, 0]), lambda: rh.palette_cells(rgb, cls, 2, [1, 256, 1])):
         with pytest.raises(RhccqError):
@@ -196,9 +199,9 @@ def test_build_python_surface_arguments(rh):
     cells = BC.chain_case("photo96_k64")[0]
     pal, counts, splits, boxes = rh.palette_build(rh.dev(cells), 64)
     assert np.array_equal(pal.cpu().numpy(), BC.chain_reference("photo96_k64")["palette"])
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match=r"palette_build: cells \[4, 32, 32, 32\] is expected"):
         rh.palette_build(np.asarray(cells)[:3], 4)
-    with pytest.raises(TypeError):
+    with pytest.raises(TypeError, match="palette_build: cells must be integers, got float32"):
         rh.palette_build(np.asarray(cells).astype(np.float32), 4)
     with pytest.raises(RhccqError):
         rh.palette_build(cells, 0)

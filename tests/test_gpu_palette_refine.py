@@ -148,7 +148,7 @@ def test_device_argument_errors(rh, what, over, code):
                                      C.cast(warr, C.c_void_p) if warr is not None else C.c_void_p(0), over.get("max_iter", 2), p("work"), wbytes,
                                      p("history"), p("n_iter"))
     assert rc == code, what
-    assert rh._raw.rhccq_last_error(rh.ctx).decode().startswith("palette_refine:")
+    assert rh._raw.rhccq_last_error(rh.ctx).decode().startswith(RF.ERROR_MESSAGES.get(what, "palette_refine:"))
 
 
 def test_zero_pixels(rh):
@@ -176,11 +176,11 @@ def test_python_surface(rh):
     pal3, hist3, _ = rh.palette_refine(c["rgb"], c["pal"])                      # no classes, all ones, max_iter = 8
     want3 = RF.refine_reference(c["rgb"], c["pal"])
     assert tuple(hist3.shape) == (8, 2) and np.array_equal(pal3.cpu().numpy(), want3[0]) and np.array_equal(hist3.cpu().numpy(), want3[1])
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="palette_refine: class weights without a class map"):
         rh.palette_refine(c["rgb"], c["pal"], None, [1, 2, 3])
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="palette_refine: the class map must have one element per pixel"):
         rh.palette_refine(c["rgb"], c["pal"], c["cls"][:-1], [1, 2, 3])
-    with pytest.raises(TypeError):
+    with pytest.raises(TypeError, match=r"palette_refine: rgb must be uint8, got torch\.int32"):
         rh.palette_refine(c["rgb"].astype(np.int32), c["pal"])
 
 

@@ -90,11 +90,11 @@ def test_device_tensor_arguments(rh):
     idx, sums = rh.palette_remap(rh.dev(rgb), pal, rh.dev(cls == 1), 2)            # a bool map: classes 0 / 1
     _, want = RM.remap_reference(rgb, pal, (cls == 1).astype(np.uint8), 2)
     assert np.array_equal(sums.cpu().numpy(), want)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="palette_remap: n_classes without a class map"):
         rh.palette_remap(rgb, pal, None, 2)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="palette_remap: the class map must have one element per pixel"):
         rh.palette_remap(rgb, pal, cls[:-1], 2)
-    with pytest.raises(TypeError):
+    with pytest.raises(TypeError, match=r"palette_remap: rgb must be uint8, got torch\.int32"):
         rh.palette_remap(rgb.astype(np.int32), pal)
 
 

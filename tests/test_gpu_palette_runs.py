@@ -114,12 +114,15 @@ def test_python_surface_arguments(rh):
     assert np.array_equal(_idx64(idx), want_out) and np.array_equal(sums.cpu().numpy(), want_sums)
     idx, sums = rh.palette_runs(np.zeros((0, 5, 3), np.uint8), pal, 7)
     assert tuple(idx.shape) == (0, 5) and sums.cpu().numpy().tolist() == [[0, 0, 0]]
-    for bad in (lambda: rh.palette_runs(rgb, pal, slack, None, 2), lambda: rh.palette_runs(rgb, pal, [1, 2], cls, 2),
-                lambda: rh.palette_runs(rgb, pal, RN.MAX_SLACK + 1), lambda: rh.palette_runs(rgb, pal, -1),
-                lambda: rh.palette_runs(rgb.reshape(-1, 3), pal, 0), lambda: rh.palette_runs(rgb, pal, slack, cls[:-1], 2)):
-        with pytest.raises(ValueError):
+    for bad, msg in ((lambda: rh.palette_runs(rgb, pal, slack, None, 2), "n_classes without a class map"),
+                     (lambda: rh.palette_runs(rgb, pal, [1, 2], cls, 2), r"slack is one integer or n_classes \+ 1 of them"),
+                     (lambda: rh.palette_runs(rgb, pal, RN.MAX_SLACK + 1), r"a slack must be 0\.\.195075"),
+                     (lambda: rh.palette_runs(rgb, pal, -1), r"a slack must be 0\.\.195075"),
+                     (lambda: rh.palette_runs(rgb.reshape(-1, 3), pal, 0), r"rgb \[H, W, 3\] and palette \[K, 3\] are expected"),
+                     (lambda: rh.palette_runs(rgb, pal, slack, cls[:-1], 2), "the class map must have one element per pixel")):
+        with pytest.raises(ValueError, match="palette_runs: " + msg):
             bad()
-    with pytest.raises(TypeError):
+    with pytest.raises(TypeError, match=r"palette_runs: rgb must be uint8, got torch\.int32"):
         rh.palette_runs(rgb.astype(np.int32), pal, 0)
 
 
