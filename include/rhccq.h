@@ -110,6 +110,10 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              rhccq_palette_runs_rows(), or 2, 4 or 8.  Fewer rows put more workgroups on more CUs and leave more
  *                              lanes of each wave idle in the walk.  Same results. */
 #define RHCCQ_OPT_RUNS_ROWS 13
+/*   RHCCQ_OPT_DITHER_ROWS      rhccq_palette_dither: the image rows of a band (one wave; 64 / rows lanes share a pixel's palette search):
+ *                              0 (default) = rhccq_palette_dither_rows(), or 4, 8, 16 or 32.  Fewer rows give every step of the wavefront
+ *                              a shorter search and the picture more bands to hand errors through.  Same results. */
+#define RHCCQ_OPT_DITHER_ROWS 14
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -918,6 +922,41 @@ int rhccq_palette_segment(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t
                           uint64_t* sums);
 int rhccq_palette_segment_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
                                const uint32_t* penalty, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+
+/* ---- EXTENSION: error-diffusing remap onto a given palette (no reference counterpart; csrc/palette_dither.hip) -------------------------
+ * rgb, palette, cls, n_classes, idx_out and idx_elem_bytes as rhccq_palette_runs takes them; strength uint32[n_classes + 1], each entry
+ * 0..256.  s(y, x) = strength[cls[p]] when cls[p] < n_classes and strength[n_classes] otherwise (and for every pixel when cls == NULL).
+ * Floyd-Steinberg error diffusion in exact integers, raster order (rows top to bottom, every row left to right, no serpentine).  With
+ * E(y, x, c) the error pixel (y, x) passes on in channel c (0 outside the picture), per pixel and channel:
+ *   A = 7 E(y, x-1) + E(y-1, x-1) + 5 E(y-1, x) + 3 E(y-1, x+1)                          |A| <= 4080
+ *   t = clamp(rgb + floor((s A + 2048) / 4096), 0, 255)                                   floor toward minus infinity
+ *   out(y, x) = rhccq_palette_remap's row of the uint8 triple t (nearest in exact integers, ties to the lowest row)
+ *   E(y, x, c) = t - palette[out(y, x)][c]                                                from the clamped t, -255..255
+ * The strength scales what a pixel RECEIVES: a pixel of strength 0 gets exactly the remap's index b(y, x) and still passes its own
+ * error on.  Strength 0 everywhere reproduces rhccq_palette_remap's indices; 256 is Floyd-Steinberg.  idx_out receives out; sums is
+ * uint64[n_classes + 1][3], zeroed by the call: row c = {pixels, sum of |rgb - palette[out]|^2 against the ORIGINAL pixel, pixels with
+ * out != b} over the pixels with cls[p] == c, the last row over every pixel.
+ * RHCCQ_E_ARG: as rhccq_palette_runs, and a null strength, a strength above 256; device form: a null status or one not aligned to 4, and
+ * with pixels a null workspace, one not aligned to 4, or work_bytes below rhccq_palette_dither_bytes(H, W).  RHCCQ_E_LIMIT: K > 65536;
+ * device form: K > rhccq_palette_dither_max_rows() (4096: the packed palette is 32 KiB of LDS and a row number 12 bits of the search's
+ * word).  H * W == 0 succeeds with zero sums and *status = 0 (and needs no workspace).
+ * Device form: every pointer but strength_host (copied by value into the launch) is device memory; async on the context stream, no host
+ * synchronisation, nothing allocated: rhccq_palette_remap into idx_out (b), memsets of sums, status and the workspace, then ONE launch
+ * that overwrites the indices where they differ.  A one-wave workgroup owns a band of RHCCQ_OPT_DITHER_ROWS image rows and walks them as a
+ * wavefront, pixel (y, x) at step x + 2 y; the last row of a band hands its errors to the next band through the workspace, one 32-bit
+ * word per pixel whose top bit marks it written (relaxed agent-scope atomics, no flag, no fence).  Bands take their numbers from a
+ * ticket in the workspace, so a band only ever waits for one that has started: no cooperative launch, no grid sized to residency.  The
+ * wait is bounded: if a band gives up, every band stops waiting and runs to its end, *status (device memory, written by the call) is
+ * non-zero and the indices and sums are unspecified; *status == 0 otherwise.  The workspace's contents before and after the call mean nothing.
+ * Host form: the same step functions (csrc/palette_dither.h) run serially on host memory, for any K <= 65536. */
+int32_t rhccq_palette_dither_max_rows(void);                  /* host only: the largest K of the device form */
+int32_t rhccq_palette_dither_rows(void);                      /* host only: the image rows of a band by default */
+int64_t rhccq_palette_dither_bytes(int32_t H, int32_t W);     /* host only: workspace bytes for any RHCCQ_OPT_DITHER_ROWS (0 for H < 0 or W < 0) */
+int rhccq_palette_dither(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                         int32_t n_classes, const uint32_t* strength_host, void* work, int64_t work_bytes, void* idx_out, int32_t idx_elem_bytes,
+                         uint64_t* sums, int32_t* status);
+int rhccq_palette_dither_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
+                              const uint32_t* strength, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
 
 /* ---- EXTENSION: a palette from the image, exact variance splits over a colour histogram (no reference counterpart; csrc/palette_build.hip) ----
  * Greedy variance-minimising box splitting over a 32 x 32 x 32 histogram (Wu's quantiser) with exact rational comparisons: the top-down

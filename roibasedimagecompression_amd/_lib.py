@@ -208,6 +208,12 @@ PROTOTYPES = {
     "rhccq_palette_segment": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                                         c_void_p]),
     "rhccq_palette_segment_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_dither_max_rows": (c_int32, []),
+    "rhccq_palette_dither_rows": (c_int32, []),
+    "rhccq_palette_dither_bytes": (c_int64, [c_int32, c_int32]),
+    "rhccq_palette_dither": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
+                                       c_void_p, c_void_p]),
+    "rhccq_palette_dither_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_cells_block": (c_int32, []),
     "rhccq_palette_cells_chunk": (c_int32, []),
     "rhccq_palette_cells": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),

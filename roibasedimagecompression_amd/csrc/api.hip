@@ -96,6 +96,10 @@ int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value) {
       if (value != 0 && value != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_CHAIN_RELEASE: 0 or 1");
       ctx->opt_chain_release = (int)value;
       return 0;
+    case RHCCQ_OPT_DITHER_ROWS:
+      if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_DITHER_ROWS: 0, 4, 8, 16 or 32");
+      ctx->opt_dither_rows = (int)value;
+      return 0;
     default:
       return rhccq_fail(ctx, RHCCQ_E_ARG, "unknown option");
   }

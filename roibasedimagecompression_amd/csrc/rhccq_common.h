@@ -32,6 +32,7 @@ struct rhccq_ctx {
   int opt_refine_lds_rows = -1;    // rhccq_palette_refine: palettes of more rows accumulate in global memory (-1: rhccq_palette_refine_lds_rows())
   int opt_refine_max_blocks = 0;   // rhccq_palette_refine: at most this many workgroups (0: 8 per CU)
   int opt_runs_rows = 0;           // rhccq_palette_runs: image rows of a workgroup (0: kRunsRowsDefault; 2, 4 or 8)
+  int opt_dither_rows = 0;         // rhccq_palette_dither: image rows of a band (0: kDitherRowsDefault; 4, 8, 16 or 32)
   int opt_chain_release = 1; // rhccq_encode_frame: a level-1 problem goes on when its own chain of the frame's launch has ended (1, default) or when the launch has (0)
 };
 

@@ -401,7 +401,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -427,12 +427,15 @@ class ImageEncoder:
         With a target every probe and the result run with the slack, as in encode_with_palette.
         run_penalty = p or {"roi": a, "nonroi": b} (EXTENSION, default None = off; 0 is a value; exclusive with run_slack and with
         target_psnr): the same place and the same rules, with the exact row segmentation (Rhccq.palette_segment) instead of the
-        greedy rule; stats["runs"] as encode_with_palette fills it."""
+        greedy rule; stats["runs"] as encode_with_palette fills it.
+        dither = s or {"roi": a, "nonroi": b} (EXTENSION, default None = off; 0 is a value; exclusive with run_slack, run_penalty and
+        target_psnr): the same place and the same rules, with error diffusion (Rhccq.palette_dither) over the result's own palette;
+        stats["dither"] as encode_with_palette fills it, and no stats["runs"]."""
         rh = self.rh
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
-        runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr)
+        runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr, dither=dither)
         cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -481,11 +484,11 @@ class ImageEncoder:
         if searching:
             stats["reduce"], stats["target"], data, row = self._target_result(rgb, res, region_map, target_bytes, cons, exact, runs)
             if row is not None:
-                stats["runs"] = row
+                stats[self._runs_key(runs)] = row
             lap("target")
         elif runs is not None:
-            stats["runs"] = self._runs_result(rgb, res, region_map, runs)
-            lap("runs")
+            stats[self._runs_key(runs)] = self._runs_result(rgb, res, region_map, runs)
+            lap(self._runs_key(runs))
         if out_path:
             from . import container
             if data is not None:                                                  # the probe's bytes are the file
@@ -547,18 +550,18 @@ class ImageEncoder:
         return row, target, data, runs_row
 
     def _runs_result(self, rgb, res, region_map, runs):
-        """encode's run_slack / run_penalty without a target: the finished result's index map in place -> stats["runs"]"""
+        """encode's run_slack / run_penalty / dither without a target: the finished result's index map in place -> its stats row"""
         rh = self.rh
         pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
         window, cls = self._window(rgb, res, region_map)
-        idx, sums = self._runs_call(window, pal, cls, runs)
+        idx, sums, status = self._runs_call(window, pal, cls, runs)
         res.update(indices=idx.reshape(res["indices"].shape), indices_dtype="uint8" if idx.dtype == torch.uint8 else "uint16")
-        return self._runs_row(runs, rh.to_host(sums), True)
+        return self._runs_row(runs, self._runs_host(sums, status)[0], True)
 
     # ---- the run-carrying remap (EXTENSION, no reference counterpart) ------------------------------------------------------------------
     @staticmethod
     def _run_arg(fn, name, key, most, value, masked):
-        """the keyword `name` (run_slack, run_penalty) checked -> None (off), or {key: as given, "nonroi": v, "roi": v}, each v in 0..most"""
+        """the keyword `name` (run_slack, run_penalty, dither) checked -> None (off), or {key: as given, "nonroi": v, "roi": v}, each v in 0..most"""
         if value is None:
             return None
         if isinstance(value, dict):
@@ -575,8 +578,16 @@ class ImageEncoder:
         return out
 
     @staticmethod
-    def _runs_args(fn, run_slack, run_penalty, masked, target_psnr=None):
-        """run_slack and run_penalty checked together -> None (both off) or the dict of the one given (it has "slack" or "penalty")"""
+    def _runs_args(fn, run_slack, run_penalty, masked, target_psnr=None, *, dither=None):
+        """run_slack, run_penalty and dither checked together -> None (all off) or the dict of the one given (it has "slack", "penalty" or
+        "dither")"""
+        if dither is not None:
+            if run_slack is not None or run_penalty is not None:
+                raise ValueError(f"{fn}: dither is exclusive with run_slack and run_penalty")
+            if target_psnr is not None:
+                # the ladder's bound is that of the nearest-row map; a dithered pixel may be any distance from its nearest row
+                raise ValueError(f"{fn}: dither cannot be combined with target_psnr")
+            return ImageEncoder._run_arg(fn, "dither", "dither", ops.DITHER_MAX, dither, masked)
         if run_slack is not None and run_penalty is not None:
             raise ValueError(f"{fn}: run_slack and run_penalty are exclusive")
         if run_penalty is not None and target_psnr is not None:
@@ -587,12 +598,29 @@ class ImageEncoder:
         return ImageEncoder._run_arg(fn, "run_slack", "slack", ops.RUN_SLACK_MAX, run_slack, masked)
 
     def _runs_call(self, rgb, pal, cls, runs):
-        """the final index map by the rule `runs` names: the greedy carry (Rhccq.palette_runs) or the exact row segmentation
-        (Rhccq.palette_segment) -> (indices, sums device)"""
+        """the final index map by the rule `runs` names: the greedy carry (Rhccq.palette_runs), the exact row segmentation
+        (Rhccq.palette_segment) or error diffusion (Rhccq.palette_dither) -> (indices, sums device, the status word device or None: the
+        caller reads both back through _runs_host)"""
         table, nc = self._slack_table(runs, cls is not None), 2 if cls is not None else 0
+        if "dither" in runs:
+            return self.rh.palette_dither(rgb, pal, table, cls, nc, with_status=True)
         if "penalty" in runs:
-            return self.rh.palette_segment(rgb, pal, table, cls, nc)
-        return self.rh.palette_runs(rgb, pal, table, cls, nc)
+            return self.rh.palette_segment(rgb, pal, table, cls, nc) + (None,)
+        return self.rh.palette_runs(rgb, pal, table, cls, nc) + (None,)
+
+    def _runs_host(self, sums, status, *more):
+        """one read-back of a _runs_call's sums, its status word (checked) and whatever else the caller wants with them"""
+        if status is None:
+            got = self.rh.to_host(sums, *more)
+            return got if more else (got,)
+        got = self.rh.to_host(sums, *more, status)
+        self.rh.check_dither(got[-1])
+        return got[:-1]
+
+    @staticmethod
+    def _runs_key(runs):
+        """the entry of stats a rule's row goes to"""
+        return "dither" if "dither" in runs else "runs"
 
     @staticmethod
     def _slack_table(runs, masked):
@@ -604,6 +632,8 @@ class ImageEncoder:
         carried = {"all": int(sums[-1][2])}
         if masked:
             carried["roi"], carried["nonroi"] = int(sums[1][2]), int(sums[0][2])
+        if "dither" in runs:
+            return {"strength": runs["dither"], "moved": carried, "pixels": int(sums[-1][0])}
         if "penalty" in runs:
             breaks = {"all": int(sums[-1][3])}
             if masked:
@@ -618,21 +648,22 @@ class ImageEncoder:
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
     def _finish_palette(self, rgb, pal, cls, roi_weight, refine, runs=None):
-        """the refinement, if asked for, and the final remap (the run-carrying one with `runs`) -> (palette device, indices, sums host
-        {pixels, sse} per row, history host or None, iterations, stats["runs"] or None)"""
+        """the refinement, if asked for, and the final remap (by the rule `runs` names, if any) -> (palette device, indices, sums host
+        {pixels, sse} per row, history host or None, iterations, the rule's stats row or None)"""
         rh = self.rh
         hist = nit = None
         if refine:
             pal, hist, nit = rh.palette_refine(rgb, pal, cls, [1, roi_weight, 1] if cls is not None else None, max_iter=refine)
+        status = None
         if runs is not None:
-            idx, sums = self._runs_call(rgb, pal, cls, runs)
+            idx, sums, status = self._runs_call(rgb, pal, cls, runs)
         else:
             idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
         if refine:
-            sums, hist, nit = rh.to_host(sums, hist, nit)                     # one read for both
+            sums, hist, nit = self._runs_host(sums, status, hist, nit)        # one read for all
             nit = int(nit[0])
         else:
-            sums = rh.to_host(sums)
+            (sums,) = self._runs_host(sums, status)
         runs_row = None
         if runs is not None:
             runs_row = self._runs_row(runs, sums, cls is not None)
@@ -725,7 +756,7 @@ class ImageEncoder:
         # bounds the run-carrying result's squared error (exact integers).  With a run penalty a pixel may lose the penalties of its two
         # boundaries, its own and its right neighbour's (of either class): own + largest per pixel (a byte target records this bound)
         extra = None
-        if runs is not None:
+        if runs is not None and "dither" not in runs:
             px = L["pixels"]
             per = {n: runs[n] + (max(runs["nonroi"], runs["roi"]) if "penalty" in runs else 0) for n in ("nonroi", "roi")}
             extra = {"all": per["nonroi"] * px["all"]} if cls is None else {"nonroi": per["nonroi"] * px["nonroi"], "roi": per["roi"] * px["roi"]}
@@ -733,6 +764,8 @@ class ImageEncoder:
                 extra["all"] = extra["nonroi"] + extra["roi"]
 
         def bound(k):
+            if runs is not None and "dither" in runs:                                # the curve bounds the nearest-row map only
+                return {n: None for n in names}
             if extra is None:
                 return {n: L["psnr_bound"][n][live - k] for n in names}
             return {n: (psnr_from_sse(L["sse"][n][live - k] + extra[n], L["pixels"][n]) if L["pixels"][n] else None) for n in names}
@@ -785,7 +818,7 @@ class ImageEncoder:
         return out + (row, target, data)
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
-                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None):
+                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -840,7 +873,18 @@ class ImageEncoder:
         pixels whose index is not the nearest row[, roi, nonroi]}, breaks: {all: pixels whose index differs from their left
         neighbour's[, roi, nonroi]}, pixels}.  With target_psnr it raises ValueError: two penalties a pixel is the only valid bound
         and too loose to choose a rung by.  A byte target's bound_psnr adds (own + largest penalty) x pixels per table.  The palette
-        may have at most ops.palette_segment_max_rows() rows (RhccqError)."""
+        may have at most ops.palette_segment_max_rows() rows (RhccqError).
+        dither = s or {"roi": a, "nonroi": b} (the dict needs roi_mask; default None = off, and 0 is a value: the nearest-row map;
+        exclusive with run_slack and run_penalty: ValueError): the final remap, in the same place as theirs (behind refine, colours
+        and in every probe of target_bytes), is Floyd-Steinberg error diffusion in exact integers (Rhccq.palette_dither; raster
+        order, no serpentine, RGB): a pixel aims at its colour plus s / 256 of the error its left and upper neighbours left behind
+        (weights 7, 1, 5, 3 over 16) and takes the nearest row of that; 256 is the classic rule.  It keeps the local mean colour at
+        a fixed K, where the nearest-row map bands a gradient; it costs PSNR and index-map bytes.  The
+        strength is the receiving pixel's: with {"roi": 0, "nonroi": s} the pixels inside the mask keep their nearest row.
+        stats["remap"] stays the figures of the index map returned; stats["dither"] = {strength: as given, moved: {all: pixels whose
+        index is not the nearest row[, roi, nonroi]}, pixels}; there is no stats["runs"].  With target_psnr it raises ValueError:
+        the ladder's bound is that of the nearest-row map.  A byte target probes every rung with the dither on, and its bound_psnr is
+        {table: None}.  The palette may have at most ops.palette_dither_max_rows() rows (RhccqError)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
@@ -849,7 +893,7 @@ class ImageEncoder:
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None or searching))):
             raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0, colours or a target")
         cons = self._target_args("ImageEncoder.encode_with_palette", target_bytes, target_psnr, roi_mask is not None) if searching else None
-        runs = self._runs_args("ImageEncoder.encode_with_palette", run_slack, run_penalty, roi_mask is not None, target_psnr)
+        runs = self._runs_args("ImageEncoder.encode_with_palette", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither)
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -899,7 +943,7 @@ class ImageEncoder:
         if target is not None:
             stats["target"] = target
         if runs_row is not None:
-            stats["runs"] = runs_row
+            stats[self._runs_key(runs)] = runs_row
         if refined:
             stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
                                "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
@@ -937,13 +981,13 @@ class ImageEncoder:
         return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
-                 target_psnr=None, run_slack=None, run_penalty=None):
+                 target_psnr=None, run_slack=None, run_penalty=None, dither=None):
         """image: uint8[H,W,3] (numpy or device tensor), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
         variance-minimising box splitting over it in exact integers (Rhccq.palette_build: the box whose best cut removes the most
         squared error is split until N boxes exist; a row is the mean of its box's pixels), then exactly what
         encode_with_palette(image, that palette, ...) does: out_path, exact, roi_mask, report, refine, target_bytes, target_psnr,
-        run_slack and run_penalty keep their meaning and validation.  No region, SLIC or clustering stage runs, and no palette is
+        run_slack, run_penalty and dither keep their meaning and validation.  No region, SLIC or clustering stage runs, and no palette is
         needed to start from.  With roi_mask a pixel inside the mask weighs roi_weight (1..255) in the histogram, so roi_weight other
         than 1 needs only the mask here (and weighs in the refinement too when refine > 0).  N may be at most
         ops.palette_build_max_rows() (RhccqError).  Colours that share a cell of the histogram (equal in their upper five bits per
@@ -961,7 +1005,7 @@ class ImageEncoder:
             raise ValueError("ImageEncoder.quantize: roi_weight (1..255) other than 1 needs roi_mask")
         if searching:
             self._target_args("ImageEncoder.quantize", target_bytes, target_psnr, roi_mask is not None)
-        self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr)
+        self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither)
         rgb = self._frame_tensor("quantize", image)
         t0 = time.perf_counter()
         cells = self._cells("quantize", rgb, roi_mask, roi_weight)
@@ -970,7 +1014,7 @@ class ImageEncoder:
         seconds = time.perf_counter() - t0
         res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
                                        roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
-                                       run_slack=run_slack, run_penalty=run_penalty)
+                                       run_slack=run_slack, run_penalty=run_penalty, dither=dither)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         return res

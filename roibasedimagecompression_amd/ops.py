@@ -148,6 +148,19 @@ def palette_segment_tile():
     return int(_lib.load().rhccq_palette_segment_tile_cols())
 
 
+DITHER_MAX = 256                      # the largest strength Rhccq.palette_dither takes: Floyd-Steinberg in full
+
+
+def palette_dither_max_rows():
+    """the largest palette Rhccq.palette_dither takes on the device (the packed palette is 32 KiB of LDS)"""
+    return int(_lib.load().rhccq_palette_dither_max_rows())
+
+
+def palette_dither_rows():
+    """image rows of a band of Rhccq.palette_dither's wavefront by default (Rhccq.OPT_DITHER_ROWS)"""
+    return int(_lib.load().rhccq_palette_dither_rows())
+
+
 def palette_build_max_rows():
     """the most colours Rhccq.palette_build returns on the device: the boxes whose state one workgroup's LDS holds"""
     return int(_lib.load().rhccq_palette_build_max_rows())
@@ -280,6 +293,7 @@ class Rhccq:
     OPT_REFINE_MAX_BLOCKS = 11       # palette_refine: at most this many workgroups (0, default: 8 per CU)
     OPT_RUNS_ROWS = 13               # palette_runs: image rows of a workgroup (0, default: palette_runs_tile()[0]; 2, 4 or 8)
     OPT_CHAIN_RELEASE = 12           # rhccq_encode_frame: 1 (default) a level-1 problem goes on when its own chain of the frame's launch ends; 0: when the launch ends
+    OPT_DITHER_ROWS = 14             # palette_dither: image rows of a band (0, default: palette_dither_rows(); 4, 8, 16 or 32)
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""
@@ -1116,6 +1130,44 @@ class Rhccq:
         self._check(self.lib.rhccq_palette_segment(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table,
                                                    self._p(work), nbytes, self._p(idx), idx.element_size(), self._p(sums)), "palette_segment")
         return idx, sums
+
+    # -- error-diffusing remap onto a given palette (EXTENSION: csrc/palette_dither.hip) -----------------------------------
+    def palette_dither(self, rgb, palette, strength, class_map=None, n_classes=0, with_status=False):
+        """rgb uint8[H, W, 3], palette uint8[K, 3] (numpy or device; K <= palette_dither_max_rows(), else RhccqError), strength: one
+        integer 0..DITHER_MAX for every pixel, or n_classes + 1 of them (a pixel of class c < n_classes takes strength[c], every other
+        pixel strength[-1]), class_map uint8 / bool [H, W] or None -> (indices device [H, W], uint8 when K <= 256, else int16 holding
+        uint16; sums device int64 [n_classes + 1, 3]: row c = {pixels, sum of squared errors against the original pixel, pixels whose
+        index is not the nearest row} of class c, the last row over every pixel).  Floyd-Steinberg error diffusion in exact integers
+        and raster order (include/rhccq.h pins rounding and ties); the strength scales what a pixel receives: 0 gives palette_remap's
+        index, 256 the full error.  The workspace (rhccq_palette_dither_bytes) is a torch allocation of this call.
+        with_status: -> (indices, sums, status device int32[1]) without waiting for the device; the caller reads status with the sums
+        and hands it to check_dither.  Without it the call waits, checks the status itself and returns (indices, sums)."""
+        rgb, palette = A.pixels(rgb, palette, self.device, "palette_dither", rows=True)
+        H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
+        _, table = A.class_table(strength, n_classes, DITHER_MAX, "palette_dither", "strength")
+        cls = A.class_map(class_map, H * W, n_classes, self.device, "palette_dither")
+        if K < 1 or K > palette_dither_max_rows() or not 0 <= n_classes <= 16:
+            raise RhccqError(f"palette_dither: K must be 1..{palette_dither_max_rows()} on the device and n_classes 0..16")
+        idx = self.empty((H, W), A.index_dtype(K))
+        sums = self.empty((n_classes + 1, 3), torch.int64)
+        if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
+            status = self.zeros((1,), torch.int32)
+            return (idx, sums.zero_(), status) if with_status else (idx, sums.zero_())
+        status = self.empty((1,), torch.int32)
+        nbytes = int(self.lib.rhccq_palette_dither_bytes(H, W))
+        work = self.empty((nbytes // 4,), torch.int32)
+        self._check(self.lib.rhccq_palette_dither(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table, self._p(work),
+                                                  nbytes, self._p(idx), idx.element_size(), self._p(sums), self._p(status)), "palette_dither")
+        if with_status:
+            return idx, sums, status
+        self.check_dither(self.to_host(status))
+        return idx, sums
+
+    @staticmethod
+    def check_dither(status):
+        """the status word of palette_dither(with_status=True), read back: non-zero raises RhccqError (the indices and sums mean nothing)"""
+        if int(np.asarray(status).reshape(-1)[0]) != 0:
+            raise RhccqError("palette_dither: a band gave up waiting for the band above it; the indices are unspecified")
 
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------
     def palette_refine(self, rgb, palette, class_map=None, weights=None, max_iter=8):
