@@ -1078,6 +1078,49 @@ int rhccq_palette_refine_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t
 int rhccq_palette_refine_batch_host(const uint8_t* rgb, const int64_t* px_off, int32_t B, uint8_t* palettes, int32_t K_stride, const int32_t* k_rows,
                                     const uint8_t* cls, int32_t n_classes, const int32_t* weights, int32_t max_iter, uint64_t* history, int32_t* n_iter);
 
+/* ---- EXTENSION: position-only (pattern) dither onto a given palette (no reference counterpart; csrc/palette_pattern.hip) ----------------
+ * rgb, palette, cls, n_classes, idx_out and idx_elem_bytes as rhccq_palette_runs takes them; strength uint32[n_classes + 1], each entry
+ * 0..256, chosen per pixel as rhccq_palette_dither chooses it: s = strength[cls[p]] when cls[p] < n_classes and strength[n_classes]
+ * otherwise (and for every pixel when cls == NULL).  size n is 2, 4 or 8, N = n * n.  Thomas Knoll's pattern dithering in exact integers.
+ * Per pixel p = rgb(y, x), with e an error triple that starts at (0, 0, 0), for i = 0 .. N-1 and per channel:
+ *   t   = clamp(p + floor((s e + 128) / 256), 0, 255)                                     floor toward minus infinity
+ *   c_i = rhccq_palette_remap's row of the uint8 triple t (nearest in exact integers, ties to the lowest row)
+ *   e   = e + p - palette[c_i]                                                            against the ORIGINAL pixel; |e| <= 64 * 255
+ * The N candidates, duplicates kept, are ordered by (299 R + 587 G + 114 B of palette[c_i], then c_i) ascending, and
+ *   out(y, x) = ordered[M_n[y mod n][x mod n]],   M_2 = [[0, 2], [3, 1]],   M_2n = [[4 M_n, 4 M_n + 2], [4 M_n + 3, 4 M_n + 1]]   (Bayer)
+ * out depends on the pixel's value, class and position modulo n only: the same pixel at the same (y mod n, x mod n) gets the same index in
+ * any picture, tile, frame or batch slot.  c_0 is rhccq_palette_remap's index b (the first target is the pixel itself), and a strength
+ * of 0 makes every candidate b: strength 0 everywhere reproduces rhccq_palette_remap's indices for every size.  idx_out receives out; sums
+ * is uint64[n_classes + 1][3], zeroed by the call: row c = {pixels, sum of |rgb - palette[out]|^2 against the ORIGINAL pixel, pixels with
+ * out != b} over the pixels with cls[p] == c, the last row over every pixel, exactly as rhccq_palette_dither defines it.
+ * RHCCQ_E_ARG: as rhccq_palette_runs, and a null strength, a strength above 256, a size other than 2, 4, 8.  RHCCQ_E_LIMIT: K > 65536
+ * (tested before the strengths); device form: K > rhccq_palette_pattern_max_rows() (4096: the packed palette is 32 KiB of LDS and a row
+ * number 12 bits of the search's word).  H * W == 0 succeeds with zero sums.
+ * Device form: every pointer but strength_host (copied by value into the launch) is device memory; async on the context stream, no host
+ * synchronisation, nothing allocated, no workspace and no status word: a memset of sums and ONE launch.  Pixels are independent: the kernel
+ * is the remap's search run N times per pixel against the whole palette in LDS, a lane's candidates in an LDS strip of 16-bit rows; no
+ * workgroup waits for another.  (y, x) comes from the linear pixel index.
+ * Host form: the same step functions (csrc/palette_pattern.h) run serially on host memory, for any K <= 65536.
+ * Batched form: B images laid out as rhccq_palette_remap_batch takes them (px_off host and device, palettes uint8[B][K_stride][3], k_rows
+ * int32[B] read on the device, one n_classes, strength table and size for the batch), and the width of every image twice, as px_off:
+ * widths_host int32[B] (checked) and widths_dev (what the kernel reads; KEEPING THE TWO EQUAL IS THE CALLER'S DUTY).  An image's width
+ * must divide its pixels; an image of 0 pixels may have width 0.  Image b's indices and sums (uint64[B][n_classes + 1][3]) are bit for bit
+ * what the single call gives for it alone; an image with k_rows[b] < 1 gets index 0 throughout and zero sums.  RHCCQ_E_ARG beside the
+ * single call's and rhccq_palette_remap_batch's: a null widths_host or widths_dev, a misaligned widths_dev, a width that is negative or
+ * does not divide its image's pixels.  RHCCQ_E_LIMIT: K_stride > 4096 (device form), B > 65535.  A memset and one launch, one image per
+ * grid row; the host form loops over rhccq_palette_pattern_host. */
+int32_t rhccq_palette_pattern_max_rows(void);                 /* host only: the largest K of the device form */
+int rhccq_palette_pattern(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                          int32_t n_classes, const uint32_t* strength_host, int32_t size, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_pattern_host(const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* palette, int32_t K, const uint8_t* cls, int32_t n_classes,
+                               const uint32_t* strength, int32_t size, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_pattern_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t* px_off_host, const int64_t* px_off_dev, const int32_t* widths_host,
+                                const int32_t* widths_dev, int32_t B, const uint8_t* palettes, int32_t K_stride, const int32_t* k_rows, const uint8_t* cls,
+                                int32_t n_classes, const uint32_t* strength_host, int32_t size, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums);
+int rhccq_palette_pattern_batch_host(const uint8_t* rgb, const int64_t* px_off, const int32_t* widths, int32_t B, const uint8_t* palettes, int32_t K_stride,
+                                     const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, const uint32_t* strength, int32_t size, void* idx_out,
+                                     int32_t idx_elem_bytes, uint64_t* sums);
+
 #ifdef __cplusplus
 }
 #endif

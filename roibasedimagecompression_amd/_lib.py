@@ -235,6 +235,15 @@ PROTOTYPES = {
                                              c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "rhccq_palette_refine_batch_host": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                                   c_void_p]),
+    "rhccq_palette_pattern_max_rows": (c_int32, []),
+    "rhccq_palette_pattern": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                        c_void_p]),
+    "rhccq_palette_pattern_host": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                             c_void_p]),
+    "rhccq_palette_pattern_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                              c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_pattern_batch_host": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                                   c_void_p, c_int32, c_void_p]),
 }
 
 

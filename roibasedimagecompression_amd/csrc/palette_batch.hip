@@ -1,5 +1,5 @@
 // The palette build path for a batch of images (EXTENSION, no reference counterpart): rhccq_palette_cells, rhccq_palette_build,
-// rhccq_palette_remap and rhccq_palette_refine over B images that lie back to back in one buffer, every image's result bit for bit what
+// rhccq_palette_remap, rhccq_palette_refine and rhccq_palette_pattern over B images that lie back to back in one buffer, every image's result bit for bit what
 // the single-image call gives for that image alone.  The definition is in include/rhccq.h.
 //
 // Why: the split chain is one workgroup for about 2 ms at 256 colours (7 to 8 us a step) and cannot be shortened, but B chains on B
@@ -16,6 +16,7 @@
 // synchronisation.  No workgroup waits for another: no flags, no spinning, no cooperative launch, no grid sized to what is resident;
 // stream order between launches is the only synchronisation, and a batch larger than the card queues.
 #include "palette_build.h"
+#include "palette_pattern.h"
 #include "palette_refine.h"
 
 #include <vector>
@@ -83,6 +84,28 @@ __global__ __launch_bounds__(kRemapBlock) void palette_remap_batch_kernel(const 
   }
   remap_body<IdxT>(rgb + first * 3, n_px, pal + (size_t)b * K_stride * 3, K, n_classes > 0 ? cls + first : nullptr, n_classes, idx_out + first,
                    sums + (size_t)b * (n_classes + 1) * 2, blockIdx.x, gridDim.x);
+}
+
+// the pattern dither of image b: its own width gives (y, x) from its own linear pixel index
+template <int kSize, typename IdxT>
+__global__ __launch_bounds__(kPatternBlock) void palette_pattern_batch_kernel(const uint8_t* __restrict__ rgb, const long long* __restrict__ px_off,
+                                                                              const int32_t* __restrict__ widths, const uint8_t* __restrict__ pal,
+                                                                              int K_stride, const int32_t* __restrict__ k_rows,
+                                                                              const uint8_t* __restrict__ cls, int n_classes, PatternStrength strength,
+                                                                              IdxT* __restrict__ idx_out, unsigned long long* __restrict__ sums) {
+  extern __shared__ uint4 s_dyn[];
+  const int b = blockIdx.y;
+  long long n_px;
+  const long long first = batch_image(px_off, b, &n_px);
+  if ((long long)blockIdx.x * pattern_chunk(kSize) >= n_px) return;                    // (block uniform)
+  const int K = batch_rows(k_rows, b, K_stride);
+  if (K < 1) {                                                                         // no palette (a build's error code): index 0, zero sums
+    for (long long c = (long long)blockIdx.x * pattern_chunk(kSize); c < n_px; c += (long long)gridDim.x * pattern_chunk(kSize))
+      for (long long p = c + threadIdx.x; p < min(c + pattern_chunk(kSize), n_px); p += kPatternBlock) idx_out[first + p] = (IdxT)0;
+    return;
+  }
+  pattern_body<kSize, IdxT>(rgb + first * 3, n_px, max(widths[b], 1), pal + (size_t)b * K_stride * 3, K, n_classes > 0 ? cls + first : nullptr, n_classes,
+                            strength, idx_out + first, sums + (size_t)b * (n_classes + 1) * 3, blockIdx.x, gridDim.x, s_dyn);
 }
 
 template <bool kLds>
@@ -279,6 +302,85 @@ int rhccq_palette_remap_batch_host(const uint8_t* rgb, const int64_t* px_off, in
     }
     if (const int rc = rhccq_palette_remap_host(rgb + first * 3, n, palettes + (size_t)b * K_stride * 3, K, cls ? cls + first : nullptr, n_classes, idx,
                                                 idx_elem_bytes, s))
+      return rc;
+  }
+  return 0;
+}
+
+// ---- pattern ----------------------------------------------------------------------------------------------------------------------------
+// what both forms test behind batch_check: the single call's arguments over the whole concatenation (H = 1, W = its pixels would overflow
+// int32: the tests are rows_check's, spelt for a pixel count), then every image's width
+static int pattern_batch_check(rhccq_ctx* ctx, const void* rgb, const int64_t* px_off, const int32_t* widths, int32_t B, const void* palettes,
+                               int32_t K_stride, const void* k_rows, const void* cls, int32_t n_classes, const uint32_t* strength, int32_t size,
+                               const void* idx_out, int32_t idx_elem_bytes, const void* sums) {
+  const char* const what = "palette_pattern_batch";
+  if (!widths || !k_rows) return remap_fail(ctx, RHCCQ_E_ARG, what, ": null widths or k_rows");
+  if ((uintptr_t)k_rows & 3) return remap_fail(ctx, RHCCQ_E_ARG, what, ": misaligned k_rows");
+  if (const int rc = pattern_check(ctx, what, rgb, 0, 0, palettes, K_stride, cls, n_classes, strength, size, idx_out, idx_elem_bytes, sums)) return rc;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = px_off[b + 1] - px_off[b];
+    if (widths[b] < 0 || (n > 0 && (widths[b] < 1 || n % widths[b] != 0 || n / widths[b] > 0x7FFFFFFF)))
+      return remap_fail(ctx, RHCCQ_E_ARG, what, ": an image's width must divide its pixels into at most 2^31 - 1 rows");
+  }
+  return 0;
+}
+
+int rhccq_palette_pattern_batch(rhccq_ctx* ctx, const uint8_t* rgb, const int64_t* px_off_host, const int64_t* px_off_dev, const int32_t* widths_host,
+                                const int32_t* widths_dev, int32_t B, const uint8_t* palettes, int32_t K_stride, const int32_t* k_rows, const uint8_t* cls,
+                                int32_t n_classes, const uint32_t* strength_host, int32_t size, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums) {
+  if (!ctx) return RHCCQ_E_ARG;
+  int64_t max_px = 0;
+  if (const int rc = batch_check(ctx, "palette_pattern_batch", B, px_off_host, &max_px)) return rc;
+  if (!px_off_dev || !widths_dev || ((uintptr_t)widths_dev & 3)) return rhccq_fail(ctx, RHCCQ_E_ARG, "palette_pattern_batch: null px_off_dev or widths_dev, or misaligned widths_dev");
+  if (const int rc = pattern_batch_check(ctx, rgb, px_off_host, widths_host, B, palettes, K_stride, k_rows, cls, n_classes, strength_host, size, idx_out,
+                                         idx_elem_bytes, sums))
+    return rc;
+  if (K_stride > kPatternMaxRows) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "palette_pattern_batch: the device form holds at most 4096 colours");
+  RHCCQ_HIP(ctx, hipMemsetAsync(sums, 0, (size_t)B * (n_classes + 1) * 3 * sizeof(uint64_t), ctx->stream));
+  if (max_px == 0) return 0;
+  if (const int rc = rhccq_compute_units(ctx)) return rc;
+  PatternStrength strength{};
+  for (int i = 0; i <= n_classes; ++i) strength.v[i] = strength_host[i];
+  const dim3 grid(batch_grid_x(max_px, pattern_chunk(size), (long long)ctx->compute_units * 16, B), (unsigned)B), block(kPatternBlock);
+  const size_t lds = pattern_lds_bytes(K_stride);
+  const long long* off = (const long long*)px_off_dev;
+  unsigned long long* s = (unsigned long long*)sums;
+  index_dispatch(idx_elem_bytes, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+#define RHCCQ_PATTERN_BATCH_CASE(N_) \
+  case N_: hipLaunchKernelGGL((palette_pattern_batch_kernel<N_, T>), grid, block, lds, ctx->stream, rgb, off, widths_dev, palettes, (int)K_stride, k_rows, \
+                              cls, (int)n_classes, strength, (T*)idx_out, s); break;
+    switch (size) {
+      RHCCQ_PATTERN_BATCH_CASE(2) RHCCQ_PATTERN_BATCH_CASE(4)
+      default: hipLaunchKernelGGL((palette_pattern_batch_kernel<8, T>), grid, block, lds, ctx->stream, rgb, off, widths_dev, palettes, (int)K_stride,
+                                  k_rows, cls, (int)n_classes, strength, (T*)idx_out, s);
+    }
+#undef RHCCQ_PATTERN_BATCH_CASE
+  });
+  RHCCQ_LAUNCH_CHECK(ctx);
+  return 0;
+}
+
+int rhccq_palette_pattern_batch_host(const uint8_t* rgb, const int64_t* px_off, const int32_t* widths, int32_t B, const uint8_t* palettes, int32_t K_stride,
+                                     const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, const uint32_t* strength, int32_t size, void* idx_out,
+                                     int32_t idx_elem_bytes, uint64_t* sums) {
+  int64_t max_px = 0;
+  if (const int rc = batch_check(nullptr, "palette_pattern_batch", B, px_off, &max_px)) return rc;
+  if (const int rc = pattern_batch_check(nullptr, rgb, px_off, widths, B, palettes, K_stride, k_rows, cls, n_classes, strength, size, idx_out,
+                                         idx_elem_bytes, sums))
+    return rc;
+  for (int b = 0; b < B; ++b) {
+    const int64_t first = px_off[b], n = px_off[b + 1] - first;
+    uint8_t* idx = (uint8_t*)idx_out + first * idx_elem_bytes;
+    uint64_t* s = sums + (size_t)b * (n_classes + 1) * 3;
+    const int K = k_rows[b] < K_stride ? k_rows[b] : K_stride;
+    if (K < 1 || n == 0) {
+      for (int64_t j = 0; j < n * idx_elem_bytes; ++j) idx[j] = 0;
+      for (int j = 0; j < (n_classes + 1) * 3; ++j) s[j] = 0;
+      continue;
+    }
+    if (const int rc = rhccq_palette_pattern_host(rgb + first * 3, (int32_t)(n / widths[b]), widths[b], palettes + (size_t)b * K_stride * 3, K,
+                                                  cls ? cls + first : nullptr, n_classes, strength, size, idx, idx_elem_bytes, s))
       return rc;
   }
   return 0;

@@ -401,7 +401,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -430,12 +430,16 @@ class ImageEncoder:
         greedy rule; stats["runs"] as encode_with_palette fills it.
         dither = s or {"roi": a, "nonroi": b} (EXTENSION, default None = off; 0 is a value; exclusive with run_slack, run_penalty and
         target_psnr): the same place and the same rules, with error diffusion (Rhccq.palette_dither) over the result's own palette;
-        stats["dither"] as encode_with_palette fills it, and no stats["runs"]."""
+        stats["dither"] as encode_with_palette fills it, and no stats["runs"].
+        pattern = s or {"roi": a, "nonroi": b}, pattern_size = 2, 4 or 8 (EXTENSION, default None = off; 0 is a value; exclusive with
+        run_slack, run_penalty, dither and target_psnr): the same place and the same rules, with the position-only pattern dither
+        (Rhccq.palette_pattern) over the result's own palette; stats["pattern"] as encode_with_palette fills it, and no stats["runs"]."""
         rh = self.rh
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
-        runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr, dither=dither)
+        runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr, dither=dither, pattern=pattern,
+                               pattern_size=pattern_size)
         cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
@@ -550,7 +554,7 @@ class ImageEncoder:
         return row, target, data, runs_row
 
     def _runs_result(self, rgb, res, region_map, runs):
-        """encode's run_slack / run_penalty / dither without a target: the finished result's index map in place -> its stats row"""
+        """encode's run_slack / run_penalty / dither / pattern without a target: the finished result's index map in place -> its stats row"""
         rh = self.rh
         pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
         window, cls = self._window(rgb, res, region_map)
@@ -561,7 +565,7 @@ class ImageEncoder:
     # ---- the run-carrying remap (EXTENSION, no reference counterpart) ------------------------------------------------------------------
     @staticmethod
     def _run_arg(fn, name, key, most, value, masked):
-        """the keyword `name` (run_slack, run_penalty, dither) checked -> None (off), or {key: as given, "nonroi": v, "roi": v}, each v in 0..most"""
+        """the keyword `name` (run_slack, run_penalty, dither, pattern) checked -> None (off), or {key: as given, "nonroi": v, "roi": v}, each v in 0..most"""
         if value is None:
             return None
         if isinstance(value, dict):
@@ -578,9 +582,22 @@ class ImageEncoder:
         return out
 
     @staticmethod
-    def _runs_args(fn, run_slack, run_penalty, masked, target_psnr=None, *, dither=None):
-        """run_slack, run_penalty and dither checked together -> None (all off) or the dict of the one given (it has "slack", "penalty" or
-        "dither")"""
+    def _runs_args(fn, run_slack, run_penalty, masked, target_psnr=None, *, dither=None, pattern=None, pattern_size=4):
+        """run_slack, run_penalty, dither and pattern checked together -> None (all off) or the dict of the one given (it has "slack",
+        "penalty", "dither" or "pattern"; the last also "size")"""
+        if pattern is not None:
+            if run_slack is not None or run_penalty is not None:
+                raise ValueError(f"{fn}: pattern is exclusive with run_slack and run_penalty")
+            if dither is not None:
+                raise ValueError(f"{fn}: pattern and dither are exclusive")
+            if target_psnr is not None:
+                # as for dither: the ladder's bound is that of the nearest-row map
+                raise ValueError(f"{fn}: pattern cannot be combined with target_psnr")
+            if isinstance(pattern_size, bool) or pattern_size not in ops.PATTERN_SIZES:
+                raise ValueError(f"{fn}: pattern_size must be 2, 4 or 8")
+            out = ImageEncoder._run_arg(fn, "pattern", "pattern", ops.PATTERN_MAX, pattern, masked)
+            out["size"] = int(pattern_size)
+            return out
         if dither is not None:
             if run_slack is not None or run_penalty is not None:
                 raise ValueError(f"{fn}: dither is exclusive with run_slack and run_penalty")
@@ -599,9 +616,11 @@ class ImageEncoder:
 
     def _runs_call(self, rgb, pal, cls, runs):
         """the final index map by the rule `runs` names: the greedy carry (Rhccq.palette_runs), the exact row segmentation
-        (Rhccq.palette_segment) or error diffusion (Rhccq.palette_dither) -> (indices, sums device, the status word device or None: the
-        caller reads both back through _runs_host)"""
+        (Rhccq.palette_segment), error diffusion (Rhccq.palette_dither) or the pattern dither (Rhccq.palette_pattern) -> (indices, sums
+        device, the status word device or None: the caller reads both back through _runs_host)"""
         table, nc = self._slack_table(runs, cls is not None), 2 if cls is not None else 0
+        if "pattern" in runs:
+            return self.rh.palette_pattern(rgb, pal, table, runs["size"], cls, nc) + (None,)
         if "dither" in runs:
             return self.rh.palette_dither(rgb, pal, table, cls, nc, with_status=True)
         if "penalty" in runs:
@@ -620,7 +639,12 @@ class ImageEncoder:
     @staticmethod
     def _runs_key(runs):
         """the entry of stats a rule's row goes to"""
-        return "dither" if "dither" in runs else "runs"
+        return "dither" if "dither" in runs else "pattern" if "pattern" in runs else "runs"
+
+    @staticmethod
+    def _unbounded(runs):
+        """the rules whose pixels may be any distance from their nearest row: the ladder's curve bounds nothing for them"""
+        return runs is not None and ("dither" in runs or "pattern" in runs)
 
     @staticmethod
     def _slack_table(runs, masked):
@@ -634,6 +658,8 @@ class ImageEncoder:
             carried["roi"], carried["nonroi"] = int(sums[1][2]), int(sums[0][2])
         if "dither" in runs:
             return {"strength": runs["dither"], "moved": carried, "pixels": int(sums[-1][0])}
+        if "pattern" in runs:
+            return {"strength": runs["pattern"], "size": runs["size"], "moved": carried, "pixels": int(sums[-1][0])}
         if "penalty" in runs:
             breaks = {"all": int(sums[-1][3])}
             if masked:
@@ -756,7 +782,7 @@ class ImageEncoder:
         # bounds the run-carrying result's squared error (exact integers).  With a run penalty a pixel may lose the penalties of its two
         # boundaries, its own and its right neighbour's (of either class): own + largest per pixel (a byte target records this bound)
         extra = None
-        if runs is not None and "dither" not in runs:
+        if runs is not None and not self._unbounded(runs):
             px = L["pixels"]
             per = {n: runs[n] + (max(runs["nonroi"], runs["roi"]) if "penalty" in runs else 0) for n in ("nonroi", "roi")}
             extra = {"all": per["nonroi"] * px["all"]} if cls is None else {"nonroi": per["nonroi"] * px["nonroi"], "roi": per["roi"] * px["roi"]}
@@ -764,7 +790,7 @@ class ImageEncoder:
                 extra["all"] = extra["nonroi"] + extra["roi"]
 
         def bound(k):
-            if runs is not None and "dither" in runs:                                # the curve bounds the nearest-row map only
+            if self._unbounded(runs):                                                # the curve bounds the nearest-row map only
                 return {n: None for n in names}
             if extra is None:
                 return {n: L["psnr_bound"][n][live - k] for n in names}
@@ -818,7 +844,7 @@ class ImageEncoder:
         return out + (row, target, data)
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
-                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None):
+                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -884,7 +910,20 @@ class ImageEncoder:
         stats["remap"] stays the figures of the index map returned; stats["dither"] = {strength: as given, moved: {all: pixels whose
         index is not the nearest row[, roi, nonroi]}, pixels}; there is no stats["runs"].  With target_psnr it raises ValueError:
         the ladder's bound is that of the nearest-row map.  A byte target probes every rung with the dither on, and its bound_psnr is
-        {table: None}.  The palette may have at most ops.palette_dither_max_rows() rows (RhccqError)."""
+        {table: None}.  The palette may have at most ops.palette_dither_max_rows() rows (RhccqError).
+        pattern = s or {"roi": a, "nonroi": b} with pattern_size = n in ops.PATTERN_SIZES (the dict needs roi_mask; default None = off,
+        and 0 is a value: the nearest-row map; exclusive with run_slack and run_penalty, and with dither: ValueError): the final remap,
+        in the same place as theirs, is pattern dithering in exact integers (Rhccq.palette_pattern): a pixel builds n x n candidate
+        rows whose mean approaches it (each candidate the nearest row of the pixel plus s / 256 of the error the earlier ones left),
+        orders them by luma, and the Bayer threshold of (y mod n, x mod n) picks one.  The index depends on the pixel and its position
+        only, so the same pixel gets the same index in every frame, tile and batch slot, and small noise moves few indices where
+        error diffusion moves them everywhere; it is one launch of independent pixels.  On smooth content the periodic pattern reaches
+        error diffusion's block means at a fraction of its bytes; on natural content with a rich palette it comes close to its block
+        means but does not beat its bytes or PSNR (DESIGN.md section 3j).  stats["remap"] stays the figures of the index map returned;
+        stats["pattern"] = {strength: as given, size: n, moved: {all: pixels whose index is not the nearest row[, roi, nonroi]},
+        pixels}; there is no stats["runs"].  With target_psnr it raises ValueError, for dither's reason.  A byte target probes every
+        rung with the pattern on, and its bound_psnr is {table: None}.  The palette may have at most ops.palette_pattern_max_rows()
+        rows (RhccqError)."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
@@ -893,7 +932,8 @@ class ImageEncoder:
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and (roi_mask is None or not (refine or colours is not None or searching))):
             raise ValueError("ImageEncoder.encode_with_palette: roi_weight (1..255) other than 1 needs roi_mask and refine > 0, colours or a target")
         cons = self._target_args("ImageEncoder.encode_with_palette", target_bytes, target_psnr, roi_mask is not None) if searching else None
-        runs = self._runs_args("ImageEncoder.encode_with_palette", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither)
+        runs = self._runs_args("ImageEncoder.encode_with_palette", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither,
+                               pattern=pattern, pattern_size=pattern_size)
         if isinstance(palette, dict):
             palette = palette["palette"]
         pal = palette.to(rh.device) if torch.is_tensor(palette) else rh.dev(np.asarray(palette))
@@ -981,13 +1021,13 @@ class ImageEncoder:
         return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
-                 target_psnr=None, run_slack=None, run_penalty=None, dither=None):
+                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
         """image: uint8[H,W,3] (numpy or device tensor), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
         variance-minimising box splitting over it in exact integers (Rhccq.palette_build: the box whose best cut removes the most
         squared error is split until N boxes exist; a row is the mean of its box's pixels), then exactly what
         encode_with_palette(image, that palette, ...) does: out_path, exact, roi_mask, report, refine, target_bytes, target_psnr,
-        run_slack, run_penalty and dither keep their meaning and validation.  No region, SLIC or clustering stage runs, and no palette is
+        run_slack, run_penalty, dither, pattern and pattern_size keep their meaning and validation.  No region, SLIC or clustering stage runs, and no palette is
         needed to start from.  With roi_mask a pixel inside the mask weighs roi_weight (1..255) in the histogram, so roi_weight other
         than 1 needs only the mask here (and weighs in the refinement too when refine > 0).  N may be at most
         ops.palette_build_max_rows() (RhccqError).  Colours that share a cell of the histogram (equal in their upper five bits per
@@ -1005,7 +1045,8 @@ class ImageEncoder:
             raise ValueError("ImageEncoder.quantize: roi_weight (1..255) other than 1 needs roi_mask")
         if searching:
             self._target_args("ImageEncoder.quantize", target_bytes, target_psnr, roi_mask is not None)
-        self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither)
+        self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither, pattern=pattern,
+                        pattern_size=pattern_size)
         rgb = self._frame_tensor("quantize", image)
         t0 = time.perf_counter()
         cells = self._cells("quantize", rgb, roi_mask, roi_weight)
@@ -1014,7 +1055,7 @@ class ImageEncoder:
         seconds = time.perf_counter() - t0
         res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
                                        roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
-                                       run_slack=run_slack, run_penalty=run_penalty, dither=dither)
+                                       run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         return res
@@ -1023,7 +1064,7 @@ class ImageEncoder:
     # pixels and indices (128 images: 275 MiB), and 128 chains are half the card's CUs, so two slices' chains already fill it
     QUANTIZE_BATCH_SLICE = 128
 
-    def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False):
+    def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False, pattern=None, pattern_size=4):
         """images: a list of uint8[H,W,3] images of any sizes (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor
         (a contiguous device tensor is used in place, nothing is concatenated) -> a list with one result dict per image: what
         quantize(image, colours, refine=refine, roi_mask=mask, roi_weight=...) returns for that image alone, bit for bit (palette
@@ -1037,8 +1078,12 @@ class ImageEncoder:
         an image that ends with 256 rows or fewer is narrowed to uint8 afterwards, as quantize returns it.  More than
         QUANTIZE_BATCH_SLICE (128) images are queued in slices of that many, which bounds the workspace; the one read stays one.
         out_paths: one file name (or None) per image, written afterwards with container.write_frame(exact=exact), one by one.
-        target_bytes, target_psnr, run_slack, run_penalty and report are not parameters: each needs a host decision per image;
-        quantize has them.  Validation and error types follow quantize; an image whose table is empty (no pixels) raises
+        pattern = s or {"roi": a, "nonroi": b} with pattern_size (default None = off): as quantize takes them; the last stage is then
+        Rhccq.palette_pattern_batch instead of the remap, every image's result still what quantize(..., pattern=, pattern_size=) gives
+        for it alone, stats["pattern"] included.  A pixel's index depends on the pixel and its position only, which is what lets a
+        batch take this rule and not dither.  The dict needs a mask for every image.
+        target_bytes, target_psnr, run_slack, run_penalty, dither and report are not parameters: each needs a host decision per image
+        (dither: a status word and a workspace per image); quantize has them.  Validation and error types follow quantize; an image whose table is empty (no pixels) raises
         RhccqError after the read, as quantize does for it."""
         rh = self.rh
         fn = "ImageEncoder.quantize_batch"
@@ -1063,6 +1108,7 @@ class ImageEncoder:
         masked = any(m is not None for m in masks)
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not masked):
             raise ValueError(f"{fn}: roi_weight (1..255) other than 1 needs roi_masks")
+        runs = self._runs_args(fn, None, None, all(m is not None for m in masks), pattern=pattern, pattern_size=pattern_size)
         if colours > ops.palette_build_max_rows():
             raise RhccqError(f"{fn}: {colours} colours, the device form returns at most {ops.palette_build_max_rows()} (palette_build_max_rows())")
         t0 = time.perf_counter()
@@ -1089,7 +1135,11 @@ class ImageEncoder:
             hist = nit = None
             if refine:
                 pal, hist, nit = rh.palette_refine_batch(rgb, off, pal, k, cls, weights, max_iter=refine, px_off_dev=off_dev)
-            idx, sums = rh.palette_remap_batch(rgb, off, pal, k, cls, nc, px_off_dev=off_dev)
+            if runs is not None:
+                idx, sums = rh.palette_pattern_batch(rgb, off, [int(f.shape[1]) for f in part], pal, k, self._slack_table(runs, masked), runs["size"], cls,
+                                                     nc, px_off_dev=off_dev)
+            else:
+                idx, sums = rh.palette_remap_batch(rgb, off, pal, k, cls, nc, px_off_dev=off_dev)
             queued.append((off, idx, [k, occupied, sums, pal] + ([hist, nit] if refine else [])))
         host = rh.to_host(*[t for _, _, ts in queued for t in ts])                 # the one read
         out, at = [], 0
@@ -1107,10 +1157,12 @@ class ImageEncoder:
                 ind = idx[int(off[b]):int(off[b + 1])].reshape(H, W)
                 if ind.dtype != torch.uint8 and rows <= 256:
                     ind = ind.to(torch.uint8)
-                remap = {"all": self._remap_row(*sums[b][-1])}
+                remap = {"all": self._remap_row(*sums[b][-1][:2])}
                 if masks[i] is not None:
-                    remap["nonroi"], remap["roi"] = self._remap_row(*sums[b][0]), self._remap_row(*sums[b][1])
+                    remap["nonroi"], remap["roi"] = self._remap_row(*sums[b][0][:2]), self._remap_row(*sums[b][1][:2])
                 stats = {"remap": remap}
+                if runs is not None:
+                    stats["pattern"] = self._runs_row(runs, sums[b], masks[i] is not None)
                 if refine:
                     n = int(nit[b])
                     stats["refine"] = {"iterations": n, "converged": n == 0 or int(hist[b][n - 1, 1]) == 0,
@@ -1148,7 +1200,7 @@ class ImageEncoder:
         return self.rh.palette_build(cells, colours)[0]
 
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
-                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None):
+                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None, pattern=None, pattern_size=4):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -1170,7 +1222,11 @@ class ImageEncoder:
         run_penalty: one number (default None = off), by the same rules (exclusive with run_slack and with target_psnr).
         key_colours = N (default None = off: key frames are encoded in full, as above): a key frame is made by
         quantize(image, colours=N) instead of encode, in about the time of a few remaps; roi_quality and nonroi_quality are not used
-        then, max_colours is exclusive with it (ValueError), and target_bytes, target_psnr, run_slack and run_penalty go to quantize."""
+        then, max_colours is exclusive with it (ValueError), and target_bytes, target_psnr, run_slack and run_penalty go to quantize.
+        pattern: one number (default None = off) with pattern_size, by run_slack's rules (exclusive with it, with run_penalty and with
+        target_psnr): key frames and remapped or refined frames alike end in the pattern dither (Rhccq.palette_pattern), whose index for
+        a pixel depends on the pixel and its position only, so what does not change between frames keeps its index.  The PSNR the
+        key-frame rule compares is that of the dithered map, the map that is returned."""
         rh = self.rh
         refine, roi_weight = int(refine), int(roi_weight)
         if key_colours is not None:
@@ -1185,7 +1241,9 @@ class ImageEncoder:
             self._target_args("ImageEncoder.encode_sequence", target_bytes, target_psnr, True)
         if isinstance(run_slack, dict) or isinstance(run_penalty, dict):
             raise ValueError("ImageEncoder.encode_sequence: run_slack / run_penalty is one number (a remapped frame has no region map)")
-        self._runs_args("ImageEncoder.encode_sequence", run_slack, run_penalty, False, target_psnr)
+        if isinstance(pattern, dict):
+            raise ValueError("ImageEncoder.encode_sequence: pattern is one number (a remapped frame has no region map)")
+        self._runs_args("ImageEncoder.encode_sequence", run_slack, run_penalty, False, target_psnr, pattern=pattern, pattern_size=pattern_size)
         if refine < 0 or refine > 64:
             raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
@@ -1196,13 +1254,14 @@ class ImageEncoder:
             path = out_paths[n] if out_paths is not None else None
             if key_pal is not None:
                 window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
-                res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack, run_penalty=run_penalty)
+                res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack, run_penalty=run_penalty, pattern=pattern,
+                                               pattern_size=pattern_size)
                 row = res["stats"]["remap"]["all" if window is None else "roi"]
                 kept = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 refined = False
                 if not kept and refine:
                     res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1,
-                                                   run_slack=run_slack, run_penalty=run_penalty)
+                                                   run_slack=run_slack, run_penalty=run_penalty, pattern=pattern, pattern_size=pattern_size)
                     row = res["stats"]["remap"]["all" if window is None else "roi"]
                     kept = refined = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 if kept:
@@ -1217,10 +1276,10 @@ class ImageEncoder:
                     continue
             if key_colours is not None:
                 res = self.quantize(image, colours=key_colours, out_path=path, exact=exact, target_bytes=target_bytes, target_psnr=target_psnr,
-                                    run_slack=run_slack, run_penalty=run_penalty)
+                                    run_slack=run_slack, run_penalty=run_penalty, pattern=pattern, pattern_size=pattern_size)
             else:
                 res = self.encode(image, roi_quality, nonroi_quality, out_path=path, exact=exact, max_colours=max_colours, target_bytes=target_bytes,
-                                  target_psnr=target_psnr, run_slack=run_slack, run_penalty=run_penalty)
+                                  target_psnr=target_psnr, run_slack=run_slack, run_penalty=run_penalty, pattern=pattern, pattern_size=pattern_size)
             (top, left), (h, w) = res["top_left"], res["shape"]
             rgb = image.to(rh.device) if torch.is_tensor(image) else rh.dev(np.ascontiguousarray(image, dtype=np.uint8))
             key_frame_shape = (int(rgb.shape[0]), int(rgb.shape[1]))

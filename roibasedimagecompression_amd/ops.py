@@ -161,6 +161,15 @@ def palette_dither_rows():
     return int(_lib.load().rhccq_palette_dither_rows())
 
 
+PATTERN_MAX = 256                     # the largest strength Rhccq.palette_pattern takes: the candidates' mean approaches the pixel in full
+PATTERN_SIZES = (2, 4, 8)             # the sides of the threshold matrix Rhccq.palette_pattern takes: 4, 16 or 64 candidates a pixel
+
+
+def palette_pattern_max_rows():
+    """the largest palette Rhccq.palette_pattern takes on the device (the packed palette is 32 KiB of LDS)"""
+    return int(_lib.load().rhccq_palette_pattern_max_rows())
+
+
 def palette_build_max_rows():
     """the most colours Rhccq.palette_build returns on the device: the boxes whose state one workgroup's LDS holds"""
     return int(_lib.load().rhccq_palette_build_max_rows())
@@ -1169,6 +1178,39 @@ class Rhccq:
         if int(np.asarray(status).reshape(-1)[0]) != 0:
             raise RhccqError("palette_dither: a band gave up waiting for the band above it; the indices are unspecified")
 
+    # -- position-only (pattern) dither onto a given palette (EXTENSION: csrc/palette_pattern.hip) --------------------------------
+    @staticmethod
+    def _pattern_size(size, fn):
+        size = int(size)
+        if size not in PATTERN_SIZES:
+            raise ValueError(f"{fn}: size must be 2, 4 or 8")
+        return size
+
+    def palette_pattern(self, rgb, palette, strength, size=4, class_map=None, n_classes=0):
+        """rgb uint8[H, W, 3], palette uint8[K, 3] (numpy or device; K <= palette_pattern_max_rows(), else RhccqError), strength: one
+        integer 0..PATTERN_MAX for every pixel, or n_classes + 1 of them (a pixel of class c < n_classes takes strength[c], every other
+        pixel strength[-1]), size in PATTERN_SIZES, class_map uint8 / bool [H, W] or None -> (indices device [H, W], uint8 when
+        K <= 256, else int16 holding uint16; sums device int64 [n_classes + 1, 3]: row c = {pixels, sum of squared errors against the
+        original pixel, pixels whose index is not the nearest row} of class c, the last row over every pixel).  Pattern dithering in
+        exact integers (include/rhccq.h pins rounding, order and ties): a pixel builds size x size candidate rows whose mean approaches
+        it, orders them by luma, and the Bayer threshold of (y mod size, x mod size) picks one.  The index depends on the pixel and its
+        position only; strength 0 gives palette_remap's index.  One launch, no workspace, no status word, no read back."""
+        fn = "palette_pattern"
+        rgb, palette = A.pixels(rgb, palette, self.device, fn, rows=True)
+        H, W, K, n_classes = int(rgb.shape[0]), int(rgb.shape[1]), int(palette.shape[0]), int(n_classes)
+        _, table = A.class_table(strength, n_classes, PATTERN_MAX, fn, "strength")
+        size = self._pattern_size(size, fn)
+        cls = A.class_map(class_map, H * W, n_classes, self.device, fn)
+        if K < 1 or K > palette_pattern_max_rows() or not 0 <= n_classes <= 16:
+            raise RhccqError(f"{fn}: K must be 1..{palette_pattern_max_rows()} on the device and n_classes 0..16")
+        idx = self.empty((H, W), A.index_dtype(K))
+        sums = self.empty((n_classes + 1, 3), torch.int64)
+        if H * W == 0:                                   # (empty tensors have null pointers: nothing to launch)
+            return idx, sums.zero_()
+        self._check(self.lib.rhccq_palette_pattern(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table, size,
+                                                   self._p(idx), idx.element_size(), self._p(sums)), fn)
+        return idx, sums
+
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------
     def palette_refine(self, rgb, palette, class_map=None, weights=None, max_iter=8):
         """rgb uint8[..., 3], palette uint8[K, 3] (numpy or device), class_map uint8 / bool, one element per pixel, or None;
@@ -1368,6 +1410,38 @@ class Rhccq:
         self._check(self.lib.rhccq_palette_remap_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), B, self._p(palettes), K,
                                                        self._p(k_rows), self._p(cls), n_classes, self._p(idx), idx.element_size(), self._p(sums)),
                     "palette_remap_batch")
+        return idx, sums
+
+    def palette_pattern_batch(self, rgb, px_off, widths, palettes, k_rows, strength, size=4, class_map=None, n_classes=0, px_off_dev=None):
+        """palette_pattern for B images laid out as palette_cells_batch takes them; widths: B host integers, the width of every image
+        (it divides the image's pixels; its rows and columns give the threshold's position); palettes uint8[B, K_stride, 3] and
+        k_rows int32[B] as palette_remap_batch takes them (K_stride <= palette_pattern_max_rows(), else RhccqError); one strength
+        (table), size and n_classes for the batch -> (indices device [pixels], concatenated like rgb: uint8 when K_stride <= 256, else
+        int16 holding uint16; sums device int64[B, n_classes + 1, 3], rows as palette_pattern's).  Image b's part is bit for bit what
+        palette_pattern gives for it alone; an image with k_rows[b] < 1 gets index 0 and zero sums.  One launch, no read back."""
+        fn = "palette_pattern_batch"
+        rgb, off, off_dev, cls, n = self._batch_pixels(fn, rgb, px_off, px_off_dev, class_map)
+        B, n_classes = len(off) - 1, int(n_classes)
+        palettes, k_rows = self._batch_palettes(fn, palettes, k_rows, B)
+        K = int(palettes.shape[1])
+        _, table = A.class_table(strength, n_classes, PATTERN_MAX, fn, "strength")
+        size = self._pattern_size(size, fn)
+        wid = np.ascontiguousarray(np.asarray(widths), dtype=np.int64).reshape(-1)
+        px = np.diff(off)
+        if len(wid) != B or (wid < 0).any() or (wid > INT_MAX).any() or ((px > 0) & ((wid < 1) | (px % np.maximum(wid, 1) != 0))).any():
+            raise ValueError(f"{fn}: widths must hold one width per image that divides the image's pixels")
+        wid = wid.astype(np.int32)
+        A.class_map(cls, n, n_classes, self.device, fn)
+        if not 0 <= n_classes <= 16 or K > palette_pattern_max_rows():
+            raise RhccqError(f"{fn}: K_stride must be 1..{palette_pattern_max_rows()} on the device and n_classes 0..16")
+        idx = self.empty((n,), A.index_dtype(K))
+        sums = self.empty((B, n_classes + 1, 3), torch.int64)
+        if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
+            return idx, sums.zero_()
+        wid_dev = self.dev(wid)
+        self._check(self.lib.rhccq_palette_pattern_batch(self.ctx, self._p(rgb), C.c_void_p(off.ctypes.data), self._p(off_dev), C.c_void_p(wid.ctypes.data),
+                                                         self._p(wid_dev), B, self._p(palettes), K, self._p(k_rows), self._p(cls), n_classes, table, size,
+                                                         self._p(idx), idx.element_size(), self._p(sums)), fn)
         return idx, sums
 
     def palette_refine_batch(self, rgb, px_off, palettes, k_rows, class_map=None, weights=None, max_iter=8, px_off_dev=None):
