@@ -138,7 +138,15 @@ int rhccq_eps_threshold(double eps, int32_t* thr_host, int32_t* boundary_host, d
  *   job_base[c] + labels[c][p] - 1 when labels[c][p] > 0 (labels[c] == NULL: every pixel belongs
  *   to job job_base[c]).  Sets the colour bit of every non-black pixel, accumulates per-job
  *   stats {min_r, max_r, min_c, max_c, count, n_black} (int32[6] each, caller-initialised to
- *   {INT_MAX,-1,INT_MAX,-1,0,0}); black pixels set their bit only when black_is_colour != 0. */
+ *   {INT_MAX,-1,INT_MAX,-1,0,0}); black pixels set their bit only when black_is_colour != 0.
+ *
+ * Alignment.  rgb on 4 bytes for rhccq_job_scan, rhccq_job_scan_bytes, rhccq_job_stats, rhccq_job_blackfix, rhccq_job_index,
+ *   rhccq_job_index_entries and rhccq_frame_remap (their kernels read 4 pixels as three dwords; RHCCQ_E_ARG otherwise);
+ *   rhccq_job_sort_unique reads rgb byte by byte and takes any address.  Every label map labels[c] on 16 bytes (read as int4),
+ *   for every entry point of this section.  The per-class planes of idx_out, entries / entries_out and rankmap are
+ *   int32[n_class][H*W] with no padding: class c starts at c*H*W elements, so the buffers need 4-byte alignment only, whatever
+ *   H*W is -- the kernels' 16-byte vector accesses to them rely on gfx950's unaligned global access (tests/job_cases.py holds
+ *   the shapes with H*W mod 4 != 0). */
 int rhccq_job_scan(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, int32_t n_class,
                    const int32_t* const* labels_host /* host array of device ptrs */,
                    const int32_t* job_base_host, int32_t black_is_colour, uint32_t* bitmaps,

@@ -89,6 +89,9 @@ __device__ __forceinline__ void load4px(const uint8_t* rgb, int64_t p0, int64_t 
   }
 }
 
+// (also used on the per-class planes of `entries`, which start at c * H * W elements: with H * W mod 4 != 0 this int4 load is only
+// 4-byte aligned.  That is within the contract of include/rhccq.h and relies on gfx950's unaligned dwordx4 GLOBAL access; it would
+// not survive a move of these accesses to LDS or to buffer operations.)
 __device__ __forceinline__ void load4lab(const int32_t* lab, int64_t p0, int64_t n_px, int32_t out[4]) {
   if (lab == nullptr) {
     out[0] = out[1] = out[2] = out[3] = 1;
@@ -395,6 +398,8 @@ __global__ __launch_bounds__(256) void job_index_kernel(const uint8_t* __restric
           if (p < *fp) atomicMin(fp, p);
         }
       }
+      // the planes of class c >= 1 start at c * n_px elements: these int4 stores are 16-byte aligned only when n_px mod 4 == 0, else
+      // 4-byte aligned (the documented contract) -- fine for global memory on gfx950 (unaligned access mode), not for LDS / buffer stores
       if (entry_out) {
         int32_t* o = entry_out + (size_t)c * n_px + p0;
         if (p0 + 4 <= n_px) {
@@ -620,6 +625,7 @@ int rhccq_job_blackfix(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W,
                        const int32_t* const* labels_host, const int32_t* job_base_host, const uint8_t* job_needs_fix,
                        unsigned long long* best) {
   if (!ctx || !rgb || !job_needs_fix || !best || H <= 0 || W <= 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "job_blackfix: bad argument");
+  if (((uintptr_t)rgb & 3u) != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "job_blackfix: rgb must be 4-byte aligned");
   ClassArgs ca;
   if (int e = make_class_args(ctx, n_class, labels_host, job_base_host, &ca)) return e;
   const int64_t quads = ((int64_t)H * W + 3) / 4;
@@ -634,6 +640,7 @@ int rhccq_job_index(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, in
                     int32_t* first_pos, const int32_t* fp_lut) {
   if (!ctx || !rgb || !bitmaps || !word_prefix || !pal_off || H <= 0 || W <= 0 || (int64_t)H * W > INT32_MAX)
     return rhccq_fail(ctx, RHCCQ_E_ARG, "job_index: bad argument");
+  if (((uintptr_t)rgb & 3u) != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "job_index: rgb must be 4-byte aligned");
   ClassArgs ca;
   if (int e = make_class_args(ctx, n_class, labels_host, job_base_host, &ca)) return e;
   const int64_t quads = ((int64_t)H * W + 3) / 4;
@@ -648,6 +655,7 @@ int rhccq_job_index_entries(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32
                             const uint32_t* fix_key, int32_t* first_pos, const int32_t* fp_lut, int32_t* entries_out) {
   if (!ctx || !rgb || !bitmaps || !word_prefix || !pal_off || !first_pos || !entries_out || H <= 0 || W <= 0 || (int64_t)H * W > INT32_MAX)
     return rhccq_fail(ctx, RHCCQ_E_ARG, "job_index_entries: bad argument");
+  if (((uintptr_t)rgb & 3u) != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "job_index_entries: rgb must be 4-byte aligned");
   ClassArgs ca;
   if (int e = make_class_args(ctx, n_class, labels_host, job_base_host, &ca)) return e;
   const int64_t quads = ((int64_t)H * W + 3) / 4;
@@ -770,6 +778,7 @@ int rhccq_frame_remap(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, 
                       const int32_t* lut2, int32_t default_index, void* out, int32_t out_elem_bytes) {
   if (!ctx || !rgb || !bitmaps || !word_prefix || !pal_off || !lut || !out || H <= 0 || W <= 0)
     return rhccq_fail(ctx, RHCCQ_E_ARG, "frame_remap: bad argument");
+  if (((uintptr_t)rgb & 3u) != 0) return rhccq_fail(ctx, RHCCQ_E_ARG, "frame_remap: rgb must be 4-byte aligned");
   return frame_remap_impl(ctx, rgb, H, W, n_class, labels_host, job_base_host, bitmaps, word_prefix, pal_off, fix_key, lut, lut2, default_index, out,
                           out_elem_bytes, nullptr);
 }
