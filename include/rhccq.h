@@ -1129,6 +1129,59 @@ int rhccq_palette_pattern_batch_host(const uint8_t* rgb, const int64_t* px_off, 
                                      const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, const uint32_t* strength, int32_t size, void* idx_out,
                                      int32_t idx_elem_bytes, uint64_t* sums);
 
+/* ---- EXTENSION: indexed PNG files written on the device (no reference counterpart; csrc/png_write.hip, csrc/png_write.h) ------------------
+ * The file of an index map idx[H][W] (idx_elem_bytes 1, 2 or 4, read as unsigned) and a palette uint8[K][3], H, W >= 1, 1 <= K <= 65536:
+ *   index clamp   an index >= K is written as 0, the row rhccq_decode shows for it.
+ *   K <= 256      colour type 3.  Bit depth d = 1 (K <= 2), 2 (K <= 4), 4 (K <= 16), else 8; RHCCQ_PNG_DEPTH8 forces 8.  PLTE holds exactly K
+ *                 entries.  Every row has filter type 0.  Pixels are packed most significant bits first, the unused low bits of a row's
+ *                 last byte are zero; a row is 1 + ceil(W d / 8) bytes.
+ *   K > 256       colour type 2, depth 8: a row's raw bytes are palette[idx], R G B, bpp = 3, a row is 1 + 3 W bytes.  Each row takes the
+ *                 filter type among 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth that minimises the sum over its filtered bytes v of
+ *                 (v < 128 ? v : 256 - v); a tie goes to the lowest type.  Left and upper left of the first pixel and the row above row 0
+ *                 are zero; Average is floor((a + b) / 2); Paeth prefers a, then b, then c, with <= as the specification words it; Up reads
+ *                 the raw row above, so rows are independent.  RHCCQ_PNG_NO_FILTER writes type 0 on every row.
+ *   chunks        signature, IHDR (W, H, depth, colour type, 0, 0, 0), PLTE (colour type 3 only), ONE IDAT holding the zlib stream of all
+ *                 scanlines, IEND, and nothing else.  The stream is rhccq_zlib_compress's, or rhccq_zlib9_compress's with
+ *                 RHCCQ_PNG_EXACT (then the file is a function of idx, palette and flags alone, byte for byte what zlib.compress(scan, 9)
+ *                 gives inside the same framing).  Every CRC is the standard CRC-32 (zlib.crc32) over chunk type and data.
+ * RHCCQ_E_ARG: H < 1, W < 1, K outside 1..65536, idx_elem_bytes not 1, 2 or 4, flag bits other than the three below, a null pointer
+ * (filter_rows and n_dev may be null), an idx not aligned to its element.  RHCCQ_E_LIMIT: scanline bytes (H rows) beyond what the chosen
+ * encoder takes (both refuse 2 GiB; rhccq_png_scanlines applies the level-9 encoder's limit), out_cap below the bound.
+ * Device forms: every pointer is device memory; async on the context stream, no host synchronisation, nothing allocated.
+ *   rhccq_png_scanlines   scan receives H rows; filter_rows (device int64[5], may be NULL) how many rows took each filter type.  Colour type 3 is
+ *                         one launch over the output's 4-byte words (a lane builds a whole word and stores it once; the first and last
+ *                         bytes of a misaligned scan go bytewise); colour type 2 is one launch with a workgroup per image row: the five costs
+ *                         in one pass, a reduction, the winner written in a second pass.
+ *   rhccq_crc32           zlib.crc32 of data[0 .. n), n = *n_dev (device int64, clamped to 0..n_cap) or n_cap when n_dev is NULL, into
+ *                         *crc_out (device).  Two launches: a workgroup takes the plain remainder of a 16 KiB piece (slice-by-4 tables in
+ *                         LDS), then ONE workgroup joins the remainders by multiplying with x^(8 len) mod P as a tree (zlib's crc32_combine
+ *                         algebra).  No workgroup waits for another; pieces past n contribute nothing; bytes outside data[0 .. n) are
+ *                         read only within the 16-byte aligned blocks that hold a byte of it, and masked.  workspace: at least
+ *                         rhccq_crc32_bytes(n_cap) bytes, aligned to 4.
+ *   rhccq_png_encode      the whole file into out, its length into *out_len (device int64).  workspace (aligned to 256) and out_cap come from
+ *                         rhccq_png_sizes.  One launch writes signature, IHDR, PLTE (the palette is device memory) and IDAT's type, one the
+ *                         scanlines into the workspace, the encoder writes its stream behind IDAT's type, the CRC runs over type and stream
+ *                         with the stream's device-side length, and a last launch writes IDAT's length, its CRC and IEND.  Afterwards the
+ *                         workspace holds the scanlines at its start and, 16 bytes behind them rounded up to 256, filter_rows (int64[5]).
+ * Host forms (serial, no GPU, host memory): the same functions of csrc/png_write.h.  rhccq_png_encode_host needs RHCCQ_PNG_EXACT (RHCCQ_E_ARG
+ * without it: the fast encoder has no host form) and an out_cap of at least rhccq_png_sizes' bound. */
+#define RHCCQ_PNG_EXACT 1
+#define RHCCQ_PNG_DEPTH8 2
+#define RHCCQ_PNG_NO_FILTER 4
+/* host only: bytes of the scanlines, of rhccq_png_encode's workspace and the bound of the file (any of the three may be NULL) */
+int rhccq_png_sizes(int32_t H, int32_t W, int32_t K, int32_t flags, int64_t* scan_bytes, int64_t* workspace_bytes, int64_t* out_bound);
+int rhccq_png_scanlines(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t H, int32_t W, const uint8_t* palette, int32_t K,
+                        int32_t flags, uint8_t* scan, int64_t* filter_rows);
+int64_t rhccq_crc32_bytes(int64_t n_cap);                     /* host only: rhccq_crc32's workspace; negative for n_cap < 0 */
+int rhccq_crc32(rhccq_ctx* ctx, const uint8_t* data, int64_t n_cap, const int64_t* n_dev, void* workspace, uint32_t* crc_out);
+int rhccq_png_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t H, int32_t W, const uint8_t* palette, int32_t K,
+                     int32_t flags, void* workspace, uint8_t* out, int64_t out_cap, int64_t* out_len);
+int rhccq_png_scanlines_host(const void* idx, int32_t idx_elem_bytes, int32_t H, int32_t W, const uint8_t* palette, int32_t K, int32_t flags,
+                             uint8_t* scan, int64_t* filter_rows);
+int rhccq_crc32_host(const uint8_t* data, int64_t n, uint32_t* crc_out);
+int rhccq_png_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t H, int32_t W, const uint8_t* palette, int32_t K, int32_t flags,
+                          uint8_t* out, int64_t out_cap, int64_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,14 @@ PROTOTYPES = {
                                               c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_pattern_batch_host": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                                    c_void_p, c_int32, c_void_p]),
+    "rhccq_png_sizes": (c_int32, [c_int32, c_int32, c_int32, c_int32, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rhccq_png_scanlines": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "rhccq_crc32_bytes": (c_int64, [c_int64]),
+    "rhccq_crc32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rhccq_png_encode": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_png_scanlines_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "rhccq_crc32_host": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "rhccq_png_encode_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
 }
 
 

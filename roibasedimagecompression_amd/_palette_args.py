@@ -120,6 +120,23 @@ def index_dtype(K):
     return torch.uint8 if K <= 256 else torch.int16
 
 
+def index_map(indices, H, W, device, fn):
+    """an index map of H x W elements in the dtypes container._index_tensor accepts -> a flat contiguous device tensor: uint8, int16
+    holding uint16, or int32 (from int32 / int64; numpy uint16 becomes the int16 storage, any other numpy integers int32)"""
+    if not torch.is_tensor(indices):
+        a = np.ascontiguousarray(indices)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"{fn}: indices must be integers, got {a.dtype}")
+        a = a if a.dtype == np.uint8 else a.view(np.int16) if a.dtype == np.uint16 else a.astype(np.int32)
+        indices = torch.from_numpy(a)
+    if indices.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise TypeError(f"{fn}: indices must be uint8, int16 (uint16 storage), int32 or int64, got {indices.dtype}")
+    if indices.numel() != H * W:
+        raise ValueError(f"{fn}: indices must have H * W elements")
+    t = indices.to(device).reshape(-1)
+    return (t.to(torch.int32) if t.dtype == torch.int64 else t).contiguous()
+
+
 def k_out_rows(k, fn, empty="every count is zero", over="the counts add up to more than 2^32 - 1"):
     """the k_out a chain wrote: the rows it made, or the negative code of an error only the counts (the table) show"""
     if k < 0:

@@ -109,6 +109,46 @@ def write_frame(result, filename, rh=None, exact=False):
     return save_compressed_device(pkg, filename, rh, exact=exact)
 
 
+def _png_frame(result, rh, fn):
+    """a result (palette, indices, shape) -> (rh, flat device indices, H, W, uint8 palette array)"""
+    if not isinstance(result, dict) or "palette" not in result or "indices" not in result or "shape" not in result:
+        raise RhccqError(f"{fn}: a FrameEncoder result (palette, indices, shape) is required")
+    rh = rh or default_context()
+    pal = result["palette"]
+    if not isinstance(pal, torch.Tensor):
+        pal = np.array(pal, dtype=np.uint8).reshape(-1, 3)
+    h, w = (int(v) for v in result["shape"][:2])
+    return rh, _index_tensor(result["indices"], rh)[0], h, w, pal
+
+
+def png_bytes(result, rh=None, exact=False, depth8=False, filter=True):
+    """the PNG file of a result (palette, indices, shape: what write_frame takes) as bytes, built on the device: palette PNG
+    (colour type 3, 1 / 2 / 4 / 8 bits) up to 256 rows, truecolour with adaptive row filters above (include/rhccq.h).  An index past
+    the palette shows row 0, as read_frame's image does.  exact=True: IDAT through the level-9 encoder, the file a function of the
+    result alone"""
+    return png_file(result, rh, exact=exact, depth8=depth8, filter=filter)[0]
+
+
+def png_file(result, rh=None, exact=False, depth8=False, filter=True):
+    """png_bytes with what the file is: -> (bytes, {"bytes": their number, "colour_type": 3 or 2, "depth": bits a sample,
+    "filter_rows": [rows of filter type 0, 1, 2, 3, 4]}); the file and the five counts come down in one copy each, together"""
+    rh, idx, h, w, pal = _png_frame(result, rh, "write_png")
+    out, length, rows = rh._png_encode(idx, h, w, pal, exact, depth8, filter)
+    n = int(length.item())
+    data, rows = rh.to_host(out[:n], rows)
+    K = len(pal)
+    depth = 8 if (K > 16 or depth8) else 1 if K <= 2 else 2 if K <= 4 else 4
+    return data.tobytes(), {"bytes": n, "colour_type": 3 if K <= 256 else 2, "depth": depth, "filter_rows": [int(v) for v in rows]}
+
+
+def write_png(result, filename, rh=None, exact=False, depth8=False, filter=True):
+    """png_bytes written to `filename`; returns the file's length in bytes"""
+    data = png_bytes(result, rh, exact=exact, depth8=depth8, filter=filter)
+    with open(filename, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
 def load_compressed_device(path, rh=None):
     """load_compressed with the outer zlib layer inflated on the device: the framing is read on the host, the pickle comes
     back through page-locked memory and is parsed by the same allow-list unpickler.  Returns the same dict."""

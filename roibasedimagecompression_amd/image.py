@@ -16,6 +16,7 @@ bit for bit, without the host round trips of the reference-shaped functions.
 The ROI and SLIC stages are the same parity-unpinned restatements script_flow runs."""
 import ctypes as C
 import math
+import os
 import time
 
 import numpy as np
@@ -401,7 +402,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -433,8 +434,10 @@ class ImageEncoder:
         stats["dither"] as encode_with_palette fills it, and no stats["runs"].
         pattern = s or {"roi": a, "nonroi": b}, pattern_size = 2, 4 or 8 (EXTENSION, default None = off; 0 is a value; exclusive with
         run_slack, run_penalty, dither and target_psnr): the same place and the same rules, with the position-only pattern dither
-        (Rhccq.palette_pattern) over the result's own palette; stats["pattern"] as encode_with_palette fills it, and no stats["runs"]."""
+        (Rhccq.palette_pattern) over the result's own palette; stats["pattern"] as encode_with_palette fills it, and no stats["runs"].
+        png_path (EXTENSION, default None = off): as encode_with_palette takes it, for the rectangle the result covers."""
         rh = self.rh
+        png_path = self._png_arg("ImageEncoder.encode", png_path)
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
@@ -501,6 +504,9 @@ class ImageEncoder:
             else:
                 container.write_frame(res, out_path, rh, exact=exact)
             lap("container")
+        if png_path:
+            stats["png"] = self._png_write(res, png_path, exact)
+            lap("png")
         if report:
             stats["quality"] = self.quality(rgb, res, region_map)
             lap("report")
@@ -508,6 +514,25 @@ class ImageEncoder:
         res["classes"] = classes
         res["stats"] = stats
         return res
+
+    # ---- the result as a PNG file (EXTENSION: csrc/png_write.hip) ---------------------------------------------------------------
+    @staticmethod
+    def _png_arg(fn, png_path):
+        """png_path as given -> a file name or None"""
+        if png_path is None:
+            return None
+        if not isinstance(png_path, (str, os.PathLike)):
+            raise TypeError(f"{fn}: png_path must be a file name, got {type(png_path).__name__}")
+        if not os.fspath(png_path):
+            raise ValueError(f"{fn}: png_path must not be empty")
+        return os.fspath(png_path)
+
+    def _png_write(self, res, png_path, exact):
+        from . import container
+        data, row = container.png_file(res, self.rh, exact=exact)
+        with open(png_path, "wb") as f:
+            f.write(data)
+        return row
 
     # ---- a given palette (EXTENSION, no reference counterpart) ------------------------------------------------------------------
     def _reduce(self, pal, counts, colours):
@@ -844,7 +869,8 @@ class ImageEncoder:
         return out + (row, target, data)
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
-                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
+                            target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4,
+                            png_path=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -923,8 +949,13 @@ class ImageEncoder:
         stats["pattern"] = {strength: as given, size: n, moved: {all: pixels whose index is not the nearest row[, roi, nonroi]},
         pixels}; there is no stats["runs"].  With target_psnr it raises ValueError, for dither's reason.  A byte target probes every
         rung with the pattern on, and its bound_psnr is {table: None}.  The palette may have at most ops.palette_pattern_max_rows()
-        rows (RhccqError)."""
+        rows (RhccqError).
+        png_path (default None = off; independent of out_path): the index map returned, after every rule above, is also written as
+        a PNG file built on the device (container.write_png: a palette PNG up to 256 rows, truecolour with adaptive row filters above;
+        exact= is shared with out_path and sends IDAT through the level-9 encoder).  stats["png"] = {bytes, colour_type, depth,
+        filter_rows}.  A target_bytes counts the .rhccq file's bytes, not the PNG's."""
         rh = self.rh
+        png_path = self._png_arg("ImageEncoder.encode_with_palette", png_path)
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
         if refine < 0 or refine > 64:
@@ -995,6 +1026,9 @@ class ImageEncoder:
             else:
                 container.write_frame(res, out_path, rh, exact=exact)
             lap("container")
+        if png_path:
+            stats["png"] = self._png_write(res, png_path, exact)
+            lap("png")
         if report:
             host = image.cpu().numpy() if torch.is_tensor(image) else np.ascontiguousarray(image, dtype=np.uint8)
             _, _, rgb_r, rstats = self.regions(host, roi_mask)
@@ -1021,7 +1055,7 @@ class ImageEncoder:
         return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
-                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4):
+                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None):
         """image: uint8[H,W,3] (numpy or device tensor), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
         variance-minimising box splitting over it in exact integers (Rhccq.palette_build: the box whose best cut removes the most
@@ -1033,8 +1067,9 @@ class ImageEncoder:
         ops.palette_build_max_rows() (RhccqError).  Colours that share a cell of the histogram (equal in their upper five bits per
         channel) are never separated, so fewer than N rows come back when fewer cells are occupied, and two boxes may round to the
         same row.  stats["build"] = {asked: N, rows: rows built, cells: occupied cells, steps: splits}; everything else as
-        encode_with_palette fills it."""
+        encode_with_palette fills it.  png_path: as encode_with_palette takes it."""
         rh = self.rh
+        png_path = self._png_arg("ImageEncoder.quantize", png_path)
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
         if colours < 1:
@@ -1055,7 +1090,8 @@ class ImageEncoder:
         seconds = time.perf_counter() - t0
         res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
                                        roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
-                                       run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size)
+                                       run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size,
+                                       png_path=png_path)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         return res

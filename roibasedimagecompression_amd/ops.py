@@ -1895,6 +1895,90 @@ class Rhccq:
         n = int(length.item())
         return self.to_host(out[:n]).tobytes()
 
+    # -- indexed PNG files (EXTENSION: csrc/png_write.hip; include/rhccq.h pins the file) ----------------------------
+    @staticmethod
+    def _png_flags(exact=False, depth8=False, filter=True):
+        return (1 if exact else 0) | (2 if depth8 else 0) | (0 if filter else 4)
+
+    def _png_args(self, fn, indices, H, W, palette):
+        H, W = int(H), int(W)
+        palette = A.as_uint8(palette, self.device, fn, "palette")
+        if palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError(f"{fn}: palette [K, 3] is expected")
+        K = int(palette.shape[0])
+        if H < 1 or W < 1 or not 1 <= K <= 65536:
+            raise RhccqError(f"{fn}: H >= 1, W >= 1 and K 1..65536 are expected")
+        return A.index_map(indices, H, W, self.device, fn), H, W, palette, K
+
+    def png_sizes(self, H, W, K, exact=False, depth8=False, filter=True):
+        """-> (scanline bytes, png_encode's workspace bytes, the file's bound) of an H x W map over K palette rows (host only)"""
+        s, ws, bound = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = self._raw.rhccq_png_sizes(int(H), int(W), int(K), self._png_flags(exact, depth8, filter), C.byref(s), C.byref(ws), C.byref(bound))
+        if rc:
+            raise RhccqError(f"png_sizes: rhccq_png_sizes({H}, {W}, {K}) failed ({rc})")
+        return s.value, ws.value, bound.value
+
+    def png_scanlines(self, indices, H, W, palette, depth8=False, filter=True):
+        """indices (H * W elements: uint8, int16 holding uint16, int32 / int64; numpy or device), palette uint8[K, 3] -> (scan uint8 device:
+        the H filtered scanlines of the PNG file, filter_rows int64[5] device: rows per filter type).  K <= 256: packed indices at 1, 2,
+        4 or 8 bits (depth8=True: 8), filter type 0; K > 256: palette[idx] as R G B under the row's cheapest filter (filter=False: type
+        0).  An index >= K is written as 0.  One launch."""
+        fn = "png_scanlines"
+        idx, H, W, palette, K = self._png_args(fn, indices, H, W, palette)
+        n = self.png_sizes(H, W, K, True, depth8, filter)[0]
+        scan = self.empty((n,), torch.uint8)
+        rows = self.empty((5,), torch.int64)
+        self._check(self.lib.rhccq_png_scanlines(self.ctx, self._p(idx), idx.element_size(), H, W, self._p(palette), K,
+                                                 self._png_flags(False, depth8, filter), self._p(scan), self._p(rows)), fn)
+        return scan, rows
+
+    def crc32_async(self, t, n=None):
+        """contiguous device tensor (its raw bytes) -> the CRC-32 (zlib.crc32) as a device tensor of one int32 element holding the 32
+        bits; n: a device int64 tensor with the number of leading bytes to take (clamped to the tensor), or None for all.  Two launches,
+        nothing waits for the device."""
+        if not t.is_cuda or not t.is_contiguous():
+            raise RhccqError("crc32: a contiguous device tensor is required")
+        cap = t.numel() * t.element_size()
+        if n is not None and (not torch.is_tensor(n) or n.dtype != torch.int64 or not n.is_cuda or n.numel() != 1):
+            raise RhccqError("crc32: n must be a device int64 tensor of one element")
+        work = self.empty((max(int(self._raw.rhccq_crc32_bytes(cap)), 4),), torch.uint8)
+        out = self.empty((1,), torch.int32)
+        self._check(self.lib.rhccq_crc32(self.ctx, self._p(t) if cap else C.c_void_p(0), cap, self._p(n), self._p(work), self._p(out)), "crc32")
+        return out
+
+    def crc32(self, t, n=None):
+        """zlib.crc32 of a contiguous device tensor's bytes (the first n of them: n an int, or a device int64 tensor) as a Python int"""
+        if n is not None and not torch.is_tensor(n):
+            n = int(n)
+            if not 0 <= n <= t.numel() * t.element_size():
+                raise ValueError("crc32: n must be 0..the tensor's bytes")
+            t, n = t.reshape(-1).view(torch.uint8)[:n], None
+        return int(self.to_host(self.crc32_async(t, n))[0]) & 0xFFFFFFFF
+
+    def png_encode_async(self, indices, H, W, palette, exact=False, depth8=False, filter=True):
+        """indices and palette as png_scanlines takes them -> (uint8 device buffer, int64 device length): the PNG file is
+        out[:length] -- signature, IHDR, PLTE (K <= 256), one IDAT, IEND -- built on the device; nothing waits for it.  exact=True: IDAT
+        is zlib.compress(scanlines, 9) byte for byte (the level-9 encoder), so the file is a function of the arguments alone."""
+        return self._png_encode(indices, H, W, palette, exact, depth8, filter)[:2]
+
+    def _png_encode(self, indices, H, W, palette, exact, depth8, filter):
+        """-> (out, length, filter_rows int64[5] device: a view of the call's workspace)"""
+        fn = "png_encode"
+        idx, H, W, palette, K = self._png_args(fn, indices, H, W, palette)
+        scan, ws, bound = self.png_sizes(H, W, K, exact, depth8, filter)
+        work = self.empty((ws,), torch.uint8)
+        out = self.empty((bound,), torch.uint8)
+        length = self.empty((1,), torch.int64)
+        self._check(self.lib.rhccq_png_encode(self.ctx, self._p(idx), idx.element_size(), H, W, self._p(palette), K,
+                                              self._png_flags(exact, depth8, filter), self._p(work), self._p(out), bound, self._p(length)), fn)
+        at = (scan + 255) // 256 * 256 + 16
+        return out, length, work[at:at + 40].view(torch.int64)
+
+    def png_encode(self, indices, H, W, palette, exact=False, depth8=False, filter=True):
+        """png_encode_async's file as bytes: one read of the length, one copy of the file"""
+        out, length = self.png_encode_async(indices, H, W, palette, exact, depth8, filter)
+        return self.to_host(out[:int(length.item())]).tobytes()
+
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
     ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
     _ZS_MSG = {1: "incorrect header check", 2: "invalid block type, code lengths, symbol or distance",
