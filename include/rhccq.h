@@ -1182,6 +1182,120 @@ int rhccq_crc32_host(const uint8_t* data, int64_t n, uint32_t* crc_out);
 int rhccq_png_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t H, int32_t W, const uint8_t* palette, int32_t K, int32_t flags,
                           uint8_t* out, int64_t out_cap, int64_t* out_len);
 
+/* ---- EXTENSION: PNG files read on the device (no reference counterpart; csrc/png_read.hip, csrc/png_read.h) --------------------------------
+ * Files accepted.  The 8-byte signature, then chunks (length, type, data, CRC-32 over type and data).  IHDR first, 13 bytes, W, H in
+ * 1..2^31 - 1; (colour type, depth) one of 0:{1,2,4,8,16}, 2:{8,16}, 3:{1,2,4,8}, 4:{8,16}, 6:{8,16}; compression 0, filter method 0;
+ * interlace 0 (interlace 1: RHCCQ_PNG_UNSUPPORTED).  PLTE (3 K bytes, 1 <= K <= 256) is required before IDAT for colour type 3, ignored for
+ * types 2 and 6, an error for types 0 and 4.  tRNS (before IDAT; behind PLTE for type 3) is optional: type 3 up to K alpha bytes (missing
+ * ones are 255), type 0 one 16-bit key, type 2 three, types 4 and 6 an error.  At least one IDAT; IDATs are consecutive, of any lengths
+ * (zero included), their payloads joined are ONE zlib stream.  IEND (empty) is required, bytes behind it are ignored.  Any other chunk
+ * whose first type byte has bit 5 set is skipped (its CRC is still checked); an unknown critical chunk is an error.
+ * Status.  One RHCCQ_PNG_* status and one detail word; of several faults the one that stands first below is reported:
+ *   BAD_SIGNATURE
+ *   BAD_CHUNK      framing: a chunk that runs past the end of the file (or a length above 2^31 - 1), IHDR not first or repeated, PLTE / tRNS
+ *                  repeated or behind IDAT, IDATs not consecutive, a non-empty IEND, no IDAT, no IEND, an unknown critical chunk; and, where
+ *                  the header is valid, what it decides: PLTE missing (type 3) or present (types 0, 4), PLTE's or tRNS's length, tRNS in front
+ *                  of PLTE (type 3) or present at all (types 4, 6).  detail: the index of the chunk at which the fault shows, or the number
+ *                  of chunks where one is missing
+ *   BAD_HEADER     IHDR's length or contents
+ *   UNSUPPORTED    interlace 1
+ *   LIMIT          scanline bytes H (1 + rowbytes), or IDAT bytes, of 2^31 or more: the inflater's limit
+ *   BAD_CRC        detail: the index of the first chunk whose CRC does not match
+ *   BAD_STREAM     detail: the RHCCQ_ZS_* code of the zlib stream
+ *   BAD_LENGTH     the stream does not inflate to exactly H (1 + rowbytes) bytes (it is inflated with that out_cap); detail: the length it
+ *                  has (or needs), clamped to 2^31 - 1
+ *   BAD_FILTER     detail: the first row whose filter type byte is above 4
+ *   STALLED        the unfilter's bounded wait between bands ran out (see below); never seen on a device that makes progress
+ * BAD_SIGNATURE .. LIMIT are decided by rhccq_png_parse_host, a pure function of the file's bytes, before any device work.
+ * Unfilter.  The PNG specification's: bpp = max(1, channels * depth / 8) bytes, rowbytes = ceil(W * channels * depth / 8); bytes left of a
+ * row and the row above row 0 are zero; arithmetic modulo 256; Average adds floor((a + b) / 2) computed in 9 bits; Paeth has p = a + b - c
+ * and prefers a, then b, then c, with <= as the specification words it.  A row whose type byte is above 4 is copied as type 0.
+ * Expand.  Samples below 8 bits are unpacked most significant bits first; grey at depth d < 8 is scaled by 255 / (2^d - 1), exactly; a 16-bit
+ * sample gives its high byte; grey goes to R = G = B; colour type 3 gives palette[idx], an index at or past K shows row 0 (rhccq_decode's
+ * rule).  Alpha is the alpha channel (its high byte at 16 bits), or the tRNS entry of the index (255 past the entries), or 0 where the
+ * full-depth samples equal the tRNS key (its low `depth` bits) and 255 elsewhere, or 255 where the file has none.
+ * Device forms: every pointer but info is device memory; async on the context stream, no host synchronisation, nothing allocated.  Every
+ * stage stays inside its buffers for ANY bytes: offsets and lengths of a table are tested against n again inside the kernels.
+ *   rhccq_crc32_segments  crc_out[i] = zlib.crc32(data[offset_i .. offset_i + length_i + extra)) for the n_seg rows of a table in TWO launches
+ *                         whatever n_seg is: a workgroup per (segment, 16 KiB piece) takes a plain remainder as rhccq_crc32 does (it finds
+ *                         its segment by a search over first_piece), then a wave per segment joins its pieces.  No workgroup waits for
+ *                         another.  data must be aligned to 16; the table's first_piece column and total_pieces come from
+ *                         rhccq_crc32_segments_plan (host only), workspace is 4 * total_pieces bytes (at least 4), aligned to 4.  A row that
+ *                         does not lie inside data[0 .. n) counts as empty.
+ *   rhccq_png_unfilter    scan: H rows of 1 + rowbytes bytes (rowbytes a multiple of bpp, bpp 1, 2, 3, 4, 6 or 8) -> raw_out: H rows of
+ *                         rowbytes bytes.  A one-wave workgroup owns a band of rhccq_png_unfilter_band_rows() rows, a lane a row; at step u
+ *                         lane r stands at the filter unit (bpp bytes) u - r, takes "above" from lane r - 1 across lanes and keeps left and
+ *                         upper left in registers; bytes go through LDS tiles of rhccq_png_unfilter_tile() steps.  The last row of a band
+ *                         reaches the next band through words of the workspace that carry three bytes and a mark, fetched
+ *                         rhccq_png_unfilter_granule() units at a time.  A band's number is a ticket drawn at its start, so it waits only
+ *                         for bands that have started; a band whose first row has type 0 or 1 waits for nothing; every wait is bounded (past
+ *                         the bound: STALLED, and the output means nothing).  status (device int32[2]): OK, BAD_FILTER or STALLED and the
+ *                         detail.  workspace: rhccq_png_unfilter_bytes(H, rowbytes, bpp) bytes, aligned to 4.
+ *   rhccq_png_expand      raw rows -> rgb[H][W][3], alpha[H][W] (may be NULL), idx[H][W] (may be NULL; written for colour type 3 only).
+ *                         palette: K rows of 3 bytes (type 3), trns: trns_bytes bytes as the chunk holds them (may be NULL with 0).
+ *   rhccq_png_decode      segment CRCs (unless RHCCQ_PNG_READ_NO_CRC), IDAT join (one launch over the joined stream: a lane finds the chunk
+ *                         of its 16 bytes by a search over the table), rhccq_zlib_decompress, unfilter, expand, and one launch that keeps
+ *                         the first failing stage's status by the precedence above in status (device int32[2]).  Later stages run on whatever
+ *                         they get.  info and the table are rhccq_png_parse_host's (the table copied to the device, file aligned to 16);
+ *                         with info->status set nothing runs but the launch that writes it to status.  workspace: rhccq_png_read_sizes,
+ *                         aligned to 256; afterwards the scanlines lie at rhccq_png_read_scan_offset(info) in it.
+ * Host forms (serial, no GPU, host memory): the same step functions of csrc/png_read.h. */
+#define RHCCQ_PNG_OK 0
+#define RHCCQ_PNG_BAD_SIGNATURE 1
+#define RHCCQ_PNG_BAD_CHUNK 2
+#define RHCCQ_PNG_BAD_HEADER 3
+#define RHCCQ_PNG_UNSUPPORTED 4
+#define RHCCQ_PNG_LIMIT 5
+#define RHCCQ_PNG_BAD_CRC 6
+#define RHCCQ_PNG_BAD_STREAM 7
+#define RHCCQ_PNG_BAD_LENGTH 8
+#define RHCCQ_PNG_BAD_FILTER 9
+#define RHCCQ_PNG_STALLED 10
+#define RHCCQ_PNG_READ_NO_CRC 1
+/* a byte range of one buffer.  As a PNG chunk: offset is that of the chunk's type field, length its data length (the CRC covers
+   length + 4 bytes from offset), dst the offset of an IDAT's payload in the joined stream, -1 for every other chunk */
+typedef struct rhccq_segment {
+  int64_t offset, length, first_piece, dst;
+} rhccq_segment;
+typedef struct rhccq_png_info {
+  int32_t status, detail;                 /* RHCCQ_PNG_OK .. RHCCQ_PNG_LIMIT */
+  int32_t width, height, depth, colour_type, interlace, channels, bpp;
+  int32_t palette_rows, trns_bytes;       /* K (0 unless colour type 3); bytes of tRNS (0: none) */
+  int32_t n_chunks, first_idat, n_idat;   /* chunks walked; the IDATs are chunks first_idat .. first_idat + n_idat - 1 */
+  int64_t rowbytes, scan_bytes;           /* H (1 + rowbytes) */
+  int64_t plte_offset, trns_offset;       /* of the chunks' data, -1 without */
+  int64_t idat_bytes, crc_pieces;         /* the joined stream; total_pieces of the chunk table (extra 4) */
+} rhccq_png_info;
+/* host only.  RHCCQ_E_ARG for a null file (with n > 0), info or n_chunks, n < 0, or chunks_cap < 0; otherwise RHCCQ_OK with info->status set.
+   chunks (may be NULL with chunks_cap 0) receives the first chunks_cap rows, *n_chunks their full number (at most n / 12) */
+int rhccq_png_parse_host(const uint8_t* file, int64_t n, rhccq_png_info* info, rhccq_segment* chunks, int64_t chunks_cap, int64_t* n_chunks);
+/* host only: fills first_piece of every row and *total_pieces */
+int rhccq_crc32_segments_plan(rhccq_segment* table, int64_t n_seg, int64_t extra, int64_t* total_pieces);
+int rhccq_crc32_segments(rhccq_ctx* ctx, const uint8_t* data, int64_t n, const rhccq_segment* table_dev, int64_t n_seg, int64_t extra,
+                         int64_t total_pieces, void* workspace, uint32_t* crc_out);
+int rhccq_crc32_segments_host(const uint8_t* data, int64_t n, const rhccq_segment* table, int64_t n_seg, int64_t extra, uint32_t* crc_out);
+int32_t rhccq_png_unfilter_band_rows(void);
+int32_t rhccq_png_unfilter_tile(void);
+int32_t rhccq_png_unfilter_granule(void);
+int64_t rhccq_png_unfilter_bytes(int32_t H, int64_t rowbytes, int32_t bpp);       /* host only; negative for bad arguments */
+int rhccq_png_unfilter(rhccq_ctx* ctx, const uint8_t* scan, int32_t H, int64_t rowbytes, int32_t bpp, uint8_t* raw_out, void* workspace,
+                       int32_t* status);
+int rhccq_png_unfilter_host(const uint8_t* scan, int32_t H, int64_t rowbytes, int32_t bpp, uint8_t* raw_out, int32_t* status);
+int rhccq_png_expand(rhccq_ctx* ctx, const uint8_t* raw, int32_t H, int32_t W, int32_t colour_type, int32_t depth, const uint8_t* palette,
+                     int32_t K, const uint8_t* trns, int32_t trns_bytes, uint8_t* rgb, uint8_t* alpha, uint8_t* idx);
+int rhccq_png_expand_host(const uint8_t* raw, int32_t H, int32_t W, int32_t colour_type, int32_t depth, const uint8_t* palette, int32_t K,
+                          const uint8_t* trns, int32_t trns_bytes, uint8_t* rgb, uint8_t* alpha, uint8_t* idx);
+/* the IDAT join alone: idat_dev holds the n_idat IDAT rows of a chunk table (dst ascending from 0), stream (aligned to 16) receives
+   `total` bytes, rounded up to 16 with zeros */
+int rhccq_png_join(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_segment* idat_dev, int32_t n_idat, int64_t total, uint8_t* stream);
+/* host only: rhccq_png_decode's workspace for a parsed file of n bytes */
+int rhccq_png_read_sizes(const rhccq_png_info* info, int64_t n, int64_t* workspace_bytes);
+int64_t rhccq_png_read_scan_offset(const rhccq_png_info* info);
+int rhccq_png_decode(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_png_info* info, const rhccq_segment* table_dev, int32_t flags,
+                     void* workspace, uint8_t* rgb, uint8_t* alpha, uint8_t* idx, int32_t* status);
+/* file in host memory; parses it itself; status: host int32[2] */
+int rhccq_png_decode_host(const uint8_t* file, int64_t n, int32_t flags, uint8_t* rgb, uint8_t* alpha, uint8_t* idx, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,19 @@ class ClassDesc(C.Structure):
                 ("quality", c_int32), ("reserved", c_int32)]
 
 
+class Segment(C.Structure):
+    """struct rhccq_segment (include/rhccq.h): a byte range of one buffer; a PNG chunk"""
+    _fields_ = [("offset", c_int64), ("length", c_int64), ("first_piece", c_int64), ("dst", c_int64)]
+
+
+class PngInfo(C.Structure):
+    """struct rhccq_png_info (include/rhccq.h): what rhccq_png_parse_host reads from a file's framing"""
+    _fields_ = [("status", c_int32), ("detail", c_int32), ("width", c_int32), ("height", c_int32), ("depth", c_int32), ("colour_type", c_int32),
+                ("interlace", c_int32), ("channels", c_int32), ("bpp", c_int32), ("palette_rows", c_int32), ("trns_bytes", c_int32),
+                ("n_chunks", c_int32), ("first_idat", c_int32), ("n_idat", c_int32), ("rowbytes", c_int64), ("scan_bytes", c_int64),
+                ("plte_offset", c_int64), ("trns_offset", c_int64), ("idat_bytes", c_int64), ("crc_pieces", c_int64)]
+
+
 class FrameResult(C.Structure):
     """struct rhccq_frame_result (include/rhccq.h)"""
     _fields_ = [("n_colours", c_int32), ("index_bytes", c_int32), ("shape", c_int32 * 2), ("top_left", c_int32 * 2), ("quality3", c_int32),
@@ -252,6 +265,23 @@ PROTOTYPES = {
     "rhccq_png_scanlines_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "rhccq_crc32_host": (c_int32, [c_void_p, c_int64, c_void_p]),
     "rhccq_png_encode_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    "rhccq_png_parse_host": (c_int32, [c_void_p, c_int64, C.POINTER(PngInfo), c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_crc32_segments_plan": (c_int32, [c_void_p, c_int64, c_int64, C.POINTER(c_int64)]),
+    "rhccq_crc32_segments": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "rhccq_crc32_segments_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "rhccq_png_unfilter_band_rows": (c_int32, []),
+    "rhccq_png_unfilter_tile": (c_int32, []),
+    "rhccq_png_unfilter_granule": (c_int32, []),
+    "rhccq_png_unfilter_bytes": (c_int64, [c_int32, c_int64, c_int32]),
+    "rhccq_png_unfilter": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_png_unfilter_host": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
+    "rhccq_png_expand": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_png_expand_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_png_join": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p]),
+    "rhccq_png_read_sizes": (c_int32, [C.POINTER(PngInfo), c_int64, C.POINTER(c_int64)]),
+    "rhccq_png_read_scan_offset": (c_int64, [C.POINTER(PngInfo)]),
+    "rhccq_png_decode": (c_int32, [c_void_p, c_void_p, c_int64, C.POINTER(PngInfo), c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_png_decode_host": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

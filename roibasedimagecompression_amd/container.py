@@ -9,6 +9,7 @@ side (load_compressed_device, lossless_decompress_device, read_frame) inflates e
 (csrc/zlib_inflate.hip) and leaves the index map on the device.  There is no CPU fallback: without a GPU these functions
 raise like Rhccq(0) does."""
 import io
+import os
 import pickle
 import struct
 
@@ -199,6 +200,58 @@ def read_frame(path, rh=None):
     return {"image": img, "palette": pal, "indices": idx, "shape": (h, w), "dtype": name}
 
 
+def read_png(src, rh=None, check_crc=True):
+    """a PNG file -> {"image": uint8[H, W, 3] device, "alpha": uint8[H, W] device or None, "shape": (H, W), "info": {colour_type, depth,
+    interlace, chunks, idat_chunks, filter_rows}} decoded on the device (include/rhccq.h "PNG files read on the device": chunk CRCs, IDAT
+    join, inflate, unfilter, expand).  src: a file name, bytes, or a uint8 device tensor holding the file (read back once for its
+    framing).  Colour type 3 also gives "palette" (uint8[K, 3] device), "palette_alpha" (uint8[K] device or None), "indices" (uint8, flat)
+    and "dtype" ("uint8"): what read_frame returns, so write_png, write_frame and reduce_frame's steps take it as they take a .rhccq
+    file's frame.  The host reads the file once, parses its framing (rhccq_png_parse_host) and uploads it once; one read of the two status
+    words and the five filter counts is the only wait.  A file the definition refuses raises RhccqError naming status and detail.
+    check_crc=False skips the chunk CRCs.  Not read: interlaced files, 16-bit output (a 16-bit sample gives its high byte), gamma and
+    colour-management chunks, APNG."""
+    from .ops import PNG_STATUS, png_parse
+    rh = rh or default_context()
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.uint8:
+            raise RhccqError("read_png: a file name, bytes or a uint8 device tensor is required")
+        data, file = rh.to_host(src.reshape(-1).to(rh.device)).tobytes(), src
+    elif isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytearray(src)                                    # (writable: torch takes the buffer as it is)
+        file = np.frombuffer(data, np.uint8)
+    else:
+        with open(src, "rb") as f:
+            data = bytearray(os.fstat(f.fileno()).st_size)
+            del data[f.readinto(data):]
+        file = np.frombuffer(data, np.uint8)
+    info, table = png_parse(data)
+
+    def refuse(status, detail):
+        raise RhccqError(f"read_png: RHCCQ_PNG_{PNG_STATUS[status]} (status {status}), detail {detail}")
+    if info.status:
+        refuse(info.status, info.detail)
+    out = rh.png_decode(file, info, table, check_crc=check_crc)
+    H, W = info.height, info.width
+    types = out["scan"][::info.rowbytes + 1]
+    rows = (types.unsqueeze(1) == torch.arange(5, device=types.device, dtype=torch.uint8)).sum(0)
+    status, rows = rh.to_host(out["status"], rows)
+    if int(status[0]):
+        refuse(int(status[0]), int(status[1]))
+    res = {"image": out["rgb"], "alpha": out["alpha"], "shape": (H, W),
+           "info": {"colour_type": info.colour_type, "depth": info.depth, "interlace": info.interlace, "chunks": info.n_chunks, "idat_chunks": info.n_idat,
+                    "filter_rows": [int(v) for v in rows]}}
+    if info.colour_type == 3:
+        K = info.palette_rows
+        res["palette"] = out["file"][info.plte_offset:info.plte_offset + 3 * K].reshape(K, 3).clone()
+        res["palette_alpha"] = None
+        if info.trns_bytes:
+            res["palette_alpha"] = torch.full((K,), 255, dtype=torch.uint8, device=rh.device)
+            res["palette_alpha"][:info.trns_bytes] = out["file"][info.trns_offset:info.trns_offset + info.trns_bytes]
+        res["indices"] = out["indices"].reshape(-1)
+        res["dtype"] = "uint8"
+    return res
+
+
 def index_histogram(indices, n_rows, rh=None, weights=None):
     """how often every palette row is used: int64[n_rows] on the device from an index map (uint8, int16 holding uint16, int32 or
     int64, any shape), by torch.bincount.  An index past the palette counts for row 0, the row a decoder shows for it.  weights:
@@ -214,19 +267,33 @@ def index_histogram(indices, n_rows, rh=None, weights=None):
     return torch.bincount(wide, weights=weights.reshape(-1).to(torch.float64), minlength=n_rows).to(torch.int64)
 
 
+def reduce_png(src, dst, colours, rh=None, exact=False):
+    """reduce_frame for a palette PNG (colour type 3): read_png, the same reduction over the file's own PLTE and index map, write_png at
+    the end.  -> reduce_frame's dict ("bytes" is the PNG file's length).  Any other colour type raises RhccqError."""
+    rh = rh or default_context()
+    fr = read_png(src, rh)
+    if "palette" not in fr:
+        raise RhccqError(f"reduce_png: a palette PNG (colour type 3) is required, the file has colour type {fr['info']['colour_type']}")
+    return _reduce_read(fr, write_png, "reduce_png", dst, colours, rh, exact)
+
+
 def reduce_frame(src, dst, colours, rh=None, exact=False):
     """a .rhccq file to one of at most `colours` palette rows, without the source image: read_frame, the histogram of the indices,
     Rhccq.palette_reduce (exact pairwise merging, include/rhccq.h), every index through the reduction's map (no pixel carries an
     unused row, so no -1 is read), write_frame.  A file that has no more than `colours` used rows only loses its unused ones.
     -> {"from": rows read, "to": rows written, "bytes": write_frame's value, "psnr": the new decode against the old decode (inf
     when nothing merged)}.  The palette may have at most ops.palette_reduce_max_rows() rows (RhccqError)."""
-    from .ops import psnr_from_sse
     rh = rh or default_context()
-    fr = read_frame(src, rh)
+    return _reduce_read(read_frame(src, rh), write_frame, "reduce_frame", dst, colours, rh, exact)
+
+
+def _reduce_read(fr, write, fn, dst, colours, rh, exact):
+    """reduce_frame's steps behind the read: fr is read_frame's or read_png's dict, write is write_frame or write_png"""
+    from .ops import psnr_from_sse
     pal = fr["palette"].contiguous()
     K = int(pal.shape[0])
     if int(colours) < 1:
-        raise ValueError("reduce_frame: colours >= 1 is expected")
+        raise ValueError(f"{fn}: colours >= 1 is expected")
     h, w = fr["shape"]
     wide = fr["indices"].reshape(-1).to(torch.int32)
     if fr["indices"].dtype == torch.int16:
@@ -235,7 +302,7 @@ def reduce_frame(src, dst, colours, rh=None, exact=False):
     new_pal, _, map_, _ = rh.palette_reduce(pal, index_histogram(wide, K, rh), min(int(colours), K))
     idx = rh.remap(wide, map_.contiguous())
     res = {"palette": rh.to_host(new_pal), "indices": idx, "shape": (h, w)}
-    size = write_frame(res, dst, rh, exact=exact)
+    size = write(res, dst, rh, exact=exact)
     one_class = torch.zeros((h, w), dtype=torch.uint8, device=rh.device)
     row = rh.class_error_sums_indexed(fr["image"].contiguous(), idx, new_pal.contiguous(), one_class, 1)[0]
     return {"from": K, "to": int(new_pal.shape[0]), "bytes": size, "psnr": psnr_from_sse(int(row[0]) + int(row[1]) + int(row[2]), h * w)}

@@ -134,7 +134,7 @@ inline void crc_x2n(uint32_t* x2n) {
   for (int k = 1; k < 32; ++k) x2n[k] = p = crc_mul(p, p);
 }
 // x^e mod P (zlib's x2nmodp: the table wraps because x^(2^32) = x)
-inline uint32_t crc_xpow(const uint32_t* x2n, uint64_t e) {
+RHCCQ_PNG_HD uint32_t crc_xpow(const uint32_t* x2n, uint64_t e) {
   uint32_t p = kCrcOne;
   for (int k = 0; e; e >>= 1, ++k)
     if (e & 1) p = crc_mul(x2n[k & 31], p);
@@ -173,6 +173,79 @@ inline uint32_t crc_state(uint32_t state, const uint8_t* data, int64_t n) {
   for (int64_t i = 0; i < n; ++i) state = crc_byte(state, data[i]);
   return state;
 }
+
+#if defined(__HIPCC__)
+// ---- CRC-32 on the device: what the kernels of png_write.hip and png_read.hip share ---------------------------------------------------
+// the bytes lo .. hi - 1 (of 0..3) of a word kept, the others zero
+__device__ __forceinline__ uint32_t crc_keep(uint32_t w, long long lo, long long hi) {
+  const int l = lo < 0 ? 0 : lo > 4 ? 4 : (int)lo, h = hi < 0 ? 0 : hi > 4 ? 4 : (int)hi;
+  if (h <= l) return 0u;
+  const uint32_t mh = h == 4 ? 0xFFFFFFFFu : (1u << (8 * h)) - 1u, ml = (1u << (8 * l)) - 1u;   // l < 4 here
+  return w & mh & ~ml;
+}
+
+struct CrcPieceLds {
+  uint32_t tab[4][256];
+  uint4 data[kCrcBlock / 64][64 * 5];                                // a lane's 64 bytes in an 80-byte strip
+  uint32_t wave[kCrcBlock / 64];
+};
+
+// a workgroup of kCrcBlock lanes: the plain remainder of the piece that starts at the virtual byte v0 of the string at base (aligned to 16),
+// of which the bytes front .. end - 1 are the message and all others count as zero; v0 < end.  Valid in thread 0; two barriers.
+__device__ __forceinline__ uint32_t crc_piece_remainder(CrcPieceLds& lds, const uint8_t* __restrict__ base, long long front, long long end, long long v0,
+                                                        const CrcConsts& k) {
+  {
+    uint32_t c = threadIdx.x;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      c = crc_shift8(c);
+      lds.tab[t][threadIdx.x] = c;                                     // byte, then t zero bytes
+    }
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int u = lane + 64 * j;
+    const long long v = v0 + (long long)w * kCrcWave + 16 * u;
+    uint4 x = make_uint4(0u, 0u, 0u, 0u);
+    if (v + 16 > front && v < end) {
+      x = *(const uint4*)(base + v);
+      if (v < front || v + 16 > end) {
+        x.x = crc_keep(x.x, front - v, end - v);
+        x.y = crc_keep(x.y, front - v - 4, end - v - 4);
+        x.z = crc_keep(x.z, front - v - 8, end - v - 8);
+        x.w = crc_keep(x.w, front - v - 12, end - v - 12);
+      }
+    }
+    lds.data[w][(u >> 2) * 5 + (u & 3)] = x;
+  }
+  __syncthreads();
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint4 x = lds.data[w][lane * 5 + j];
+    const uint32_t q[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      c ^= q[i];
+      c = lds.tab[3][c & 255u] ^ lds.tab[2][(c >> 8) & 255u] ^ lds.tab[1][(c >> 16) & 255u] ^ lds.tab[0][c >> 24];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {                                      // lane i takes in the 2^j lanes behind it
+    const uint32_t right = __shfl_down(c, 1 << j, 64);
+    c = crc_mul(c, k.lane[j]) ^ right;
+  }
+  if (lane == 0) lds.wave[w] = c;
+  __syncthreads();
+  uint32_t r = 0;
+  if (threadIdx.x == 0) {
+    r = lds.wave[0];
+    for (int i = 1; i < kCrcBlock / 64; ++i) r = crc_mul(r, k.wave) ^ lds.wave[i];
+  }
+  return r;
+}
+#endif
 
 // ---- chunk framing the host knows in full --------------------------------------------------------------------------------------------
 inline void put_be32(uint8_t* p, uint32_t v) {

@@ -126,74 +126,17 @@ __device__ __forceinline__ long long crc_len(const long long* n_dev, long long n
   return n < 0 ? 0 : n > n_cap ? n_cap : n;
 }
 
-// the bytes lo .. hi - 1 (of 0..3) of a word kept, the others zero
-__device__ __forceinline__ uint32_t crc_keep(uint32_t w, long long lo, long long hi) {
-  const int l = lo < 0 ? 0 : lo > 4 ? 4 : (int)lo, h = hi < 0 ? 0 : hi > 4 ? 4 : (int)hi;
-  if (h <= l) return 0u;
-  const uint32_t mh = h == 4 ? 0xFFFFFFFFu : (1u << (8 * h)) - 1u, ml = (1u << (8 * l)) - 1u;   // l < 4 here
-  return w & mh & ~ml;
-}
-
 // base = data - front is aligned to 16; the message is the virtual bytes front .. front + n - 1 of the string that starts at base
 __global__ __launch_bounds__(kCrcBlock) void crc_partials(const uint8_t* __restrict__ base, int front, long long n_cap, const long long* __restrict__ n_dev,
                                                           long long n_add, CrcConsts k, uint32_t* __restrict__ partials) {
-  __shared__ uint32_t s_tab[4][256];
-  __shared__ uint4 s_data[kCrcBlock / 64][64 * 5];                   // a lane's 64 bytes in an 80-byte strip
-  __shared__ uint32_t s_wave[kCrcBlock / 64];
+  __shared__ CrcPieceLds lds;
   const long long end = front + crc_len(n_dev, n_add, n_cap), v0 = (long long)blockIdx.x * kCrcPiece;
   if (v0 >= end || end == front) {                                   // a piece past the message, or no message (uniform)
     if (threadIdx.x == 0) partials[blockIdx.x] = 0u;
     return;
   }
-  {
-    uint32_t c = threadIdx.x;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      c = crc_shift8(c);
-      s_tab[t][threadIdx.x] = c;                                     // byte, then t zero bytes
-    }
-  }
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int u = lane + 64 * j;
-    const long long v = v0 + (long long)w * kCrcWave + 16 * u;
-    uint4 x = make_uint4(0u, 0u, 0u, 0u);
-    if (v + 16 > front && v < end) {
-      x = *(const uint4*)(base + v);
-      if (v < front || v + 16 > end) {
-        x.x = crc_keep(x.x, front - v, end - v);
-        x.y = crc_keep(x.y, front - v - 4, end - v - 4);
-        x.z = crc_keep(x.z, front - v - 8, end - v - 8);
-        x.w = crc_keep(x.w, front - v - 12, end - v - 12);
-      }
-    }
-    s_data[w][(u >> 2) * 5 + (u & 3)] = x;
-  }
-  __syncthreads();
-  uint32_t c = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint4 x = s_data[w][lane * 5 + j];
-    const uint32_t q[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      c ^= q[i];
-      c = s_tab[3][c & 255u] ^ s_tab[2][(c >> 8) & 255u] ^ s_tab[1][(c >> 16) & 255u] ^ s_tab[0][c >> 24];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {                                      // lane i takes in the 2^j lanes behind it
-    const uint32_t right = __shfl_down(c, 1 << j, 64);
-    c = crc_mul(c, k.lane[j]) ^ right;
-  }
-  if (lane == 0) s_wave[w] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t r = s_wave[0];
-    for (int i = 1; i < kCrcBlock / 64; ++i) r = crc_mul(r, k.wave) ^ s_wave[i];
-    partials[blockIdx.x] = r;
-  }
+  const uint32_t r = crc_piece_remainder(lds, base, front, end, v0, k);
+  if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
 // x^e for e < 2^32 - 1 as the product of the table entries of e's bits: 32 lanes of a wave (lanes 32..63 may hold another e), valid in every lane

@@ -444,6 +444,7 @@ class ImageEncoder:
         runs = self._runs_args("ImageEncoder.encode", run_slack, run_penalty, True, target_psnr, dither=dither, pattern=pattern,
                                pattern_size=pattern_size)
         cons = self._target_args("ImageEncoder.encode", target_bytes, target_psnr, True) if searching else None
+        image, png_in = self._png_in(image)
         if torch.is_tensor(image):
             image = image.cpu().numpy()                          # (the ROI chain's edge search reads a host image)
         image = np.ascontiguousarray(image, dtype=np.uint8)
@@ -511,9 +512,23 @@ class ImageEncoder:
             stats["quality"] = self.quality(rgb, res, region_map)
             lap("report")
         stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
+        if png_in is not None:
+            stats["png_in"] = png_in
         res["classes"] = classes
         res["stats"] = stats
         return res
+
+    # ---- a PNG file as the image (EXTENSION: csrc/png_read.hip) -----------------------------------------------------------------
+    def _png_in(self, image):
+        """image as encode, encode_with_palette and quantize take it -> (the image, stats["png_in"] or None): a file name is read on the
+        device (container.read_png); the file's alpha, if any, is ignored and reported"""
+        if not isinstance(image, (str, os.PathLike)):
+            return image, None
+        from . import container
+        fr = container.read_png(os.fspath(image), self.rh)
+        info = fr["info"]
+        return fr["image"], {"shape": list(fr["shape"]), "colour_type": info["colour_type"], "depth": info["depth"], "alpha_ignored": fr["alpha"] is not None,
+                             "chunks": info["chunks"], "idat_chunks": info["idat_chunks"]}
 
     # ---- the result as a PNG file (EXTENSION: csrc/png_write.hip) ---------------------------------------------------------------
     @staticmethod
@@ -971,6 +986,7 @@ class ImageEncoder:
         if pal.dtype != torch.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
             raise ValueError("ImageEncoder.encode_with_palette: a uint8 K x 3 palette, K >= 1, is expected")
         pal = pal.contiguous()
+        image, png_in = self._png_in(image)
         rgb = image.to(rh.device).contiguous() if torch.is_tensor(image) else rh.dev(np.asarray(image))
         if rgb.dtype != torch.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("ImageEncoder.encode_with_palette: a uint8 H x W x 3 image is expected")
@@ -1036,6 +1052,8 @@ class ImageEncoder:
             stats["quality"] = self.quality(rgb_r, res, self.region_map)
             lap("report")
         stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
+        if png_in is not None:
+            stats["png_in"] = png_in
         res["stats"] = stats
         return res
 
@@ -1056,7 +1074,8 @@ class ImageEncoder:
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
                  target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None):
-        """image: uint8[H,W,3] (numpy or device tensor), colours = N -> the result dict of encode_with_palette for a palette of at most N
+        """image: uint8[H,W,3] (numpy or device tensor) or the name of a PNG file (read on the device by container.read_png; its alpha is
+        ignored and stats["png_in"] says what the file was), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
         variance-minimising box splitting over it in exact integers (Rhccq.palette_build: the box whose best cut removes the most
         squared error is split until N boxes exist; a row is the mean of its box's pixels), then exactly what
@@ -1082,6 +1101,7 @@ class ImageEncoder:
             self._target_args("ImageEncoder.quantize", target_bytes, target_psnr, roi_mask is not None)
         self._runs_args("ImageEncoder.quantize", run_slack, run_penalty, roi_mask is not None, target_psnr, dither=dither, pattern=pattern,
                         pattern_size=pattern_size)
+        image, png_in = self._png_in(image)
         rgb = self._frame_tensor("quantize", image)
         t0 = time.perf_counter()
         cells = self._cells("quantize", rgb, roi_mask, roi_weight)
@@ -1094,6 +1114,8 @@ class ImageEncoder:
                                        png_path=png_path)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
+        if png_in is not None:
+            res["stats"]["png_in"] = png_in
         return res
 
     # images of one slice of quantize_batch: a slice holds 1 MiB of histogram and 1.1 MiB of summed-volume table per image beside its

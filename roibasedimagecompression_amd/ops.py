@@ -181,6 +181,37 @@ def palette_cells_granules():
     return int(lib.rhccq_palette_cells_block()), int(lib.rhccq_palette_cells_chunk())
 
 
+def png_unfilter_band_rows():
+    """rows of a band of Rhccq.png_unfilter's wavefront: a one-wave workgroup, a lane a row"""
+    return int(_lib.load().rhccq_png_unfilter_band_rows())
+
+
+def png_unfilter_tile():
+    """steps (filter units of a row) of the tile Rhccq.png_unfilter's kernel stages through LDS"""
+    return int(_lib.load().rhccq_png_unfilter_tile())
+
+
+def png_unfilter_granule():
+    """filter units a band of Rhccq.png_unfilter fetches from the band above at a time"""
+    return int(_lib.load().rhccq_png_unfilter_granule())
+
+
+PNG_STATUS = ("OK", "BAD_SIGNATURE", "BAD_CHUNK", "BAD_HEADER", "UNSUPPORTED", "LIMIT", "BAD_CRC", "BAD_STREAM", "BAD_LENGTH", "BAD_FILTER", "STALLED")
+
+
+def png_parse(data):
+    """rhccq_png_parse_host (host only, a pure function of the bytes) -> (_lib.PngInfo, the chunk table int64[n_chunks, 4]: offset of the
+    type field, data length, first CRC piece, offset in the joined IDAT stream or -1)"""
+    a = np.frombuffer(data, dtype=np.uint8)
+    cap = a.size // 12 + 1
+    table = np.zeros((cap, 4), np.int64)
+    info, count = _lib.PngInfo(), C.c_int64()
+    rc = _lib.load().rhccq_png_parse_host(C.c_void_p(a.ctypes.data if a.size else 0), a.size, C.byref(info), C.c_void_p(table.ctypes.data), cap, C.byref(count))
+    if rc:
+        raise RhccqError(f"png_parse: rhccq_png_parse_host failed ({rc})")
+    return info, table[:count.value]
+
+
 PALETTE_CELLS_SHAPE = (4, 32, 32, 32)  # Rhccq.palette_cells' table: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3)
 
 
@@ -1978,6 +2009,116 @@ class Rhccq:
         """png_encode_async's file as bytes: one read of the length, one copy of the file"""
         out, length = self.png_encode_async(indices, H, W, palette, exact, depth8, filter)
         return self.to_host(out[:int(length.item())]).tobytes()
+
+    # -- PNG files read on the device (EXTENSION: csrc/png_read.hip; include/rhccq.h pins the definition) ----------------
+    def _aligned_bytes(self, t, fn, what):
+        """a uint8 tensor or array -> flat, contiguous, on the device and aligned to 16 (a view into a larger buffer is copied)"""
+        t = A.as_uint8(t, self.device, fn, what).reshape(-1)
+        return t.clone() if t.data_ptr() % 16 else t
+
+    def crc32_segments(self, data, segments, extra=0):
+        """data: uint8 (device or numpy); segments: (offset, length) pairs -> a device int32 tensor holding zlib.crc32 of every
+        data[offset : offset + length + extra] (its 32 bits), in two launches whatever their number; a range outside data counts as
+        empty.  Nothing waits for the device."""
+        fn = "crc32_segments"
+        data = self._aligned_bytes(data, fn, "data")
+        seg = np.ascontiguousarray(segments, dtype=np.int64).reshape(-1, 2)
+        table = np.zeros((len(seg), 4), np.int64)
+        table[:, :2] = seg
+        total = C.c_int64()
+        rc = self._raw.rhccq_crc32_segments_plan(C.c_void_p(table.ctypes.data), len(table), int(extra), C.byref(total))
+        if rc:
+            raise RhccqError(f"{fn}: rhccq_crc32_segments_plan failed ({rc}): extra >= 0 is expected")
+        out = self.empty((max(len(table), 1),), torch.int32)
+        work = self.empty((max(total.value, 1),), torch.int32)
+        table_dev = self.dev(table.reshape(-1))
+        self._check(self.lib.rhccq_crc32_segments(self.ctx, self._p(data), data.numel(), self._p(table_dev), len(table), int(extra), total.value,
+                                                  self._p(work), self._p(out)), fn)
+        return out[:len(table)]
+
+    def png_unfilter(self, scan, H, rowbytes, bpp, out=None):
+        """scan: uint8, H scanlines of 1 + rowbytes bytes (a filter type byte and the filtered bytes) -> (raw uint8[H * rowbytes] device,
+        status int32[2] device: PNG_STATUS index -- OK, BAD_FILTER (a type byte above 4: that row is copied) or STALLED -- and its
+        detail).  bpp: bytes of a filter unit, 1, 2, 3, 4, 6 or 8; rowbytes a multiple of it.  out: a caller's uint8 device buffer."""
+        fn = "png_unfilter"
+        H, rowbytes, bpp = int(H), int(rowbytes), int(bpp)
+        scan = A.as_uint8(scan, self.device, fn, "scan").reshape(-1)
+        ws = int(self._raw.rhccq_png_unfilter_bytes(H, rowbytes, bpp)) if 0 < H <= INT_MAX else -1
+        if ws < 0:
+            raise RhccqError(f"{fn}: H >= 1, rowbytes >= 1 a multiple of bpp, bpp 1, 2, 3, 4, 6 or 8 and scanlines below 2 GiB are expected")
+        if scan.numel() != H * (rowbytes + 1):
+            raise ValueError(f"{fn}: scan must have H * (rowbytes + 1) bytes")
+        raw = self.empty((H * rowbytes,), torch.uint8) if out is None else out
+        if raw.dtype != torch.uint8 or not raw.is_cuda or not raw.is_contiguous() or raw.numel() != H * rowbytes:
+            raise ValueError(f"{fn}: out must be a contiguous uint8 device tensor of H * rowbytes bytes")
+        work = self.empty((ws // 4,), torch.int32)
+        status = self.empty((2,), torch.int32)
+        self._check(self.lib.rhccq_png_unfilter(self.ctx, self._p(scan), H, rowbytes, bpp, self._p(raw), self._p(work), self._p(status)), fn)
+        return raw, status
+
+    def png_expand(self, raw, H, W, colour_type, depth, palette=None, trns=None):
+        """raw rows (uint8, H rows of ceil(W channels depth / 8) bytes) -> (rgb uint8[H, W, 3], alpha uint8[H, W], indices uint8[H, W] or
+        None unless colour type 3), all on the device.  palette uint8[K, 3] (colour type 3), trns: the bytes of a tRNS chunk or None."""
+        fn = "png_expand"
+        H, W, ct, depth = int(H), int(W), int(colour_type), int(depth)
+        raw = A.as_uint8(raw, self.device, fn, "raw").reshape(-1)
+        channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}.get(ct)
+        if H < 1 or W < 1 or channels is None or depth not in (1, 2, 4, 8, 16):
+            raise RhccqError(f"{fn}: H >= 1, W >= 1 and a colour type and depth PNG allows are expected")
+        if raw.numel() != H * ((W * channels * depth + 7) // 8):
+            raise ValueError(f"{fn}: raw must have H * ceil(W * channels * depth / 8) bytes")
+        K = 0
+        if ct == 3:
+            if palette is None:
+                raise ValueError(f"{fn}: colour type 3 needs a palette")
+            palette = A.as_uint8(palette, self.device, fn, "palette")
+            if palette.ndim != 2 or palette.shape[1] != 3:
+                raise ValueError(f"{fn}: palette [K, 3] is expected")
+            K = int(palette.shape[0])
+        t = None if trns is None or len(trns) == 0 else A.as_uint8(np.frombuffer(bytes(trns), np.uint8) if not torch.is_tensor(trns) else trns, self.device, fn, "trns")
+        rgb = self.empty((H, W, 3), torch.uint8)
+        alpha = self.empty((H, W), torch.uint8)
+        idx = self.empty((H, W), torch.uint8) if ct == 3 else None
+        self._check(self.lib.rhccq_png_expand(self.ctx, self._p(raw), H, W, ct, depth, self._p(palette) if ct == 3 else C.c_void_p(0), K,
+                                              self._p(t), 0 if t is None else t.numel(), self._p(rgb), self._p(alpha), self._p(idx)), fn)
+        return rgb, alpha, idx
+
+    def png_decode(self, file, info=None, table=None, check_crc=True):
+        """file: the PNG file's bytes as a uint8 device tensor (or bytes / numpy, uploaded); info, table: png_parse's (parsed from the
+        bytes when None, which reads a device tensor back) -> {"rgb" uint8[H, W, 3], "alpha" uint8[H, W] or None, "indices"
+        uint8[H, W] or None, "status" int32[2] (PNG_STATUS index, detail), "scan": the inflated scanlines, "file": the bytes on the
+        device}, all on the device; nothing waits for it.  With a status the framing shows (info.status) there are no outputs."""
+        fn = "png_decode"
+        if info is None:
+            host = self.to_host(file).tobytes() if torch.is_tensor(file) else bytearray(file)
+            info, table = png_parse(host)
+            if not torch.is_tensor(file):
+                file = np.frombuffer(host, np.uint8)
+        status = self.empty((2,), torch.int32)
+        if info.status:
+            self._check(self.lib.rhccq_png_decode(self.ctx, C.c_void_p(0), 0, C.byref(info), C.c_void_p(0), 0, C.c_void_p(0), C.c_void_p(0),
+                                                  C.c_void_p(0), C.c_void_p(0), self._p(status)), fn)
+            return {"rgb": None, "alpha": None, "indices": None, "status": status, "scan": None, "file": None}
+        file = self._aligned_bytes(file, fn, "file")
+        n = file.numel()
+        table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+        if len(table) != info.n_chunks:
+            raise ValueError(f"{fn}: the table must have info.n_chunks rows")
+        ws = C.c_int64()
+        rc = self._raw.rhccq_png_read_sizes(C.byref(info), n, C.byref(ws))
+        if rc:
+            raise RhccqError(f"{fn}: rhccq_png_read_sizes failed ({rc}): info does not describe a file of {n} bytes")
+        H, W, ct = info.height, info.width, info.colour_type
+        has_alpha = ct in (4, 6) or info.trns_bytes > 0
+        work = self.empty((ws.value,), torch.uint8)
+        table_dev = self.dev(table.reshape(-1))
+        rgb = self.empty((H, W, 3), torch.uint8)
+        alpha = self.empty((H, W), torch.uint8) if has_alpha else None
+        idx = self.empty((H, W), torch.uint8) if ct == 3 else None
+        self._check(self.lib.rhccq_png_decode(self.ctx, self._p(file), n, C.byref(info), self._p(table_dev), 0 if check_crc else 1, self._p(work),
+                                              self._p(rgb), self._p(alpha), self._p(idx), self._p(status)), fn)
+        at = int(self._raw.rhccq_png_read_scan_offset(C.byref(info)))
+        return {"rgb": rgb, "alpha": alpha, "indices": idx, "status": status, "scan": work[at:at + info.scan_bytes], "file": file}
 
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
     ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
