@@ -1296,6 +1296,64 @@ int rhccq_png_decode(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq
 /* file in host memory; parses it itself; status: host int32[2] */
 int rhccq_png_decode_host(const uint8_t* file, int64_t n, int32_t flags, uint8_t* rgb, uint8_t* alpha, uint8_t* idx, int32_t* status);
 
+/* ---- EXTENSION: GIF files written on the device (no reference counterpart; csrc/gif_write.hip, csrc/gif_write.h) ---------------------------
+ * The file of n_frames >= 1 index maps idx[n_frames][H][W] (idx_elem_bytes 1, 2 or 4, read as unsigned), H, W in 1..65535, over palettes of
+ * 1..256 rows uint8[K][3].  The file is a pure function of the arguments; device form and host form agree byte for byte.
+ *   layout        "GIF89a", the logical screen descriptor (W, H, packed, 0, 0).  EITHER one global colour table (packed = 0x80 | (tb - 1) << 4
+ *                 | (tb - 1)) OR, with RHCCQ_GIF_LOCAL, a local table in every frame (packed = 0x70), never both.  A table has 2^tb
+ *                 entries, tb = max(1, bits(entries - 1)): the palette's rows first, zeros behind them.  With more than one frame a
+ *                 NETSCAPE2.0 application extension carries the loop count (0..65535).  Every frame: a graphic control extension (4 bytes:
+ *                 disposal method 1 "do not dispose", the frame's delay in centiseconds 0..65535, transparency flag and index), an image
+ *                 descriptor at (0, 0) of W x H, not interlaced, the local table if any, the minimum code size m = max(2, tb), the code
+ *                 stream in sub-blocks of 255 bytes (the last one shorter), a zero byte.  The trailer 0x3B.  The file stays below 2^31 bytes.
+ *   pixels        an index at or past the palette's rows is written as 0 (rhccq_png_encode's rule).
+ *   delta         RHCCQ_GIF_DELTA: global table and K <= 255 only.  The transparent index T = K counts as an entry for tb and m.  In every
+ *                 frame f > 0 a pixel whose clamped index equals frame f - 1's at the same position is written as T, and the frame's
+ *                 extension carries the transparency flag and T; frame 0 is written in full, without the flag.
+ *   code stream   clear = 2^m, end = clear + 1.  The stream opens with Clear at m + 1 bits.  The frame's pixels in raster order are cut into
+ *                 segments of S = rhccq_gif_segment_pixels() = 16 384 pixels (the last may be shorter).  A segment starts with next = clear
+ *                 + 2, width = m + 1 and an empty dictionary and runs the greedy LZW: the current string is extended while (string, pixel)
+ *                 is in the dictionary, else the string's code goes out at `width` bits.  After EVERY data code, the segment's last
+ *                 included: entry `next` is consumed (it holds (string, pixel) where a pixel follows, nothing behind the segment's last
+ *                 code); if next == 2^width and width < 12 then width += 1; next += 1.  If next == 4096 and another pixel of the segment
+ *                 follows, Clear goes out at `width` bits and the segment's state starts again.  Behind its last data code a segment emits,
+ *                 at the width that step left, Clear if another segment follows and End otherwise.  Codes are packed least significant
+ *                 bit first; the stream is padded with zero bits to a byte.
+ * RHCCQ_E_ARG (before any device work): n_frames < 1 (or above 2^20), H or W outside 1..65535, a table of 0 or more than 256 rows or more than
+ * k_stride, idx_elem_bytes not 1, 2 or 4, unknown flag bits, RHCCQ_GIF_DELTA with RHCCQ_GIF_LOCAL or with 256 rows, a delay or loop outside
+ * 0..65535, a null pointer, an idx not aligned to its element, a workspace not aligned to 256, out_len / stream_bytes not aligned to 8.
+ * RHCCQ_E_LIMIT: a bound of 2^31 bytes or more, more than 2^30 segments, out_cap or stream_stride below rhccq_gif_sizes' bounds.
+ * k_rows, delays: HOST tables.  k_rows has one entry (global table) or n_frames (RHCCQ_GIF_LOCAL); delays has n_frames.  palettes: device,
+ * uint8[K][3] (global) or uint8[n_frames][k_stride][3] (local; frame f shows the first k_rows[f] rows of its block).
+ * Device forms: async on the context stream, no host synchronisation, nothing allocated, no workgroup waits for another.  idx is read in
+ * aligned 16-byte blocks: where idx or a frame's first pixel is not aligned to 16, up to 15 bytes in front of the first and behind the last
+ * index are read (never across a page, always together with a byte of idx) and not used.  RHCCQ_GIF_TRIE picks the other dictionary of
+ * the LZW launch; the file does not change.
+ *   rhccq_gif_lzw      the n code streams alone: frame f's bytes at streams + f * stream_stride, its length in stream_bytes[f] (device int64).
+ *   rhccq_gif_encode   the whole file into out, its length into *out_len (device int64).  One launch runs the LZW of all (frame, segment)
+ *                      pairs (a one-wave workgroup each, the dictionary in LDS, packed 32-bit words into the segment's slot of the workspace),
+ *                      one the prefix sums of the segments' bit counts, one the frames' places in the file, one the framing, and one joins
+ *                      the segments: a lane per 32-bit word of a frame's stream gathers the segments that cover it and stores its bytes
+ *                      at their sub-blocked places.  Afterwards the workspace holds the frames' stream lengths (int64[n_frames]) at its start.
+ * Host forms (serial, no GPU, host memory): the same step functions of csrc/gif_write.h; stream_bytes (host int64[n_frames]) may be NULL in
+ * rhccq_gif_encode_host. */
+#define RHCCQ_GIF_LOCAL 1
+#define RHCCQ_GIF_DELTA 2
+#define RHCCQ_GIF_TRIE 4      /* the segments' dictionary is a sibling-linked trie (16 KiB of LDS) instead of the hash table (32 KiB): the same bytes */
+int32_t rhccq_gif_segment_pixels(void);
+/* host only: bytes of the workspace, the bound of one frame's code stream and of the file (any of the three may be NULL) */
+int rhccq_gif_sizes(int32_t n_frames, int32_t H, int32_t W, int32_t flags, int64_t* workspace_bytes, int64_t* stream_bound, int64_t* out_bound);
+int rhccq_gif_lzw(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                  void* workspace, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes);
+int rhccq_gif_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                     int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, void* workspace, uint8_t* out,
+                     int64_t out_cap, int64_t* out_len);
+int rhccq_gif_lzw_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                       uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes);
+int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                          const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
+                          int64_t* stream_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -282,6 +282,14 @@ PROTOTYPES = {
     "rhccq_png_read_scan_offset": (c_int64, [C.POINTER(PngInfo)]),
     "rhccq_png_decode": (c_int32, [c_void_p, c_void_p, c_int64, C.POINTER(PngInfo), c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rhccq_png_decode_host": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_gif_segment_pixels": (c_int32, []),
+    "rhccq_gif_sizes": (c_int32, [c_int32, c_int32, c_int32, c_int32, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rhccq_gif_lzw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_gif_encode": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                   c_void_p, c_int64, c_void_p]),
+    "rhccq_gif_lzw_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "rhccq_gif_encode_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                        c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -150,6 +150,73 @@ def write_png(result, filename, rh=None, exact=False, depth8=False, filter=True)
     return len(data)
 
 
+def _gif_frames(results, rh, delta):
+    """one result or a list of them -> (rh, flat device indices of all frames, n, H, W, palettes as Rhccq.gif_encode_async takes them,
+    rows per local table or None)"""
+    if isinstance(results, dict):
+        results = [results]
+    if not isinstance(results, (list, tuple)) or not results:
+        raise RhccqError("write_gif: a result (palette, indices, shape) or a list of them is required")
+    for r in results:
+        if not isinstance(r, dict) or "palette" not in r or "indices" not in r or "shape" not in r:
+            raise RhccqError("write_gif: a FrameEncoder result (palette, indices, shape) is required")
+    # what the definition refuses is decided on the host, before any device work
+    h, w = (int(v) for v in results[0]["shape"][:2])
+    if any(tuple(int(v) for v in r["shape"][:2]) != (h, w) for r in results):
+        raise ValueError("write_gif: every frame must have the same shape")
+    if h > 65535 or w > 65535:
+        raise ValueError("write_gif: a GIF frame is at most 65535 x 65535")
+    pals = [r["palette"].cpu().numpy() if isinstance(r["palette"], torch.Tensor) else r["palette"] for r in results]
+    pals = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1, 3) for p in pals]
+    if max(len(p) for p in pals) > 256:
+        raise ValueError("write_gif: a GIF colour table has at most 256 rows")
+    same = all(np.array_equal(p, pals[0]) for p in pals[1:])
+    if delta and not same:
+        raise ValueError("write_gif: delta needs one palette for all frames (a global colour table)")
+    if delta and len(pals[0]) > 255:
+        raise ValueError("write_gif: delta needs a palette of at most 255 rows (the transparent index is one more entry)")
+    frames = [_png_frame(r, rh, "write_gif") for r in results]
+    rh = frames[0][0]
+    idx = [f[1] for f in frames]
+    if len({t.dtype for t in idx}) > 1:
+        idx = [t.to(torch.int32) & 0xFFFF if t.dtype == torch.int16 else t.to(torch.int32) for t in idx]
+    idx = idx[0] if len(idx) == 1 else torch.cat(idx)
+    if same:
+        return rh, idx, len(frames), h, w, pals[0], None
+    block = np.zeros((len(pals), max(len(p) for p in pals), 3), np.uint8)
+    for f, p in enumerate(pals):
+        block[f, :len(p)] = p
+    return rh, idx, len(frames), h, w, block, [len(p) for p in pals]
+
+
+def gif_file(results, rh=None, delay=4, loop=0, delta=False):
+    """gif_bytes with what the file is: -> (bytes, {"bytes": their number, "frames", "table": "global" | "local", "colours": rows of the
+    largest table, "delta", "stream_bytes": [bytes of every frame's code stream]}); the file and the stream lengths come down together"""
+    rh, idx, n, h, w, pals, rows = _gif_frames(results, rh, delta)
+    out, length, lens = rh.gif_encode_async(idx, n, h, w, pals, rows, delay, loop, delta)
+    size = int(length.item())
+    data, lens = rh.to_host(out[:size], lens)
+    return data.tobytes(), {"bytes": size, "frames": n, "table": "global" if rows is None else "local", "colours": int(pals.shape[-2]),
+                            "delta": bool(delta), "stream_bytes": [int(v) for v in lens]}
+
+
+def gif_bytes(results, rh=None, delay=4, loop=0, delta=False):
+    """the GIF89a file of one result (palette, indices, shape: what write_png takes) or of a list of them of one shape as bytes, built
+    on the device (include/rhccq.h "GIF files written on the device").  One global colour table when every result carries the same
+    palette (the same object, or equal rows), else a local table a frame.  delay: centiseconds, one number or one a frame; loop: the
+    animation's repeat count, 0 for ever.  delta=True (global table, at most 255 rows): a pixel that equals the frame in front is
+    written as the transparent index.  An index past the palette shows row 0, as in write_png."""
+    return gif_file(results, rh, delay, loop, delta)[0]
+
+
+def write_gif(results, filename, rh=None, delay=4, loop=0, delta=False):
+    """gif_bytes written to `filename`; returns the file's length in bytes"""
+    data = gif_bytes(results, rh, delay, loop, delta)
+    with open(filename, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
 def load_compressed_device(path, rh=None):
     """load_compressed with the outer zlib layer inflated on the device: the framing is read on the host, the pickle comes
     back through page-locked memory and is parsed by the same allow-list unpickler.  Returns the same dict."""

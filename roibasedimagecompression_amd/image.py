@@ -402,7 +402,7 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -435,9 +435,12 @@ class ImageEncoder:
         pattern = s or {"roi": a, "nonroi": b}, pattern_size = 2, 4 or 8 (EXTENSION, default None = off; 0 is a value; exclusive with
         run_slack, run_penalty, dither and target_psnr): the same place and the same rules, with the position-only pattern dither
         (Rhccq.palette_pattern) over the result's own palette; stats["pattern"] as encode_with_palette fills it, and no stats["runs"].
-        png_path (EXTENSION, default None = off): as encode_with_palette takes it, for the rectangle the result covers."""
+        png_path (EXTENSION, default None = off): as encode_with_palette takes it, for the rectangle the result covers.
+        gif_path (EXTENSION, default None = off): as encode_with_palette takes it (ValueError above 256 rows: max_colours or a target bring
+        a result below)."""
         rh = self.rh
         png_path = self._png_arg("ImageEncoder.encode", png_path)
+        gif_path = self._png_arg("ImageEncoder.encode", gif_path, "gif_path")
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
@@ -508,6 +511,9 @@ class ImageEncoder:
         if png_path:
             stats["png"] = self._png_write(res, png_path, exact)
             lap("png")
+        if gif_path:
+            stats["gif"] = self._gif_write(res, gif_path)
+            lap("gif")
         if report:
             stats["quality"] = self.quality(rgb, res, region_map)
             lap("report")
@@ -532,20 +538,29 @@ class ImageEncoder:
 
     # ---- the result as a PNG file (EXTENSION: csrc/png_write.hip) ---------------------------------------------------------------
     @staticmethod
-    def _png_arg(fn, png_path):
-        """png_path as given -> a file name or None"""
+    def _png_arg(fn, png_path, what="png_path"):
+        """png_path (or gif_path) as given -> a file name or None"""
         if png_path is None:
             return None
         if not isinstance(png_path, (str, os.PathLike)):
-            raise TypeError(f"{fn}: png_path must be a file name, got {type(png_path).__name__}")
+            raise TypeError(f"{fn}: {what} must be a file name, got {type(png_path).__name__}")
         if not os.fspath(png_path):
-            raise ValueError(f"{fn}: png_path must not be empty")
+            raise ValueError(f"{fn}: {what} must not be empty")
         return os.fspath(png_path)
 
     def _png_write(self, res, png_path, exact):
         from . import container
         data, row = container.png_file(res, self.rh, exact=exact)
         with open(png_path, "wb") as f:
+            f.write(data)
+        return row
+
+    # ---- results as a GIF file (EXTENSION: csrc/gif_write.hip) ------------------------------------------------------------------
+    def _gif_write(self, results, gif_path, delay=4, loop=0, delta=False):
+        """container.gif_file written to gif_path -> its row for stats["gif"]"""
+        from . import container
+        data, row = container.gif_file(results, self.rh, delay=delay, loop=loop, delta=delta)
+        with open(gif_path, "wb") as f:
             f.write(data)
         return row
 
@@ -885,7 +900,7 @@ class ImageEncoder:
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
                             target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4,
-                            png_path=None):
+                            png_path=None, gif_path=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -968,9 +983,13 @@ class ImageEncoder:
         png_path (default None = off; independent of out_path): the index map returned, after every rule above, is also written as
         a PNG file built on the device (container.write_png: a palette PNG up to 256 rows, truecolour with adaptive row filters above;
         exact= is shared with out_path and sends IDAT through the level-9 encoder).  stats["png"] = {bytes, colour_type, depth,
-        filter_rows}.  A target_bytes counts the .rhccq file's bytes, not the PNG's."""
+        filter_rows}.  A target_bytes counts the .rhccq file's bytes, not the PNG's.
+        gif_path (default None = off; independent of out_path and png_path): the index map returned is also written as a one-frame GIF89a
+        file built on the device (container.write_gif: one global colour table, segmented LZW, include/rhccq.h).  stats["gif"] = {bytes,
+        frames: 1, table: "global", colours, delta: False, stream_bytes}.  A result of more than 256 rows raises ValueError."""
         rh = self.rh
         png_path = self._png_arg("ImageEncoder.encode_with_palette", png_path)
+        gif_path = self._png_arg("ImageEncoder.encode_with_palette", gif_path, "gif_path")
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
         if refine < 0 or refine > 64:
@@ -1045,6 +1064,9 @@ class ImageEncoder:
         if png_path:
             stats["png"] = self._png_write(res, png_path, exact)
             lap("png")
+        if gif_path:
+            stats["gif"] = self._gif_write(res, gif_path)
+            lap("gif")
         if report:
             host = image.cpu().numpy() if torch.is_tensor(image) else np.ascontiguousarray(image, dtype=np.uint8)
             _, _, rgb_r, rstats = self.regions(host, roi_mask)
@@ -1073,7 +1095,7 @@ class ImageEncoder:
         return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
-                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None):
+                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None):
         """image: uint8[H,W,3] (numpy or device tensor) or the name of a PNG file (read on the device by container.read_png; its alpha is
         ignored and stats["png_in"] says what the file was), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
@@ -1086,9 +1108,13 @@ class ImageEncoder:
         ops.palette_build_max_rows() (RhccqError).  Colours that share a cell of the histogram (equal in their upper five bits per
         channel) are never separated, so fewer than N rows come back when fewer cells are occupied, and two boxes may round to the
         same row.  stats["build"] = {asked: N, rows: rows built, cells: occupied cells, steps: splits}; everything else as
-        encode_with_palette fills it.  png_path: as encode_with_palette takes it."""
+        encode_with_palette fills it.  png_path, gif_path: as encode_with_palette takes them (gif_path raises ValueError when
+        colours is above 256, before anything runs)."""
         rh = self.rh
         png_path = self._png_arg("ImageEncoder.quantize", png_path)
+        gif_path = self._png_arg("ImageEncoder.quantize", gif_path, "gif_path")
+        if gif_path and int(colours) > 256:
+            raise ValueError("ImageEncoder.quantize: gif_path needs colours <= 256 (a GIF colour table has at most 256 rows)")
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
         if colours < 1:
@@ -1111,7 +1137,7 @@ class ImageEncoder:
         res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
                                        roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
                                        run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size,
-                                       png_path=png_path)
+                                       png_path=png_path, gif_path=gif_path)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         if png_in is not None:
@@ -1122,7 +1148,8 @@ class ImageEncoder:
     # pixels and indices (128 images: 275 MiB), and 128 chains are half the card's CUs, so two slices' chains already fill it
     QUANTIZE_BATCH_SLICE = 128
 
-    def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False, pattern=None, pattern_size=4):
+    def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False, pattern=None, pattern_size=4,
+                       gif_path=None, delay=4):
         """images: a list of uint8[H,W,3] images of any sizes (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor
         (a contiguous device tensor is used in place, nothing is concatenated) -> a list with one result dict per image: what
         quantize(image, colours, refine=refine, roi_mask=mask, roi_weight=...) returns for that image alone, bit for bit (palette
@@ -1142,10 +1169,17 @@ class ImageEncoder:
         batch take this rule and not dither.  The dict needs a mask for every image.
         target_bytes, target_psnr, run_slack, run_penalty, dither and report are not parameters: each needs a host decision per image
         (dither: a status word and a workspace per image); quantize has them.  Validation and error types follow quantize; an image whose table is empty (no pixels) raises
-        RhccqError after the read, as quantize does for it."""
+        RhccqError after the read, as quantize does for it.
+        gif_path (default None = off), delay (centiseconds, one number or one an image): the results are also written as ONE GIF89a
+        file on the device (container.write_gif), every image a frame with its own palette in a local colour table, no delta; the
+        images must then be of one size and colours at most 256 (ValueError).  stats["gif"] (the same row in every result) =
+        {bytes, frames, table: "local" ("global" when all palettes came out equal), colours, delta: False, stream_bytes}."""
         rh = self.rh
         fn = "ImageEncoder.quantize_batch"
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
+        gif_path = self._png_arg(fn, gif_path, "gif_path")
+        if gif_path and colours > 256:
+            raise ValueError(f"{fn}: gif_path needs colours <= 256 (a GIF colour table has at most 256 rows)")
         if colours < 1:
             raise ValueError(f"{fn}: colours >= 1 is required")
         if refine < 0 or refine > 64:
@@ -1163,6 +1197,8 @@ class ImageEncoder:
         paths = [None] * B if out_paths is None else list(out_paths)
         if B < 1 or len(masks) != B or len(paths) != B:
             raise ValueError(f"{fn}: at least one image, and one mask and one path (or None) per image, are expected")
+        if gif_path and any(f.shape[:2] != frames[0].shape[:2] for f in frames):
+            raise ValueError(f"{fn}: gif_path needs images of one size")
         masked = any(m is not None for m in masks)
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not masked):
             raise ValueError(f"{fn}: roi_weight (1..255) other than 1 needs roi_masks")
@@ -1233,6 +1269,10 @@ class ImageEncoder:
             for res, p in zip(out, paths):
                 if p:
                     container.write_frame(res, p, rh, exact=exact)
+        if gif_path:
+            row = self._gif_write(out, gif_path, delay=delay)
+            for res in out:
+                res["stats"]["gif"] = row
         seconds = {"batch": round(time.perf_counter() - t0, 4)}
         for res in out:
             res["stats"]["seconds"] = dict(seconds)
@@ -1256,6 +1296,98 @@ class ImageEncoder:
         for image, mask in zip(images, masks):
             cells = self._cells("shared_palette", self._frame_tensor("shared_palette", image), mask, roi_weight, into=cells)
         return self.rh.palette_build(cells, colours)[0]
+
+    def animate(self, images, colours=256, gif_path=None, delay=4, loop=0, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
+                pattern_size=4):
+        """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor ->
+        {"palette": uint8[k, 3], "indices": device uint8[B, H, W], "indices_dtype": "uint8", "shape": (H, W), "stats"}: an animated GIF89a built on the device from end to end.  One shared_palette over all frames (at most `colours` rows,
+        1..256; with delta at most 255, because the transparent index is one more table entry: stats["gif"]["colours"] says what was
+        built), refine = N > 0 Lloyd iterations of that ONE palette over the pixels of all frames (Rhccq.palette_refine), every frame
+        onto the palette in one batch launch (Rhccq.palette_remap_batch, or palette_pattern_batch with pattern = s or {"roi": a,
+        "nonroi": b} and pattern_size, as quantize_batch takes them), then the file (Rhccq.gif_encode: one global colour table, delay
+        in centiseconds -- one number or one a frame --, loop = the repeat count, 0 for ever).  delta=True writes a pixel that keeps its
+        index from the frame in front as transparent; a frame's index map is what encode_with_palette(frame, palette[, pattern=]) gives
+        for it alone, so with pattern a pixel that does not change keeps its index and costs nothing.  roi_masks: one mask (or None) a
+        frame; a pixel inside weighs roi_weight (1..255) in the shared histogram and the refinement.  gif_path: where the file is written
+        (None: it is built, stats["gif"] says what it is, and it is dropped).  stats = {"build": {asked, rows}, "remap": [a row a frame], "pattern": [a row a frame] with pattern, "refine" with refine,
+        "gif": container.gif_file's row, "seconds"}.
+        dither, run_slack, run_penalty and the targets are not parameters: error diffusion is not frame-stable (a changed pixel moves
+        the indices of everything to its right and below, so delta would find nothing), and the run rules and targets decide per
+        image on the host."""
+        rh = self.rh
+        fn = "ImageEncoder.animate"
+        colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
+        gif_path = self._png_arg(fn, gif_path, "gif_path")
+        if not 1 <= colours <= 256:
+            raise ValueError(f"{fn}: colours must be 1..256 (a GIF colour table has at most 256 rows)")
+        if refine < 0 or refine > 64:
+            raise ValueError(f"{fn}: refine must be 0..64")
+        stacked = None
+        if (torch.is_tensor(images) or isinstance(images, np.ndarray)) and images.ndim == 4:
+            stacked = images.to(rh.device).contiguous() if torch.is_tensor(images) else rh.dev(images)
+            if stacked.dtype != torch.uint8 or stacked.shape[3] != 3:
+                raise ValueError(f"{fn}: a uint8 B x H x W x 3 tensor is expected")
+            frames = list(stacked)                                               # views
+        else:
+            frames = [self._frame_tensor("animate", im) for im in images]
+        B = len(frames)
+        masks = [None] * B if roi_masks is None else list(roi_masks)
+        if B < 1 or len(masks) != B:
+            raise ValueError(f"{fn}: at least one frame, and one mask (or None) per frame, are expected")
+        if any(f.shape[:2] != frames[0].shape[:2] for f in frames):
+            raise ValueError(f"{fn}: every frame must have the same shape")
+        H, W = int(frames[0].shape[0]), int(frames[0].shape[1])
+        if H > 65535 or W > 65535:
+            raise ValueError(f"{fn}: a GIF frame is at most 65535 x 65535")
+        masked = any(m is not None for m in masks)
+        if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not masked):
+            raise ValueError(f"{fn}: roi_weight (1..255) other than 1 needs roi_masks")
+        runs = self._runs_args(fn, None, None, all(m is not None for m in masks), pattern=pattern, pattern_size=pattern_size)
+        t0 = time.perf_counter()
+        asked = min(colours, 255) if delta else colours
+        pal = self.shared_palette(frames, asked, masks if masked else None, roi_weight)
+        rgb = stacked.reshape(-1, 3) if stacked is not None else frames[0].reshape(-1, 3) if B == 1 else torch.cat([f.reshape(-1, 3) for f in frames])
+        off = (np.arange(B + 1) * (H * W)).astype(np.int64)
+        nc, weights, cls = 0, None, None
+        if masked:
+            from .api.roi import region_map_from_mask
+            nc, weights = 2, [1, roi_weight, 1]
+            maps = [torch.full((H * W,), 2, dtype=torch.uint8, device=rh.device) if m is None else region_map_from_mask(f, m, rh).reshape(-1)
+                    for f, m in zip(frames, masks)]
+            cls = maps[0] if B == 1 else torch.cat(maps)
+        hist = nit = None
+        if refine:
+            pal, hist, nit = rh.palette_refine(rgb, pal, cls, weights, max_iter=refine)
+        K = int(pal.shape[0])
+        pals = pal.unsqueeze(0).expand(B, K, 3).contiguous()
+        k = torch.full((B,), K, dtype=torch.int32, device=rh.device)
+        off_dev = rh.dev(off)
+        if runs is not None:
+            idx, sums = rh.palette_pattern_batch(rgb, off, [W] * B, pals, k, self._slack_table(runs, masked), runs["size"], cls, nc, px_off_dev=off_dev)
+        else:
+            idx, sums = rh.palette_remap_batch(rgb, off, pals, k, cls, nc, px_off_dev=off_dev)
+        out, length, lens = rh.gif_encode_async(idx, B, H, W, pal, None, delay, loop, bool(delta))
+        host = rh.to_host(*([sums, pal, length, lens] + ([hist, nit] if refine else [])))
+        sums, pal_host, size, lens = host[0], host[1], int(host[2][0]), host[3]
+        stats = {"build": {"asked": asked, "rows": K}, "remap": []}
+        for b in range(B):
+            row = {"all": self._remap_row(*sums[b][-1][:2])}
+            if masks[b] is not None:
+                row["nonroi"], row["roi"] = self._remap_row(*sums[b][0][:2]), self._remap_row(*sums[b][1][:2])
+            stats["remap"].append(row)
+        if runs is not None:
+            stats["pattern"] = [self._runs_row(runs, sums[b], masks[b] is not None) for b in range(B)]
+        if refine:
+            n = int(host[5][0])
+            stats["refine"] = {"iterations": n, "converged": n == 0 or int(host[4][n - 1, 1]) == 0, "sse": [int(v) for v in host[4][:n, 0]],
+                               "changed": [int(v) for v in host[4][:n, 1]]}
+        stats["gif"] = {"bytes": size, "frames": B, "table": "global", "colours": K, "delta": bool(delta), "stream_bytes": [int(v) for v in lens]}
+        if gif_path:
+            with open(gif_path, "wb") as f:
+                f.write(rh.to_host(out[:size]).tobytes())
+        stats["seconds"] = {"animate": round(time.perf_counter() - t0, 4)}
+        return {"palette": np.ascontiguousarray(pal_host), "indices": idx.reshape(B, H, W), "indices_dtype": "uint8", "shape": (H, W),
+                "stats": stats}
 
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
                         target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None, pattern=None, pattern_size=4):

@@ -196,6 +196,11 @@ def png_unfilter_granule():
     return int(_lib.load().rhccq_png_unfilter_granule())
 
 
+def gif_segment_pixels():
+    """pixels of a segment of Rhccq.gif_lzw / gif_encode: every segment is one LZW problem, closed by a Clear code"""
+    return int(_lib.load().rhccq_gif_segment_pixels())
+
+
 PNG_STATUS = ("OK", "BAD_SIGNATURE", "BAD_CHUNK", "BAD_HEADER", "UNSUPPORTED", "LIMIT", "BAD_CRC", "BAD_STREAM", "BAD_LENGTH", "BAD_FILTER", "STALLED")
 
 
@@ -2008,6 +2013,91 @@ class Rhccq:
     def png_encode(self, indices, H, W, palette, exact=False, depth8=False, filter=True):
         """png_encode_async's file as bytes: one read of the length, one copy of the file"""
         out, length = self.png_encode_async(indices, H, W, palette, exact, depth8, filter)
+        return self.to_host(out[:int(length.item())]).tobytes()
+
+    # -- GIF files (EXTENSION: csrc/gif_write.hip; include/rhccq.h pins the file) -------------------------------------
+    @staticmethod
+    def _gif_flags(local, delta, dictionary="hash"):
+        if dictionary not in ("hash", "trie"):
+            raise ValueError('gif: dictionary must be "hash" or "trie"')
+        return (1 if local else 0) | (2 if delta else 0) | (4 if dictionary == "trie" else 0)
+
+    def _gif_args(self, fn, frames, n, H, W, rows, local, delta, dictionary="hash"):
+        """-> (flat device indices, the int32 rows array, flags); every refusal of the definition is a ValueError"""
+        n, H, W = int(n), int(H), int(W)
+        if n < 1:
+            raise ValueError(f"{fn}: at least one frame is expected")
+        if not (1 <= H <= 65535 and 1 <= W <= 65535):
+            raise ValueError(f"{fn}: H and W must be 1..65535")
+        rows = [int(k) for k in rows]
+        if len(rows) != (n if local else 1):
+            raise ValueError(f"{fn}: one row count per table is expected")
+        if min(rows) < 1 or max(rows) > 256:
+            raise ValueError(f"{fn}: a table must have 1..256 rows")
+        if delta and local:
+            raise ValueError(f"{fn}: delta needs a global table")
+        if delta and rows[0] > 255:
+            raise ValueError(f"{fn}: delta needs a table of at most 255 rows (the transparent index is one more entry)")
+        return A.index_map(frames, n * H, W, self.device, fn), (C.c_int32 * len(rows))(*rows), self._gif_flags(local, delta, dictionary)
+
+    def gif_sizes(self, n, H, W, local=False, delta=False):
+        """-> (workspace bytes, the bound of one frame's code stream, the bound of the file) of n frames of H x W (host only)"""
+        ws, stream, bound = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = self._raw.rhccq_gif_sizes(int(n), int(H), int(W), (1 if local else 0) | (2 if delta else 0), C.byref(ws), C.byref(stream), C.byref(bound))
+        if rc:
+            raise RhccqError(f"gif_sizes: rhccq_gif_sizes({n}, {H}, {W}) failed ({rc})")
+        return ws.value, stream.value, bound.value
+
+    def gif_lzw(self, frames, n, H, W, rows, local=False, delta=False, dictionary="hash"):
+        """frames: n * H * W indices (uint8, int16 holding uint16, int32 / int64; numpy or device), rows: [K] or, local, one K a frame ->
+        (streams uint8[n, bound] device, lengths int64[n] device): frame f's GIF code stream is streams[f, :lengths[f]] (include/rhccq.h:
+        segments of gif_segment_pixels() pixels, each an LZW problem of one wave).  delta: a pixel that equals the frame in front is
+        written as the transparent index K.  dictionary: "hash" (the open-addressed table, 32 KiB of LDS a segment) or "trie" (sibling-linked,
+        16 KiB); the streams are the same.  Nothing waits for the device."""
+        fn = "gif_lzw"
+        idx, k_rows, flags = self._gif_args(fn, frames, n, H, W, rows, local, delta, dictionary)
+        ws, stream, _ = self.gif_sizes(n, H, W, local, delta)
+        work = self.empty((ws,), torch.uint8)
+        out = self.empty((int(n), stream), torch.uint8)
+        lengths = self.empty((int(n),), torch.int64)
+        self._check(self.lib.rhccq_gif_lzw(self.ctx, self._p(idx), idx.element_size(), int(n), int(H), int(W), k_rows, flags, self._p(work), self._p(out),
+                                           stream, self._p(lengths)), fn)
+        return out, lengths
+
+    def gif_encode_async(self, frames, n, H, W, palettes, rows=None, delays=4, loop=0, delta=False, dictionary="hash"):
+        """frames as gif_lzw takes them; palettes uint8[K, 3] (ONE global table) or uint8[n, K_stride, 3] with rows = the rows of every
+        frame's local table; delays: centiseconds, one number or one a frame -> (uint8 device buffer, int64 device length, int64[n] device
+        stream lengths: a view of the call's workspace).  The GIF89a file is out[:length], built on the device; nothing waits for it.
+        dictionary: as gif_lzw takes it."""
+        fn = "gif_encode"
+        palettes = A.as_uint8(palettes, self.device, fn, "palettes")
+        local = palettes.ndim == 3
+        if palettes.ndim not in (2, 3) or palettes.shape[-1] != 3 or (local and palettes.shape[0] != int(n)):
+            raise ValueError(f"{fn}: palettes [K, 3] or [n, K, 3] are expected")
+        if local and rows is None:
+            rows = [palettes.shape[1]] * int(n)
+        if not local:
+            rows = [palettes.shape[0]]
+        if palettes.shape[-2] > 256 or max(int(k) for k in rows) > palettes.shape[-2]:
+            raise ValueError(f"{fn}: a table must have 1..256 rows, all of them in palettes")
+        idx, k_rows, flags = self._gif_args(fn, frames, n, H, W, rows, local, delta, dictionary)
+        n, H, W = int(n), int(H), int(W)
+        delays = [int(delays)] * n if np.ndim(delays) == 0 else [int(d) for d in delays]
+        if len(delays) != n or min(delays) < 0 or max(delays) > 65535:
+            raise ValueError(f"{fn}: delays must be one number or one a frame, each 0..65535 centiseconds")
+        if not 0 <= int(loop) <= 65535:
+            raise ValueError(f"{fn}: loop must be 0..65535")
+        ws, _, bound = self.gif_sizes(n, H, W, local, delta)
+        work = self.empty((ws,), torch.uint8)
+        out = self.empty((bound,), torch.uint8)
+        length = self.empty((1,), torch.int64)
+        self._check(self.lib.rhccq_gif_encode(self.ctx, self._p(idx), idx.element_size(), n, H, W, self._p(palettes), int(palettes.shape[-2]), k_rows,
+                                              (C.c_int32 * n)(*delays), int(loop), flags, self._p(work), self._p(out), bound, self._p(length)), fn)
+        return out, length, work[:8 * n].view(torch.int64)
+
+    def gif_encode(self, frames, n, H, W, palettes, rows=None, delays=4, loop=0, delta=False):
+        """gif_encode_async's file as bytes: one read of the length, one copy of the file"""
+        out, length, _ = self.gif_encode_async(frames, n, H, W, palettes, rows, delays, loop, delta)
         return self.to_host(out[:int(length.item())]).tobytes()
 
     # -- PNG files read on the device (EXTENSION: csrc/png_read.hip; include/rhccq.h pins the definition) ----------------
