@@ -114,6 +114,16 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              0 (default) = rhccq_palette_dither_rows(), or 4, 8, 16 or 32.  Fewer rows give every step of the wavefront
  *                              a shorter search and the picture more bands to hand errors through.  Same results. */
 #define RHCCQ_OPT_DITHER_ROWS 14
+/*   RHCCQ_OPT_KMEANS_WIDE_PAIRS  rhccq_kmeans: a problem of k <= 1024 centres and at least this many (point, centre) pairs, n x k, takes the
+ *                              "wide" Lloyd path: load, mean / tolerance and k-means++ as ever in the problem's one workgroup, then every
+ *                              Lloyd iteration as two launches on the context's stream, an E-step over tiles of 64 points on many CUs and
+ *                              an M-step of one workgroup; launches, not waits between workgroups, are the synchronisation.  0 = never;
+ *                              1 = every problem the path supports (0 .. 2^30).  Every other problem of the call runs the one-workgroup
+ *                              kernel.  Same results: the same per-pair arithmetic, centres in ascending order, exact integer member sums.
+ *   RHCCQ_OPT_KMEANS_CHUNK     rhccq_kmeans: how many Lloyd iterations of the wide path are enqueued between two looks of the host at the
+ *                              problems' state records (1 .. 300); launches behind a problem's end return at once.  Same results. */
+#define RHCCQ_OPT_KMEANS_WIDE_PAIRS 15
+#define RHCCQ_OPT_KMEANS_CHUNK 16
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -244,7 +254,8 @@ int rhccq_cluster_means(rhccq_ctx* ctx, const unsigned long long* sums, int64_t 
  * (k-1)*T per problem at rand_off (numpy RandomState(42).uniform stream, generated on the host);
  * work: double workspace, 8*k doubles per problem at 8*koff (koff = desc-order prefix of k, given
  * as koff int64[n_prob]); labels_out int32 at the same offsets as keys; info int32[n_prob][4] =
- * {n_iter, strict, relocations, reserved}. */
+ * {n_iter, strict, relocations, path}, path = 1 for a problem that took the wide Lloyd path (RHCCQ_OPT_KMEANS_WIDE_PAIRS; it needs
+ * context scratch for its state records, and the call then reads `desc` and the records back), 0 for the one-workgroup kernel. */
 int rhccq_kmeans(rhccq_ctx* ctx, const uint32_t* keys, const int32_t* desc, const int64_t* koff,
                  const double* rand, int32_t n_prob, int32_t max_n, double* work, int32_t* labels_out,
                  int32_t* info);

@@ -100,6 +100,14 @@ int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value) {
       if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_DITHER_ROWS: 0, 4, 8, 16 or 32");
       ctx->opt_dither_rows = (int)value;
       return 0;
+    case RHCCQ_OPT_KMEANS_WIDE_PAIRS:
+      if (value < 0 || value > (1ll << 30)) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_KMEANS_WIDE_PAIRS: 0 .. 2^30");
+      ctx->opt_kmeans_wide_pairs = (int)value;
+      return 0;
+    case RHCCQ_OPT_KMEANS_CHUNK:
+      if (value < 1 || value > 300) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_KMEANS_CHUNK: 1 .. 300");
+      ctx->opt_kmeans_chunk = (int)value;
+      return 0;
     default:
       return rhccq_fail(ctx, RHCCQ_E_ARG, "unknown option");
   }

@@ -258,6 +258,8 @@ struct Lane {
     ctx->opt_reassign_lds = root->opt_reassign_lds;
     ctx->opt_reassign_order = root->opt_reassign_order;
     ctx->opt_init_shards = root->opt_init_shards;
+    ctx->opt_kmeans_wide_pairs = root->opt_kmeans_wide_pairs;
+    ctx->opt_kmeans_chunk = root->opt_kmeans_chunk;
     for (auto& s : sub) s->adopt_options(root);
   }
   void reset() {
@@ -871,10 +873,13 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs, bool batch_mbk = false) {
     if (trace_on()) {
       std::vector<int32_t> inf(run.size() * 4);
       L.download(inf.data(), d_info, inf.size());
-      int it_max = 0;
-      for (size_t i = 0; i < run.size(); ++i) it_max = std::max(it_max, inf[4 * i]);
-      fprintf(stderr, "[rhccq] kmeans split round: %zu nodes, %zu points, largest %d, %lld clusters, %.2f ms, most Lloyd iterations %d (node 0: %d)\n", run.size(),
-              cat.size(), max_n, (long long)ktot, now_ms() - t_km, it_max, inf[0]);
+      int it_max = 0, n_wide = 0;
+      for (size_t i = 0; i < run.size(); ++i) {
+        it_max = std::max(it_max, inf[4 * i]);
+        n_wide += inf[4 * i + 3] == 1;                   // rhccq_kmeans: the wide Lloyd path
+      }
+      fprintf(stderr, "[rhccq] kmeans split round: %zu nodes (%d wide), %zu points, largest %d, %lld clusters, %.2f ms, most Lloyd iterations %d (node 0: %d)\n",
+              run.size(), n_wide, cat.size(), max_n, (long long)ktot, now_ms() - t_km, it_max, inf[0]);
     }
     for (size_t i = 0; i < run.size(); ++i) {
       const int ndi = run[i].first;

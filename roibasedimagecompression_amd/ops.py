@@ -339,6 +339,8 @@ class Rhccq:
     OPT_RUNS_ROWS = 13               # palette_runs: image rows of a workgroup (0, default: palette_runs_tile()[0]; 2, 4 or 8)
     OPT_CHAIN_RELEASE = 12           # rhccq_encode_frame: 1 (default) a level-1 problem goes on when its own chain of the frame's launch ends; 0: when the launch ends
     OPT_DITHER_ROWS = 14             # palette_dither: image rows of a band (0, default: palette_dither_rows(); 4, 8, 16 or 32)
+    OPT_KMEANS_WIDE_PAIRS = 15       # kmeans_split: problems of k <= 1024 and at least this many (point, centre) pairs run their Lloyd iterations as launches on many CUs (0: never, 1: all of them)
+    OPT_KMEANS_CHUNK = 16            # kmeans_split: Lloyd iterations of the wide path enqueued between two looks at the state records (1 .. 300)
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""
