@@ -124,6 +124,10 @@ const char* rhccq_last_error(const rhccq_ctx* ctx);
  *                              problems' state records (1 .. 300); launches behind a problem's end return at once.  Same results. */
 #define RHCCQ_OPT_KMEANS_WIDE_PAIRS 15
 #define RHCCQ_OPT_KMEANS_CHUNK 16
+/*   RHCCQ_OPT_GIF_READ_CHAIN   rhccq_gif_unlzw / rhccq_gif_decode: how a segment's len / first chains are resolved in LDS: 0 (default) =
+ *                              pointer doubling by the whole workgroup (12 rounds), 1 = one lane walks the entries in order.  Same results;
+ *                              kept for the measurement of tools/gifreadbench.py. */
+#define RHCCQ_OPT_GIF_READ_CHAIN 17
 int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value);
 int rhccq_sync(rhccq_ctx* ctx);                 /* hipStreamSynchronize on the context stream */
 void* rhccq_stream(rhccq_ctx* ctx);             /* the hipStream_t in use */
@@ -1364,6 +1368,136 @@ int rhccq_gif_lzw_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames
 int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
                           const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
                           int64_t* stream_bytes);
+
+/* ---- EXTENSION: GIF files read on the device (no reference counterpart; csrc/gif_read.hip, csrc/gif_read.h) --------------------------------
+ * Framing.  "GIF87a" or "GIF89a", the logical screen descriptor (W, H, packed, background, aspect), a global colour table of 2 << (packed & 7)
+ * rows if packed & 0x80.  Then any sequence of extensions (0x21, a label, sub-blocks up to a zero length) and images (0x2C) up to the trailer
+ * 0x3B; bytes behind the trailer are ignored.  Of the extensions the graphic control extension (label 0xF9, first sub-block of 4 bytes or
+ * more: disposal = (flags >> 2) & 7, the transparent index if flags & 1, the delay in centiseconds) and the loop count of an application
+ * extension (label 0xFF, first sub-block the 11 bytes "NETSCAPE2.0" or "ANIMEXTS1.0", then a sub-block of 3 bytes or more that starts with
+ * 1: the first one counts) are read, every other one is skipped sub-block by sub-block.  A graphic control extension applies to the next
+ * image only (the last one in front of it).  An image: x, y, w, h, packed (0x80 a local table of 2 << (packed & 7) rows follows, 0x40
+ * interlaced), the local table, the minimum code size m in 2..8, data sub-blocks of 1..255 bytes, a zero byte.
+ * Code stream.  A frame's sub-blocks joined; codes are packed least significant bit first.  clear = 2^m, end = clear + 1.  The decoder
+ * starts in the state behind a Clear (an opening Clear is usual, not required).  Behind a Clear (or the start) the codes are counted
+ * j = 0, 1, ...; code j has width(j) = min(12, bit_length(clear + 1 + j)) bits.  Code j >= 1 creates entry e = clear + 1 + j = (string of
+ * code j - 1) + (first pixel of the string of code j) while e < 4096; once the table is full 12-bit codes go on and create nothing until a
+ * Clear (a deferred Clear).  The stream ends at End or where fewer bits remain than the next code needs; bits and sub-blocks behind End are
+ * ignored.  A valid code j is < clear for j = 0 and <= min(clear + 1 + j, 4095) otherwise (code j == e is the string of code j - 1 and its
+ * own first pixel).
+ * Pixels.  A frame must decode to exactly w x h pixels.  The rows of an interlaced frame arrive in four passes (rows 0, 8, ..; 4, 12, ..;
+ * 2, 6, ..; 1, 3, ..) and are put back.  Index i shows row i of the frame's table, the local one if there is one, else the global one; an
+ * index at or past the table's rows shows (0, 0, 0).
+ * Composition.  The canvas is the logical screen; a pixel is a colour and a covered bit, at the start (0, 0, 0) and not covered.  Frame f
+ * paints every pixel of its rectangle whose index is not its transparent index: colour, covered.  images[f] and alpha[f] (255 covered, 0
+ * not) are the canvas after painting.  Then the frame's disposal: 0, 1, 4..7 keep the canvas; 2 makes the rectangle (0, 0, 0), not
+ * covered; 3 puts the rectangle back to what it was before the frame painted.
+ * Status.  One RHCCQ_GIFR_* status and one detail word.  The host parser walks the file once and reports the first fault it meets:
+ *   BAD_SIGNATURE  fewer than 6 bytes or another signature; detail 0
+ *   TRUNCATED      the file ends inside a block or without a trailer; detail: the offset of that block's first byte (6 for the screen
+ *                  descriptor, 13 for the global table, the introducer's offset for an extension or image, n where the trailer is missing)
+ *   BAD_BLOCK      an introducer other than 0x21, 0x2C, 0x3B; detail: its offset
+ *   BAD_HEADER     a screen of zero width or height (detail 6), or m outside 2..8 (detail: the offset of m)
+ *   BAD_FRAME      an image of zero width or height or one that leaves the screen; detail: the frame (tested before its table and m)
+ *   NO_TABLE       neither a local nor a global table; detail: the frame
+ *   NO_FRAMES      the trailer is met and no image was; detail 0
+ *   LIMIT          at the image 2^20 + 1, or at the trailer: the file, the images F x H x W x 3, or the segment table (below) of 2^31
+ *                  bytes or more; detail 0
+ * and the device, for a file the parser accepts, the lowest frame with a fault:
+ *   BAD_CODE       an invalid code; detail: the frame
+ *   BAD_LENGTH     the frame's strings are not w x h pixels in all; detail: the frame (BAD_CODE wins in the same frame)
+ * An invalid code is decoded as code 0; a refused file's outputs mean nothing, and no stage leaves its buffers whatever the bytes are.
+ * Decoding.  A segment is the run of data codes between two Clears (or the start, End, the end of the bits); an empty one is dropped.  All
+ * bit offsets in a segment are a closed form of j, so nothing but the walk from segment to segment is serial:
+ *   join      the sub-blocks of all frames -> one stream a frame, each at a 16-byte aligned offset with at least 16 zero bytes behind it;
+ *   scan      a workgroup a frame: rhccq_gif_read_scan_step() codes a step (four tiles of rhccq_gif_read_tile()) are tested for Clear, End
+ *             and the end of the bits; the first hit closes the segment (start bit, codes) into the frame's rows of the segment table;
+ *   plan      the frames' segment counts -> their places in one work list;
+ *   lengths   a workgroup takes (frame, segment) pairs off the list: the codes are loaded by offset and tested, prefix links go to LDS, the
+ *             chains len[e] = len[prefix[e]] + 1, first[e] = first[prefix[e]] are resolved by pointer doubling (12 rounds), the entries
+ *             packed prefix 12 | suffix 8 | len 12 bits; the segment's pixel total goes to its row;
+ *   offsets   a workgroup a frame: prefix sums of the totals (saturating at 2^32 - 1), the frame's pixel count, BAD_LENGTH;
+ *   emit      as lengths, then a tile of codes at a time: a prefix sum of len[code j], and every lane writes its code's string backwards
+ *             along the prefix links, every write clipped to the frame's w x h;
+ *   compose   a thread a screen pixel walks the frames in order with the canvas state and the disposal-3 backup in registers.
+ * No workgroup waits for another.  rhccq_gif_frame.first_row and rhccq_gif_info.seg_rows size the segment table from the file alone: a
+ * frame of B stream bytes has at most 8 B / (2 (m + 1)) + 1 segments that are not empty (a data code and the code that closes it), 16 bytes
+ * a row.
+ * Device forms: every pointer but info and `frames` is device memory; async on the context stream, no host synchronisation, nothing
+ * allocated.  frames_dev is a copy of `frames`; every kernel tests the offsets it takes from it against the buffers' sizes again.
+ * RHCCQ_E_ARG: a null pointer, a negative size, tables not aligned to 8, a workspace not aligned to 256, streams not aligned to 16, status
+ * or counts not aligned to 4 / 8, a frame table that does not fit the sizes given.  The file itself may start at any byte: it is read
+ * byte by byte.  RHCCQ_E_LIMIT: n_frames above
+ * 2^20 or a size of 2^31 or more.
+ * Host forms (serial, no GPU, host memory): the same step functions of csrc/gif_read.h. */
+#define RHCCQ_GIFR_OK 0
+#define RHCCQ_GIFR_BAD_SIGNATURE 1
+#define RHCCQ_GIFR_TRUNCATED 2
+#define RHCCQ_GIFR_BAD_BLOCK 3
+#define RHCCQ_GIFR_BAD_HEADER 4
+#define RHCCQ_GIFR_BAD_FRAME 5
+#define RHCCQ_GIFR_NO_TABLE 6
+#define RHCCQ_GIFR_NO_FRAMES 7
+#define RHCCQ_GIFR_LIMIT 8
+#define RHCCQ_GIFR_BAD_CODE 9
+#define RHCCQ_GIFR_BAD_LENGTH 10
+typedef struct rhccq_gif_info {
+  int32_t status, detail;                 /* RHCCQ_GIFR_OK .. RHCCQ_GIFR_LIMIT */
+  int32_t width, height;                  /* the logical screen */
+  int32_t global_rows, loop;              /* rows of the global table (0: none); the loop count, -1 where the file has none */
+  int32_t n_frames, n_blocks;             /* images; data sub-blocks of all images */
+  int64_t global_offset;                  /* of the global table in the file, -1 without */
+  int64_t stream_bytes;                   /* the joined streams: every frame's at a 16-byte aligned offset, 16 bytes or more between two */
+  int64_t pixels;                         /* the sum of w x h over the frames */
+  int64_t seg_rows;                       /* rows of the segment table */
+} rhccq_gif_info;
+typedef struct rhccq_gif_frame {
+  int32_t x, y, w, h;
+  int32_t m, interlace;
+  int32_t table_rows, transparent;        /* rows of the frame's table; the transparent index, -1 without */
+  int32_t disposal, delay;                /* 0..7; centiseconds */
+  int32_t first_block, n_blocks;          /* its rows of the sub-block table */
+  int64_t table_offset;                   /* of the frame's colour table in the file */
+  int64_t stream_offset, stream_bytes;    /* its code stream in the joined streams */
+  int64_t pixel_offset;                   /* the sum of w x h over the frames in front */
+  int64_t first_row;                      /* its rows of the segment table: first_row .. the next frame's (seg_rows behind the last) */
+} rhccq_gif_frame;
+/* host only.  blocks: one rhccq_segment a data sub-block (offset of its first data byte, length, first_piece = its frame, dst = the byte's
+   place in the joined streams).  frames / blocks receive the first frames_cap / blocks_cap rows (may be NULL with 0), *n_frames / *n_blocks
+   the full numbers.  RHCCQ_E_ARG for a null file (with n > 0), info or counter, or a negative size; else RHCCQ_OK with info->status set */
+int rhccq_gif_parse_host(const uint8_t* file, int64_t n, rhccq_gif_info* info, rhccq_gif_frame* frames, int64_t frames_cap, int64_t* n_frames,
+                         rhccq_segment* blocks, int64_t blocks_cap, int64_t* n_blocks);
+int32_t rhccq_gif_read_tile(void);        /* codes a step of the lengths and the emit launches (a lane a code) */
+int32_t rhccq_gif_read_scan_step(void);   /* codes a step of the scan launch: a whole number of tiles, a lane one code of each */
+int32_t rhccq_gif_read_threads(void);     /* threads of all three launches' workgroups; the segments a step of a frame's prefix sums takes */
+/* host only: rhccq_gif_decode's workspace for a parsed file of n bytes; rhccq_gif_unlzw's for a frame table alone */
+int rhccq_gif_read_sizes(const rhccq_gif_info* info, int64_t n, int64_t* workspace_bytes);
+int64_t rhccq_gif_unlzw_bytes(const rhccq_gif_frame* frames, int32_t n_frames);   /* negative for bad arguments */
+/* the join alone: blocks_dev holds the n_blocks rows (dst ascending), streams (aligned to 16) receives `total` bytes (a multiple of 16),
+   zero where no sub-block lies */
+int rhccq_gif_join(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_segment* blocks_dev, int64_t n_blocks, int64_t total, uint8_t* streams);
+/* streams: stream_bytes joined bytes as the parser lays them out -> pixels: frame f's strings in stream order (not yet de-interlaced) from
+   pixels + frames[f].pixel_offset, n_pixels bytes in all.  counts (device int64[n_frames]): the pixels every frame's stream holds; the
+   device form adds segment totals that saturate at 2^32 - 1 each, more than any frame has, so such a count is only a lower bound.
+   status: device int32[2].  Afterwards the workspace holds uint32[4] at its start: the lowest frame with a bad code, the lowest with a
+   bad length (2^32 - 1: none), the segments of all frames, 0 */
+int rhccq_gif_unlzw(rhccq_ctx* ctx, const uint8_t* streams, int64_t stream_bytes, const rhccq_gif_frame* frames, const rhccq_gif_frame* frames_dev,
+                    int32_t n_frames, void* workspace, uint8_t* pixels, int64_t n_pixels, int64_t* counts, int32_t* status);
+/* pixels as rhccq_gif_unlzw leaves them; the colour tables are read from the file -> rgb[F][H][W][3], alpha[F][H][W] (may be NULL), idx:
+   frame f's de-interlaced indices h x w from idx + frames[f].pixel_offset (may be NULL) */
+int rhccq_gif_compose(rhccq_ctx* ctx, const uint8_t* pixels, int64_t n_pixels, const uint8_t* file, int64_t n, const rhccq_gif_frame* frames_dev,
+                      int32_t n_frames, int32_t H, int32_t W, uint8_t* rgb, uint8_t* alpha, uint8_t* idx);
+/* the whole read: join, rhccq_gif_unlzw, rhccq_gif_compose.  info, frames and the blocks are rhccq_gif_parse_host's; with info->status set
+   nothing runs but the launch that writes it to status.  Afterwards the workspace starts as rhccq_gif_unlzw's does */
+int rhccq_gif_decode(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_gif_info* info, const rhccq_gif_frame* frames,
+                     const rhccq_gif_frame* frames_dev, const rhccq_segment* blocks_dev, void* workspace, uint8_t* rgb, uint8_t* alpha, uint8_t* idx,
+                     int32_t* status);
+int rhccq_gif_unlzw_host(const uint8_t* streams, int64_t stream_bytes, const rhccq_gif_frame* frames, int32_t n_frames, uint8_t* pixels, int64_t n_pixels,
+                         int64_t* counts, int32_t* status, int64_t* n_segments);   /* n_segments may be NULL */
+int rhccq_gif_compose_host(const uint8_t* pixels, int64_t n_pixels, const uint8_t* file, int64_t n, const rhccq_gif_frame* frames, int32_t n_frames,
+                           int32_t H, int32_t W, uint8_t* rgb, uint8_t* alpha, uint8_t* idx);
+/* file in host memory; parses it itself; outputs sized by the parse (they may be NULL for a file the parser refuses); status: host int32[2] */
+int rhccq_gif_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, uint8_t* alpha, uint8_t* idx, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,20 @@ class PngInfo(C.Structure):
                 ("plte_offset", c_int64), ("trns_offset", c_int64), ("idat_bytes", c_int64), ("crc_pieces", c_int64)]
 
 
+class GifInfo(C.Structure):
+    """struct rhccq_gif_info (include/rhccq.h): what rhccq_gif_parse_host reads from a file's framing"""
+    _fields_ = [("status", c_int32), ("detail", c_int32), ("width", c_int32), ("height", c_int32), ("global_rows", c_int32), ("loop", c_int32),
+                ("n_frames", c_int32), ("n_blocks", c_int32), ("global_offset", c_int64), ("stream_bytes", c_int64), ("pixels", c_int64),
+                ("seg_rows", c_int64)]
+
+
+class GifFrame(C.Structure):
+    """struct rhccq_gif_frame (include/rhccq.h): one image of a GIF file"""
+    _fields_ = [("x", c_int32), ("y", c_int32), ("w", c_int32), ("h", c_int32), ("m", c_int32), ("interlace", c_int32), ("table_rows", c_int32),
+                ("transparent", c_int32), ("disposal", c_int32), ("delay", c_int32), ("first_block", c_int32), ("n_blocks", c_int32),
+                ("table_offset", c_int64), ("stream_offset", c_int64), ("stream_bytes", c_int64), ("pixel_offset", c_int64), ("first_row", c_int64)]
+
+
 class FrameResult(C.Structure):
     """struct rhccq_frame_result (include/rhccq.h)"""
     _fields_ = [("n_colours", c_int32), ("index_bytes", c_int32), ("shape", c_int32 * 2), ("top_left", c_int32 * 2), ("quality3", c_int32),
@@ -290,6 +304,20 @@ PROTOTYPES = {
     "rhccq_gif_lzw_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "rhccq_gif_encode_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
                                         c_int64, c_void_p, c_void_p]),
+    "rhccq_gif_parse_host": (c_int32, [c_void_p, c_int64, C.POINTER(GifInfo), c_void_p, c_int64, C.POINTER(c_int64), c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_gif_read_tile": (c_int32, []),
+    "rhccq_gif_read_scan_step": (c_int32, []),
+    "rhccq_gif_read_threads": (c_int32, []),
+    "rhccq_gif_read_sizes": (c_int32, [C.POINTER(GifInfo), c_int64, C.POINTER(c_int64)]),
+    "rhccq_gif_unlzw_bytes": (c_int64, [c_void_p, c_int32]),
+    "rhccq_gif_join": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "rhccq_gif_unlzw": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_gif_compose": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_gif_decode": (c_int32, [c_void_p, c_void_p, c_int64, C.POINTER(GifInfo), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "rhccq_gif_unlzw_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, C.POINTER(c_int64)]),
+    "rhccq_gif_compose_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_gif_decode_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -12,6 +12,7 @@ import io
 import os
 import pickle
 import struct
+import time
 
 import numpy as np
 import torch
@@ -316,6 +317,69 @@ def read_png(src, rh=None, check_crc=True):
             res["palette_alpha"][:info.trns_bytes] = out["file"][info.trns_offset:info.trns_offset + info.trns_bytes]
         res["indices"] = out["indices"].reshape(-1)
         res["dtype"] = "uint8"
+    return res
+
+
+def read_gif(src, rh=None):
+    """a GIF file (87a or 89a, animated or not) -> {"images": uint8[F, H, W, 3] device, "alpha": uint8[F, H, W] device, "shape": (H, W),
+    "loop": the file's loop count or None, "delays": [centiseconds a frame], "frames": [{"rect": (x, y, w, h), "interlaced", "disposal",
+    "transparent": index or None, "palette": uint8[k, 3] (the frame's table, local or global), "indices": uint8[h, w] device}], "stats":
+    {"bytes", "frames", "segments", "stream_bytes": [a frame], "seconds"}} decoded on the device (include/rhccq.h "GIF files read on the
+    device": sub-block join, Clear-to-Clear parallel LZW decode, composition).  images[f] is the logical screen after frame f painted
+    (transparency and the disposal methods applied); alpha[f] is 255 where some frame has painted and 0 elsewhere, and such an uncovered
+    pixel has colour (0, 0, 0).  src: a file name or bytes.  The host reads the file once, parses its framing (rhccq_gif_parse_host) and
+    uploads it once; one read of the status words is the only wait.  A file the definition refuses raises RhccqError naming status and
+    detail (its .status and .detail carry them).  Not done: the plain-text extension is skipped, not drawn; the background colour index
+    is ignored."""
+    from .ops import GIF_READ_STATUS, gif_parse
+    rh = rh or default_context()
+    t0 = time.perf_counter()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytearray(src)
+    else:
+        with open(src, "rb") as f:
+            data = bytearray(os.fstat(f.fileno()).st_size)
+            del data[f.readinto(data):]
+    parsed = gif_parse(data)
+    info, table = parsed[0], parsed[1]
+
+    def refuse(status, detail):
+        e = RhccqError(f"read_gif: RHCCQ_GIFR_{GIF_READ_STATUS[status]} (status {status}), detail {detail}")
+        e.status, e.detail = status, detail
+        raise e
+    if info.status:
+        refuse(info.status, info.detail)
+    out = rh.gif_decode(np.frombuffer(data, np.uint8), parsed)
+    status, head = rh.to_host(out["status"], out["head"])
+    if int(status[0]):
+        refuse(int(status[0]), int(status[1]))
+    host = np.frombuffer(data, np.uint8)
+    frames = []
+    for f in range(info.n_frames):
+        fr = table[f]
+        at = fr.pixel_offset
+        frames.append({"rect": (fr.x, fr.y, fr.w, fr.h), "interlaced": bool(fr.interlace), "disposal": fr.disposal,
+                       "transparent": None if fr.transparent < 0 else fr.transparent,
+                       "palette": host[fr.table_offset:fr.table_offset + 3 * fr.table_rows].reshape(-1, 3).copy(),
+                       "indices": out["indices"][at:at + fr.w * fr.h].reshape(fr.h, fr.w)})
+    return {"images": out["rgb"], "alpha": out["alpha"], "shape": (info.height, info.width), "loop": None if info.loop < 0 else info.loop,
+            "delays": [table[f].delay for f in range(info.n_frames)], "frames": frames,
+            "stats": {"bytes": len(data), "frames": info.n_frames, "segments": int(head[2]) & 0xFFFFFFFF,
+                      "stream_bytes": [table[f].stream_bytes for f in range(info.n_frames)], "seconds": round(time.perf_counter() - t0, 4)}}
+
+
+def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4):
+    """an animated GIF to one of at most `colours` colours, on the device from end to end: read_gif, then ImageEncoder.animate over the
+    composed frames with the file's own delays and loop count (0 where it has none), written to dst.  The frames enter as the viewer
+    shows them, so cropped rectangles, transparency and disposal methods are gone from the result; a pixel no frame has covered enters
+    as colour (0, 0, 0).  -> animate's dict, with stats["read"] = read_gif's stats."""
+    from .image import ImageEncoder
+    rh = rh or default_context()
+    src = read_gif(src, rh)
+    enc = ImageEncoder(rh)
+    res = enc.animate(src["images"], colours, gif_path=dst, delay=src["delays"], loop=src["loop"] or 0, delta=delta, refine=refine, pattern=pattern,
+                      pattern_size=pattern_size)
+    res["stats"]["read"] = src["stats"]
     return res
 
 

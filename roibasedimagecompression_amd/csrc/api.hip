@@ -108,6 +108,10 @@ int rhccq_ctx_set_int(rhccq_ctx* ctx, int32_t option, int64_t value) {
       if (value < 1 || value > 300) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_KMEANS_CHUNK: 1 .. 300");
       ctx->opt_kmeans_chunk = (int)value;
       return 0;
+    case RHCCQ_OPT_GIF_READ_CHAIN:
+      if (value != 0 && value != 1) return rhccq_fail(ctx, RHCCQ_E_ARG, "RHCCQ_OPT_GIF_READ_CHAIN: 0 or 1");
+      ctx->opt_gif_read_chain = (int)value;
+      return 0;
     default:
       return rhccq_fail(ctx, RHCCQ_E_ARG, "unknown option");
   }

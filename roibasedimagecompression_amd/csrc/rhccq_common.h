@@ -35,6 +35,7 @@ struct rhccq_ctx {
   int opt_dither_rows = 0;         // rhccq_palette_dither: image rows of a band (0: kDitherRowsDefault; 4, 8, 16 or 32)
   int opt_kmeans_wide_pairs = 100000;   // rhccq_kmeans: problems of at least this many (point, centre) pairs run their Lloyd iterations as launches on many CUs (0: never; km_wide_host.h; measured: tools/kmeansbench.py)
   int opt_kmeans_chunk = 16;       // rhccq_kmeans: Lloyd iterations of the wide path enqueued between two looks at the state records
+  int opt_gif_read_chain = 0;      // rhccq_gif_unlzw: a segment's chains by pointer doubling (0, default) or by one lane's pass in order (1)
   int opt_chain_release = 1; // rhccq_encode_frame: a level-1 problem goes on when its own chain of the frame's launch has ended (1, default) or when the launch has (0)
 };
 

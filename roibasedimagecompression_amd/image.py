@@ -1297,7 +1297,7 @@ class ImageEncoder:
             cells = self._cells("shared_palette", self._frame_tensor("shared_palette", image), mask, roi_weight, into=cells)
         return self.rh.palette_build(cells, colours)[0]
 
-    def animate(self, images, colours=256, gif_path=None, delay=4, loop=0, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
+    def animate(self, images, colours=256, gif_path=None, delay=None, loop=None, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
                 pattern_size=4):
         """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor ->
         {"palette": uint8[k, 3], "indices": device uint8[B, H, W], "indices_dtype": "uint8", "shape": (H, W), "stats"}: an animated GIF89a built on the device from end to end.  One shared_palette over all frames (at most `colours` rows,
@@ -1313,7 +1313,10 @@ class ImageEncoder:
         "gif": container.gif_file's row, "seconds"}.
         dither, run_slack, run_penalty and the targets are not parameters: error diffusion is not frame-stable (a changed pixel moves
         the indices of everything to its right and below, so delta would find nothing), and the run rules and targets decide per
-        image on the host."""
+        image on the host.
+        images may also be an animated GIF itself: a file name ending in .gif, or bytes that start with "GIF8".  It is read on the device
+        (container.read_gif: the composed frames, an uncovered pixel as colour 0), and delay and loop default to the file's own (loop 0
+        where the file has no loop count); otherwise they default to 4 and 0."""
         rh = self.rh
         fn = "ImageEncoder.animate"
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
@@ -1322,6 +1325,13 @@ class ImageEncoder:
             raise ValueError(f"{fn}: colours must be 1..256 (a GIF colour table has at most 256 rows)")
         if refine < 0 or refine > 64:
             raise ValueError(f"{fn}: refine must be 0..64")
+        if (isinstance(images, str) and images.lower().endswith(".gif")) or (isinstance(images, (bytes, bytearray, memoryview)) and bytes(images[:4]) == b"GIF8"):
+            from . import container
+            src = container.read_gif(images, rh)
+            images = src["images"]
+            delay = src["delays"] if delay is None else delay
+            loop = (src["loop"] or 0) if loop is None else loop
+        delay, loop = 4 if delay is None else delay, 0 if loop is None else loop
         stacked = None
         if (torch.is_tensor(images) or isinstance(images, np.ndarray)) and images.ndim == 4:
             stacked = images.to(rh.device).contiguous() if torch.is_tensor(images) else rh.dev(images)

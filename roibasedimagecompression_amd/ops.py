@@ -217,6 +217,46 @@ def png_parse(data):
     return info, table[:count.value]
 
 
+GIF_READ_STATUS = ("OK", "BAD_SIGNATURE", "TRUNCATED", "BAD_BLOCK", "BAD_HEADER", "BAD_FRAME", "NO_TABLE", "NO_FRAMES", "LIMIT", "BAD_CODE", "BAD_LENGTH")
+
+
+def gif_read_tile():
+    """codes a step of Rhccq.gif_unlzw's lengths and emit launches: a lane a code"""
+    return int(_lib.load().rhccq_gif_read_tile())
+
+
+def gif_read_scan_step():
+    """codes a step of Rhccq.gif_unlzw's scan launch tests for Clear and End: a whole number of tiles, a lane one code of each"""
+    return int(_lib.load().rhccq_gif_read_scan_step())
+
+
+def gif_read_threads():
+    """threads of a workgroup of Rhccq.gif_unlzw's launches: also the segments a step of its per-frame prefix sums takes"""
+    return int(_lib.load().rhccq_gif_read_threads())
+
+
+def gif_parse(data):
+    """rhccq_gif_parse_host (host only, a pure function of the bytes) -> (_lib.GifInfo, a ctypes array of _lib.GifFrame, one an image, the
+    sub-block table int64[n_blocks, 4]: offset of the first data byte, length, frame, place in the joined streams)"""
+    a = np.frombuffer(data, dtype=np.uint8)
+    lib = _lib.load()
+    info, nf, nb = _lib.GifInfo(), C.c_int64(), C.c_int64()
+    ptr = C.c_void_p(a.ctypes.data if a.size else 0)
+    rc = lib.rhccq_gif_parse_host(ptr, a.size, C.byref(info), None, 0, C.byref(nf), None, 0, C.byref(nb))
+    if rc:
+        raise RhccqError(f"gif_parse: rhccq_gif_parse_host failed ({rc})")
+    frames = (_lib.GifFrame * max(nf.value, 1))()
+    blocks = np.zeros((max(nb.value, 1), 4), np.int64)
+    if info.status == 0:
+        lib.rhccq_gif_parse_host(ptr, a.size, C.byref(info), C.cast(frames, C.c_void_p), nf.value, C.byref(nf), C.c_void_p(blocks.ctypes.data), nb.value, C.byref(nb))
+    return info, frames, blocks[:nb.value]
+
+
+def gif_frames_array(frames, n):
+    """the first n rows of a ctypes array of _lib.GifFrame as bytes (uint8, what the device copy holds)"""
+    return np.frombuffer(C.string_at(C.addressof(frames), n * C.sizeof(_lib.GifFrame)), np.uint8).copy()
+
+
 PALETTE_CELLS_SHAPE = (4, 32, 32, 32)  # Rhccq.palette_cells' table: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3)
 
 
@@ -341,6 +381,7 @@ class Rhccq:
     OPT_DITHER_ROWS = 14             # palette_dither: image rows of a band (0, default: palette_dither_rows(); 4, 8, 16 or 32)
     OPT_KMEANS_WIDE_PAIRS = 15       # kmeans_split: problems of k <= 1024 and at least this many (point, centre) pairs run their Lloyd iterations as launches on many CUs (0: never, 1: all of them)
     OPT_KMEANS_CHUNK = 16            # kmeans_split: Lloyd iterations of the wide path enqueued between two looks at the state records (1 .. 300)
+    OPT_GIF_READ_CHAIN = 17          # gif_unlzw / gif_decode: a segment's len / first chains by pointer doubling (0, default) or by one lane's pass in order (1); same results
 
     def _bind_stream(self):
         """kernels follow torch's current stream (see _StreamBoundLib)"""
@@ -2211,6 +2252,99 @@ class Rhccq:
                                               self._p(rgb), self._p(alpha), self._p(idx), self._p(status)), fn)
         at = int(self._raw.rhccq_png_read_scan_offset(C.byref(info)))
         return {"rgb": rgb, "alpha": alpha, "indices": idx, "status": status, "scan": work[at:at + info.scan_bytes], "file": file}
+
+    # -- GIF files read on the device (EXTENSION: csrc/gif_read.hip; include/rhccq.h pins the definition) ----------------
+    def _gif_out(self, fn, what, t, shape):
+        """a caller's output buffer (a contiguous uint8 device tensor of `shape`'s size), or a new one"""
+        if t is None:
+            return self.empty(shape, torch.uint8)
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"{fn}: {what} must be a contiguous uint8 device tensor of {int(np.prod(shape))} bytes")
+        return t
+
+    def _gif_frames(self, fn, frames, n_frames):
+        n_frames = int(n_frames)
+        if not isinstance(frames, C.Array) or frames._type_ is not _lib.GifFrame or not 1 <= n_frames <= len(frames):
+            raise ValueError(f"{fn}: frames must be gif_parse's array and 1 <= n_frames <= its length")
+        return n_frames, self.dev(gif_frames_array(frames, n_frames))
+
+    def gif_unlzw(self, streams, frames, n_frames, pixels=None):
+        """streams: the joined code streams (uint8, laid out as gif_parse's frames say: every frame's at a 16-byte aligned offset, 16 bytes
+        or more behind it); frames: gif_parse's array -> (pixels uint8[sum of w h] device: frame f's strings in stream order from
+        frames[f].pixel_offset, counts int64[n_frames] device, status int32[2] device: GIF_READ_STATUS index -- OK, BAD_CODE, BAD_LENGTH --
+        and the frame, head int32[4] device: the fault words and the number of segments).  pixels: a caller's buffer.  Nothing waits."""
+        fn = "gif_unlzw"
+        n_frames, frames_dev = self._gif_frames(fn, frames, n_frames)
+        streams = self._aligned_bytes(streams, fn, "streams")
+        n_pixels = sum(int(frames[f].w) * int(frames[f].h) for f in range(n_frames))
+        ws = int(self._raw.rhccq_gif_unlzw_bytes(C.cast(frames, C.c_void_p), n_frames))
+        if ws < 0:
+            raise RhccqError(f"{fn}: rhccq_gif_unlzw_bytes failed ({ws}): the frame table is not gif_parse's")
+        pixels = self._gif_out(fn, "pixels", pixels, (max(n_pixels, 1),))
+        work = self.empty((ws,), torch.uint8)
+        counts = self.empty((n_frames,), torch.int64)
+        status = self.empty((2,), torch.int32)
+        self._check(self.lib.rhccq_gif_unlzw(self.ctx, self._p(streams), streams.numel(), C.cast(frames, C.c_void_p), self._p(frames_dev), n_frames,
+                                             self._p(work), self._p(pixels), n_pixels, self._p(counts), self._p(status)), fn)
+        return pixels, counts, status, work[:16].view(torch.int32)
+
+    def gif_compose(self, pixels, file, frames, n_frames, H, W, rgb=None, alpha=None, idx=None, want_idx=True):
+        """pixels as gif_unlzw leaves them, file: the GIF file's bytes (the colour tables are read from it), frames: gif_parse's array ->
+        (rgb uint8[F, H, W, 3], alpha uint8[F, H, W], idx uint8[sum of w h]: every frame's de-interlaced indices from its pixel_offset,
+        None with want_idx=False) on the device.  rgb, alpha, idx: a caller's buffers."""
+        fn = "gif_compose"
+        n_frames, frames_dev = self._gif_frames(fn, frames, n_frames)
+        H, W = int(H), int(W)
+        if not (1 <= H <= 65535 and 1 <= W <= 65535):
+            raise ValueError(f"{fn}: H and W must be 1..65535")
+        pixels = A.as_uint8(pixels, self.device, fn, "pixels").reshape(-1)
+        file = A.as_uint8(file, self.device, fn, "file").reshape(-1)
+        rgb = self._gif_out(fn, "rgb", rgb, (n_frames, H, W, 3))
+        alpha = self._gif_out(fn, "alpha", alpha, (n_frames, H, W))
+        idx = self._gif_out(fn, "idx", idx, (max(pixels.numel(), 1),)) if want_idx or idx is not None else None
+        self._check(self.lib.rhccq_gif_compose(self.ctx, self._p(pixels), pixels.numel(), self._p(file), file.numel(), self._p(frames_dev), n_frames, H, W,
+                                               self._p(rgb), self._p(alpha), self._p(idx)), fn)
+        return rgb, alpha, idx
+
+    def gif_decode(self, file, parsed=None, rgb=None, alpha=None, idx=None):
+        """file: the GIF file's bytes as a uint8 device tensor (or bytes / numpy, uploaded); parsed: gif_parse's triple (parsed from the
+        bytes when None, which reads a device tensor back) -> {"rgb" uint8[F, H, W, 3], "alpha" uint8[F, H, W], "indices" uint8[sum of
+        w h] (frame f's de-interlaced h x w map from its pixel_offset), "status" int32[2] (GIF_READ_STATUS index, detail), "head" int32[4]
+        (the fault words, the segments of all frames), "file": the bytes on the device, "info", "frames"}; nothing waits for the device.
+        With a status the framing shows (info.status) there are no outputs.  rgb, alpha, idx: a caller's buffers."""
+        fn = "gif_decode"
+        if parsed is None:
+            host = self.to_host(file).tobytes() if torch.is_tensor(file) else bytearray(file)
+            parsed = gif_parse(host)
+            if not torch.is_tensor(file):
+                file = np.frombuffer(host, np.uint8)
+        info, frames, blocks = parsed
+        if not torch.is_tensor(file) and not isinstance(file, np.ndarray):
+            file = np.frombuffer(bytes(file), np.uint8).copy()
+        status = self.empty((2,), torch.int32)
+        null = C.c_void_p(0)
+        if info.status:
+            self._check(self.lib.rhccq_gif_decode(self.ctx, null, 0, C.byref(info), null, null, null, null, null, null, null, self._p(status)), fn)
+            return {"rgb": None, "alpha": None, "indices": None, "status": status, "head": None, "file": None, "info": info, "frames": frames}
+        file = A.as_uint8(file, self.device, fn, "file").reshape(-1)                 # (any alignment: the kernels read it byte by byte)
+        n, F, H, W = file.numel(), info.n_frames, info.height, info.width
+        ws = C.c_int64()
+        rc = self._raw.rhccq_gif_read_sizes(C.byref(info), n, C.byref(ws))
+        if rc:
+            raise RhccqError(f"{fn}: rhccq_gif_read_sizes failed ({rc}): info does not describe a file of {n} bytes")
+        blocks = np.ascontiguousarray(blocks, dtype=np.int64).reshape(-1, 4)
+        if len(blocks) != info.n_blocks:
+            raise ValueError(f"{fn}: the sub-block table must have info.n_blocks rows")
+        _, frames_dev = self._gif_frames(fn, frames, F)
+        blocks_dev = self.dev(blocks.reshape(-1)) if len(blocks) else None
+        work = self.empty((ws.value,), torch.uint8)
+        rgb = self._gif_out(fn, "rgb", rgb, (F, H, W, 3))
+        alpha = self._gif_out(fn, "alpha", alpha, (F, H, W))
+        idx = self._gif_out(fn, "idx", idx, (info.pixels,))
+        self._check(self.lib.rhccq_gif_decode(self.ctx, self._p(file), n, C.byref(info), C.cast(frames, C.c_void_p), self._p(frames_dev), self._p(blocks_dev),
+                                              self._p(work), self._p(rgb), self._p(alpha), self._p(idx), self._p(status)), fn)
+        return {"rgb": rgb, "alpha": alpha, "indices": idx, "status": status, "head": work[:16].view(torch.int32), "file": file, "info": info,
+                "frames": frames}
 
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
     ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
