@@ -305,15 +305,40 @@ int64_t rhccq_cluster_plan_host(const unsigned long long* sums, int64_t k, int64
  * 0 or fp >= fp_none do not appear (lut 0).  gkeys / gfp: room for 1 + sum(counts); lut[c]: counts[c] ints.  Pure host code. */
 int rhccq_merge_palettes_host(int32_t n_comp, const uint32_t* const* keys, const int64_t* const* fp, const int32_t* counts,
                               int64_t fp_none, uint32_t* gkeys, int64_t* gfp, int32_t* const* lut, int64_t* n_out);
-/* RandomState.randint(0, n, size) of numpy's legacy generator replayed ON THE HOST from raw MT19937 words in host memory
- * (masked rejection, one word per attempt): sklearn MiniBatchKMeans draws its validation and init samples this way before
- * k-means++ (clustering.py:207-218 -> _kmeans.py MiniBatchKMeans.fit).  out: int32[size] or NULL (stream position only).
+/* ---- numpy's legacy RandomState(42), replayed from its raw MT19937 words (csrc/mt_replay.h: the one replay of the process) ----
+ * RandomState.randint(0, n, size) ON THE HOST from raw words in host memory (masked rejection, one word per attempt): sklearn
+ * MiniBatchKMeans draws its validation and init samples this way before k-means++ (clustering.py:207-218 -> _kmeans.py
+ * MiniBatchKMeans.fit).  out: int32[size] or NULL (stream position only).
  * Returns the words consumed, -1 when the table ends first, -2 for a bad argument.  Pure host code, no ctx. */
 int64_t rhccq_mt_randint_host(const uint32_t* words, int64_t n_words, int64_t pos, int64_t n, int64_t size, int32_t* out);
+/* out[i] = raw word pos + i of MT19937(seed 42), i < count (host memory; what the tests compare with numpy's generator).  Host only. */
+int rhccq_mt_words_host(int64_t pos, int64_t count, uint32_t* out);
+/* random_sample() with the stream at raw word `pos` (two words; -1.0 for pos < 0), and RandomState.choice(n, p = ones / n) from its one
+ * uniform u (-1 for n outside 1 .. 2^31 - 1): the first centre of k-means++.  Host only, safe from several threads. */
+double rhccq_mt_double_host(int64_t pos);
+int32_t rhccq_first_centre_index(int64_t n, double u);
+/* What MiniBatchKMeans(k, batch_size=1000, random_state=42).fit of n points fixes ahead of its k-means++ chain. */
+typedef struct rhccq_mbk_draw {
+  int64_t batch;      /* min(1000, n) */
+  int64_t limit;      /* steps at most: 100 n / batch */
+  int64_t init_size;  /* 3 batch, 3 k if that is below k, n at most */
+  int64_t n_uniforms; /* uniforms of the chain: max((k - 1) T, 1) */
+  int64_t pos;        /* raw word of the first k-means++ uniform: behind the validation draw, the init sample and the first centre */
+  int64_t cursor0;    /* stream position behind the k-means++ uniforms: pos + 2 (k - 1) T */
+  int32_t T;          /* n_local_trials: 2 + floor(ln k) */
+  int32_t first;      /* first centre (position in the init sample) */
+} rhccq_mbk_draw;
+/* Fills *out and init_idx (int32[cap], cap >= init_size: the init sample in draw order, 0 .. n-1 when init_size == n).  init_idx NULL:
+ * only what follows from (n, k) alone (pos, cursor0, first stay 0), so that a caller can size the buffer.  RHCCQ_E_ARG, and nothing
+ * written, unless 1 <= k <= n < 2^31 and cap suffices.  Host only, safe from several threads. */
+int rhccq_mbk_draws(int64_t n, int64_t k, rhccq_mbk_draw* out, int32_t* init_idx, int64_t cap);
+/* At least the first n raw words on the context's device, complete on return: *words_dev, *count >= n.  One table per device and
+ * process, shared by every context; a pointer handed out stays readable for the life of the process. */
+int rhccq_mt_words(rhccq_ctx* ctx, int64_t n, const uint32_t** words_dev, int64_t* count);
 /* out[i] = the i-th double numpy's legacy RandomState.uniform(size=count) / random_sample() yields when its
  * MT19937 stream stands at raw word `pos`: ((w[pos+2i] >> 5) * 2^26 + (w[pos+2i+1] >> 6)) / 2^53.  words: the raw
- * 32-bit outputs of MT19937(seed 42), resident on the device (roibasedimagecompression_amd/mt.py generates them
- * with numpy itself).  Serves the uniform(size=n_local_trials) draws of k-means++ (sklearn `_kmeans_plusplus`). */
+ * 32-bit outputs of MT19937(seed 42), resident on the device (rhccq_mt_words).
+ * Serves the uniform(size=n_local_trials) draws of k-means++ (sklearn `_kmeans_plusplus`). */
 int rhccq_mt_uniforms(rhccq_ctx* ctx, const uint32_t* words, int64_t pos, int64_t count, double* out);
 /* greedy k-means++ (sklearn _kmeans_plusplus) on the init sample in exact integers, candidates searched over the
  * cumulative closest-distance sums in DRAW order; writes centres[(koff+j)*4 + {0,1,2}] (doubles, raw 0..255

@@ -20,6 +20,12 @@ class MbkProblem(C.Structure):
                 ("init_n", c_int64), ("rand_off", c_int64), ("first", c_int32), ("T", c_int32)]
 
 
+class MbkDraw(C.Structure):
+    """struct rhccq_mbk_draw (include/rhccq.h): what a MiniBatchKMeans fit fixes ahead of its k-means++ chain"""
+    _fields_ = [("batch", c_int64), ("limit", c_int64), ("init_size", c_int64), ("n_uniforms", c_int64), ("pos", c_int64),
+                ("cursor0", c_int64), ("T", c_int32), ("first", c_int32)]
+
+
 class ClassDesc(C.Structure):
     """struct rhccq_class_desc (include/rhccq.h): one region class of a frame for rhccq_encode_frame"""
     _fields_ = [("labels", c_void_p), ("n_seg", c_int32), ("n_region", c_int32), ("seg_region", c_void_p), ("region_bbox", c_void_p),
@@ -116,6 +122,11 @@ PROTOTYPES = {
     "rhccq_mbk_steps_overlapped": (c_int32, [c_void_p, c_void_p, C.POINTER(MbkProblem), c_int32, c_int64, c_int32, c_void_p, c_int64, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, C.POINTER(c_int32)]),
     "rhccq_mt_randint_host": (c_int64, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "rhccq_mt_words_host": (c_int32, [c_int64, c_int64, c_void_p]),
+    "rhccq_mt_double_host": (c_double, [c_int64]),
+    "rhccq_first_centre_index": (c_int32, [c_int64, c_double]),
+    "rhccq_mbk_draws": (c_int32, [c_int64, c_int64, C.POINTER(MbkDraw), c_void_p, c_int64]),
+    "rhccq_mt_words": (c_int32, [c_void_p, c_int64, C.POINTER(c_void_p), C.POINTER(c_int64)]),
     "rhccq_scatter_min_host": (c_int32, [c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_cluster_plan_host": (c_int64, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "rhccq_merge_palettes_host": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,8 +1,11 @@
 // Context management and host-only entry points of librhccq_hip.so.
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <vector>
 
+#include "mt_replay.h"
 #include "rhccq_common.h"
 
 int rhccq_upload(rhccq_ctx* ctx, const void* host, size_t bytes, void** dev_out) {
@@ -128,6 +131,69 @@ void* rhccq_stream(rhccq_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; 
 int rhccq_ctx_set_stream(rhccq_ctx* ctx, void* hip_stream) {
   if (!ctx) return RHCCQ_E_ARG;
   ctx->stream = (hipStream_t)hip_stream;                // not owned; later entry points launch on it
+  return 0;
+}
+
+// ---- numpy's RandomState(42) replayed (mt_replay.h) ------------------------------------------------------------------------------
+int64_t rhccq_mt_randint_host(const uint32_t* words, int64_t n_words, int64_t pos, int64_t n, int64_t size, int32_t* out) {
+  return rhccq_mt::randint(words, n_words, pos, n, size, out);
+}
+
+int rhccq_mt_words_host(int64_t pos, int64_t count, uint32_t* out) {
+  if (pos < 0 || count < 0 || (count > 0 && !out)) return RHCCQ_E_ARG;
+  if (count) memcpy(out, rhccq_mt::Words::get().host(pos + count)->data() + pos, (size_t)count * 4);
+  return 0;
+}
+
+double rhccq_mt_double_host(int64_t pos) { return pos < 0 ? -1.0 : rhccq_mt::Words::get().dbl(pos); }
+
+int32_t rhccq_first_centre_index(int64_t n, double u) { return n < 1 || n > 0x7fffffffll ? -1 : rhccq_mt::first_centre_index(n, u); }
+
+int rhccq_mbk_draws(int64_t n, int64_t k, rhccq_mbk_draw* out, int32_t* init_idx, int64_t cap) {
+  if (!out || k < 1 || k > n || n > 0x7fffffffll) return RHCCQ_E_ARG;
+  rhccq_fit::Problem c = rhccq_fit::problem(n, k);
+  if (init_idx) {
+    if (cap < c.init_size) return RHCCQ_E_ARG;
+    c = rhccq_mt::mbk_draws(n, k, init_idx);
+  }
+  *out = rhccq_mbk_draw{c.batch, c.limit, c.init_size, c.n_uniforms, c.pos, c.cursor0, c.T, c.first};
+  return 0;
+}
+
+// The one word table of a device: uploaded once, regrown geometrically; a superseded table stays allocated (kernels queued on other
+// streams may still read it, and there are log2 of them at most)
+int rhccq_mt_words(rhccq_ctx* ctx, int64_t n, const uint32_t** words_dev, int64_t* count) {
+  if (!ctx || n < 1 || !words_dev || !count) return rhccq_fail(ctx, RHCCQ_E_ARG, "mt_words: bad argument");
+  struct Table {
+    const uint32_t* p = nullptr;
+    int64_t n = 0;
+  };
+  static std::mutex mu;
+  static std::map<int, Table> tables;
+  std::lock_guard<std::mutex> g(mu);
+  Table& t = tables[ctx->device];
+  if (t.n < n) {
+    const int64_t want = std::max<int64_t>({n, 2 * t.n, (int64_t)1 << 22});
+    const auto h = rhccq_mt::Words::get().host(want);
+    int cur = 0;
+    RHCCQ_HIP(ctx, hipGetDevice(&cur));
+    if (cur != ctx->device) RHCCQ_HIP(ctx, hipSetDevice(ctx->device));
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)want * 4);
+    if (e == hipSuccess) {
+      e = hipMemcpy(p, h->data(), (size_t)want * 4, hipMemcpyHostToDevice);   // blocking: complete on return
+      if (e != hipSuccess) (void)hipFree(p);
+    }
+    if (cur != ctx->device) (void)hipSetDevice(cur);
+    if (e != hipSuccess) {
+      ctx->err = std::string("mt_words: ") + hipGetErrorString(e);
+      return RHCCQ_E_HIP;
+    }
+    t.p = (const uint32_t*)p;
+    t.n = want;
+  }
+  *words_dev = t.p;
+  *count = t.n;
   return 0;
 }
 

@@ -37,6 +37,7 @@
 #include "frame_level2_host.h"
 #include "host_raii.h"
 #include "mbk_fit_host.h"
+#include "mt_replay.h"
 #include "rhccq_common.h"
 
 namespace {
@@ -60,129 +61,10 @@ bool trace_on() {
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// ---- numpy's legacy RandomState(42) as raw MT19937 words (mt.py's counterpart; every k-means fit of the reference restarts from
-// random_state=42: clustering.py:211-218, 751-752) ------------------------------------------------------------------------------
-class MtTable {
- public:
-  static MtTable& get() {
-    static MtTable t;
-    return t;
-  }
-  // raw words [0, n) on the host (snapshot: stays valid while the table grows behind it)
-  std::shared_ptr<const std::vector<uint32_t>> host(int64_t n) {
-    std::lock_guard<std::mutex> g(mu_);
-    if ((int64_t)words_->size() < n) {
-      const size_t have = words_->size();
-      const size_t want = std::max<size_t>({(size_t)n, 2 * have, (size_t)1 << 20});
-      auto nw = std::make_shared<std::vector<uint32_t>>(*words_);
-      nw->resize(want);
-      for (size_t i = have; i < want; ++i) (*nw)[i] = next();
-      words_ = nw;
-    }
-    return words_;
-  }
-  // the first >= n words on the device (uploaded once, regrown geometrically; a superseded table stays allocated: kernels queued on
-  // other streams may still read it, and there are log2 of them at most)
-  void device(int dev, int64_t n, const uint32_t** ptr, int64_t* count) {
-    auto h = host(n);
-    std::lock_guard<std::mutex> g(dmu_);
-    Dev& d = dev_[dev];
-    if (d.n < n) {
-      const int64_t want = std::max<int64_t>({n, 2 * d.n, (int64_t)1 << 22});
-      h = host(want);
-      void* p = nullptr;
-      EF_HIP(hipMalloc(&p, (size_t)want * 4));
-      EF_HIP(hipMemcpy(p, h->data(), (size_t)want * 4, hipMemcpyHostToDevice));
-      d.p = (const uint32_t*)p;
-      d.n = want;
-    }
-    *ptr = d.p;
-    *count = d.n;
-  }
-  // RandomState.randint(0, n, size) at raw word `pos`: words consumed (out may be NULL: stream position only)
-  int64_t randint(int64_t pos, int64_t n, int64_t size, int32_t* out) {
-    if (n <= 1) {
-      if (out) std::fill(out, out + size, 0);
-      return 0;                                        // numpy draws nothing for a one-value range
-    }
-    int bits = 0;
-    while (((int64_t)1 << bits) < n) ++bits;
-    int64_t win = (int64_t)((double)size / ((double)n / (double)((int64_t)1 << bits)) * 1.05) + 256;
-    while (true) {
-      auto w = host(pos + win);
-      const int64_t used = rhccq_mt_randint_host(w->data(), (int64_t)w->size(), pos, n, size, out);
-      if (used >= 0) return used;
-      if (used != -1) throw Err{RHCCQ_E_ARG, "rhccq_mt_randint_host: bad argument"};
-      win = 2 * win + 1024;
-    }
-  }
-  // random_sample() at raw word `pos` (two words)
-  double dbl(int64_t pos) {
-    auto w = host(pos + 2);
-    return ((double)((*w)[pos] >> 5) * 67108864.0 + (double)((*w)[pos + 1] >> 6)) / 9007199254740992.0;
-  }
-
- private:
-  MtTable() : words_(std::make_shared<std::vector<uint32_t>>()) {
-    uint32_t seed = 42u;
-    for (int i = 0; i < 624; ++i) {
-      key_[i] = seed;
-      seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)i + 1u;
-    }
-    pos_ = 624;
-  }
-  uint32_t next() {
-    if (pos_ == 624) {
-      uint32_t* k = key_;
-      int i;
-      for (i = 0; i < 624 - 397; ++i) {
-        const uint32_t y = (k[i] & 0x80000000u) | (k[i + 1] & 0x7fffffffu);
-        k[i] = k[i + 397] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-      }
-      for (; i < 623; ++i) {
-        const uint32_t y = (k[i] & 0x80000000u) | (k[i + 1] & 0x7fffffffu);
-        k[i] = k[i + (397 - 624)] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-      }
-      const uint32_t y = (k[623] & 0x80000000u) | (k[0] & 0x7fffffffu);
-      k[623] = k[396] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-      pos_ = 0;
-    }
-    uint32_t y = key_[pos_++];
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= y >> 18;
-    return y;
-  }
-  struct Dev {
-    const uint32_t* p = nullptr;
-    int64_t n = 0;
-  };
-  std::mutex mu_, dmu_;
-  std::shared_ptr<std::vector<uint32_t>> words_;
-  std::map<int, Dev> dev_;
-  uint32_t key_[624];
-  int pos_;
-};
-
-// RandomState.choice(n, p = ones / n): searchsorted(cumsum(p) / cumsum(p)[-1], u, 'right') -- numpy's cumsum adds sequentially
-int32_t first_centre_index(int64_t n, double u) {
-  const double p = 1.0 / (double)n;
-  std::vector<double> cdf((size_t)n);
-  double acc = 0.0;
-  for (int64_t i = 0; i < n; ++i) {
-    acc = acc + p;
-    cdf[(size_t)i] = acc;
-  }
-  const double last = cdf[(size_t)n - 1];
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (cdf[(size_t)mid] / last <= u) lo = mid + 1;
-    else hi = mid;
-  }
-  return (int32_t)std::min(lo, n - 1);
-}
+// numpy's RandomState(42) and the draws ahead of a fit's k-means++ chain: mt_replay.h; the word table of a device: rhccq_mt_words
+using rhccq_mt::first_centre_index;
+using rhccq_mt::mbk_draws;
+using rhccq_mt::MbkDraws;
 
 // ---- a sibling context: HIP stream + bump arena of device memory, kept between frames -----------------------------------------
 struct Arena {
@@ -315,28 +197,7 @@ struct FrameState {
 void free_frame_state(void* p) { delete (FrameState*)p; }
 
 // ---- MiniBatchKMeans(k, batch_size=1000, random_state=42, n_init='auto').fit_predict of 1 .. 32 palettes resident on the device
-// (ops.py::minibatch_kmeans; reference call site clustering.py:207-218).  What the host decides on the way is mbk_fit_host.h ------------
-// The draws of one fit ahead of its k-means++ chain (sklearn _init_centroids with init_size, then kmeans_plusplus): host only
-struct MbkDraws {
-  rhccq_fit::Problem c;
-  std::vector<int32_t> init_idx;
-};
-
-MbkDraws mbk_draws(int64_t n, int64_t k) {
-  MtTable& mt = MtTable::get();
-  MbkDraws d;
-  d.c = rhccq_fit::problem(n, k);
-  const int64_t init_size = d.c.init_size;
-  int64_t pos = 0;
-  pos += mt.randint(pos, n, init_size, nullptr);                         // validation_indices: stream position only
-  d.init_idx.resize((size_t)init_size);
-  if (init_size < n) pos += mt.randint(pos, n, init_size, d.init_idx.data());
-  else for (int64_t i = 0; i < n; ++i) d.init_idx[(size_t)i] = (int32_t)i;
-  const int32_t first = first_centre_index(init_size, mt.dbl(pos));
-  rhccq_fit::chain_at(d.c, pos + 2, first);
-  return d;
-}
-
+// (ops.py::minibatch_kmeans; reference call site clustering.py:207-218).  What the host decides on the way is mbk_fit_host.h, its draws mt_replay.h -
 // A chain run ahead for one fit (RHCCQ_OPT_FRAME_CHAINS): its centres once `done` has fired, or, with RHCCQ_OPT_CHAIN_RELEASE, once
 // *flag shows `tag` (chain_release_host.h); tag 0: the kernel publishes nothing, the event alone
 struct PreChain {
@@ -390,7 +251,7 @@ double* mbk_chains(rhccq_ctx* c, Arena& A, const uint32_t* keys, const std::vect
   const int32_t N = (int32_t)probs.size();
   const uint32_t* words;
   int64_t n_words;
-  MtTable::get().device(c->device, tot.words, &words, &n_words);
+  EF_RC(c, rhccq_mt_words(c, tot.words, &words, &n_words));
   mark(&ChainClocks::words, false);
   double* d_rand = (double*)A.alloc((size_t)tot.utot * 8);
   std::vector<int32_t> init_idx;
@@ -479,7 +340,7 @@ void mbk_fit(Lane& L, const uint32_t* keys, std::vector<rhccq_mbk_problem>& prob
     if (ch.any()) {
       const uint32_t* words;
       int64_t n_words;
-      MtTable::get().device(L.device, ch.need, &words, &n_words);
+      EF_RC(c, rhccq_mt_words(c, ch.need, &words, &n_words));
       if (step == 0 || !plan.tiled)                                      // (the first call writes the problem tables; the grid E-step: nobody is overlapped)
         EF_RC(c, rhccq_mbk_steps(c, keys, probs.data(), N, step, ch.ns, words, n_words, centres, weights, state, work, wbytes,
                                  (plan.tiled ? RHCCQ_ESTEP_TILES : RHCCQ_ESTEP_GRID) | (ch.no_reassign ? RHCCQ_STEPS_NO_REASSIGN : 0), split));
@@ -823,7 +684,7 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs, bool batch_mbk = false) {
       }
     for (int nd : larges[s]) frontier.push_back(nd);
   }
-  const double u0 = MtTable::get().dbl(0);              // RandomState(42).random_sample()[0]: the first centre's draw of every KMeans fit
+  const double u0 = rhccq_mt::Words::get().dbl(0);              // RandomState(42).random_sample()[0]: the first centre's draw of every KMeans fit
   while (!frontier.empty()) {
     std::vector<std::pair<int, int64_t>> run;
     for (int nd : frontier) {
@@ -857,7 +718,7 @@ void cluster_jobs(Lane& L, std::vector<Job>& jobs, bool batch_mbk = false) {
     }
     const uint32_t* words;
     int64_t n_words;
-    MtTable::get().device(L.device, 2 + 2 * need, &words, &n_words);
+    EF_RC(c, rhccq_mt_words(c, 2 + 2 * need, &words, &n_words));
     double* d_rand = L.dalloc<double>((size_t)need);
     EF_RC(c, rhccq_mt_uniforms(c, words, 2, need, d_rand));             // the doubles behind u0
     uint32_t* d_keys = L.upload(cat.data(), cat.size());

@@ -1747,7 +1747,7 @@ __device__ __forceinline__ void walk_members(const int* __restrict__ lab, const 
   }
 }
 
-// ---- numpy's legacy RandomState, replayed from its raw MT19937 words (resident on the device, mt.py) ----------
+// ---- numpy's legacy RandomState, replayed from its raw MT19937 words (resident on the device, mt_replay.h) ----------
 // RandomState.randint(0, rng + 1, count) at word `cursor` (_bounded_integers.pyx, legacy use_masked path): candidates
 // `word & mask` (mask = smallest 2^b - 1 >= rng), one word each, kept when <= rng.  All threads of the workgroup:
 // thread t looks at kDrawWords consecutive words per round, a block scan orders the survivors.  out[0 .. count) (LDS)
@@ -2600,7 +2600,7 @@ __global__ __launch_bounds__(256) void sample_unpack_kernel(const unsigned long 
   if (t < total) perm[base + t] = (int32_t)(uint32_t)sorted[t];
 }
 
-// ---- uniform(size=count) of numpy's legacy RandomState from the resident raw MT19937 words (mt.py) ---------
+// ---- uniform(size=count) of numpy's legacy RandomState from the resident raw MT19937 words (mt_replay.h) ---------
 __global__ __launch_bounds__(256) void mt_uniforms_kernel(const uint32_t* __restrict__ words, long long pos, long long count,
                                                           double* __restrict__ out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -2832,38 +2832,6 @@ int rhccq_mbk_order(rhccq_ctx* ctx, const uint32_t* keys, const rhccq_mbk_proble
     RHCCQ_LAUNCH_CHECK(ctx);
   }
   return 0;
-}
-
-// RandomState.randint(0, n, size) of numpy's legacy generator replayed ON THE HOST from raw MT19937 words (host memory): masked
-// rejection, one word per attempt (_bounded_integers.pyx, legacy path for ranges below 2^32).  out (int32[size], may be NULL when
-// only the stream position matters: sklearn's validation draw) receives the values; returns the words consumed, -1 when the
-// table ends first, -2 for a bad argument.  No HIP call inside: the k-means++ set-up of a frame's problems runs on several host
-// threads and this loop, unlike its numpy twin (mt.py), does not hold the interpreter lock.
-int64_t rhccq_mt_randint_host(const uint32_t* words, int64_t n_words, int64_t pos, int64_t n, int64_t size, int32_t* out) {
-  if (!words || pos < 0 || n <= 0 || n > 0x7fffffffll || size < 0 || n_words < 0) return -2;
-  if (size == 0) return 0;
-  const uint32_t rng = (uint32_t)(n - 1);
-  if (rng == 0u) {                                         // numpy draws nothing for a one-value range
-    if (out) memset(out, 0, sizeof(int32_t) * (size_t)size);
-    return 0;
-  }
-  uint32_t mask = rng;
-  mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-  int64_t got = 0;
-  if (out) {
-    for (int64_t i = pos; i < n_words; ++i) {
-      const uint32_t v = words[i] & mask;
-      out[got] = (int32_t)v;                               // (kept only when accepted: `got` moves on)
-      got += v <= rng;
-      if (got == size) return i + 1 - pos;
-    }
-  } else {
-    for (int64_t i = pos; i < n_words; ++i) {
-      got += (words[i] & mask) <= rng;
-      if (got == size) return i + 1 - pos;
-    }
-  }
-  return -1;
 }
 
 int rhccq_mt_uniforms(rhccq_ctx* ctx, const uint32_t* words, int64_t pos, int64_t count, double* out) {

@@ -4,7 +4,7 @@
 // the decisions it gets alone.
 //
 //   slots     the names of the double[16] state of a problem (include/rhccq.h, rhccq_mbk_steps) and a view that reads them
-//   Problem   what follows from (n, k) alone, and from where the MT19937 replay left the stream (MtTable does the replay)
+//   Problem   what follows from (n, k) alone, and from where the MT19937 replay left the stream (mt_replay.h does the replay)
 //   Totals    the problems of a batch laid out into rhccq_mbk_problem, with the sums the set-up allocates by
 //   Plan      between two launches of steps: who runs, on which schedule, for how many steps, with how many MT19937 words
 #pragma once

@@ -22,13 +22,11 @@ import torch
 
 from . import _lib
 from . import _palette_args as A
-from ._lib import MbkProblem, RhccqError
-from .mt import MtWords
+from ._lib import MbkDraw, MbkProblem, RhccqError
 
 INT_MAX = 2 ** 31 - 1
 BITMAP_WORDS = 524288
 MINIBATCH_THRESHOLD = 10000          # clustering.py:205
-SEED = 42                            # random_state=42 at every sklearn call site of the reference
 
 
 _DRAW_POOL = None
@@ -54,6 +52,7 @@ def _draw_pool():
 
 
 _LANE_POOLS = {}
+_pool_lock = threading.Lock()
 
 
 def lane_pool(kind):
@@ -62,7 +61,7 @@ def lane_pool(kind):
     tens of microseconds, starting a thread per problem and frame cost 0.3-0.8 ms each in front of the k-means++ chains."""
     pool = _LANE_POOLS.get(kind)
     if pool is None:
-        with _words_lock:
+        with _pool_lock:
             pool = _LANE_POOLS.get(kind)
             if pool is None:
                 from concurrent.futures import ThreadPoolExecutor
@@ -277,53 +276,6 @@ def eps_threshold(eps):
     return thr.value, bnd.value, r2.value
 
 
-class _MtStream:
-    """numpy legacy MT19937 RandomState(42): u0 = the draw consumed by choice() for the first centre,
-    then the uniform(size=T) draws of k-means++ are consecutive doubles.  Every KMeans fit of the
-    reference restarts from seed 42, so one cached prefix serves all split problems."""
-
-    def __init__(self):
-        self.host = np.zeros(0)
-        self.dev = None
-
-    def ensure(self, n, device):
-        if len(self.host) < n + 1:
-            m = max(n + 1, 2 * len(self.host), 1 << 16)
-            self.host = np.random.RandomState(SEED).random_sample(m)
-            self.dev = None
-        if self.dev is None or self.dev.device != device:
-            self.dev = torch.from_numpy(self.host[1:].copy()).to(device)
-        return self.dev
-
-    def u0(self):
-        if len(self.host) == 0:
-            self.host = np.random.RandomState(SEED).random_sample(1 << 16)
-            self.dev = None
-        return self.host[0]
-
-
-_first_cache = {}
-_first_lock = threading.Lock()
-_words_lock = threading.Lock()
-
-
-def first_centre_index(n, u0):
-    """RandomState.choice(n, p=ones/n): searchsorted(cumsum(p)/cumsum(p)[-1], u0, 'right').  Called from the lanes of
-    a StreamEncoder and from the draw pool: the value is computed locally, the cache only ever hands out finished ones."""
-    key = (n, u0)
-    v = _first_cache.get(key)
-    if v is None:
-        p = np.full(n, 1.0) / np.float64(n)
-        cdf = np.cumsum(p)
-        cdf /= cdf[-1]
-        v = min(int(np.searchsorted(cdf, u0, side="right")), n - 1)
-        with _first_lock:
-            if len(_first_cache) > 4096:                     # a stream of frames brings ever new (n, u0): keep it bounded
-                _first_cache.clear()
-            _first_cache[key] = v
-    return v
-
-
 class _StreamBoundLib:
     """The C ABI as seen by one Rhccq: before every entry point that takes the context, the context is re-bound to
     torch's CURRENT stream when that changed (rhccq_ctx_set_stream) -- every buffer of this module is allocated, zeroed
@@ -366,9 +318,6 @@ class Rhccq:
         if rc:
             raise RhccqError(f"rhccq_ctx_create failed ({rc})")
         self.ctx = h
-        self.mt = _MtStream()
-        self.mtw = MtWords()
-        self._mtw_dev = None
 
     OPT_INIT_LDS_BLOCKS, OPT_INIT_MAX_ITEMS, OPT_INIT_KERNEL, OPT_INIT_SHARDS, OPT_INIT_CANDS_PER_WAVE, OPT_REASSIGN_LDS = 1, 2, 3, 4, 5, 6
     OPT_REASSIGN_ORDER = 7           # 1 (default): numpy's scalar-quicksort tie order of the capped reassignment; 0: stable (rounds 1-3)
@@ -401,35 +350,12 @@ class Rhccq:
         for _, ln in self.__dict__.get("_lanes", {}).values():
             ln.set_option(option, value)
 
-    def _mt_words_dev(self, n):
-        """at least the first n raw MT19937 words on the device (uploaded once, regrown geometrically; the lanes of a
-        pipelined call share their parent's table)"""
-        owner = getattr(self, "_parent", None) or self
-        t = owner._mtw_dev
-        if t is None or t.numel() < n:
-            with _words_lock:
-                t = owner._mtw_dev
-                if t is None or t.numel() < n:
-                    have = 0 if t is None else t.numel()
-                    w = owner.mtw.ensure(max(n, 2 * have, 1 << 22))
-                    t = torch.from_numpy(w.view(np.int32)).to(self.device)      # blocking copy: complete on return
-                    torch.cuda.current_stream(self.device).synchronize()
-                    # a superseded table may still be read by kernels another lane has queued on ITS stream: keep it alive until
-                    # every stream of the family has passed an event recorded now, then hand its block back to the allocator
-                    retired = owner.__dict__.setdefault("_mtw_retired", [])
-                    retired[:] = [(tab, evs) for tab, evs in retired if not all(e.query() for e in evs)]
-                    if owner._mtw_dev is not None:
-                        streams = [torch.cuda.current_stream(self.device), torch.cuda.default_stream(self.device)]
-                        streams += [ls for ls, _ in owner.__dict__.get("_lanes", {}).values()]
-                        evs = []
-                        for ls in streams:
-                            e = torch.cuda.Event()
-                            e.record(ls)
-                            evs.append(e)
-                        retired.append((owner._mtw_dev, evs))
-                    owner._mtw_dev = t
-        t.record_stream(torch.cuda.current_stream(self.device))                 # (allocated on whichever lane grew it, used on this one)
-        return t
+    def _mt_words(self, n):
+        """(device address, count >= n) of the first raw MT19937 words of RandomState(42): rhccq_mt_words, the process's one table of
+        this device (csrc/mt_replay.h), complete on return; the address stays readable for the life of the process"""
+        words, count = C.c_void_p(), C.c_int64()
+        self._check(self.lib.rhccq_mt_words(self.ctx, int(n), C.byref(words), C.byref(count)), "mt_words")
+        return words, count.value
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -691,13 +617,15 @@ class Rhccq:
         koff = np.concatenate([[0], np.cumsum(k_list)]).astype(np.int64)
         desc = np.zeros((n_prob, 6), np.int32)
         need = 1
-        u0 = self.mt.u0()
+        u0 = self.lib.rhccq_mt_double_host(0)               # RandomState(42).random_sample(): the first centre's draw of every KMeans fit
         for i, (n, k) in enumerate(zip(sizes, k_list)):
             assert 1 <= k <= n
             T = 2 + int(math.log(k))
-            desc[i] = (offs[i], n, k, 0, first_centre_index(n, u0), T)
+            desc[i] = (offs[i], n, k, 0, self.lib.rhccq_first_centre_index(n, u0), T)
             need = max(need, (k - 1) * T)
-        rand = self.mt.ensure(need, self.device)
+        words, _ = self._mt_words(2 + 2 * need)
+        rand = self.empty((need,), torch.float64)
+        self._check(self.lib.rhccq_mt_uniforms(self.ctx, words, 2, need, self._p(rand)), "mt_uniforms")     # the doubles behind u0
         keys = self.dev(np.concatenate(key_list).astype(np.uint32).view(np.int32))
         d_desc, d_koff = self.dev(desc), self.dev(koff[:-1].copy())
         work = self.empty((8 * int(koff[-1]) + 8,), torch.float64)
@@ -728,13 +656,12 @@ class Rhccq:
     MBK_FIRST_POLL = 16
 
     def _lane(self, i):
-        """a sibling context on its own HIP stream (host thread `i` of a pipelined call); shares the MT19937 word table"""
+        """a sibling context on its own HIP stream (host thread `i` of a pipelined call)"""
         lanes = self.__dict__.setdefault("_lanes", {})
         if i not in lanes:
             stream = torch.cuda.Stream(self.device)
             with torch.cuda.stream(stream):
                 rh = Rhccq(self.device.index)
-            rh.mtw, rh._parent = self.mtw, getattr(self, "_parent", None) or self      # (the root context owns the MT19937 word table)
             for opt, val in self.__dict__.get("_options", {}).items():
                 rh.set_option(opt, val)
             lanes[i] = (stream, rh)
@@ -816,7 +743,7 @@ class Rhccq:
         since = int(st[0, 12 if par else 3])
         split = estep_split or next((sp for sp in (1, 2, 4, 8) if ((k + 511) // 512) * 2 * sp >= 1536), 8)
         # MT19937 words for a BOUNDED horizon -- the chunks in flight plus the one being queued, counted from the last cursor the host
-        # has seen -- regrown between chunks (a superseded table stays alive for the kernels already queued on it, _mt_words_dev):
+        # has seen -- regrown between chunks (a superseded table stays allocated for the kernels already queued on it, rhccq_mt_words):
         # a draw of 1000 rows consumes < 2000 words on average even at the worst acceptance (1/2), a reassigning step (at most one in
         # 10 k / 1000 + the first steps) another ~1400 for its shuffle; twice that plus the kernels' own end-of-table margins.  (Sizing
         # for all 100 n / 1000 possible steps asked for ~2.5 GB per 1.5 M-colour problem that then stopped after tens of steps.)
@@ -831,8 +758,8 @@ class Rhccq:
         while True:
             if step < limit:
                 ns = int(min(chunk, limit - step))
-                words = self._mt_words_dev(cur_known + (step - steps_known + ns + 4) * 4200 + 8 * words_per_step)
-                self._check(self.lib.rhccq_mbk_steps_overlapped(self.ctx, self._p(keys), probs, 1, step, ns, self._p(words), words.numel(),
+                words, n_words = self._mt_words(cur_known + (step - steps_known + ns + 4) * 4200 + 8 * words_per_step)
+                self._check(self.lib.rhccq_mbk_steps_overlapped(self.ctx, self._p(keys), probs, 1, step, ns, words, n_words,
                                                                 self._p(centres), self._p(weights), self._p(state), self._p(work), wbytes,
                                                                 split, since, C.byref(carry)), "mbk_steps_overlapped")
                 for _ in range(ns):                          # the schedule's own arithmetic (sklearn _random_reassign)
@@ -900,62 +827,33 @@ class Rhccq:
         keys = parts[0] if n_prob == 1 else torch.cat(parts)
         init_list = []
         ioff = roff = 0
-        # numpy's RandomState(42) stream of every problem, replayed from the cached raw MT19937 words (mt.py): the
-        # sample indices on the host (vectorised rejection sampling), the k-means++ uniforms on the device
-        mtw = self.mtw
-        upos = []
-
-        def randint(pos, n, size, want):
-            # (the native loop of rhccq_mt_randint_host: the problems' draws run on several threads, numpy's passes queue on the GIL)
-            win = int(size / (n / (1 << int(n - 1).bit_length())) * 1.05) + 256 if n > 1 else 0
-            out = np.empty(size, np.int32) if want else None
-            while True:
-                w = mtw.ensure(pos + win)
-                used = int(self.lib.rhccq_mt_randint_host(w.ctypes.data, len(w), pos, n, size, out.ctypes.data if want else None))
-                if used >= 0:
-                    return out, used
-                if used != -1:
-                    raise RhccqError("rhccq_mt_randint_host: bad argument")
-                win = 2 * win + 1024
+        # numpy's RandomState(42) stream of every problem (rhccq_mbk_draws, csrc/mt_replay.h): the sample indices on the host,
+        # the k-means++ uniforms on the device
+        lib = self.lib
 
         def draw(args):
-            n, k = args
-            bs = min(1000, n)
-            init_size = 3 * bs
-            if init_size < k:
-                init_size = 3 * k
-            init_size = min(init_size, n)
-            pos = 0
-            _, used = randint(pos, n, init_size, False)          # validation_indices: stream position only
-            pos += used
-            if init_size < n:
-                init_idx, used = randint(pos, n, init_size, True)
-                pos += used
-            else:
-                init_idx = np.arange(n, dtype=np.int32)
-            first = first_centre_index(init_size, mtw.double(pos))
-            return init_idx, first, pos + 2
+            n, k = int(args[0]), int(args[1])
+            d = MbkDraw()
+            if lib.rhccq_mbk_draws(n, k, C.byref(d), None, 0):
+                raise RhccqError(f"rhccq_mbk_draws({n}, {k}): bad argument")
+            init_idx = np.empty(d.init_size, np.int32)
+            lib.rhccq_mbk_draws(n, k, C.byref(d), init_idx.ctypes.data, init_idx.size)
+            return d, init_idx
 
         todo = list(zip(sizes, k_list))
-        # the numpy passes of a replay release the GIL: the problems' draws run side by side (the GPU waits for them)
+        # the calls release the GIL: the problems' draws run side by side (the GPU waits for them)
         drawn = list(_draw_pool().map(draw, todo)) if n_prob > 1 else [draw(todo[0])]
-        cursor0 = []
-        for i, ((n, k), (init_idx, first, pos)) in enumerate(zip(todo, drawn)):
-            init_size = len(init_idx)
-            T = 2 + int(math.log(k))
-            nu = max((k - 1) * T, 1)
-            cursor0.append(pos + 2 * (k - 1) * T)             # stream position behind the k-means++ uniforms
+        for i, ((n, k), (d, init_idx)) in enumerate(zip(todo, drawn)):
             p = probs[i]
             p.off, p.n, p.k, p.koff = int(offs[i]), n, k, int(koff[i])
-            p.init_off, p.init_n, p.rand_off, p.first, p.T = ioff, init_size, roff, first, T
+            p.init_off, p.init_n, p.rand_off, p.first, p.T = ioff, d.init_size, roff, d.first, d.T
             init_list.append(init_idx)
-            upos.append((pos, nu, roff))
-            ioff += init_size
-            roff += nu
-        words = self._mt_words_dev(max(pos + 2 * nu for pos, nu, _ in upos))
+            ioff += d.init_size
+            roff += d.n_uniforms
+        words, _ = self._mt_words(max(d.pos + 2 * d.n_uniforms for d, _ in drawn))
         d_rand = self.empty((roff,), torch.float64)
-        for pos, nu, ro in upos:
-            self._check(self.lib.rhccq_mt_uniforms(self.ctx, self._p(words), pos, nu, C.c_void_p(d_rand.data_ptr() + 8 * ro)), "mt_uniforms")
+        for p, (d, _) in zip(probs, drawn):
+            self._check(self.lib.rhccq_mt_uniforms(self.ctx, words, d.pos, d.n_uniforms, C.c_void_p(d_rand.data_ptr() + 8 * p.rand_off)), "mt_uniforms")
         d_init = self.dev(np.concatenate(init_list))           # sklearn's draw order
         # internal pruning index: the sample positions in Morton order of their colours, on the device: 64 consecutive
         # entries form a compact box, which is what the exact block pruning of mbk_init_kernel relies on
@@ -979,14 +877,14 @@ class Rhccq:
         weights = self.zeros((K,), torch.float64)
         st0 = np.zeros((n_prob, 16))
         st0[:, 8] = k_list                                   # every centre starts with zero weight
-        st0[:, 9] = cursor0                                  # MT19937 words consumed so far
+        st0[:, 9] = [d.cursor0 for d, _ in drawn]            # MT19937 words consumed so far: the stream behind the k-means++ uniforms
         state = self.dev(st0)
-        cur_max = max(cursor0)
+        cur_max = int(st0[:, 9].max())
         WORDS_PER_STEP = 16384                               # kWordsMargin of mbk_update_kernel
         wbytes = int(self.lib.rhccq_mbk_work_bytes(probs, n_prob))
         work = self.empty((max(wbytes, 8),), torch.uint8)
         k_arr = np.asarray(k_list, np.int64)
-        limit = np.array([(100 * n) // min(1000, n) for n in sizes], np.int64)
+        limit = np.array([d.limit for d, _ in drawn], np.int64)
         running = np.ones(n_prob, bool)
         step = 0                                             # launch index = step index of every problem still running
         carry = C.c_int32(0)
@@ -1021,7 +919,7 @@ class Rhccq:
             # few workgroups left (a straggler problem): several threads share a batch point in the tiled E-step
             wgs = int(((k_arr[running] + 511) // 512).sum()) * 2
             split = estep_split or next((sp for sp in (1, 2, 4, 8) if wgs * sp >= 1536), 8)
-            words = self._mt_words_dev(cur_max + (ns + 3) * WORDS_PER_STEP)     # a step consumes at most WORDS_PER_STEP
+            words, n_words = self._mt_words(cur_max + (ns + 3) * WORDS_PER_STEP)     # a step consumes at most WORDS_PER_STEP
             if step > 0:
                 # no running problem reassigns during these steps (no centre without weight, fewer than 10 k samples since the last
                 # reassignment throughout): the second launch of a reassigning step is left out (RHCCQ_STEPS_NO_REASSIGN)
@@ -1029,7 +927,7 @@ class Rhccq:
                 quiet = (st[:, 13 if par else 8] == 0) & (st[:, 12 if par else 3] + ns * bs_arr < 10 * k_arr)
                 if quiet[running].all():
                     mode |= 0x100
-            self._check(self.lib.rhccq_mbk_steps(self.ctx, self._p(keys), probs, n_prob, step, ns, self._p(words), words.numel(),
+            self._check(self.lib.rhccq_mbk_steps(self.ctx, self._p(keys), probs, n_prob, step, ns, words, n_words,
                                                  self._p(centres), self._p(weights), self._p(state), self._p(work), wbytes, mode, split),
                         "mbk_steps")
             step += ns

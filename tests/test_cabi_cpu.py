@@ -190,45 +190,67 @@ def test_decoder_kat_files():
         assert hashlib.sha256(np.array(idx, np.dtype(rec["d"])).tobytes()).hexdigest() == rec["indices_sha256"], f
 
 
+def _mt_words_host(lib, count):
+    w = np.empty(count, np.uint32)
+    assert lib.rhccq_mt_words_host(0, count, w.ctypes.data) == 0
+    return w
+
+
+def _mt_randint(lib, pos, n, size):
+    """RandomState.randint(0, n, size) at word `pos` from the library's own words: (values, words consumed)"""
+    out = np.empty(size, np.int32)
+    win = 2 * size + 1024
+    while True:
+        w = _mt_words_host(lib, pos + win)
+        used = lib.rhccq_mt_randint_host(w.ctypes.data, len(w), pos, n, size, out.ctypes.data)
+        if used >= 0:
+            return out, used
+        assert used == -1
+        win *= 2
+
+
 def test_mt_replay_equals_numpy_randomstate():
-    """mt.MtWords replays RandomState(42).randint / random_sample / uniform from the raw MT19937 words: the draws of
-    MiniBatchKMeans' init (validation indices, init sample, first centre, k-means++ uniforms) for several sizes,
-    including power-of-two boundaries of the rejection mask and the one-value range that consumes nothing."""
-    from roibasedimagecompression_amd.mt import MtWords
-    m = MtWords()
+    """The library's replay (csrc/mt_replay.h: its own MT19937 words, rhccq_mt_randint_host, rhccq_mt_double_host) against
+    RandomState(42).randint / random_sample / uniform: the draws of MiniBatchKMeans' init (validation indices, init sample, first
+    centre, k-means++ uniforms) for several sizes, including power-of-two boundaries of the rejection mask and the one-value
+    range that consumes nothing."""
+    from roibasedimagecompression_amd import _lib
+    lib = _lib.load()
     for n, size, count in ((1500000, 90000, 1000), (10000, 3000, 50), (65536, 70000, 10), (65537, 100, 5), (3, 10, 4), (1, 5, 3),
                            (2 ** 31 - 5, 1000, 7), (30000, 30000, 12)):
         rs = np.random.RandomState(42)
         a, b = rs.randint(0, n, size), rs.randint(0, n, size)
         u0, u = rs.random_sample(), rs.uniform(size=count)
         pos = 0
-        v1, used = m.randint(pos, n, size)
+        v1, used = _mt_randint(lib, pos, n, size)
         pos += used
-        v2, used = m.randint(pos, n, size)
+        v2, used = _mt_randint(lib, pos, n, size)
         pos += used
         assert np.array_equal(a, v1) and np.array_equal(b, v2), n
-        assert m.double(pos) == u0
-        assert np.array_equal(m.doubles(pos + 2, count), u)
+        assert lib.rhccq_mt_double_host(pos) == u0
+        assert np.array_equal([lib.rhccq_mt_double_host(pos + 2 + 2 * i) for i in range(count)], u)
+    assert lib.rhccq_mt_double_host(-1) == -1.0
+    assert lib.rhccq_mt_words_host(-1, 1, v1.ctypes.data) == -1 and lib.rhccq_mt_words_host(0, 1, None) == -1
 
 
 def test_native_randint_replay_equals_numpy_randomstate():
-    """rhccq_mt_randint_host (the host loop the k-means++ set-up calls from several threads) against RandomState(42) itself and
-    against the numpy replay of mt.py: values, words consumed, the position-only form, a table that ends one word early."""
+    """rhccq_mt_randint_host (the host loop of the k-means++ set-up) against RandomState(42) itself, over the generator's raw words as
+    numpy gives them: values, words consumed, the position-only form, a table that ends one word early."""
     from roibasedimagecompression_amd import _lib
-    from roibasedimagecompression_amd.mt import MtWords
     lib = _lib.load()
-    m = MtWords()
+    # (full-range uint32 draws are the raw 32-bit outputs, one word each)
+    w = np.random.RandomState(42).randint(0, 1 << 32, size=1 << 19, dtype=np.uint32)
+    assert np.array_equal(w, _mt_words_host(lib, len(w)))
     for n, size in ((1500000, 90000), (10000, 3000), (65536, 70000), (65537, 100), (3, 10), (1, 5), (2 ** 31 - 5, 1000), (30000, 30000)):
         rs = np.random.RandomState(42)
         a, b = rs.randint(0, n, size), rs.randint(0, n, size)
-        _, u1 = m.randint(0, n, size)
-        _, u2 = m.randint(u1, n, size)
-        w = m.ensure(u1 + u2 + 8)
         o1, o2 = np.empty(size, np.int32), np.empty(size, np.int32)
-        assert lib.rhccq_mt_randint_host(w.ctypes.data, len(w), 0, n, size, o1.ctypes.data) == u1
-        assert lib.rhccq_mt_randint_host(w.ctypes.data, len(w), 0, n, size, None) == u1
-        assert lib.rhccq_mt_randint_host(w.ctypes.data, len(w), u1, n, size, o2.ctypes.data) == u2
-        assert np.array_equal(a, o1) and np.array_equal(b, o2), n
+        u1 = lib.rhccq_mt_randint_host(w.ctypes.data, len(w), 0, n, size, o1.ctypes.data)
+        assert u1 >= 0 and lib.rhccq_mt_randint_host(w.ctypes.data, len(w), 0, n, size, None) == u1
+        u2 = lib.rhccq_mt_randint_host(w.ctypes.data, len(w), u1, n, size, o2.ctypes.data)
+        assert u2 >= 0 and np.array_equal(a, o1) and np.array_equal(b, o2), n
+        p = u1 + u2                                        # the words consumed are numpy's own: its next double comes from there
+        assert rs.random_sample() == (float(int(w[p]) >> 5) * 67108864.0 + float(int(w[p + 1]) >> 6)) / 9007199254740992.0
         if u1:
             assert lib.rhccq_mt_randint_host(w.ctypes.data, u1 - 1, 0, n, size, None) == -1
     assert lib.rhccq_mt_randint_host(None, 10, 0, 5, 5, None) == -2

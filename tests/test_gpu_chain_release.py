@@ -6,7 +6,6 @@ kernel that publishes nothing falls back to the launch's event; and the hand-off
 The frames are uniform-random RGB, W = 256, quality 50, in horizontal bands: nearly every pixel is a colour of its own, so a segment of P
 pixels is a MiniBatchKMeans problem (>= 10 000 colours) of k ~ P / 20, and its chain's length goes with k."""
 import ctypes as C
-import math
 import time
 
 import numpy as np
@@ -135,62 +134,40 @@ def test_option_validation(rh):
 
 # ---- the hand-off -----------------------------------------------------------------------------------------------------------------
 def _chain_inputs(rh, palettes, ks):
-    """what rhccq_mbk_init takes for these problems (ops.minibatch_kmeans's set-up: RandomState(42) replayed per problem)"""
+    """what rhccq_mbk_init takes for these problems (ops.minibatch_kmeans's set-up: rhccq_mbk_draws per problem, the uniforms from the
+    device's word table)"""
     import torch
-    from roibasedimagecompression_amd._lib import MbkProblem
-    from roibasedimagecompression_amd.ops import first_centre_index
+    from roibasedimagecompression_amd._lib import MbkDraw, MbkProblem
     n_prob = len(palettes)
     probs = (MbkProblem * n_prob)()
-    mtw = rh.mtw
-
-    def randint(pos, n, size, want):
-        win = int(size / (n / (1 << int(n - 1).bit_length())) * 1.05) + 256
-        out = np.empty(size, np.int32) if want else None
-        while True:
-            w = mtw.ensure(pos + win)
-            used = int(rh.lib.rhccq_mt_randint_host(w.ctypes.data, len(w), pos, n, size, out.ctypes.data if want else None))
-            if used >= 0:
-                return out, used
-            assert used == -1
-            win = 2 * win + 1024
-
     keys = rh.dev(np.concatenate(palettes).astype(np.uint32).view(np.int32))
-    init_list, upos = [], []
+    init_list, draws = [], []
     off = koff = ioff = roff = 0
     for i, (pal, k) in enumerate(zip(palettes, ks)):
-        n = len(pal)
-        init_size = 3 * min(1000, n)
-        if init_size < k:
-            init_size = 3 * k
-        init_size = min(init_size, n)
-        assert init_size < n
-        _, pos = randint(0, n, init_size, False)
-        init_idx, used = randint(pos, n, init_size, True)
-        pos += used
-        first = first_centre_index(init_size, mtw.double(pos))
-        pos += 2
-        T = 2 + int(math.log(k))
-        nu = max((k - 1) * T, 1)
+        n, d = len(pal), MbkDraw()
+        assert rh._raw.rhccq_mbk_draws(n, k, C.byref(d), None, 0) == 0 and d.init_size < n
+        init_idx = np.empty(d.init_size, np.int32)
+        assert rh._raw.rhccq_mbk_draws(n, k, C.byref(d), init_idx.ctypes.data, d.init_size) == 0
         p = probs[i]
         p.off, p.n, p.k, p.koff = off, n, k, koff
-        p.init_off, p.init_n, p.rand_off, p.first, p.T = ioff, init_size, roff, first, T
+        p.init_off, p.init_n, p.rand_off, p.first, p.T = ioff, d.init_size, roff, d.first, d.T
         init_list.append(init_idx)
-        upos.append((pos, nu, roff))
+        draws.append(d)
         off += n
         koff += k
-        ioff += init_size
-        roff += nu
-    words = rh._mt_words_dev(max(pos + 2 * nu for pos, nu, _ in upos))
+        ioff += d.init_size
+        roff += d.n_uniforms
+    words, _ = rh._mt_words(max(d.pos + 2 * d.n_uniforms for d in draws))
     d_rand = rh.empty((roff,), torch.float64)
-    for pos, nu, ro in upos:
-        rh._check(rh.lib.rhccq_mt_uniforms(rh.ctx, rh._p(words), pos, nu, C.c_void_p(d_rand.data_ptr() + 8 * ro)), "mt_uniforms")
+    for p, d in zip(probs, draws):
+        rh._check(rh.lib.rhccq_mt_uniforms(rh.ctx, words, d.pos, d.n_uniforms, C.c_void_p(d_rand.data_ptr() + 8 * p.rand_off)), "mt_uniforms")
     d_init = rh.dev(np.concatenate(init_list))
     obytes = int(rh.lib.rhccq_mbk_order_bytes(ioff))
     otmp = rh.empty((obytes,), torch.uint8)
     d_perm = rh.empty((ioff,), torch.int32)
     rh._check(rh.lib.rhccq_mbk_order(rh.ctx, rh._p(keys), probs, n_prob, rh._p(d_init), rh._p(d_perm), rh._p(otmp), obytes), "mbk_order")
     torch.cuda.synchronize()
-    return dict(keys=keys, probs=probs, n_prob=n_prob, d_init=d_init, d_perm=d_perm, d_rand=d_rand, K=koff, keep=(otmp, words))
+    return dict(keys=keys, probs=probs, n_prob=n_prob, d_init=d_init, d_perm=d_perm, d_rand=d_rand, K=koff, keep=otmp)
 
 
 # the chain kernel's two publishing variants: init samples in global memory (a problem above 5 760 samples; the release record lies in the

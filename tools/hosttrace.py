@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import threading, time
 import torch
 import bench
-from roibasedimagecompression_amd import ops, frame, palette, mt
+from roibasedimagecompression_amd import ops, frame, palette
 from roibasedimagecompression_amd.ops import Rhccq
 from roibasedimagecompression_amd.frame import FrameEncoder
 
@@ -47,9 +47,7 @@ for ln in list(getattr(rh, "_lanes", {}).values()):
     for l2 in list(getattr(ln[1], "_lanes", {}).values()):
         l2[1].lib = L(l2[1].lib)
 Rhccq.minibatch_kmeans = wrap(Rhccq.minibatch_kmeans, "PY minibatch_kmeans")
-Rhccq._mt_words_dev = wrap(Rhccq._mt_words_dev, "PY _mt_words_dev")
 Rhccq.dev = wrap(Rhccq.dev, "PY dev(H2D)")
-mt.MtWords.randint = wrap(mt.MtWords.randint, "PY mt.randint")
 frame.cluster_palettes = wrap(frame.cluster_palettes, "PY cluster_palettes")
 FrameEncoder.level1_jobs = wrap(FrameEncoder.level1_jobs, "PY level1_jobs")
 FrameEncoder.prepare = wrap(FrameEncoder.prepare, "PY prepare")
