@@ -350,7 +350,6 @@ __global__ __launch_bounds__(256) void compose_kernel(const uint8_t* __restrict_
 }
 
 // ---- layouts and launches ------------------------------------------------------------------------------------------------------------
-static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 // rhccq_gif_unlzw's workspace: the head, the frames' segment counts, the work list's bases, the segment table
 struct LzwLayout { int64_t o_nseg, o_base, o_rows, total; };
 static LzwLayout lzw_layout(int64_t n_frames, int64_t seg_rows) {

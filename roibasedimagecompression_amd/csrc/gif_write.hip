@@ -273,7 +273,6 @@ __global__ __launch_bounds__(256) void gif_frame_kernel(const uint8_t* __restric
 struct Sizes {
   int64_t P, nseg, slot, stream, o_ftab, o_flen, o_foff, o_bits, o_off, o_words, work, bound;
 };
-static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 static int gif_shape(rhccq_ctx* ctx, const char* fn, int n, int H, int W, int flags, Sizes& s) {
   static thread_local std::string msg;

@@ -380,7 +380,6 @@ __global__ __launch_bounds__(256) void finish_kernel(const uint8_t* __restrict__
 struct ReadLayout {
   int64_t o_head, o_crc, o_part, o_stream, o_scan, o_raw, o_unf, o_inf, total;
 };
-static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static int read_layout(const rhccq_png_info& f, ReadLayout& l) {
   int64_t inf = 0;
   if (const int rc = rhccq_zlib_inflate_sizes(f.idat_bytes, f.scan_bytes, &inf)) return rc;

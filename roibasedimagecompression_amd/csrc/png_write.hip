@@ -262,7 +262,6 @@ static int64_t png_limit(int flags) { return flags & RHCCQ_PNG_EXACT ? kScanMax 
 struct Sizes {
   int64_t scan, enc_work, enc_bound, o_misc, o_crc, o_enc, work, bound;
 };
-static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static int png_layout(int H, int W, int K, int flags, Sizes& s) {
   s.scan = (int64_t)H * png_row_bytes(W, K, flags);
   const int rc = flags & RHCCQ_PNG_EXACT ? rhccq_zlib9_sizes(s.scan, &s.enc_work, &s.enc_bound) : rhccq_zlib_sizes(s.scan, &s.enc_work, &s.enc_bound);

@@ -76,6 +76,9 @@ namespace rhccq {
 
 constexpr int kWave = 64;
 
+// the next multiple of 256: every piece of a caller's workspace starts at one
+inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
 __device__ __forceinline__ uint32_t key_r(uint32_t k) { return (k >> 16) & 255u; }
 __device__ __forceinline__ uint32_t key_g(uint32_t k) { return (k >> 8) & 255u; }
 __device__ __forceinline__ uint32_t key_b(uint32_t k) { return k & 255u; }

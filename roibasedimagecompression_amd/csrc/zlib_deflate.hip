@@ -3,23 +3,24 @@
 // a single host core doing the work.  Format-compatible with zlib's inflate, not byte-identical to zlib's deflate.
 //
 // Pipeline of one rhccq_zlib_compress call (every launch on the context stream, all memory in the caller's workspace):
-//   zl_zero      clear the packing words (the output is assembled by OR-ing bits into 32-bit words)
-//   zl_chain     one wave per 64 KiB hash chunk: prev[i] = distance to the nearest earlier position with the same
-//                3-byte hash (0: none within 32 KiB).  The chunk re-inserts its 32 KiB look-back into an LDS head
-//                table, so prev[] is one global function of the input and chains run across chunk boundaries.
+//   words_zero   clear the packing words (the output is assembled by OR-ing bits into 32-bit words); deflate_core.h
+//   hash_chain_kernel<zl_hash>   one wave per 64 KiB hash chunk: prev[i] = distance to the nearest earlier position with
+//                the same 3-byte hash (0: none within 32 KiB), one global function of the input; deflate_core.h
 //   zl_match     one thread per position: walk the chain (at most kMaxChain candidates), longest match, nearest on
 //                ties; lengths clamped to the position's 4 KiB parse chunk; 3-byte matches farther than 4 KiB dropped
 //   zl_parse     one thread per parse chunk: lazy rule next(i) -- the match at i unless i+1 has a longer one
-//   zl_adler     one workgroup per parse chunk: (sum b, sum (L-k) b_k) of its bytes, combined in zl_scan
+//   adler_partials_kernel<kParse>   one workgroup per parse chunk: (sum b, sum (L-k) b_k) of its bytes, folded in zl_scan;
+//                deflate_core.h
 //   zl_plan      one workgroup per 64 KiB block: symbol histograms, length-limited Huffman codes with the tie order
 //                (frequency, symbol), run-length coded code lengths, cheapest of dynamic / fixed / stored
 //   zl_bits      one workgroup per parse chunk: bits of its symbols under its block's code
 //   zl_scan      one lane: bit offset of every block and parse chunk, Adler-32, zlib header, trailer, length
 //   zl_emit      one workgroup per parse chunk: symbols at their bit offsets (exclusive scan), or raw bytes of a stored block
 //   zl_header    one thread per block: block header, tree description, end-of-block code, stored LEN / NLEN
-//   zl_copy      packing words -> the caller's output buffer
+//   words_copy   packing words -> the caller's output buffer; deflate_core.h
 // The output bytes are a function of the input bytes alone: no atomic whose order matters (only histogram adds,
 // maxima and ORs of disjoint bits), no read of workspace memory this call did not write first.
+#include "deflate_core.h"
 #include "rhccq_common.h"
 
 #include <hip/hip_runtime.h>
@@ -29,9 +30,9 @@
 
 namespace zl {
 
-constexpr int kHashBits = 15;
-constexpr int kHashChunk = 65536;          // positions a zl_chain workgroup owns
-constexpr int kWindow = 32768;             // RFC 1951 distance limit
+using namespace rhccq::deflate;            // the symbol algebra, Adler-32, kWindow, kHashBits, kHashChunk and the shared kernels
+using rhccq::align256;
+
 constexpr int kParse = 4096;               // parse chunk: matches never cross its end
 constexpr int kChunksPerBlock = 16;
 constexpr int kBlock = kParse * kChunksPerBlock;   // input bytes of one DEFLATE block (up to two stored pieces)
@@ -72,39 +73,12 @@ ZL_HD void zl_put(uint32_t* w, uint64_t off, uint32_t v, int nb) {
 
 ZL_HD void zl_put_byte(uint32_t* w, uint64_t pos, uint32_t b) { zl_or(w + (pos >> 2), (b & 255u) << (8 * (pos & 3))); }
 
-ZL_HD int zl_log2(uint32_t v) { return 31 - __builtin_clz(v); }
-
-// length 3..258 -> symbol 257..285, extra bits, extra value
-ZL_HD void zl_len_sym(int len, int& sym, int& eb, int& ev) {
-  const int l = len - 3;
-  if (l < 8) { sym = 257 + l; eb = 0; ev = 0; return; }
-  if (l == 255) { sym = 285; eb = 0; ev = 0; return; }
-  const int e = zl_log2((uint32_t)l) - 2;
-  sym = 257 + 4 * e + 4 + ((l >> e) & 3);
-  eb = e;
-  ev = l & ((1 << e) - 1);
-}
-
-// distance 1..32768 -> symbol 0..29, extra bits, extra value
-ZL_HD void zl_dist_sym(int dist, int& sym, int& eb, int& ev) {
-  const int d = dist - 1;
-  if (d < 4) { sym = d; eb = 0; ev = 0; return; }
-  const int e = zl_log2((uint32_t)d) - 1;
-  sym = 2 * e + 2 + ((d >> e) & 1);
-  eb = e;
-  ev = d & ((1 << e) - 1);
-}
-
-ZL_HD int zl_len_extra(int sym) { return (sym < 265 || sym == 285) ? 0 : (sym - 261) >> 2; }
-ZL_HD int zl_dist_extra(int sym) { return sym < 4 ? 0 : (sym >> 1) - 1; }
-ZL_HD int zl_fixed_len(int sym) { return sym < 144 ? 8 : sym < 256 ? 9 : sym < 280 ? 7 : 8; }
-
 // symbols of the parse: literal byte b, or 0x80000000 | (len - 3) << 16 | (dist - 1)
 ZL_HD int zl_sym_bits(uint32_t s, const uint32_t* lc, const uint32_t* dc) {
   if (!(s >> 31)) return (int)(lc[s & 255] >> 16);
-  int ls, le, lv, ds, de, dv;
-  zl_len_sym((int)((s >> 16) & 255) + 3, ls, le, lv);
-  zl_dist_sym((int)(s & 0xFFFF) + 1, ds, de, dv);
+  int le, lv, de, dv;
+  const int ls = 257 + len_code((int)((s >> 16) & 255) + 3, le, lv);
+  const int ds = dist_code((int)(s & 0xFFFF) + 1, de, dv);
   return (int)(lc[ls] >> 16) + le + (int)(dc[ds] >> 16) + de;
 }
 
@@ -114,9 +88,9 @@ ZL_HD uint64_t zl_put_sym(uint32_t* w, uint64_t off, uint32_t s, const uint32_t*
     zl_put(w, off, c & 0xFFFF, (int)(c >> 16));
     return off + (c >> 16);
   }
-  int ls, le, lv, ds, de, dv;
-  zl_len_sym((int)((s >> 16) & 255) + 3, ls, le, lv);
-  zl_dist_sym((int)(s & 0xFFFF) + 1, ds, de, dv);
+  int le, lv, de, dv;
+  const int ls = 257 + len_code((int)((s >> 16) & 255) + 3, le, lv);
+  const int ds = dist_code((int)(s & 0xFFFF) + 1, de, dv);
   const uint32_t c = lc[ls], d = dc[ds];
   zl_put(w, off, c & 0xFFFF, (int)(c >> 16));
   off += c >> 16;
@@ -178,15 +152,6 @@ ZL_HD int zl_parse_chunk(const uint32_t* m, const uint8_t* in, int64_t s, int64_
   return k;
 }
 
-ZL_HD uint32_t zl_rev(uint32_t code, int len) {
-  uint32_t r = 0;
-  for (int k = 0; k < len; ++k) {
-    r = (r << 1) | (code & 1);
-    code >>= 1;
-  }
-  return r;
-}
-
 // canonical codes (RFC 1951 3.2.2) of lengths len[0..n), bit-reversed for LSB-first packing
 ZL_HD void zl_canon(const uint8_t* len, int n, uint32_t* out) {
   int bl[16];
@@ -202,7 +167,7 @@ ZL_HD void zl_canon(const uint8_t* len, int n, uint32_t* out) {
   }
   for (int s = 0; s < n; ++s) {
     const int L = len[s];
-    out[s] = L ? (zl_rev(next[L]++, L) | (uint32_t)L << 16) : 0u;
+    out[s] = L ? (bit_reverse(next[L]++, L) | (uint32_t)L << 16) : 0u;
   }
 }
 
@@ -323,27 +288,26 @@ ZL_HD void zl_plan_block(Block* B, const uint32_t* fl, const int16_t* ol, int ml
     }
   const int ncl = zl_pad_order(fc, used, mc, 19, ordc);
   zl_huff_lengths(fc, ordc, ncl, 7, cl, htmp);
-  const int corder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
   int hclen = 19;
-  while (hclen > 4 && !cl[corder[hclen - 1]]) --hclen;
+  while (hclen > 4 && !cl[codelen_order(hclen - 1)]) --hclen;
   zl_canon(cl, 19, B->ccode);
   // costs
   int64_t hdr = 14 + 3 * hclen;
   for (int t = 0; t < nt; ++t) {
     const int s = B->tok[t] & 31;
-    hdr += cl[s] + (s == 16 ? 2 : s == 17 ? 3 : s == 18 ? 7 : 0);
+    hdr += cl[s] + codelen_extra(s);
   }
   int64_t dyn = 3 + hdr, fix = 3;
   for (int s = 0; s < 286; ++s)
     if (fl[s]) {
-      const int e = s > 256 ? zl_len_extra(s) : 0;
+      const int e = s > 256 ? len_extra(s - 257) : 0;
       dyn += (int64_t)fl[s] * (ll[s] + e);
-      fix += (int64_t)fl[s] * (zl_fixed_len(s) + e);
+      fix += (int64_t)fl[s] * (fixed_litlen_bits(s) + e);
     }
   for (int s = 0; s < 30; ++s)
     if (fd[s]) {
-      dyn += (int64_t)fd[s] * (dl[s] + zl_dist_extra(s));
-      fix += (int64_t)fd[s] * (5 + zl_dist_extra(s));
+      dyn += (int64_t)fd[s] * (dl[s] + dist_extra(s));
+      fix += (int64_t)fd[s] * (5 + dist_extra(s));
     }
   const int64_t pieces = blen > 0 ? (blen + kStoredMax - 1) / kStoredMax : 1;
   const int64_t stored = pieces * 42 + 8 * blen;      // worst-case alignment: 3 + 7 + 32 per piece
@@ -359,7 +323,7 @@ ZL_HD void zl_plan_block(Block* B, const uint32_t* fl, const int16_t* ol, int ml
   } else if (fix <= dyn) {
     B->type = 1;
     B->hdr_bits = 0;
-    for (int s = 0; s < 288; ++s) ll[s] = (uint8_t)zl_fixed_len(s);
+    for (int s = 0; s < 288; ++s) ll[s] = (uint8_t)fixed_litlen_bits(s);
     for (int s = 0; s < 32; ++s) dl[s] = 5;
   } else {
     B->type = 2;
@@ -394,16 +358,9 @@ ZL_HD int64_t zl_scan(const Block* blocks, int nb, const int64_t* chunk_bits, in
       off += B.lcode[256] >> 16;
     }
   }
-  // Adler-32 (RFC 1950): per chunk (sum b, sum (L - k) b_k) mod 65521, folded in order
-  uint64_t s1 = 1, s2 = 0;
-  for (int c = 0; c < nc; ++c) {
-    const int64_t L = (n - (int64_t)c * kParse) < kParse ? (n - (int64_t)c * kParse) : kParse;
-    s2 = (s2 + (uint64_t)(L > 0 ? L : 0) % 65521u * s1 + adl[2 * c + 1]) % 65521u;
-    s1 = (s1 + adl[2 * c]) % 65521u;
-  }
   const uint64_t end = (off + 7) >> 3;
   zl_put(words, 0, 0x9C78u, 16);                   // CMF 0x78 (deflate, 32 KiB window), FLG 0x9C: FCHECK makes 0x789C % 31 == 0
-  const uint32_t adler = (uint32_t)(s2 << 16 | s1);
+  const uint32_t adler = adler_fold(adl, n, kParse);
   for (int k = 0; k < 4; ++k) zl_put_byte(words, end + k, adler >> (24 - 8 * k));
   return (int64_t)end + 4;
 }
@@ -428,18 +385,17 @@ ZL_HD void zl_block_header(const Block& B, int b, int nb, int nc, const int64_t*
   zl_put(words, off, (last ? 1u : 0u) | (uint32_t)B.type << 1, 3);
   off += 3;
   if (B.type == 2) {
-    const int corder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     zl_put(words, off, (uint32_t)(B.hlit - 257), 5);
     zl_put(words, off + 5, (uint32_t)(B.hdist - 1), 5);
     zl_put(words, off + 10, (uint32_t)(B.hclen - 4), 4);
     off += 14;
-    for (int k = 0; k < B.hclen; ++k, off += 3) zl_put(words, off, B.ccode[corder[k]] >> 16, 3);
+    for (int k = 0; k < B.hclen; ++k, off += 3) zl_put(words, off, B.ccode[codelen_order(k)] >> 16, 3);
     for (int t = 0; t < B.ntok; ++t) {
       const int s = B.tok[t] & 31, x = B.tok[t] >> 5;
       const uint32_t c = B.ccode[s];
       zl_put(words, off, c & 0xFFFF, (int)(c >> 16));
       off += c >> 16;
-      const int eb = s == 16 ? 2 : s == 17 ? 3 : s == 18 ? 7 : 0;
+      const int eb = codelen_extra(s);
       zl_put(words, off, (uint32_t)x, eb);
       off += eb;
     }
@@ -455,8 +411,6 @@ struct Layout {
   int64_t nc, nb, nhc, bound, words;
   int64_t o_prev, o_m, o_sym, o_nsym, o_bits, o_coff, o_adl, o_blk, o_boff, o_words, total;
 };
-
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 inline Layout layout(int64_t n) {
   Layout L;
@@ -482,42 +436,6 @@ inline Layout layout(int64_t n) {
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------
 
-__global__ void zl_zero(uint32_t* w, int64_t nw) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) w[i] = 0;
-}
-
-// one wave per hash chunk; LDS head table of the last position (+1) of every hash seen so far in this chunk's window
-__global__ __launch_bounds__(64) void zl_chain(const uint8_t* __restrict__ in, int64_t n, uint16_t* __restrict__ prev) {
-  __shared__ uint32_t head[1 << kHashBits];
-  const int lane = threadIdx.x;
-  for (int k = lane; k < (1 << kHashBits); k += 64) head[k] = 0;
-  __syncthreads();
-  const int64_t cs = (int64_t)blockIdx.x * kHashChunk;
-  const int64_t ce = cs + kHashChunk < n ? cs + kHashChunk : n;
-  const int64_t ws = cs > kWindow ? cs - kWindow : 0;
-  for (int64_t base = ws; base < ce; base += 64) {
-    const int64_t i = base + lane;
-    const bool valid = i < ce && i + 2 < n;
-    const uint32_t h = valid ? zl_hash(in, i) : (0xFFFF0000u | (uint32_t)lane);
-    // nearest earlier lane of this batch with the same hash: bit k of eq = lane - k has it (63 independent shuffles,
-    // unrolled so that they are in flight together instead of one wait each)
-    uint64_t eq = 0;
-#pragma unroll
-    for (int k = 1; k < 64; ++k) eq |= (uint64_t)(__shfl(h, (lane - k) & 63, 64) == h) << k;
-    eq &= (2ull << lane) - 2ull;                   // bits 1..lane: lanes below this one
-    const int pl = eq ? lane - __builtin_ctzll(eq) : -1;
-    int64_t p = -1;
-    if (valid) p = pl >= 0 ? base + pl : (int64_t)head[h] - 1;
-    __syncthreads();
-    if (valid) atomicMax(&head[h], (uint32_t)(i + 1));
-    __syncthreads();
-    if (i >= cs && i < ce) {
-      const int64_t d = p >= 0 ? i - p : 0;
-      prev[i] = (uint16_t)((p >= 0 && d <= kWindow) ? d : 0);
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void zl_match(const uint8_t* __restrict__ in, int64_t n, const uint16_t* __restrict__ prev,
                                                 uint32_t* __restrict__ m) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -534,25 +452,6 @@ __global__ __launch_bounds__(64) void zl_parse(const uint32_t* __restrict__ m, c
   const int64_t s = (int64_t)c * kParse;
   const int64_t e = s + kParse < n ? s + kParse : n;
   nsym[c] = s < e ? zl_parse_chunk(m, in, s, e, sym + s) : 0;
-}
-
-__global__ __launch_bounds__(256) void zl_adler(const uint8_t* __restrict__ in, int64_t n, uint32_t* __restrict__ adl) {
-  __shared__ unsigned long long red[8];
-  const int c = blockIdx.x;
-  const int64_t s = (int64_t)c * kParse;
-  const int64_t L = n - s < kParse ? n - s : kParse;
-  unsigned long long a = 0, b = 0;
-  for (int64_t k = threadIdx.x; k < L; k += 256) {
-    const unsigned long long v = in[s + k];
-    a += v;
-    b += (unsigned long long)(L - k) * v;
-  }
-  a = rhccq::block_sum(a, red);
-  b = rhccq::block_sum(b, red);
-  if (threadIdx.x == 0) {
-    adl[2 * c] = (uint32_t)(a % 65521u);
-    adl[2 * c + 1] = (uint32_t)(b % 65521u);
-  }
 }
 
 __global__ __launch_bounds__(256) void zl_plan(const uint32_t* __restrict__ sym, const int32_t* __restrict__ nsym, int64_t n, int nc,
@@ -575,11 +474,9 @@ __global__ __launch_bounds__(256) void zl_plan(const uint32_t* __restrict__ sym,
       if (!(s >> 31)) {
         atomicAdd(&fl[s & 255], 1u);
       } else {
-        int ls, le, lv, ds, de, dv;
-        zl_len_sym((int)((s >> 16) & 255) + 3, ls, le, lv);
-        zl_dist_sym((int)(s & 0xFFFF) + 1, ds, de, dv);
-        atomicAdd(&fl[ls], 1u);
-        atomicAdd(&fd[ds], 1u);
+        int le, lv, de, dv;
+        atomicAdd(&fl[257 + len_code((int)((s >> 16) & 255) + 3, le, lv)], 1u);
+        atomicAdd(&fd[dist_code((int)(s & 0xFFFF) + 1, de, dv)], 1u);
       }
     }
   }
@@ -662,11 +559,6 @@ __global__ void zl_header(const Block* __restrict__ blocks, int nb, int nc, cons
   if (b < nb) zl_block_header(blocks[b], b, nb, nc, block_off, chunk_off, chunk_bits, words);
 }
 
-__global__ void zl_copy(const uint32_t* __restrict__ words, int64_t nbytes, uint8_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbytes; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (uint8_t)(words[i >> 2] >> (8 * (i & 3)));
-}
-
 }  // namespace zl
 
 extern "C" {
@@ -701,20 +593,20 @@ int rhccq_zlib_compress(rhccq_ctx* ctx, const void* in, int64_t n, void* workspa
   hipStream_t st = ctx->stream;
   const int nc = (int)L.nc, nb = (int)L.nb;
   const int zgrid = (int)((L.words + 255) / 256 < 4096 ? (L.words + 255) / 256 : 4096);
-  zl_zero<<<zgrid, 256, 0, st>>>(words, L.words);
+  words_zero<0><<<zgrid, 256, 0, st>>>(words, L.words, nullptr);
   if (n > 0) {
-    zl_chain<<<(int)L.nhc, 64, 0, st>>>(src, n, prev);
+    hash_chain_kernel<zl_hash><<<(int)L.nhc, 64, 0, st>>>(src, n, prev);
     zl_match<<<(int)((n + 255) / 256), 256, 0, st>>>(src, n, prev, m);
   }
   zl_parse<<<(nc + 63) / 64, 64, 0, st>>>(m, src, n, nc, sym, nsym);
-  zl_adler<<<nc, 256, 0, st>>>(src, n, adl);
+  adler_partials_kernel<kParse><<<nc, 256, 0, st>>>(src, n, adl);
   zl_plan<<<nb, 256, 0, st>>>(sym, nsym, n, nc, blk);
   zl_bits<<<nc, 256, 0, st>>>(sym, nsym, blk, bits);
   zl_scan_k<<<1, 64, 0, st>>>(blk, nb, bits, nc, adl, n, coff, boff, words, out_len);
   zl_emit<<<nc, 256, 0, st>>>(sym, nsym, blk, coff, boff, src, n, words);
   zl_header<<<(nb + 63) / 64, 64, 0, st>>>(blk, nb, nc, boff, coff, bits, words);
   const int cgrid = (int)((L.bound + 255) / 256 < 8192 ? (L.bound + 255) / 256 : 8192);
-  zl_copy<<<cgrid, 256, 0, st>>>(words, L.bound, out);
+  words_copy<<<cgrid, 256, 0, st>>>(words, L.bound, out);
   RHCCQ_LAUNCH_CHECK(ctx);
   return RHCCQ_OK;
 }

@@ -14,21 +14,23 @@
 // the 4096-candidate walk at p-1, pending match of the 1024-candidate walk at p-1}.
 //
 // Pipeline of one rhccq_zlib9_compress call (every launch on the context stream, all memory in the caller's workspace):
-//   z9_zero      clear the packing words and the statistics
-//   z9_chain     one wave per 64 KiB: prev[p] = distance to the nearest earlier position with the same zlib hash (0: none in 32 KiB)
+//   words_zero   clear the packing words and the statistics; deflate_core.h
+//   hash_chain_kernel<hash3>   one wave per 64 KiB: prev[p] = distance to the nearest earlier position with the same zlib hash
+//                (0: none in 32 KiB); deflate_core.h
 //   z9_search    one thread per position: the chain walk, (length, distance) after 1024 and after 4096 candidates
 //   z9_seg       one workgroup per 4 KiB segment: successors of its 4 x 4096 nodes, pointer jumping in LDS until every node
 //                points past the segment: exit node and symbol count of each of the 258 x 4 possible entry nodes
 //   z9_link      one lane: the real parse's entry node and first symbol of every segment, the symbol count
 //   z9_walk      one thread per segment: the parse from its entry node, symbols written at their ranks
-//   z9_adler     one workgroup per 4 KiB: Adler-32 partial sums
+//   adler_partials_kernel<kAdler>   one workgroup per 4 KiB: Adler-32 partial sums; deflate_core.h
 //   z9_block     one workgroup per block of 16 383 symbols: histograms, then zlib's build_tree / gen_bitlen / gen_codes,
 //                build_bl_tree and _tr_flush_block's choice of stored / fixed / dynamic
 //   z9_offsets   one lane: bit offset of every block, zlib header, Adler-32 trailer, length
 //   z9_emit      one workgroup per block: block header and trees (lane 0), symbols at their bit offsets (exclusive scan),
 //                or the stored bytes
-//   z9_copy      packing words -> the caller's output buffer
+//   words_copy   packing words -> the caller's output buffer; deflate_core.h
 // rhccq_zlib9_compress_host runs the same functions serially (the search only at the nodes the parse visits, as zlib does).
+#include "deflate_core.h"
 #include "rhccq_common.h"
 
 #include <hip/hip_runtime.h>
@@ -41,6 +43,9 @@
 
 namespace z9 {
 
+using namespace rhccq::deflate;            // the symbol algebra, Adler-32, kHashChunk and the shared kernels
+using rhccq::align256;
+
 constexpr int kWSize = 32768;
 constexpr int kMaxDist = kWSize - 262;     // MAX_DIST: 32 506
 constexpr int kTooFar = 4096;
@@ -49,7 +54,6 @@ constexpr int kChainLong = 4096, kChainShort = 1024, kGood = 32;
 constexpr int kBlockSyms = 16383;          // lit_bufsize - 1: a block is flushed after this many symbols
 constexpr int kSeg = 4096;                 // positions of a z9_seg / z9_walk segment
 constexpr int kEntries = 258 * 4;          // possible entry nodes of a segment: the first node at or past its start
-constexpr int kHashChunk = 65536;
 constexpr int kAdler = 4096;
 constexpr int kHeap = 2 * 286 + 1;         // HEAP_SIZE
 constexpr int64_t kMaxIn = ((int64_t)1 << 31) - 1;
@@ -177,38 +181,8 @@ Z9_HD int step(const uint32_t* r1, const uint32_t* r4, int64_t p, int s, int64_t
 
 // ---- trees.c ---------------------------------------------------------------------------------------------------
 
-Z9_HD int len_code(int len, int& extra_bits, int& extra_val) {   // 3..258 -> 0..28 (symbol - 257)
-  const int l = len - 3;
-  if (l == 255) { extra_bits = 0; extra_val = 0; return 28; }
-  if (l < 8) { extra_bits = 0; extra_val = 0; return l; }
-  const int e = 29 - __builtin_clz((uint32_t)l);                  // floor(log2 l) - 2
-  extra_bits = e;
-  extra_val = l & ((1 << e) - 1);
-  return 4 * e + 4 + ((l >> e) & 3);
-}
-
-Z9_HD int dist_code(int dist, int& extra_bits, int& extra_val) {  // 1..32768 -> 0..29
-  const int d = dist - 1;
-  if (d < 4) { extra_bits = 0; extra_val = 0; return d; }
-  const int e = 30 - __builtin_clz((uint32_t)d);                  // floor(log2 d) - 1
-  extra_bits = e;
-  extra_val = d & ((1 << e) - 1);
-  return 2 * e + 2 + ((d >> e) & 1);
-}
-
-Z9_HD int extra_l(int code) { return (code < 8 || code == 28) ? 0 : (code - 4) >> 2; }
-Z9_HD int extra_d(int code) { return code < 4 ? 0 : (code >> 1) - 1; }
-Z9_HD int extra_bl(int code) { return code == 16 ? 2 : code == 17 ? 3 : code == 18 ? 7 : 0; }
-Z9_HD int static_llen(int s) { return s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8; }
-
-Z9_HD uint32_t bi_reverse(uint32_t code, int len) {
-  uint32_t r = 0;
-  for (int k = 0; k < len; ++k) {
-    r = (r << 1) | (code & 1);
-    code >>= 1;
-  }
-  return r;
-}
+// len_code / dist_code (zlib's _length_code / d_code), len_extra / dist_extra / codelen_extra (extra_lbits / extra_dbits / extra_blbits),
+// fixed_litlen_bits (static_ltree), codelen_order (bl_order) and bit_reverse (bi_reverse) are deflate_core.h's
 
 struct Tree {
   uint32_t freq[kHeap];
@@ -259,12 +233,12 @@ Z9_HD void gen_bitlen(Work& w, Tree& t, int max_code, int which) {
     if (n > max_code) continue;
     w.bl_count[bits]++;
     int xbits = 0;
-    if (which == 0 && n >= 257) xbits = extra_l(n - 257);
-    if (which == 1) xbits = extra_d(n);
-    if (which == 2) xbits = extra_bl(n);
+    if (which == 0 && n >= 257) xbits = len_extra(n - 257);
+    if (which == 1) xbits = dist_extra(n);
+    if (which == 2) xbits = codelen_extra(n);
     const uint64_t f = t.freq[n];
     w.opt_len += f * (uint64_t)(bits + xbits);
-    if (which == 0) w.static_len += f * (uint64_t)(static_llen(n) + xbits);
+    if (which == 0) w.static_len += f * (uint64_t)(fixed_litlen_bits(n) + xbits);
     if (which == 1) w.static_len += f * (uint64_t)(5 + xbits);
   }
   if (overflow == 0) return;
@@ -300,7 +274,7 @@ Z9_HD void gen_codes(Tree& t, int max_code, const int* bl_count) {
   for (int n = 0; n <= max_code; n++) {
     const int l = t.len[n];
     if (l == 0) continue;
-    t.code[n] = (uint16_t)bi_reverse(next[l]++, l);
+    t.code[n] = (uint16_t)bit_reverse(next[l]++, l);
   }
 }
 
@@ -321,7 +295,7 @@ Z9_HD int build_tree(Work& w, Tree& t, int elems, int which) {
     t.freq[node] = 1;
     w.depth[node] = 0;
     w.opt_len--;
-    if (which == 0) w.static_len -= (uint64_t)static_llen(node);
+    if (which == 0) w.static_len -= (uint64_t)fixed_litlen_bits(node);
     if (which == 1) w.static_len -= 5;
   }
   for (int n = w.heap_len / 2; n >= 1; n--) pqdownheap(w, t, n);
@@ -428,12 +402,6 @@ Z9_HD uint64_t send_tree(const uint16_t* len, int max_code, const uint32_t* bl, 
   return off;
 }
 
-__host__ __device__ constexpr int bl_order(int k) {
-  return k == 0 ? 16 : k == 1 ? 17 : k == 2 ? 18 : k == 3 ? 0 : k == 4 ? 8 : k == 5 ? 7 : k == 6 ? 9 : k == 7 ? 6 : k == 8 ? 10 :
-         k == 9 ? 5 : k == 10 ? 11 : k == 11 ? 4 : k == 12 ? 12 : k == 13 ? 3 : k == 14 ? 13 : k == 15 ? 2 : k == 16 ? 14 :
-         k == 17 ? 1 : 15;
-}
-
 // _tr_flush_block's trees and choice for one block whose histograms are in w.lt.freq[0..286) / w.dt.freq[0..30)
 // (end of block not yet counted).  stored_ok: block_start >= 0 in zlib's window.
 Z9_HD void plan_block(Work& w, Block& B, bool stored_ok) {
@@ -449,7 +417,7 @@ Z9_HD void plan_block(Work& w, Block& B, bool stored_ok) {
   build_tree(w, w.bt, 19, 2);
   int max_blindex;
   for (max_blindex = 18; max_blindex >= 3; max_blindex--)
-    if (w.bt.len[bl_order(max_blindex)] != 0) break;
+    if (w.bt.len[codelen_order(max_blindex)] != 0) break;
   w.opt_len += 3 * ((uint64_t)max_blindex + 1) + 5 + 5 + 4;
   uint64_t opt_lenb = (w.opt_len + 3 + 7) >> 3;
   const uint64_t static_lenb = (w.static_len + 3 + 7) >> 3;
@@ -468,7 +436,7 @@ Z9_HD void plan_block(Work& w, Block& B, bool stored_ok) {
     uint16_t sl[288];
     int cnt[16];
     for (int b = 0; b < 16; ++b) cnt[b] = 0;
-    for (int s = 0; s < 288; ++s) cnt[sl[s] = (uint16_t)static_llen(s)]++;
+    for (int s = 0; s < 288; ++s) cnt[sl[s] = (uint16_t)fixed_litlen_bits(s)]++;
     uint32_t next[16], code = 0;
     cnt[0] = 0;
     for (int b = 1; b <= 15; b++) {
@@ -476,10 +444,10 @@ Z9_HD void plan_block(Work& w, Block& B, bool stored_ok) {
       next[b] = code;
     }
     for (int s = 0; s < 288; ++s) {
-      const uint32_t c = bi_reverse(next[sl[s]]++, sl[s]);
+      const uint32_t c = bit_reverse(next[sl[s]]++, sl[s]);
       if (s < 286) B.lcode[s] = c | (uint32_t)sl[s] << 16;
     }
-    for (int s = 0; s < 30; ++s) B.dcode[s] = bi_reverse((uint32_t)s, 5) | 5u << 16;
+    for (int s = 0; s < 30; ++s) B.dcode[s] = bit_reverse((uint32_t)s, 5) | 5u << 16;
   } else {
     B.type = 2;
     B.bits = (int64_t)w.opt_len;
@@ -540,7 +508,7 @@ Z9_HD uint64_t block_header(const Block& B, uint64_t off, uint32_t* w, int64_t n
     put_bits(w, nw, off + 5, (uint32_t)(B.dcodes - 1), 5);
     put_bits(w, nw, off + 10, (uint32_t)(B.blcodes - 4), 4);
     off += 14;
-    for (int r = 0; r < B.blcodes; ++r, off += 3) put_bits(w, nw, off, B.blcode[bl_order(r)] >> 16, 3);
+    for (int r = 0; r < B.blcodes; ++r, off += 3) put_bits(w, nw, off, B.blcode[codelen_order(r)] >> 16, 3);
     off = send_tree(B.llen, B.lcodes - 1, B.blcode, w, nw, off);
     off = send_tree(B.dlen, B.dcodes - 1, B.blcode, w, nw, off);
   }
@@ -577,8 +545,6 @@ struct Layout {
   int64_t o_prev, o_r1, o_r4, o_summ, o_sent, o_sbase, o_misc, o_spos, o_sld, o_blk, o_boff, o_adl, o_words, o_stats, total;
 };
 
-inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 inline Layout layout(int64_t n) {
   Layout L;
   L.nseg = (n + kSeg - 1) / kSeg;
@@ -606,42 +572,6 @@ inline Layout layout(int64_t n) {
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
-
-__global__ void z9_zero(uint32_t* w, int64_t nw, int64_t* stats) {
-  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = t0; i < nw; i += (int64_t)gridDim.x * blockDim.x) w[i] = 0;
-  if (t0 < ST_N) stats[t0] = 0;
-}
-
-// one wave per 64 KiB: LDS head table (last position + 1 of every hash) over the chunk and its 32 KiB look-back
-__global__ __launch_bounds__(64) void z9_chain(const uint8_t* __restrict__ in, int64_t n, uint16_t* __restrict__ prev) {
-  __shared__ uint32_t head[1 << 15];
-  const int lane = threadIdx.x;
-  for (int k = lane; k < (1 << 15); k += 64) head[k] = 0;
-  __syncthreads();
-  const int64_t cs = (int64_t)blockIdx.x * kHashChunk;
-  const int64_t ce = cs + kHashChunk < n ? cs + kHashChunk : n;
-  const int64_t ws = cs > kWSize ? cs - kWSize : 0;
-  for (int64_t base = ws; base < ce; base += 64) {
-    const int64_t i = base + lane;
-    const bool valid = i < ce && i + 2 < n;
-    const uint32_t h = valid ? hash3(in, i) : (0xFFFF0000u | (uint32_t)lane);
-    uint64_t eq = 0;
-#pragma unroll
-    for (int k = 1; k < 64; ++k) eq |= (uint64_t)(__shfl(h, (lane - k) & 63, 64) == h) << k;
-    eq &= (2ull << lane) - 2ull;
-    const int pl = eq ? lane - __builtin_ctzll(eq) : -1;
-    int64_t p = -1;
-    if (valid) p = pl >= 0 ? base + pl : (int64_t)head[h] - 1;
-    __syncthreads();
-    if (valid) atomicMax(&head[h], (uint32_t)(i + 1));
-    __syncthreads();
-    if (i >= cs && i < ce) {
-      const int64_t d = p >= 0 ? i - p : 0;
-      prev[i] = (uint16_t)((p >= 0 && d <= kWSize) ? d : 0);
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void z9_search(const uint8_t* __restrict__ in, int64_t n, const uint16_t* __restrict__ prev,
                                                  uint32_t* __restrict__ r1, uint32_t* __restrict__ r4, int64_t* __restrict__ stats) {
@@ -754,35 +684,6 @@ __global__ __launch_bounds__(64) void z9_walk(const uint32_t* __restrict__ r1, c
   if (threadIdx.x == 0 && nodes) atomicAdd((unsigned long long*)&stats[ST_NODES], nodes);
 }
 
-__global__ __launch_bounds__(256) void z9_adler(const uint8_t* __restrict__ in, int64_t n, uint32_t* __restrict__ adl) {
-  __shared__ unsigned long long red[8];
-  const int64_t c = blockIdx.x;
-  const int64_t s = c * kAdler;
-  const int64_t L = n - s < kAdler ? n - s : kAdler;
-  unsigned long long a = 0, b = 0;
-  for (int64_t k = threadIdx.x; k < L; k += 256) {
-    const unsigned long long v = in[s + k];
-    a += v;
-    b += (unsigned long long)(L - k) * v;
-  }
-  a = rhccq::block_sum(a, red);
-  b = rhccq::block_sum(b, red);
-  if (threadIdx.x == 0) {
-    adl[2 * c] = (uint32_t)(a % 65521u);
-    adl[2 * c + 1] = (uint32_t)(b % 65521u);
-  }
-}
-
-Z9_HD uint32_t adler_fold(const uint32_t* adl, int64_t nad, int64_t n) {
-  uint64_t s1 = 1, s2 = 0;
-  for (int64_t c = 0; c < nad; ++c) {
-    const int64_t L = n - c * kAdler < kAdler ? n - c * kAdler : kAdler;
-    s2 = (s2 + (uint64_t)(L > 0 ? L : 0) % 65521u * s1 + adl[2 * c + 1]) % 65521u;
-    s1 = (s1 + adl[2 * c]) % 65521u;
-  }
-  return (uint32_t)(s2 << 16 | s1);
-}
-
 // symbol range, input range and stored eligibility of block b (nb blocks, tot symbols)
 Z9_HD void block_range(const uint32_t* spos, const uint32_t* sld, int64_t n, int64_t tot, int64_t nb, int64_t b, Block& B, bool& stored_ok) {
   B.sym0 = b * kBlockSyms;
@@ -833,11 +734,11 @@ __global__ __launch_bounds__(256) void z9_block(const uint8_t* __restrict__ in, 
 }
 
 __global__ void z9_offsets(const Block* __restrict__ blocks, const int64_t* __restrict__ misc, int64_t* __restrict__ boff,
-                           const uint32_t* __restrict__ adl, int64_t nad, int64_t n, uint32_t* __restrict__ words, int64_t nw,
+                           const uint32_t* __restrict__ adl, int64_t n, uint32_t* __restrict__ words, int64_t nw,
                            int64_t* __restrict__ out_len) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const int64_t len = block_offsets(blocks, misc[2], boff);
-  put_frame(words, nw, len, adler_fold(adl, nad, n));
+  put_frame(words, nw, len, adler_fold(adl, n, kAdler));
   *out_len = len;
 }
 
@@ -875,11 +776,6 @@ __global__ __launch_bounds__(256) void z9_emit(const uint8_t* __restrict__ in, c
     const uint32_t eob = B.lcode[256];
     put_bits(words, nw, data0 + (uint64_t)tot, eob & 0xFFFF, (int)(eob >> 16));
   }
-}
-
-__global__ void z9_copy(const uint32_t* __restrict__ words, int64_t nbytes, uint8_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbytes; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (uint8_t)(words[i >> 2] >> (8 * (i & 3)));
 }
 
 __global__ void z9_stats_copy(const int64_t* __restrict__ src, int64_t* __restrict__ dst) {
@@ -924,22 +820,22 @@ int rhccq_zlib9_compress(rhccq_ctx* ctx, const void* in, int64_t n, void* worksp
   int64_t* stats = (int64_t*)(ws + L.o_stats);
   hipStream_t st = ctx->stream;
   const int zgrid = (int)((L.words + 255) / 256 < 4096 ? (L.words + 255) / 256 : 4096);
-  z9_zero<<<zgrid, 256, 0, st>>>(words, L.words, stats);
+  words_zero<ST_N><<<zgrid, 256, 0, st>>>(words, L.words, stats);
   if (n > 0) {
-    z9_chain<<<(int)((n + kHashChunk - 1) / kHashChunk), 64, 0, st>>>(src, n, prev);
+    hash_chain_kernel<hash3><<<(int)((n + kHashChunk - 1) / kHashChunk), 64, 0, st>>>(src, n, prev);
     z9_search<<<(int)((n + 255) / 256), 256, 0, st>>>(src, n, prev, r1, r4, stats);
     z9_seg<<<(int)L.nseg, 256, 0, st>>>(r1, r4, n, summ, stats);
   }
   z9_link<<<1, 64, 0, st>>>(summ, L.nseg, sent, sbase, misc);
   if (n > 0) {
     z9_walk<<<(int)((L.nseg + 63) / 64), 64, 0, st>>>(r1, r4, n, L.nseg, sent, sbase, misc, spos, sld, stats);
-    z9_adler<<<(int)L.nad, 256, 0, st>>>(src, n, adl);
+    adler_partials_kernel<kAdler><<<(int)L.nad, 256, 0, st>>>(src, n, adl);
   }
   z9_block<<<(int)L.nbmax, 256, 0, st>>>(src, n, spos, sld, misc, blk, stats);
-  z9_offsets<<<1, 64, 0, st>>>(blk, misc, boff, adl, n > 0 ? L.nad : 0, n, words, L.words, out_len);
+  z9_offsets<<<1, 64, 0, st>>>(blk, misc, boff, adl, n, words, L.words, out_len);
   z9_emit<<<(int)L.nbmax, 256, 0, st>>>(src, spos, sld, misc, blk, boff, words, L.words);
   const int cgrid = (int)((L.bnd + 255) / 256 < 8192 ? (L.bnd + 255) / 256 : 8192);
-  z9_copy<<<cgrid, 256, 0, st>>>(words, L.bnd, out);
+  words_copy<<<cgrid, 256, 0, st>>>(words, L.bnd, out);
   RHCCQ_LAUNCH_CHECK(ctx);
   return RHCCQ_OK;
 }
@@ -962,7 +858,7 @@ int rhccq_zlib9_compress_host(const void* in, int64_t n, uint8_t* out, int64_t o
   const int64_t bnd = bound(n);
   if (out_cap < bnd) return RHCCQ_E_ARG;
   const uint8_t* src = (const uint8_t*)in;
-  // hash chains as z9_chain builds them
+  // hash chains as hash_chain_kernel<hash3> builds them
   std::vector<uint16_t> prev((size_t)n + 1, 0);
   {
     std::vector<int64_t> head(1 << 15, -1);
@@ -1036,12 +932,9 @@ int rhccq_zlib9_compress_host(const void* in, int64_t n, uint8_t* out, int64_t o
     for (int64_t i = B.sym0; i < B.sym0 + B.nsym; ++i) off = put_sym(B, sld[i], src[spos[i]], words.data(), nw, off);
     put_bits(words.data(), nw, off, B.lcode[256] & 0xFFFF, (int)(B.lcode[256] >> 16));
   }
-  uint64_t s1 = 1, s2 = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    s1 = (s1 + src[i]) % 65521u;
-    s2 = (s2 + s1) % 65521u;
-  }
-  put_frame(words.data(), nw, len, (uint32_t)(s2 << 16 | s1));
+  std::vector<uint32_t> adl((size_t)(2 * ((n + kAdler - 1) / kAdler)));
+  for (int64_t c = 0; c * kAdler < n; ++c) adler_chunk_sums(src + c * kAdler, n - c * kAdler < kAdler ? n - c * kAdler : kAdler, &adl[2 * c]);
+  put_frame(words.data(), nw, len, adler_fold(adl.data(), n, kAdler));
   for (int64_t i = 0; i < len; ++i) out[i] = (uint8_t)(words[(size_t)(i >> 2)] >> (8 * (i & 3)));
   *out_len = len;
   return RHCCQ_OK;

@@ -18,13 +18,17 @@
 //               before the worker's start, which only an earlier worker knows.
 //   zi_resolve  pointer jumping over the markers: every round replaces a marker by what its source holds; a chain of
 //               markers crosses at most one worker per hop, so ceil(log2(candidates)) + 1 rounds resolve all of them
-//   zi_emit     entries -> output bytes, and (sum b, sum (L - k) b_k) per 64 KiB chunk
-//   zi_final    one lane: Adler-32 of the chunks against the trailer
+//   zi_emit     entries -> output bytes, and (sum b, sum (L - k) b_k) per 64 KiB chunk (the sums of deflate_core.h's
+//               adler_chunk_sums, accumulated in the pass that writes the bytes)
+//   zi_final    one lane: Adler-32 of the chunks (deflate_core.h's adler_fold) against the trailer
+// The symbol bases and extra bits, the code-length order, the bit reversal, the Adler-32 modulus and fold are deflate_core.h's,
+// shared with the encoders whose mapping they invert.  Only the fixed code's lengths are written out in zi_worker (see there).
 // The parsing, table construction, block decoding, candidate test and chain walk are __host__ __device__ functions;
 // rhccq_zlib_decompress_host runs the same functions serially on the CPU (a test vehicle, never a fallback).
 // Malformed input never faults: every input read is bounds-checked against n (bits past the end read as zero and end
 // the decode as TRUNCATED), every write against out_cap and the workspace, every table index against its table, every
 // loop has a bound, and errors travel through the status word.
+#include "deflate_core.h"
 #include "rhccq_common.h"
 
 #include <hip/hip_runtime.h>
@@ -53,6 +57,9 @@
 
 namespace zi {
 
+using namespace rhccq::deflate;            // the symbol algebra and Adler-32
+using rhccq::align256;
+
 constexpr int64_t kSpan = 8192;            // input bytes per candidate search span (the parallelism knob)
 constexpr int64_t kSpanBits = kSpan * 8;
 constexpr int kRing = 32768;               // RFC 1951 window = the LDS ring of zi_write
@@ -60,7 +67,6 @@ constexpr int kWin = 4096;                 // input bytes a worker stages in LDS
 constexpr int kFast = 10;                  // bits of the direct Huffman lookup
 constexpr int64_t kAdlChunk = 65536;
 constexpr uint32_t kMark = 0x80000000u;
-constexpr uint32_t kBase = 65521u;
 
 // worker states besides the public RHCCQ_ZS_* errors
 constexpr int32_t kNone = -1;              // no candidate in this span
@@ -179,15 +185,6 @@ ZI_HD bool zi_code_ok(int kraft, int mx, int kind) {
   return true;
 }
 
-ZI_HD uint32_t zi_rev(uint32_t code, int len) {
-  uint32_t r = 0;
-  for (int k = 0; k < len && k < 16; ++k) {
-    r = (r << 1) | (code & 1);
-    code >>= 1;
-  }
-  return r;
-}
-
 // cooperative table build from len[0..n) (n <= 288), read by every lane after the call
 ZI_HD_NOINLINE void zi_build(Tab* t, const uint8_t* len, int n, int lane, int nl) {
   ZI_WSYNC();
@@ -222,7 +219,7 @@ ZI_HD_NOINLINE void zi_build(Tab* t, const uint8_t* len, int n, int lane, int nl
     if (L < 1 || L > kFast) continue;
     const uint32_t c = (uint32_t)(t->next[L] + (k - t->base[L]));
     if (c >= (1u << L)) continue;                    // only an invalid (over-subscribed) code gets here; never built
-    for (uint32_t x = zi_rev(c, L); x < (1u << kFast); x += 1u << L) t->fast[x] = (uint16_t)(s << 4 | L);
+    for (uint32_t x = bit_reverse(c, L); x < (1u << kFast); x += 1u << L) t->fast[x] = (uint16_t)(s << 4 | L);
   }
   ZI_WSYNC();
 }
@@ -258,20 +255,6 @@ ZI_HD int zi_decode(BR& r, const Tab* t, int lane, int nl) {
 
 ZI_HD int zi_bad_or_short(const BR& r) { return r.n * 8 - r.pos() < 15 ? RHCCQ_ZS_TRUNCATED : RHCCQ_ZS_BAD_DATA; }
 
-ZI_HD int zi_len_base(int s) {  // s = 257..285
-  if (s < 265) return s - 254;
-  if (s == 285) return 258;
-  const int e = (s - 261) >> 2;
-  return ((4 + ((s - 265) & 3)) << e) + 3;
-}
-ZI_HD int zi_len_extra(int s) { return (s < 265 || s == 285) ? 0 : (s - 261) >> 2; }
-ZI_HD int zi_dist_base(int d) {  // d = 0..29
-  if (d < 4) return d + 1;
-  const int e = (d >> 1) - 1;
-  return ((2 + (d & 1)) << e) + 1;
-}
-ZI_HD int zi_dist_extra(int d) { return d < 4 ? 0 : (d >> 1) - 1; }
-
 // dynamic block tree description after the 3-bit block header: lens[0..nlen + ndist) (written by lane 0), validated
 // as zlib validates it.  Returns RHCCQ_ZS_OK, BAD_DATA or TRUNCATED.  The reader is copied in and out so that the
 // caller's stays in registers; every array here is indexed by unrolled constants for the same reason.
@@ -284,7 +267,6 @@ ZI_HD_NOINLINE int zi_dynamic(BR* rp, uint8_t* lens, int* nlen_out, int* ndist_o
   *nlen_out = nlen;
   *ndist_out = ndist;
   uint32_t cl[19], rc[19];
-  constexpr int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 #pragma unroll
   for (int k = 0; k < 19; ++k) cl[k] = 0;
   if (r.over()) {
@@ -296,7 +278,7 @@ ZI_HD_NOINLINE int zi_dynamic(BR* rp, uint8_t* lens, int* nlen_out, int* ndist_o
 #pragma unroll
     for (int k = 0; k < 19; ++k) got[k] = k < ncode ? br_get(r, 3, lane, nl) : 0u;
 #pragma unroll
-    for (int k = 0; k < 19; ++k) cl[order[k]] = got[k];
+    for (int k = 0; k < 19; ++k) cl[codelen_order(k)] = got[k];
     if (r.over()) st = RHCCQ_ZS_TRUNCATED;
   }
   if (st == RHCCQ_ZS_OK) {
@@ -328,7 +310,7 @@ ZI_HD_NOINLINE int zi_dynamic(BR* rp, uint8_t* lens, int* nlen_out, int* ndist_o
       for (int q = 0; q < k; ++q) rank += cl[q] == cl[k] ? 1u : 0u;
 #pragma unroll
       for (int L = 1; L < 8; ++L) f = cl[k] == (uint32_t)L ? first[L] : f;
-      rc[k] = cl[k] ? zi_rev(f + rank, (int)cl[k]) : 0xFFFFu;
+      rc[k] = cl[k] ? bit_reverse(f + rank, (int)cl[k]) : 0xFFFFu;
     }
     int lk = 0, lm = 0, dk = 0, dm = 0;
     const int total = nlen + ndist;
@@ -481,6 +463,8 @@ ZI_HD void zi_worker(const uint8_t* in, int64_t n, int64_t start, const int64_t*
       if (bt == 1) {
         if (!fixed) {
           ZI_WSYNC();
+          // deflate_core.h's fixed_litlen_bits(s) for s < 288, then distance codes of 5 bits.  Written out on purpose: as
+          // s < 288 ? fixed_litlen_bits(s) : 5 the compiler gives zi_write 185 VGPRs for 180 and 14 more SGPR spills (zi_spec: 14 too)
           for (int s = lane; s < 318; s += nl) L->lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
           zi_build(&L->lt, L->lens, 288, lane, nl);
           zi_build(&L->dt, L->lens + 288, 30, lane, nl);
@@ -528,7 +512,7 @@ ZI_HD void zi_worker(const uint8_t* in, int64_t n, int64_t start, const int64_t*
           err = RHCCQ_ZS_BAD_DATA;
           break;
         }
-        const int len = zi_len_base(s) + (int)br_get(r, zi_len_extra(s), lane, nl);
+        const int len = len_base(s - 257) + (int)br_get(r, len_extra(s - 257), lane, nl);
         const int ds = zi_decode(r, &L->dt, lane, nl);
         if (ds < 0) {
           err = zi_bad_or_short(r);
@@ -538,7 +522,7 @@ ZI_HD void zi_worker(const uint8_t* in, int64_t n, int64_t start, const int64_t*
           err = RHCCQ_ZS_BAD_DATA;
           break;
         }
-        const int dist = zi_dist_base(ds) + (int)br_get(r, zi_dist_extra(ds), lane, nl);
+        const int dist = dist_base(ds) + (int)br_get(r, dist_extra(ds), lane, nl);
         if (r.over()) {
           err = RHCCQ_ZS_TRUNCATED;
           break;
@@ -640,19 +624,6 @@ ZI_HD void zi_chain(const uint8_t* in, int64_t n, const int64_t* cand, const Rec
   *status = st;
 }
 
-ZI_HD uint32_t zi_adler_final(const uint32_t* part, int64_t total) {
-  // part[2c] = sum of chunk c's bytes, part[2c + 1] = sum (L_c - k) b_k, both mod 65521
-  const int64_t nch = (total + kAdlChunk - 1) / kAdlChunk;
-  uint64_t a = 1, b = (uint64_t)(total % kBase);
-  for (int64_t c = 0; c < nch; ++c) {
-    const int64_t s = c * kAdlChunk, L = total - s < kAdlChunk ? total - s : kAdlChunk;
-    const uint64_t after = (uint64_t)((total - s - L) % kBase);
-    a = (a + part[2 * c]) % kBase;
-    b = (b + part[2 * c + 1] + after * part[2 * c]) % kBase;
-  }
-  return (uint32_t)(b << 16 | a);
-}
-
 ZI_HD void zi_finish(const uint8_t* in, int64_t n, const Ctl* ctl, const uint32_t* part, int64_t* out_len, int32_t* status) {
   if (!ctl->go) return;
   const int64_t t = ctl->tpos;
@@ -661,7 +632,7 @@ ZI_HD void zi_finish(const uint8_t* in, int64_t n, const Ctl* ctl, const uint32_
     return;
   }
   const uint32_t want = (uint32_t)in[t] << 24 | (uint32_t)in[t + 1] << 16 | (uint32_t)in[t + 2] << 8 | (uint32_t)in[t + 3];
-  if (zi_adler_final(part, ctl->total) != want) {
+  if (adler_fold(part, ctl->total, kAdlChunk) != want) {
     *status = RHCCQ_ZS_ADLER;
     *out_len = 0;
     return;
@@ -675,8 +646,6 @@ struct Layout {
   int64_t o_cand, o_rec, o_chain, o_choff, o_ctl, o_adl, o_tok, total;
 };
 
-inline int64_t up(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 inline Layout layout(int64_t n, int64_t out_cap) {
   Layout L;
   L.ns = n > 0 ? (n + kSpan - 1) / kSpan : 1;
@@ -685,19 +654,19 @@ inline Layout layout(int64_t n, int64_t out_cap) {
   for (int64_t v = 1; v < L.ns; v <<= 1) L.rounds++;
   int64_t o = 0;
   L.o_cand = o;
-  o = up(o + 8 * L.ns);
+  o = align256(o + 8 * L.ns);
   L.o_rec = o;
-  o = up(o + (int64_t)sizeof(Rec) * L.ns);
+  o = align256(o + (int64_t)sizeof(Rec) * L.ns);
   L.o_chain = o;
-  o = up(o + 4 * L.ns);
+  o = align256(o + 4 * L.ns);
   L.o_choff = o;
-  o = up(o + 8 * L.ns);
+  o = align256(o + 8 * L.ns);
   L.o_ctl = o;
-  o = up(o + (int64_t)sizeof(Ctl));
+  o = align256(o + (int64_t)sizeof(Ctl));
   L.o_adl = o;
-  o = up(o + 8 * L.nadl);
+  o = align256(o + 8 * L.nadl);
   L.o_tok = o;
-  o = up(o + 4 * (out_cap > 0 ? out_cap : 1));
+  o = align256(o + 4 * (out_cap > 0 ? out_cap : 1));
   L.total = o;
   return L;
 }
@@ -794,8 +763,8 @@ __global__ __launch_bounds__(256) void zi_emit(const Ctl* __restrict__ ctl, cons
     a = rhccq::block_sum(a, red);
     w = rhccq::block_sum(w, red);
     if (threadIdx.x == 0) {
-      part[2 * c] = (uint32_t)(a % kBase);
-      part[2 * c + 1] = (uint32_t)(w % kBase);
+      part[2 * c] = (uint32_t)(a % kAdlerMod);
+      part[2 * c + 1] = (uint32_t)(w % kAdlerMod);
     }
     __syncthreads();
   }
@@ -905,17 +874,10 @@ int rhccq_zlib_decompress_host(const uint8_t* in, int64_t n, uint8_t* out, int64
       tok[p] = s < p ? tok[s] : 0u;
     }
   std::vector<uint32_t> part(2 * Ly.nadl);
+  for (int64_t p = 0; p < ctl.total; ++p) out[p] = (uint8_t)(tok[p] & 255u);
   for (int64_t c = 0; c * kAdlChunk < ctl.total; ++c) {
-    const int64_t s = c * kAdlChunk, L = ctl.total - s < kAdlChunk ? ctl.total - s : kAdlChunk;
-    uint64_t a = 0, w = 0;
-    for (int64_t k = 0; k < L; ++k) {
-      const uint32_t v = tok[s + k] & 255u;
-      out[s + k] = (uint8_t)v;
-      a += v;
-      w += (uint64_t)(L - k) * v;
-    }
-    part[2 * c] = (uint32_t)(a % kBase);
-    part[2 * c + 1] = (uint32_t)(w % kBase);
+    const int64_t s = c * kAdlChunk;
+    adler_chunk_sums(out + s, ctl.total - s < kAdlChunk ? ctl.total - s : kAdlChunk, &part[2 * c]);
   }
   zi_finish(in, n, &ctl, part.data(), out_len, status);
   return RHCCQ_OK;

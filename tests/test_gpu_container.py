@@ -4,6 +4,8 @@ reference's index maps within 2 % of zlib level 9, and the files read back throu
 the host path's do."""
 import ctypes as C
 import glob
+import hashlib
+import json
 import os
 import zlib
 
@@ -57,6 +59,22 @@ def test_round_trip_awkward_inputs(rh):
         assert zlib.decompress(out) == data, name
         assert len(out) <= bound, (name, len(out), bound)
         assert out[0] == 0x78 and (out[0] << 8 | out[1]) % 31 == 0, name
+
+
+def test_bytes_pinned(rh):
+    """The stream is a function of the input bytes alone, across commits too: length and SHA-256 of every case of _inputs() of at most
+    150 000 bytes, and of `mix`, against tests/golden/zlib_fast_digests.json (taken from the encoder before its RFC core moved into
+    csrc/deflate_core.h).  A change that is meant to alter the bytes regenerates the fixture and says so."""
+    with open(os.path.join(G, "zlib_fast_digests.json")) as fh:
+        want = json.load(fh)
+    got = {}
+    for name, data in _inputs():
+        if len(data) <= 150000 or name == "mix":
+            out = _deflate(rh, data)
+            got[name] = {"length": len(out), "sha256": hashlib.sha256(out).hexdigest()}
+    assert sorted(got) == sorted(want) and len(want) == 38
+    for name in got:
+        assert got[name] == want[name], name
 
 
 def _raw_compress(rh, t, fill):
