@@ -22,6 +22,7 @@
 
 #include "km_wide_host.h"
 #include "rhccq_common.h"
+#include "wave_dpp.h"
 
 namespace rhccq {
 

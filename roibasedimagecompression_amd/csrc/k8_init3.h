@@ -92,15 +92,6 @@ __device__ __forceinline__ int g3_rank_in(unsigned long long m) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// inclusive scan over lanes 0 .. 31 only (what lanes 32 .. 63 end up with is not a scan): the wave total of those lanes must fit 32 bits
-__device__ __forceinline__ unsigned half_incscan_u32(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8  -> scan inside each row of 16
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-  return v;
-}
 // (measured and dropped: the items counter's fetch-and-add as a hand-written ds_add_rtn_u32 instead of atomicAdd() under `if (lane == 0)` with the
 // compiler's wave-aggregation around it -- 3.60 vs 3.57 us per pick: the inline wait and memory clobber cost more than the dozen instructions saved)
 // a whole 16-byte table entry in ONE ds_read_b128: left alone the compiler fetches box and maximum separately (b96 + b32), and 64 lanes reading
@@ -117,16 +108,6 @@ __device__ __forceinline__ uint4 g3_lds_b128(const uint4* p) {
 // ... plus a base: v_mbcnt adds its last operand for free
 __device__ __forceinline__ int g3_rank_add(unsigned long long m, int base) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
-}
-__device__ __forceinline__ unsigned dpp_quad_sum(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ unsigned dpp_quad_max(unsigned v) {
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));
-  return v;
 }
 
 // commit of one improved sample: both copies of the sample, the two levels of draw-order sums
@@ -164,7 +145,7 @@ __device__ __forceinline__ void g3_commit_quad(bool on, int b, uint32_t ck, int 
     g3_store1(i3, w3, n3, bb.z, bb.w, m0 + 3, samp, dsamp, dsum, dtop);
   }
   unsigned mx = max(max((unsigned)(w0 + (int)n0), (unsigned)(w1 + (int)n1)), max((unsigned)(w2 + (int)n2), (unsigned)(w3 + (int)n3)));
-  mx = dpp_quad_max(on ? mx : 0u);
+  mx = dpp_group_max<4>(on ? mx : 0u);
   if (on && j == 0) {
     blk[b].w = mx;
     const int slot = atomicAdd(n_touch, 1);
@@ -240,10 +221,10 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
     const int b = b0 + rq;
     const uint2 sv = samp[(b << 4) + rj];
     const uint32_t kk = sv.x & 0xffffffu;
-    const unsigned r1 = dpp_row_max(key_r(kk)), r0 = 255u - dpp_row_max(255u - key_r(kk));
-    const unsigned g1 = dpp_row_max(key_g(kk)), g0 = 255u - dpp_row_max(255u - key_g(kk));
-    const unsigned b1 = dpp_row_max(key_b(kk)), bl0 = 255u - dpp_row_max(255u - key_b(kk));
-    const unsigned dm = dpp_row_max((unsigned)(j_cprime(sv.y) + (int)norm2_key(kk)));
+    const unsigned r1 = dpp_group_max<16>(key_r(kk)), r0 = 255u - dpp_group_max<16>(255u - key_r(kk));
+    const unsigned g1 = dpp_group_max<16>(key_g(kk)), g0 = 255u - dpp_group_max<16>(255u - key_g(kk));
+    const unsigned b1 = dpp_group_max<16>(key_b(kk)), bl0 = 255u - dpp_group_max<16>(255u - key_b(kk));
+    const unsigned dm = dpp_group_max<16>((unsigned)(j_cprime(sv.y) + (int)norm2_key(kk)));
     if (rj == 0) blk[b] = make_uint4(box_pair(r0, r1), box_pair(g0, g1), box_pair(bl0, b1), dm);
   }
   for (int d = wave; d < nd; d += kG3Waves) {
@@ -353,7 +334,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
         // the whole potential fits 32 bits (every pick of a photo's chain: 90 000 samples x ~10^4): ONE scan of the <= 24 top-level
         // sums over half a wave (5 shifted adds) instead of two 16-bit-limb scans over the whole wave and 64-bit compares
         const unsigned v = lane < ntop ? v_top : 0u;
-        const unsigned inc = half_incscan_u32(v);
+        const unsigned inc = dpp_incscan_u32<32>(v);
         const unsigned exc = inc - v;
 #pragma unroll
         for (int c2 = 0; c2 < kCW; ++c2) {
@@ -383,7 +364,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
 #pragma unroll
         for (int c2 = 0; c2 < kCW; ++c2) {
           const unsigned w2 = v2[c2];
-          const unsigned inc2 = wave_incscan_u32(w2);
+          const unsigned inc2 = dpp_incscan_u32<64>(w2);
           const unsigned long long m2 = __ballot(w2 > 0 && (inc2 - w2) < rr[c2] && rr[c2] <= inc2);
           found[c2] = found[c2] && m2 != 0ull;
           const int l2 = m2 ? __ffsll((long long)m2) - 1 : 0;
@@ -399,8 +380,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int c2 = 0; c2 < kCW; ++c2) {
-          const int i = (bh[c2] << 6) + lane;
-          const unsigned inc3 = wave_incscan_u32(sv[c2].y);                       // 64 x 195075 fits 32 bits
+          const unsigned inc3 = dpp_incscan_u32<64>(sv[c2].y);                       // 64 x 195075 fits 32 bits
           const unsigned long long m3 = __ballot(inc3 >= rr3[c2]);               // (a padding slot adds nothing: never the first lane to reach the target)
           const int l3 = m3 ? __ffsll((long long)m3) - 1 : min(63, n - 1 - (bh[c2] << 6));
           // R = 0: position 0; a target beyond the total (cannot happen): the last sample
@@ -691,7 +671,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
       for (int i = tid - NW * 64; i < n_touched * 16; i += kG3Threads - NW * 64) {
         const int sb = touch_r[i >> 4], b = sb * 16 + (i & 15);
         unsigned m = b < nb ? blk[b].w : 0u;
-        m = dpp_row_max(m);
+        m = dpp_group_max<16>(m);
         if ((i & 15) == 0) { sup[sb].w = m; supw[sb] = m; }
       }
       // ... and the maxima of their hypers, straight from the leaves (256 per hyper, four per lane): independent of the super writes
@@ -704,7 +684,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
         for (int i = tid - NW * 64; i < n_touched * 16; i += kG3Threads - NW * 64) {
           const int h = touch_r[i >> 4] >> 4;
           unsigned m = supw[h * 16 + (i & 15)];
-          m = dpp_row_max(m);
+          m = dpp_group_max<16>(m);
           if ((i & 15) == 0) hyp[h].w = m;
         }
       }
@@ -777,7 +757,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
           const int t = (int)(kw[s] >> 24) & (kTMaxI - 1);
           const uint2 cc = kc[s];
           unsigned imp = j_eval4(cc.x, (int)cc.y, ka[s], kb[s]);
-          imp = dpp_quad_sum((kw[s] >> 28) ? 0u : imp);
+          imp = dpp_group_sum<4>((kw[s] >> 28) ? 0u : imp);
           if (qj == 0 && imp) atomicAdd(&sh.delta[t], (unsigned long long)imp);
         }
       }
@@ -791,7 +771,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
           const uint2 cc = sh.ck[w >> 24];
           imp = j_eval4(cc.x, (int)cc.y, p4[0], p4[1]);
         }
-        imp = dpp_quad_sum(imp);
+        imp = dpp_group_sum<4>(imp);
         if (on && qj == 0 && imp) atomicAdd(&sh.delta[w >> 24], (unsigned long long)imp);
       }
     } else {
@@ -838,10 +818,10 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
     const unsigned dhi = lane < T ? (unsigned)(dv >> 32) : 0u, dlo = lane < T ? (unsigned)dv : 0u;
     unsigned long long bd;
     if (__builtin_amdgcn_readfirstlane((int)(pot >> 32)) == 0) {
-      bd = (unsigned)__builtin_amdgcn_readlane((int)dpp_row_max(dlo), 0);
+      bd = (unsigned)__builtin_amdgcn_readlane((int)dpp_group_max<16>(dlo), 0);
     } else {
-      const unsigned mhi = (unsigned)__builtin_amdgcn_readlane((int)dpp_row_max(dhi), 0);
-      const unsigned mlo = (unsigned)__builtin_amdgcn_readlane((int)dpp_row_max(dhi == mhi ? dlo : 0u), 0);
+      const unsigned mhi = (unsigned)__builtin_amdgcn_readlane((int)dpp_group_max<16>(dhi), 0);
+      const unsigned mlo = (unsigned)__builtin_amdgcn_readlane((int)dpp_group_max<16>(dhi == mhi ? dlo : 0u), 0);
       bd = ((unsigned long long)mhi << 32) | mlo;
     }
     const int best = __ffsll((long long)__ballot(lane < T && dv == bd)) - 1;
@@ -905,7 +885,7 @@ __global__ __launch_bounds__(kG3Threads) void mbk_init3_kernel(const uint32_t* _
         const int w0 = i0 > 0 ? nabest - e : c0;
         const unsigned n0 = norm2_key(sv.x & 0xffffffu);
         g3_store1(i0, w0, n0, sv.x, sv.y, m, samp, dsamp, dsum, dtop);
-        const unsigned mx = dpp_row_max((unsigned)(w0 + (int)n0));
+        const unsigned mx = dpp_group_max<16>((unsigned)(w0 + (int)n0));
         if (rj == 0) blk[m >> 4].w = mx;
       }
     }

@@ -33,6 +33,7 @@
 #include "chain_release_host.h"
 #include "mbk_schedule.h"
 #include "rhccq_common.h"
+#include "wave_dpp.h"
 
 namespace rhccq {
 
@@ -140,49 +141,7 @@ __device__ unsigned long long g_wave_stamps[8][16];       // [phase][wave]: cycl
 #define SUB(slot) do {} while (0)
 #endif
 
-// ---- wave helpers on DPP (VALU, no LDS crossbar): sums / max of one u32 per lane ---------------------
-__device__ __forceinline__ unsigned dpp_row_sum(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);   // row_mirror
-  return v;                                                                        // every lane: sum of its row of 16
-}
-__device__ __forceinline__ unsigned dpp_row_max(unsigned v) {
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));
-  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));
-  return v;
-}
-// wave-uniform results (scalar): sum (< 2^32 required) / max over the 64 lanes
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-  v = dpp_row_sum(v);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned)__builtin_amdgcn_readlane((int)v, 16) +
-         (unsigned)__builtin_amdgcn_readlane((int)v, 32) + (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-  v = dpp_row_max(v);
-  return max(max((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
-             max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
-}
-// inclusive scan of one u32 per lane over the wave on DPP (gfx9 row_shr / row_bcast forms): 6 shifted adds on
-// the VALU instead of 6 LDS-crossbar permutes.  The wave total must fit 32 bits.
-__device__ __forceinline__ unsigned wave_incscan_u32(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8  -> scan inside each row of 16
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
-  return v;
-}
-// exact u64 inclusive scan of values < 2^32 from two u32 scans of 16-bit limbs (limb totals < 2^32)
-__device__ __forceinline__ unsigned long long wave_incscan_limbs(unsigned v) {
-  const unsigned hi = wave_incscan_u32(v >> 16), lo = wave_incscan_u32(v & 0xffffu);
-  return ((unsigned long long)hi << 16) + lo;
-}
-
+// (the DPP sums, maxima and scans of one u32 per lane are in wave_dpp.h; this one takes the LDS crossbar for sums past 32 bits)
 __device__ __forceinline__ unsigned long long wave_incscan_u64(unsigned long long v) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -363,7 +322,7 @@ __device__ __forceinline__ void init_body(const uint32_t* __restrict__ keys, con
           // level 2: the 16 blocks of the super-block
           const int b2 = sb * 16 + (lane & 15);
           const unsigned long long v2 = (lane < 16 && b2 < nb) ? tb.dsum[b2] : 0u;
-          const unsigned long long inc2 = wave_incscan_u32((unsigned)v2);     // 16 blocks x < 1.25e7 fits 32 bits
+          const unsigned long long inc2 = dpp_incscan_u32<64>((unsigned)v2);     // 16 blocks x < 1.25e7 fits 32 bits
           const unsigned long long m2 = __ballot(lane < 16 && v2 > 0 && (double)(cum + inc2 - v2) < r && r <= (double)(cum + inc2));
           if (m2) {
             const int l2 = __ffsll((long long)m2) - 1;
@@ -372,7 +331,7 @@ __device__ __forceinline__ void init_body(const uint32_t* __restrict__ keys, con
             // level 3: the 64 samples of the block
             const int i = (b << 6) + lane;
             const uint2 sv = dsamp[i];
-            const unsigned long long inc3 = wave_incscan_u32(i < n ? sv.y : 0u);   // 64 x 195075 fits 32 bits
+            const unsigned long long inc3 = dpp_incscan_u32<64>(i < n ? sv.y : 0u);   // 64 x 195075 fits 32 bits
             const unsigned long long m3 = __ballot(i < n && (double)(cum2 + inc3) >= r);
             const int l3 = m3 ? __ffsll((long long)m3) - 1 : min(63, n - 1 - (b << 6));
             cand = (b << 6) + l3;
@@ -741,13 +700,6 @@ __device__ __forceinline__ uint2 jpack(uint32_t key, int cprime, uint32_t dpos) 
 __device__ __forceinline__ int j_cprime(uint32_t y) { return (int)(y << 13) >> 13; }
 __device__ __forceinline__ uint32_t j_dpos(uint32_t x, uint32_t y) { return (x >> 24) | ((y >> 19) << 8); }
 
-__device__ __forceinline__ unsigned row_incscan_u32(unsigned v) {                 // inclusive scan inside each row of 16 lanes
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
-  return v;
-}
 __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
   return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
 }
@@ -796,7 +748,7 @@ __device__ __forceinline__ void j_commit_row(bool on, int b, uint32_t ck, int na
     j_store1(i3, w3, n3, bb.z, bb.w, m0 + 3, samp, dsamp, dsum, dssum);
   }
   unsigned mx = max(max((unsigned)(w0 + (int)n0), (unsigned)(w1 + (int)n1)), max((unsigned)(w2 + (int)n2), (unsigned)(w3 + (int)n3)));
-  mx = dpp_row_max(on ? mx : 0u);
+  mx = dpp_group_max<16>(on ? mx : 0u);
   if (on && j == 0) {
     blk[b].w = mx;
     const int slot = atomicAdd(n_touch, 1);
@@ -1049,7 +1001,7 @@ __global__ __launch_bounds__(kJThreads) void mbk_init2_kernel(const uint32_t* __
             // level 2: the 16 draw blocks of the super-block
             const int b2 = sbh * 16 + (lane & 15);
             const unsigned v2 = (lane < 16 && b2 < nb) ? dsum[b2] : 0u;
-            const unsigned long long cum2 = base + row_incscan_u32(v2);
+            const unsigned long long cum2 = base + dpp_incscan_u32<16>(v2);
             const unsigned long long m2 = __ballot(lane < 16 && v2 > 0 && (cum2 - v2) < R && R <= cum2);
             if (m2) {
               const int l2 = __ffsll((long long)m2) - 1;
@@ -1058,7 +1010,7 @@ __global__ __launch_bounds__(kJThreads) void mbk_init2_kernel(const uint32_t* __
               // level 3: the 64 samples of the draw block
               const int i = (bh << 6) + lane;
               const uint2 sv = dsamp[i];
-              const unsigned inc3 = wave_incscan_u32(i < n ? sv.y : 0u);          // 64 x 195075 fits 32 bits
+              const unsigned inc3 = dpp_incscan_u32<64>(i < n ? sv.y : 0u);          // 64 x 195075 fits 32 bits
               const unsigned long long m3 = __ballot(i < n && inc3 >= rr);
               const int l3 = m3 ? __ffsll((long long)m3) - 1 : min(63, n - 1 - (bh << 6));
               cand = (bh << 6) + l3;
@@ -1119,7 +1071,7 @@ __global__ __launch_bounds__(kJThreads) void mbk_init2_kernel(const uint32_t* __
       for (int i = tid - T * 64; i < n_touched * 16; i += kJThreads - T * 64) {
         const int sb = touch_r[i >> 4], b = sb * 16 + (i & 15);
         unsigned m = b < nb ? blk[b].w : 0u;
-        m = dpp_row_max(m);
+        m = dpp_group_max<16>(m);
         if ((i & 15) == 0) sup[sb].w = m;
       }
     }
@@ -1189,7 +1141,7 @@ __global__ __launch_bounds__(kJThreads) void mbk_init2_kernel(const uint32_t* __
         if (4 * (wave + s * kJWaves) < n_items) {
           const int t = (int)(kw[s] >> 24) & (kTMaxI - 1);
           unsigned imp = j_eval4(sh.ckey[t], (int)sh.cna[t], ka[s], kb[s]);
-          imp = dpp_row_sum((kw[s] >> 28) ? 0u : imp);
+          imp = dpp_group_sum<16>((kw[s] >> 28) ? 0u : imp);
           if (rj == 0 && imp) atomicAdd(&sh.delta[t], (unsigned long long)imp);
         }
       }
@@ -1203,7 +1155,7 @@ __global__ __launch_bounds__(kJThreads) void mbk_init2_kernel(const uint32_t* __
           const int t = (int)(w >> 24);
           imp = j_eval4(sh.ckey[t], (int)sh.cna[t], p4[0], p4[1]);
         }
-        imp = dpp_row_sum(imp);
+        imp = dpp_group_sum<16>(imp);
         if (on && rj == 0 && imp) atomicAdd(&sh.delta[w >> 24], (unsigned long long)imp);
       }
     } else {
@@ -2425,7 +2377,7 @@ __global__ __launch_bounds__(1024) void grid_build_kernel(const MbkP* __restrict
   for (int it = 0; it < kPerWave / 64; ++it) {
     const int idx = w * kPerWave + it * 64 + lane;
     const unsigned v = cnt[idx];
-    const unsigned inc = wave_incscan_u32(v);
+    const unsigned inc = dpp_incscan_u32<64>(v);
     cnt[idx] = running + inc - v;                          // cursor = start of the cell
     running += __shfl(inc, 63, 64);
   }

@@ -16,7 +16,7 @@
 //             one DPP scan per candidate gives the thread's prefix inside its wave and the wave's total -> LDS     (barrier 2)
 //   choose    every thread adds up the wave totals per candidate (the candidate potentials), takes the first smallest, lowers its
 //             closest distances against that candidate and gets its NEXT `base` from the same wave totals: no scan of its own.
-// (included inside namespace rhccq, behind rhccq_common.h)
+// (included inside namespace rhccq, behind rhccq_common.h and wave_dpp.h)
 
 constexpr int kFlatT = 16;          // n_local_trials = 2 + int(ln k) <= 16
 constexpr int kFlatWaves = 16;      // workgroups of up to 1 024 threads
@@ -28,16 +28,6 @@ struct __align__(16) FlatShared {
   double u[2][kFlatT];                   // the uniforms of this pick and of the next (a cold line in HBM: fetched one pick ahead)
   unsigned long long red[kFlatWaves + 1];
 };
-
-__device__ __forceinline__ unsigned flat_incscan_u32(unsigned v) {   // inclusive scan over the wave on DPP (see wave_incscan_u32)
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-  return v;
-}
 
 // skey(i): colour of the sample at draw position i (0 <= i < n); n <= kS * blockDim.x; rand: (k - 1) * T uniforms in pick order;
 // chosen[0 .. k): the draw positions picked (chosen[0] = first).  All threads of the workgroup call; ends with a barrier.
@@ -74,7 +64,7 @@ __device__ __forceinline__ void kpp_flat(KeyFn skey, const int n, const int k, c
   // potential and the threads' exclusive prefixes of the closest distances, once by a block scan
   unsigned long long pot, base;
   {
-    const unsigned inc = flat_incscan_u32(loc);                       // <= 64 x 16 x 195 075 < 2^32
+    const unsigned inc = dpp_incscan_u32<64>(loc);                       // <= 64 x 16 x 195 075 < 2^32
     if (lane == 63 && act) sh.red[wave] = inc;
     if (tid < T && k > 1) sh.u[1][tid] = rand[tid];
     __syncthreads();
@@ -145,7 +135,7 @@ __device__ __forceinline__ void kpp_flat(KeyFn skey, const int n, const int k, c
 #pragma unroll
         for (int s = 0; s < kS; ++s) sm += min(cp[s], nb - 2 * (int)__builtin_amdgcn_udot4(ck, key[s], 0u, false));
         acc[t] = sna + (unsigned)sm;
-        inc[t] = flat_incscan_u32(acc[t]);
+        inc[t] = dpp_incscan_u32<64>(acc[t]);
         if (lane == 63) sh.wtot[t][wave] = inc[t];
       }
     }

@@ -6,6 +6,7 @@
 // Per channel the weighted sum A = 7 E(left) + E(up-left) + 5 E(up) + 3 E(up-right) has |A| <= 16 * 255 = 4080; with a strength of at
 // most 256, |s A + 2048| < 2^21: int32 throughout.  The shift by 12 is arithmetic, so the quotient is floored toward minus infinity.
 #pragma once
+#include "band_handoff.h"
 #include "palette_runs.h"
 
 namespace rhccq {
@@ -18,11 +19,7 @@ constexpr int kDitherPitch = kDitherCols + 1;  // dwords between the rows of a t
 constexpr int kDitherRowsMin = 4;              // image rows of a band, a power of two in [min, max]: 64 / rows lanes share a pixel's search,
 constexpr int kDitherRowsMax = 32;             // and 2..16 lanes are inside one DPP row
 constexpr int kDitherRowsDefault = 4;
-constexpr int kDitherGranule = 4;              // hand-over words a band fetches from its predecessor at a time
-constexpr int kDitherHeadWords = 64;           // the workspace's head: word 0 the ticket, word 1 the abort word; the hand-over words follow
-constexpr uint32_t kDitherWritten = 0x80000000u;
-constexpr uint32_t kDitherSpinCheck = 256u;    // a waiter looks at the abort word every so many re-reads
-constexpr uint32_t kDitherSpinBound = 1u << 24;    // and gives up after so many
+constexpr int kDitherGranule = 4;              // hand-over words a band fetches from its predecessor at a time (band_handoff.h)
 
 struct DitherStrength { uint32_t v[kRemapMaxClasses + 1]; };
 struct DitherErr { int32_t r, g, b; };
@@ -65,10 +62,7 @@ __host__ __device__ __forceinline__ uint32_t dither_entry_colour(RemapEntry e) {
 // bands of `rows` image rows
 static inline int64_t dither_bands(int64_t H, int64_t rows) { return (H + rows - 1) / rows; }
 // the workspace: the head and one word per pixel of every band's last row but the last band's, for the band height that needs the most
-static inline int64_t dither_work_bytes(int64_t H, int64_t W, int64_t rows) {
-  const int64_t bands = dither_bands(H, rows);
-  return 4 * (kDitherHeadWords + (bands > 1 ? (bands - 1) * W : 0));
-}
+static inline int64_t dither_work_bytes(int64_t H, int64_t W, int64_t rows) { return band::work_bytes(dither_bands(H, rows), W); }
 
 // the argument tests of both forms, in rhccq_palette_runs' order, then the strengths; the device form appends its own
 static inline int dither_check(rhccq_ctx* ctx, const void* rgb, int32_t H, int32_t W, const void* palette, int32_t K, const void* cls, int32_t n_classes,

@@ -20,35 +20,17 @@
 //           before the walk of tile T.  A step's pixel word is read one step ahead of its use;
 //   finish  all 64 lanes, a row segment at a time, from LDS: the index is written where it differs from b (rhccq_palette_remap's, which
 //           the call has put there), and the squared error against the ORIGINAL pixel and the moved flag go to the sums.
-// Between bands.  Row 0 of band n needs the errors of the last row of band n - 1.  That row stores every error as one word, bit 31 set,
-// into the workspace (zeroed on the stream before the launch) with relaxed agent-scope atomic stores, a granule of 4 words per store
-// instruction; band n re-reads a granule at a time with relaxed agent-scope atomic loads until all its words carry bit 31.  Value and mark are one word, so there is no flag beside it and no
-// fence.  The words of the next granule are requested a granule ahead and have usually landed when they are needed.
-// Forward progress.  A band's number is a ticket drawn from the workspace when the workgroup starts, not blockIdx: the band it waits for
-// drew its ticket earlier, so it has started, and by induction waits only for bands that have; band 0 waits for nothing.  No workgroup
-// waits for one that may not be resident, whatever the grid and the device.  The wait is bounded all the same: every 256 re-reads the
-// waiter looks at the abort word, past 2^24 re-reads it raises it and sets *status.  A band that gave up, or saw the abort word, waits
-// no more: it runs on with zeros for the words it did not get and ends in the time an unhindered band takes; what it writes means nothing.
-// (No early return from inside the walk: the compiler then merges that path into every step and waits for all memory traffic there.)
+// Between bands.  Row 0 of band n needs the errors of the last row of band n - 1: the hand-over of band_handoff.h, which also holds the
+// forward-progress argument (a band that gives up sets *status).  A word is an error and the mark; the last row's words leave a granule
+// of 4 per store instruction, and band n fetches a granule of 4 at a time.
 #include "palette_dither.h"
+#include "wave_dpp.h"
 
 namespace rhccq {
 
 // palette entries in LDS: padded to 128, so that every lane's slice is a multiple of four pairs for any G <= 16
 __host__ __device__ __forceinline__ int dither_padded(int K) { return (K + 127) & ~127; }
 static size_t dither_lds_bytes(int rows, int K) { return (size_t)dither_padded(K) * 8 + (size_t)3 * rows * kDitherPitch * 4; }
-
-// min over the G lanes that share a pixel (G a power of two <= 16, aligned: inside one DPP row), the result in all of them
-template <int G>
-__device__ __forceinline__ uint32_t dither_group_min(uint32_t v) {
-  if (G >= 2) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-  if (G >= 4) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
-  if (G >= 8) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));    // row_half_mirror
-  if (G >= 16) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
-__device__ __forceinline__ uint32_t dither_word_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ uint32_t dither_index_load(const void* idx, int eb, long long p) {
   return eb == 1 ? (uint32_t)((const uint8_t*)idx)[p] : eb == 2 ? (uint32_t)((const uint16_t*)idx)[p] : ((const uint32_t*)idx)[p];
@@ -94,7 +76,7 @@ __global__ __launch_bounds__(kDitherLanes) void palette_dither_kernel(const uint
   uint32_t* s_px = reinterpret_cast<uint32_t*>(s_pal + K2);                            // [R][65] each: the pixel | its class row << 24,
   uint32_t* s_b = s_px + R * kDitherPitch;                                             // b,
   uint32_t* s_out = s_b + R * kDitherPitch;                                            // the output index
-  if (lane == 0) s_band = __hip_atomic_fetch_add(&work[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the ticket
+  band::draw_ticket(work, &s_band, lane);
   for (int j = lane; j < K2; j += kDitherLanes) s_pal[j] = j < K ? remap_pack_entry(pal + (long long)j * 3, j) : RemapEntry{0u, 0xFFFFFFFFu};
   if (lane < kRemapMaxClasses * 3) (&s_cls[0][0])[lane] = 0ull;
   if (lane <= n_classes) s_str[lane] = strength.v[lane];
@@ -105,10 +87,9 @@ __global__ __launch_bounds__(kDitherLanes) void palette_dither_kernel(const uint
   const long long y0 = (long long)band * R;
   const int nrows = (int)min((long long)R, H - y0);
   const long long nsteps = (long long)W + 2 * nrows - 1;
-  const uint32_t* up_words = work + kDitherHeadWords + (long long)(band - 1) * W;      // (band > 0 only) the last row of the band above
-  uint32_t* my_words = work + kDitherHeadWords + (long long)band * W;
+  const uint32_t* up_words = band::words(work, band - 1, W);                           // (band > 0 only) the last row of the band above
+  uint32_t* my_words = band::words(work, band, W);
   const bool hand_on = band + 1 < nbands;
-  uint32_t* abort_word = work + 1;
 
   DitherTile<R> t;
   dither_load<R>(t, rgb, idx, eb, cls, y0, nrows, W, 0ll, lane);
@@ -135,27 +116,8 @@ __global__ __launch_bounds__(kDitherLanes) void palette_dither_kernel(const uint
     uint32_t w_next = s_px[o_row];
     for (int s = 0; s < ns; ++s) {
       const long long u = u0 + s;
-      if (waiting && (u & (kDitherGranule - 1)) == 0) {                                // the words of columns u .. u + 3 of the row above
-        const long long c = u + lane;
-        const bool on = lane < kDitherGranule && c < W;
-        for (uint32_t spins = 0; !__all(!on || (pending & kDitherWritten) != 0u); ++spins) {
-          if ((spins & (kDitherSpinCheck - 1u)) == kDitherSpinCheck - 1u) {
-            const bool told = __any(dither_word_load(abort_word) != 0u);               // another band gave up
-            if (told || spins > kDitherSpinBound) {                                    // stop waiting, here and for the rest of the band
-              if (!told && lane == 0) {                                                // this one gives up: the others and the caller are told
-                __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-              waiting = false;
-              break;
-            }
-          }
-          if (spins) __builtin_amdgcn_s_sleep(2);
-          pending = dither_word_load(up_words + min(c, (long long)W - 1));             // (every lane loads, a clamped address: no masked load)
-        }
-        gran = on ? pending : 0u;                                                      // (consumed before the next request is issued)
-        pending = dither_word_load(up_words + min(c + kDitherGranule, (long long)W - 1));   // (the lanes that are not `on` then are ignored then)
-      }
+      if (waiting && (u & (kDitherGranule - 1)) == 0)                                  // the words of columns u .. u + 3 of the row above
+        band::fetch_granule<kDitherGranule>(up_words, u, W, lane, work + band::kAbortWord, (uint32_t*)status, waiting, gran, pending);
       const long long x = u - 1 - 2 * r;
       const bool active = r < nrows && x >= 0 && x < W;
       const uint32_t w = w_next;
@@ -165,7 +127,7 @@ __global__ __launch_bounds__(kDitherLanes) void palette_dither_kernel(const uint
       for (int j = 0; j < 4; ++j) q[j] = s_dyn[g + j * G];
       const uint32_t sv = s_str[w >> 24];
       // the error above-right: from the band above for row 0, else what the row group above computed a step ago
-      const uint32_t from_band = (uint32_t)__builtin_amdgcn_readlane((int)gran, (int)(u & (kDitherGranule - 1))) & ~kDitherWritten;
+      const uint32_t from_band = (uint32_t)__builtin_amdgcn_readlane((int)gran, (int)(u & (kDitherGranule - 1))) & ~band::kWritten;
       const uint32_t from_row = (uint32_t)__shfl_up((int)e_last, G, kDitherLanes);
       e_ul = e_up;
       e_up = e_ur;
@@ -186,21 +148,21 @@ __global__ __launch_bounds__(kDitherLanes) void palette_dither_kernel(const uint
           best = min(best, remap_eval(target, RemapEntry{c[j].z, c[j].w}));
         }
       }
-      best = dither_group_min<G>(best);
+      best = dpp_group_min<G>(best);                                                   // (G <= 16, aligned: inside one DPP row)
       const uint32_t out = best & ((1u << kRemapIdxBits) - 1u);
       const DitherErr e = dither_error(target, dither_entry_colour(s_pal[out]));
       e_left = active ? e : DitherErr{0, 0, 0};
       e_last = active ? dither_pack(e) : 0u;
       if (active && g == 0) {
         s_out[o_row + s] = out;
-        if (hand_on && r == R - 1) s_hand[x & (kDitherGranule - 1)] = e_last | kDitherWritten;
+        if (hand_on && r == R - 1) s_hand[x & (kDitherGranule - 1)] = e_last | band::kWritten;
       }
       // the last row's errors leave a granule at a time: one store instruction, and one wait for it, every fourth step
       const long long xl = u - 1 - 2 * (R - 1);                                        // (wave uniform) the last row's column
       if (hand_on && xl >= 0 && xl < W && ((xl & (kDitherGranule - 1)) == kDitherGranule - 1 || xl == W - 1)) {
         __syncthreads();
         if (lane <= (int)(xl & (kDitherGranule - 1)))
-          __hip_atomic_store(my_words + (xl & ~(long long)(kDitherGranule - 1)) + lane, s_hand[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          band::word_store(my_words + (xl & ~(long long)(kDitherGranule - 1)) + lane, s_hand[lane]);
       }
     }
     __syncthreads();

@@ -32,18 +32,16 @@
 #include <vector>
 
 #include "palette_segment.h"
+#include "wave_dpp.h"
 
 namespace rhccq {
 
 static int seg_slots(int K) { return (K + kSegLanes - 1) / kSegLanes; }
 
-// unsigned minimum over the wave, returned wave-uniform.  DPP moves only: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror and
-// row_mirror give every row of 16 lanes its minimum; lanes 0, 16, 32 and 48 go to the scalar unit
+// unsigned minimum over the wave, returned wave-uniform.  DPP moves only: the butterfly of wave_dpp.h gives every row of 16 lanes its
+// minimum; lanes 0, 16, 32 and 48 go to the scalar unit
 __device__ __forceinline__ uint32_t seg_wave_min(uint32_t v) {
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, true));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, true));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, true));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, true));
+  v = dpp_group_min<16>(v);
   const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
   const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
   // scalar minima, by name: the compiler would move the four values back to vector registers for one v_min3 and keep every use of the

@@ -5,6 +5,7 @@
 //   unfilter   unf_byte (one byte under one of the five filters) and the geometry of the banded wavefront and its hand-over words;
 //   expand     expand_pixel: one pixel of any colour type and depth to R, G, B, alpha and index.
 #pragma once
+#include "band_handoff.h"
 #include "png_write.h"
 
 namespace rhccq {
@@ -179,20 +180,14 @@ inline int64_t png_parse(const uint8_t* f, int64_t n, rhccq_png_info* info, rhcc
 // ---- unfilter ------------------------------------------------------------------------------------------------------------------------
 constexpr int kUnfRows = 64;                               // rows of a band: a lane a row
 constexpr int kUnfTile = 32;                               // steps of a staging tile
-constexpr int kUnfGranule = 16;                            // filter units a band fetches from its predecessor at a time
-constexpr int kUnfHeadWords = 64;                          // the workspace's head: 0 the ticket, 1 the abort word, 2 H - (first bad row), 3 stalled
-constexpr uint32_t kUnfWritten = 0x80000000u;              // a hand-over word: three bytes of the unit and this mark
-constexpr uint32_t kUnfSpinCheck = 256u;                   // a waiter looks at the abort word every so many re-reads
-constexpr uint32_t kUnfSpinBound = 1u << 24;               // and gives up after so many
+constexpr int kUnfGranule = 16;                            // filter units a band fetches from its predecessor at a time (band_handoff.h)
+constexpr int kUnfBadWord = 2, kUnfStalledWord = 3;        // the caller's words of the workspace's head: H - (first bad row), stalled
 
 RHCCQ_PNG_HD int unf_unit_words(int bpp) { return (bpp + 2) / 3; }
 inline int64_t unf_bands(int64_t H) { return (H + kUnfRows - 1) / kUnfRows; }
 // words of one handed-over row
 inline int64_t unf_row_words(int64_t rowbytes, int bpp) { return rowbytes / bpp * unf_unit_words(bpp); }
-inline int64_t unf_work_bytes(int64_t H, int64_t rowbytes, int bpp) {
-  const int64_t bands = unf_bands(H);
-  return 4 * (kUnfHeadWords + (bands > 1 ? (bands - 1) * unf_row_words(rowbytes, bpp) : 0));
-}
+inline int64_t unf_work_bytes(int64_t H, int64_t rowbytes, int bpp) { return band::work_bytes(unf_bands(H), unf_row_words(rowbytes, bpp)); }
 
 // the raw byte of the filtered byte x under type t (0..4) with a = left, b = above, c = upper left (raw bytes)
 RHCCQ_PNG_HD uint32_t unf_byte(int t, uint32_t x, uint32_t a, uint32_t b, uint32_t c) {

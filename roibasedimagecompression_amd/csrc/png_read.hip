@@ -25,17 +25,10 @@
 //               the row they are zero, not branched around), the walk reads and writes LDS only, and the raw bytes leave the same way.
 //               The loads are aligned dwords (the row's misalignment is an offset into its LDS row), a lane takes every 64th dword of
 //               the tile, and the loads of tile T + 1 are issued before the walk of tile T and land behind it;
-//   between bands   row 0 of band n needs the last row of band n - 1.  That row's lane stores every unit as one to three words (three bytes
-//               and bit 31 each) into the workspace, zeroed on the stream before the launch, with relaxed agent-scope atomic stores; band
-//               n re-reads a granule of 16 units at a time (a lane a word) with relaxed agent-scope atomic loads until all carry bit 31.
-//               Value and mark are one word: no flag beside it and no fence.  The next granule is requested a granule ahead.
-// Forward progress.  A band's number is a ticket drawn from the workspace when the workgroup starts, not blockIdx: the band it waits for
-// drew its ticket earlier, so it has started, and by induction waits only for bands that have; band 0 waits for nothing.  No workgroup
-// waits for one that may not be resident, whatever the grid and the device.  The wait is bounded all the same: every 256 re-reads the
-// waiter looks at the abort word, past 2^24 re-reads it raises it and sets the stalled word.  A band that gave up, or saw the abort word, waits
-// no more: it runs on with zeros for the words it did not get and ends in the time an unhindered band takes; what it writes means nothing.
-// (No early return from inside the walk: the compiler then merges that path into every step and waits for all memory traffic there.)
-// A band whose first row has filter type 0 or 1 reads nothing of the row above and does not wait at all.
+//   between bands   row 0 of band n needs the last row of band n - 1: the hand-over of band_handoff.h, which also holds the
+//               forward-progress argument (a band that gives up sets the stalled word).  That row's lane stores every unit as one to three
+//               words (three bytes and the mark each) as it produces them; band n fetches a granule of 16 units at a time.  A band whose
+//               first row has filter type 0 or 1 reads nothing of the row above and does not wait at all.
 #include "png_read.h"
 #include "rhccq_common.h"
 
@@ -141,7 +134,6 @@ __global__ __launch_bounds__(256) void idat_join_kernel(const uint8_t* __restric
 // ---- unfilter ------------------------------------------------------------------------------------------------------------------------
 struct Unit { uint32_t w[2]; };
 __device__ __forceinline__ uint32_t unit_byte(const Unit& v, int j) { return (v.w[j >> 2] >> (8 * (j & 3))) & 255u; }
-__device__ __forceinline__ uint32_t unf_word_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the dwords of a tile's rows on their way from global memory to LDS, kept exactly as loaded
 template <int DW>
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(kUnfRows) void unfilter_kernel(const uint8_t* __res
   __shared__ __attribute__((aligned(4))) uint8_t s_out[kUnfRows * kOutPitch];
   __shared__ uint32_t s_band;
   const int lane = threadIdx.x, r = lane;
-  if (lane == 0) s_band = __hip_atomic_fetch_add(&work[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the ticket
+  band::draw_ticket(work, &s_band, lane);
   __syncthreads();
 
   const int nbands = (H + kUnfRows - 1) / kUnfRows, band = (int)s_band;
@@ -186,16 +178,15 @@ __global__ __launch_bounds__(kUnfRows) void unfilter_kernel(const uint8_t* __res
   const long long in_pitch = rowbytes + 1;
   const int rel0 = (int)((uintptr_t)scan & 3), span = (int)((rel0 + H * in_pitch - 1) & ~3ll);   // (H * in_pitch < 2^31: the argument test)
   const uint8_t* base = scan - rel0;
-  const uint32_t* up_words = work + kUnfHeadWords + (long long)(band - 1) * nwords;   // (band > 0 only) the last row of the band above
-  uint32_t* my_words = work + kUnfHeadWords + (long long)band * nwords;
+  const uint32_t* up_words = band::words(work, band - 1, nwords);    // (band > 0 only) the last row of the band above
+  uint32_t* my_words = band::words(work, band, nwords);
   const bool hand_on = band + 1 < nbands;
-  uint32_t* abort_word = work + 1;
 
   UnfTile<DW> tile;
   unf_load<BPP, DW>(tile, base, rel0, (int)in_pitch, (int)y0, nrows, 0, span, lane);
   int t = r < nrows ? (int)scan[(y0 + r) * in_pitch] : 0;
   if (t > 4) {
-    __hip_atomic_fetch_max(&work[2], (uint32_t)(H - (y0 + r)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // H - row: the first bad row wins
+    __hip_atomic_fetch_max(&work[kUnfBadWord], (uint32_t)(H - (y0 + r)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // H - row: the first bad row wins
     t = 0;
   }
   bool waiting = band > 0 && __builtin_amdgcn_readfirstlane(t) >= 2; // (wave uniform) false once a band has given up
@@ -220,27 +211,8 @@ __global__ __launch_bounds__(kUnfRows) void unfilter_kernel(const uint8_t* __res
 
     for (int s = 0; s < ns; ++s) {
       const long long u = u0 + s;
-      if (waiting && (u & (kUnfGranule - 1)) == 0) {                 // the words of the units u .. u + 15 of the row above
-        const long long wi = u * WPU + lane;
-        const bool on = lane < kUnfGranule * WPU && wi < nwords;
-        for (uint32_t spins = 0; !__all(!on || (pending & kUnfWritten) != 0u); ++spins) {
-          if ((spins & (kUnfSpinCheck - 1u)) == kUnfSpinCheck - 1u) {
-            const bool told = __any(unf_word_load(abort_word) != 0u);                      // another band gave up
-            if (told || spins > kUnfSpinBound) {                     // stop waiting, here and for the rest of the band
-              if (!told && lane == 0) {                              // this one gives up: the others and the caller are told
-                __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(work + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-              waiting = false;
-              break;
-            }
-          }
-          if (spins) __builtin_amdgcn_s_sleep(2);
-          pending = unf_word_load(up_words + min(wi, nwords - 1));   // (every lane loads, a clamped address: no masked load)
-        }
-        gran = on ? pending : 0u;                                    // (consumed before the next request is issued)
-        pending = unf_word_load(up_words + min(wi + kUnfGranule * WPU, nwords - 1));       // (the lanes that are not `on` then are ignored then)
-      }
+      if (waiting && (u & (kUnfGranule - 1)) == 0)                   // the words of the units u .. u + 15 of the row above
+        band::fetch_granule<kUnfGranule * WPU>(up_words, u * WPU, nwords, lane, work + band::kAbortWord, work + kUnfStalledWord, waiting, gran, pending);
       const long long x = u - r;
       const bool active = r < nrows && x >= 0 && x < units;
       const Unit cur = cur_next;
@@ -274,10 +246,10 @@ __global__ __launch_bounds__(kUnfRows) void unfilter_kernel(const uint8_t* __res
         if (hand_on && r == kUnfRows - 1) {
 #pragma unroll
           for (int kk = 0; kk < WPU; ++kk) {
-            uint32_t word = kUnfWritten;
+            uint32_t word = band::kWritten;
 #pragma unroll
             for (int j = 3 * kk; j < 3 * kk + 3 && j < BPP; ++j) word |= unit_byte(out, j) << (8 * (j - 3 * kk));
-            __hip_atomic_store(my_words + x * WPU + kk, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            band::word_store(my_words + x * WPU + kk, word);
           }
         }
       }
@@ -296,7 +268,7 @@ __global__ __launch_bounds__(kUnfRows) void unfilter_kernel(const uint8_t* __res
 }
 
 __global__ void unfilter_status_kernel(const uint32_t* __restrict__ work, int H, int32_t* __restrict__ status) {
-  const Verdict v = png_verdict(-1, RHCCQ_ZS_OK, 0, 0, work[2], H, work[3]);
+  const Verdict v = png_verdict(-1, RHCCQ_ZS_OK, 0, 0, work[kUnfBadWord], H, work[kUnfStalledWord]);
   status[0] = v.status;
   status[1] = v.detail;
 }
@@ -371,7 +343,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const uint8_t* __restrict__
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const Verdict v = png_verdict(s_first == 0x7FFFFFFF ? -1 : s_first, *zs, *zlen, scan_bytes, unf[2], H, unf[3]);
+    const Verdict v = png_verdict(s_first == 0x7FFFFFFF ? -1 : s_first, *zs, *zlen, scan_bytes, unf[kUnfBadWord], H, unf[kUnfStalledWord]);
     status[0] = v.status;
     status[1] = v.detail;
   }

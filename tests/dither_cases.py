@@ -133,6 +133,10 @@ def _build():
     out["classes2"] = (img, pal37, cls, 2, [0, 256, 128], None)
     out["classes2_blocks"] = (img, pal37, blocks, 2, [256, 0, 0], None)
     out["classes16"] = (img, pal37, rng.integers(0, 18, img.shape[:2]).astype(np.uint8), 16, [16 * k for k in range(17)], None)
+    # the hand-over's granules of 4 words, two hand-overs each: a last granule that is exactly full (4, 8, 64), that holds one word (5, 9,
+    # 65), and widths at the staging tile's edge (63, 64, 65).  (Drawn last: the cases above keep their pictures.)
+    for w in (4, 5, 7, 8, 9, 63, 64, 65):
+        out[f"handover{2 * R + 1}x{w}"] = (_image(rng, 2 * R + 1, w), pal37, None, 0, 256, None)
     return out
 
 
