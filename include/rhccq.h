@@ -1169,6 +1169,54 @@ int rhccq_palette_pattern_batch_host(const uint8_t* rgb, const int64_t* px_off, 
                                      const int32_t* k_rows, const uint8_t* cls, int32_t n_classes, const uint32_t* strength, int32_t size, void* idx_out,
                                      int32_t idx_elem_bytes, uint64_t* sums);
 
+/* ---- EXTENSION: exact nearest-colour search through a colour-cell candidate grid (no reference counterpart; csrc/palette_grid.hip) ------
+ * A second path to rhccq_palette_remap's result, for large palettes: the palette is sorted once into per-cell candidate lists, and a pixel
+ * is evaluated against its own cell's list only.  The full search stays the default; indices and sums are identical bit for bit.
+ * Definition (all arithmetic in exact integers; c_j is palette row j):
+ *   cell     C of a pixel is (r >> 3, g >> 3, b >> 3), numbered (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3); its box is [lo, lo + 7] per
+ *            channel, lo = 8 x the cell's coordinate, hi = lo + 7.  rhccq_palette_grid_cell() is the side, 8.
+ *   dmin_j(C)  the squared distance from c_j to the nearest point of the box: per channel max(lo - c, 0, c - hi)^2, summed.
+ *   dmax_j(C)  the squared distance to the farthest point of the box: per channel max(|c - lo|, |c - hi|)^2, summed.
+ *   U(C)     min over j of dmax_j(C).
+ *   list     of C: { j : dmin_j(C) <= U(C) } in ascending j.  Every row that attains the minimum distance for any pixel of C is in it,
+ *            every tied row too: some row is within U(C) of every point of the box, and a row outside the list is farther than U(C) from
+ *            all of them.  So the search over the list that sends ties to the earliest position returns rhccq_palette_remap's index.
+ *   flagged  a cell has no list when its list is longer than rhccq_palette_grid_max_list() (1024), or when it would end beyond `entries`:
+ *            cells are placed in cell-number order, a cell of n <= 1024 rows takes n rounded up to even entries whether it fits or not,
+ *            and a cell above the cap takes none, so which cells are flagged is a function of palette and entries.  A pixel of a flagged
+ *            cell goes through the full search.
+ * Workspace of a grid (rhccq_palette_grid_bytes(K, entries); -1 for K outside 1..65536 or entries outside 0..33554432), E = entries rounded
+ * down to even and at least 2, every piece at a multiple of 256 bytes:
+ *   cells  uint32[32768][2] at 0: {first entry (even), rows of the list}; rows == 0: flagged
+ *   U      uint32[32768] at 262144, and the rows with dmin <= U: uint32[32768] at 393216 (both as the count pass left them)
+ *   lists  at 524288: E entries of two uint32, the packed row of the search (csrc/palette_remap.h) whose 12-bit index is the position in
+ *          the list; an odd list is followed by a copy of its last entry under the next position, so 16 bytes always hold two entries
+ *   rows   uint16[E] behind the lists (at the next multiple of 256): the palette row of every entry
+ * stats is uint64[4] = {listed cells, flagged cells, entries used (the end of the last listed cell), longest list}.
+ * rhccq_palette_grid: palette, work and stats are device memory (work aligned to 16, stats to 8); async on the context stream, no host
+ * synchronisation, nothing allocated; three launches (count, exclusive scan, fill).  RHCCQ_E_ARG: a null pointer, K < 1, entries < 0, a
+ * misaligned or too small workspace.  RHCCQ_E_LIMIT: K > 65536, entries > 33554432.
+ * rhccq_palette_remap_grid: rgb .. sums as rhccq_palette_remap takes them and with its results; grid and entries are what
+ * rhccq_palette_grid was given FOR THIS PALETTE (the caller's duty); work (rhccq_palette_remap_grid_bytes(n_pixels), aligned to 16) holds the
+ * overflow queue; *overflow (uint64, zeroed by the call) receives the pixels that went through the full search.  Two memsets and two
+ * launches: the walk over the lists, which appends the pixels of flagged cells to the queue, and the full search over the queue, whose
+ * length is read on the device.  Errors as rhccq_palette_remap, and RHCCQ_E_ARG for a null or misaligned grid, work or overflow and
+ * entries outside 0..33554432; RHCCQ_E_LIMIT for n_pixels >= 2^32.  rhccq_palette_grid_chunk(): the pixels a workgroup takes at a time.
+ * Host forms: the same functions run serially on host memory (tests; no GPU needed); the host remap needs no queue. */
+int32_t rhccq_palette_grid_cell(void);
+int32_t rhccq_palette_grid_max_list(void);
+int32_t rhccq_palette_grid_chunk(void);
+int64_t rhccq_palette_grid_bytes(int32_t K, int64_t entries);
+int rhccq_palette_grid(rhccq_ctx* ctx, const uint8_t* palette, int32_t K, int64_t entries, void* work, int64_t work_bytes, uint64_t* stats);
+int rhccq_palette_grid_host(const uint8_t* palette, int32_t K, int64_t entries, void* work, int64_t work_bytes, uint64_t* stats);
+int64_t rhccq_palette_remap_grid_bytes(int64_t n_pixels);
+int rhccq_palette_remap_grid(rhccq_ctx* ctx, const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                             int32_t n_classes, const void* grid, int64_t entries, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums,
+                             void* work, int64_t work_bytes, uint64_t* overflow);
+int rhccq_palette_remap_grid_host(const uint8_t* rgb, int64_t n_pixels, const uint8_t* palette, int32_t K, const uint8_t* cls,
+                                  int32_t n_classes, const void* grid, int64_t entries, void* idx_out, int32_t idx_elem_bytes, uint64_t* sums,
+                                  uint64_t* overflow);
+
 /* ---- EXTENSION: indexed PNG files written on the device (no reference counterpart; csrc/png_write.hip, csrc/png_write.h) ------------------
  * The file of an index map idx[H][W] (idx_elem_bytes 1, 2 or 4, read as unsigned) and a palette uint8[K][3], H, W >= 1, 1 <= K <= 65536:
  *   index clamp   an index >= K is written as 0, the row rhccq_decode shows for it.

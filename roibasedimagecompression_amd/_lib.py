@@ -282,6 +282,17 @@ PROTOTYPES = {
                                               c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "rhccq_palette_pattern_batch_host": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                                    c_void_p, c_int32, c_void_p]),
+    "rhccq_palette_grid_cell": (c_int32, []),
+    "rhccq_palette_grid_max_list": (c_int32, []),
+    "rhccq_palette_grid_chunk": (c_int32, []),
+    "rhccq_palette_grid_bytes": (c_int64, [c_int32, c_int64]),
+    "rhccq_palette_grid": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
+    "rhccq_palette_grid_host": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
+    "rhccq_palette_remap_grid_bytes": (c_int64, [c_int64]),
+    "rhccq_palette_remap_grid": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                           c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_palette_remap_grid_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32, c_void_p,
+                                                c_void_p]),
     "rhccq_png_sizes": (c_int32, [c_int32, c_int32, c_int32, c_int32, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int64)]),
     "rhccq_png_scanlines": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "rhccq_crc32_bytes": (c_int64, [c_int64]),

@@ -142,3 +142,44 @@ def k_out_rows(k, fn, empty="every count is zero", over="the counts add up to mo
     if k < 0:
         raise RhccqError(f"{fn} failed ({k}): " + (empty if k == -1 else over))
     return k
+
+
+class PaletteGrid:
+    """what Rhccq.palette_grid returns: the candidate grid of one palette.  palette uint8[K, 3] and work (the grid's workspace, uint8) are
+    device tensors, entries the capacity work was sized for, stats = {listed, flagged, entries, longest} (include/rhccq.h), overflow a
+    device int64[1]: the pixels the last palette_remap(grid=) through this grid sent to the full search (None before the first)."""
+
+    def __init__(self, palette, entries, work, stats):
+        self.palette, self.K, self.entries, self.work, self.stats, self.overflow = palette, int(palette.shape[0]), entries, work, stats, None
+
+
+GRID_MAX_ENTRIES = 32768 * 1024       # every cell at the per-cell cap (include/rhccq.h)
+
+
+def grid_entries(entries, fn):
+    """the capacity of a grid: None (the wrapper sizes it) or one integer 0..GRID_MAX_ENTRIES"""
+    if entries is None:
+        return None
+    if isinstance(entries, bool) or not isinstance(entries, (int, np.integer)):
+        raise TypeError(f"{fn}: entries must be an integer or None, got {type(entries).__name__}")
+    if not 0 <= int(entries) <= GRID_MAX_ENTRIES:
+        raise ValueError(f"{fn}: entries must be 0..{GRID_MAX_ENTRIES}")
+    return int(entries)
+
+
+def grid_arg(grid, palette, fn):
+    """grid= of a search: None, or the PaletteGrid of a palette of this many rows on this device"""
+    if grid is None:
+        return None
+    if not isinstance(grid, PaletteGrid):
+        raise TypeError(f"{fn}: grid must be what palette_grid returned, got {type(grid).__name__}")
+    if grid.K != int(palette.shape[0]) or grid.palette.device != palette.device:
+        raise ValueError(f"{fn}: the grid was built for a palette of {grid.K} rows on {grid.palette.device}")
+    return grid
+
+
+def search_kind(search, fn):
+    """search= of the encoder: "full", "grid", or a PaletteGrid built from the very palette that is searched"""
+    if isinstance(search, PaletteGrid) or (isinstance(search, str) and search in ("full", "grid")):
+        return search
+    raise ValueError(f'{fn}: search must be "full", "grid" or a grid from Rhccq.palette_grid, got {search!r}')

@@ -27,6 +27,7 @@ from .api.roi import min_region_size
 from .api.slic import _antialias_sigma_radius, _gaussian_weights, _mask_centroids, _mirror_index, _rgb2lab, _zoom_coordinates
 from .api.split_score import normalize_result, scores_from_stats
 from .frame import ClassSpec, FrameEncoder
+from . import _palette_args as A
 from . import ops
 from .ops import RhccqError, default_context, psnr_from_sse
 from .palette import cluster_palettes
@@ -728,9 +729,10 @@ class ImageEncoder:
         return {"pixels": pixels, "sse": sse, "mse": sse / (3.0 * pixels) if pixels else None,
                 "psnr": psnr_from_sse(sse, pixels) if pixels else None}
 
-    def _finish_palette(self, rgb, pal, cls, roi_weight, refine, runs=None):
-        """the refinement, if asked for, and the final remap (by the rule `runs` names, if any) -> (palette device, indices, sums host
-        {pixels, sse} per row, history host or None, iterations, the rule's stats row or None)"""
+    def _finish_palette(self, rgb, pal, cls, roi_weight, refine, runs=None, search="full"):
+        """the refinement, if asked for, and the final remap (by the rule `runs` names, if any; search: "full", "grid" = through a grid
+        built here from the palette that is searched, or that palette's grid) -> (palette device, indices, sums host {pixels, sse} per
+        row, history host or None, iterations, the rule's stats row or the search's or None)"""
         rh = self.rh
         hist = nit = None
         if refine:
@@ -738,14 +740,20 @@ class ImageEncoder:
         status = None
         if runs is not None:
             idx, sums, status = self._runs_call(rgb, pal, cls, runs)
+        elif search != "full":
+            grid = rh.palette_grid(pal) if search == "grid" else search
+            idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0, grid=grid)
         else:
             idx, sums = rh.palette_remap(rgb, pal, cls, 2 if cls is not None else 0)
+        more = (hist, nit) if refine else ()
+        if runs is None and search != "full":
+            more += (grid.overflow,)
+        sums, *more = self._runs_host(sums, status, *more)                     # one read for all
         if refine:
-            sums, hist, nit = self._runs_host(sums, status, hist, nit)        # one read for all
-            nit = int(nit[0])
-        else:
-            (sums,) = self._runs_host(sums, status)
+            hist, nit = more[0], int(more[1][0])
         runs_row = None
+        if runs is None and search != "full":
+            runs_row = dict({"kind": "grid"}, **grid.stats, overflow_pixels=int(more[-1][0]))
         if runs is not None:
             runs_row = self._runs_row(runs, sums, cls is not None)
             sums = sums[:, :2]
@@ -900,7 +908,7 @@ class ImageEncoder:
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
                             target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4,
-                            png_path=None, gif_path=None):
+                            png_path=None, gif_path=None, search="full"):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -986,8 +994,20 @@ class ImageEncoder:
         filter_rows}.  A target_bytes counts the .rhccq file's bytes, not the PNG's.
         gif_path (default None = off; independent of out_path and png_path): the index map returned is also written as a one-frame GIF89a
         file built on the device (container.write_gif: one global colour table, segmented LZW, include/rhccq.h).  stats["gif"] = {bytes,
-        frames: 1, table: "global", colours, delta: False, stream_bytes}.  A result of more than 256 rows raises ValueError."""
+        frames: 1, table: "global", colours, delta: False, stream_bytes}.  A result of more than 256 rows raises ValueError.
+        search = "grid" (default "full"; anything else raises ValueError): the final remap goes through the colour-cell candidate grid
+        of the palette it searches (Rhccq.palette_grid, built here, behind refine and colours; then Rhccq.palette_remap(grid=)): the
+        same indices and sums, fewer rows evaluated per pixel, which pays for large palettes.  A grid that
+        Rhccq.palette_grid built from this very palette may be given instead of "grid" and is reused (encode_sequence does so);
+        refine and colours change the palette and raise ValueError with it.  stats["search"] = {kind: "grid", listed, flagged,
+        entries, longest, overflow_pixels}.  It serves the plain remap only: with run_slack, run_penalty, dither, pattern or a
+        target it raises ValueError."""
         rh = self.rh
+        search = A.search_kind(search, "ImageEncoder.encode_with_palette")
+        if search != "full" and any(v is not None for v in (run_slack, run_penalty, dither, pattern, target_bytes, target_psnr)):
+            raise ValueError("ImageEncoder.encode_with_palette: search other than \"full\" serves the plain remap only")
+        if isinstance(search, A.PaletteGrid) and (refine or colours is not None):
+            raise ValueError("ImageEncoder.encode_with_palette: a given grid cannot be combined with refine or colours, which change the palette")
         png_path = self._png_arg("ImageEncoder.encode_with_palette", png_path)
         gif_path = self._png_arg("ImageEncoder.encode_with_palette", gif_path, "gif_path")
         refine, roi_weight = int(refine), int(roi_weight)
@@ -1035,7 +1055,7 @@ class ImageEncoder:
                 weights = None if cls is None or roi_weight == 1 else 1 + (roi_weight - 1) * (cls == 1).to(torch.int64)
                 pal, reduce_row = self._reduce(pal, index_histogram(first, int(pal.shape[0]), rh, weights), int(colours))
                 lap("reduce")
-            pal, idx, sums, hist, nit, runs_row = self._finish_palette(rgb, pal, cls, roi_weight, refine, runs)
+            pal, idx, sums, hist, nit, runs_row = self._finish_palette(rgb, pal, cls, roi_weight, refine, runs, search)
             refined = bool(refine)
             lap("remap")
         remap = {"all": self._remap_row(*sums[-1])}
@@ -1049,7 +1069,7 @@ class ImageEncoder:
         if target is not None:
             stats["target"] = target
         if runs_row is not None:
-            stats[self._runs_key(runs)] = runs_row
+            stats[self._runs_key(runs) if runs is not None else "search"] = runs_row
         if refined:
             stats["refine"] = {"iterations": nit, "converged": nit == 0 or int(hist[nit - 1, 1]) == 0,
                                "sse": [int(v) for v in hist[:nit, 0]], "changed": [int(v) for v in hist[:nit, 1]]}
@@ -1400,7 +1420,8 @@ class ImageEncoder:
                 "stats": stats}
 
     def encode_sequence(self, images, roi_quality, nonroi_quality, max_drop_db, out_paths=None, exact=False, refine=0, roi_weight=1, max_colours=None,
-                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None, pattern=None, pattern_size=4):
+                        target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, key_colours=None, pattern=None, pattern_size=4,
+                        search="full"):
         """generator over `images` (uint8[H,W,3] each): frame 0 is a key frame, a plain encode(image, roi_quality, nonroi_quality);
         every later frame is remapped onto the current key frame's palette (encode_with_palette; the palette stays on the device)
         and kept as that iff its PSNR is at least the key frame's PSNR - max_drop_db, otherwise it is encoded in full and becomes
@@ -1426,8 +1447,15 @@ class ImageEncoder:
         pattern: one number (default None = off) with pattern_size, by run_slack's rules (exclusive with it, with run_penalty and with
         target_psnr): key frames and remapped or refined frames alike end in the pattern dither (Rhccq.palette_pattern), whose index for
         a pixel depends on the pixel and its position only, so what does not change between frames keeps its index.  The PSNR the
-        key-frame rule compares is that of the dithered map, the map that is returned."""
+        key-frame rule compares is that of the dithered map, the map that is returned.
+        search = "grid" (default "full"; anything else, and any combination with run_slack, run_penalty or pattern, raises ValueError):
+        every remap goes through the candidate grid of the current key palette (encode_with_palette's search=), which is built once
+        when the palette is set or refined and reused for every frame remapped onto it; the results are the same."""
         rh = self.rh
+        if search not in ("full", "grid"):
+            raise ValueError(f'ImageEncoder.encode_sequence: search must be "full" or "grid", got {search!r}')
+        if search == "grid" and any(v is not None for v in (run_slack, run_penalty, pattern)):
+            raise ValueError("ImageEncoder.encode_sequence: search=\"grid\" serves the plain remap only")
         refine, roi_weight = int(refine), int(roi_weight)
         if key_colours is not None:
             key_colours = int(key_colours)
@@ -1448,20 +1476,22 @@ class ImageEncoder:
             raise ValueError("ImageEncoder.encode_sequence: refine must be 0..64")
         if not 1 <= roi_weight <= 255 or (roi_weight != 1 and not refine):
             raise ValueError("ImageEncoder.encode_sequence: roi_weight must be 1..255, and 1 without refine")
-        key_pal = key_psnr = key_window = key_frame_shape = None
+        key_pal = key_grid = key_psnr = key_window = key_frame_shape = None
         key_index = -1
         for n, image in enumerate(images):
             path = out_paths[n] if out_paths is not None else None
             if key_pal is not None:
                 window = key_window if tuple(image.shape[:2]) == key_frame_shape else None
+                if search == "grid" and key_grid is None:
+                    key_grid = rh.palette_grid(key_pal)
                 res = self.encode_with_palette(image, key_pal, roi_mask=window, run_slack=run_slack, run_penalty=run_penalty, pattern=pattern,
-                                               pattern_size=pattern_size)
+                                               pattern_size=pattern_size, search=key_grid or "full")
                 row = res["stats"]["remap"]["all" if window is None else "roi"]
                 kept = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 refined = False
                 if not kept and refine:
                     res = self.encode_with_palette(image, key_pal, roi_mask=window, refine=refine, roi_weight=roi_weight if window is not None else 1,
-                                                   run_slack=run_slack, run_penalty=run_penalty, pattern=pattern, pattern_size=pattern_size)
+                                                   run_slack=run_slack, run_penalty=run_penalty, pattern=pattern, pattern_size=pattern_size, search=search)
                     row = res["stats"]["remap"]["all" if window is None else "roi"]
                     kept = refined = row["psnr"] is not None and row["psnr"] >= key_psnr - max_drop_db
                 if kept:
@@ -1471,7 +1501,7 @@ class ImageEncoder:
                     res["stats"].update(key_frame=False, key_index=key_index, psnr=row["psnr"], key_psnr=key_psnr)
                     res["stats"]["refined"] = refined
                     if refined:
-                        key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+                        key_pal, key_grid = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3)), None
                     yield res
                     continue
             if key_colours is not None:
@@ -1489,7 +1519,7 @@ class ImageEncoder:
                 key_window[top:top + h, left:left + w] = 1
             rgb = rgb[top:top + h, left:left + w].contiguous()
             every = torch.zeros((h, w), dtype=torch.uint8, device=rh.device)      # one class: the whole rectangle
-            key_pal = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3))
+            key_pal, key_grid = rh.dev(np.asarray(res["palette"], np.uint8).reshape(-1, 3)), None
             row = rh.class_error_sums_indexed(rgb, res["indices"].reshape(-1), key_pal, every, 1)[0]
             key_index = n
             key_psnr = psnr_from_sse(int(row[0]) + int(row[1]) + int(row[2]), int(row[5]))

@@ -164,6 +164,21 @@ PATTERN_MAX = 256                     # the largest strength Rhccq.palette_patte
 PATTERN_SIZES = (2, 4, 8)             # the sides of the threshold matrix Rhccq.palette_pattern takes: 4, 16 or 64 candidates a pixel
 
 
+def palette_grid_cell():
+    """the side of a colour cell of Rhccq.palette_grid: a pixel's cell is (r, g, b) // this"""
+    return int(_lib.load().rhccq_palette_grid_cell())
+
+
+def palette_grid_max_list():
+    """the longest candidate list a cell of Rhccq.palette_grid keeps; a cell with more rows is flagged and its pixels take the full search"""
+    return int(_lib.load().rhccq_palette_grid_max_list())
+
+
+def palette_grid_chunk():
+    """the pixels a workgroup of Rhccq.palette_remap(grid=) takes at a time"""
+    return int(_lib.load().rhccq_palette_grid_chunk())
+
+
 def palette_pattern_max_rows():
     """the largest palette Rhccq.palette_pattern takes on the device (the packed palette is 32 KiB of LDS)"""
     return int(_lib.load().rhccq_palette_pattern_max_rows())
@@ -1051,20 +1066,58 @@ class Rhccq:
         return tot[:, :3], np.rint(tot[:, 3]).astype(np.int64)
 
     # -- nearest-colour remap onto a given palette (EXTENSION: csrc/palette_remap.hip) --------------------------
-    def palette_remap(self, rgb, palette, class_map=None, n_classes=0):
+    def palette_grid(self, palette, entries=None):
+        """palette uint8[K, 3] (numpy or device), K <= 65536 -> the PaletteGrid of it for palette_remap(grid=): per colour cell of
+        palette_grid_cell()^3 colours the exact list of rows that can be nearest to a pixel of the cell (include/rhccq.h), built on the
+        device in three launches.  entries: the capacity in list entries; cells whose lists end beyond it are flagged, as are cells of
+        more than palette_grid_max_list() rows, and their pixels take the full search.  None: a first build into the largest workspace
+        any palette of K rows needs tells what this palette needs, and the grid is built again into exactly that.  Reads the four
+        stats back (one synchronisation per build): build once per palette, not per frame."""
+        fn = "palette_grid"
+        palette = A.as_uint8(palette, self.device, fn, "palette")
+        if palette.ndim != 2 or palette.shape[1] != 3:
+            raise ValueError(f"{fn}: palette [K, 3] is expected")
+        entries, K = A.grid_entries(entries, fn), int(palette.shape[0])
+        if K < 1 or K > 65536:
+            raise RhccqError(f"{fn}: K must be 1..65536")
+
+        def build(e):
+            work = self.zeros((int(self.lib.rhccq_palette_grid_bytes(K, e)),), torch.uint8)
+            stats = self.empty((4,), torch.int64)
+            self._check(self.lib.rhccq_palette_grid(self.ctx, self._p(palette), K, e, self._p(work), work.numel(), self._p(stats)), fn)
+            listed, flagged, used, longest = (int(v) for v in stats.cpu().numpy())
+            return A.PaletteGrid(palette, e, work, {"listed": listed, "flagged": flagged, "entries": used, "longest": longest})
+        if entries is not None:
+            return build(entries)
+        return build(build(32768 * min((K + 1) & ~1, palette_grid_max_list())).stats["entries"])
+
+    def palette_remap(self, rgb, palette, class_map=None, n_classes=0, grid=None):
         """rgb uint8[..., 3], palette uint8[K, 3] (numpy or device), class_map uint8 / bool, one element per pixel, or None ->
         (indices device tensor of rgb's leading shape: uint8 when K <= 256, else int16 holding uint16; sums device int64
         [n_classes + 1, 2]: row c = {pixels, sum of squared errors} of class c, the last row over every pixel).  Each index is the
-        nearest palette row in exact integers, ties to the lowest row."""
+        nearest palette row in exact integers, ties to the lowest row.
+        grid = palette_grid(palette) (default None: every row is evaluated for every pixel): the same indices and sums through the
+        grid's candidate lists (csrc/palette_grid.hip); grid.overflow then holds the pixels that took the full search.  The grid must be
+        the one built from THIS palette: only the number of rows is checked."""
         rgb, palette = A.pixels(rgb, palette, self.device, "palette_remap")
         n, K = rgb.numel() // 3, int(palette.shape[0])
         cls = A.class_map(class_map, n, n_classes, self.device, "palette_remap")
+        grid = A.grid_arg(grid, palette, "palette_remap")
         idx = self.empty(tuple(rgb.shape[:-1]), A.index_dtype(K))
         sums = self.empty((int(n_classes) + 1, 2), torch.int64)
         if n == 0:                                       # (empty tensors have null pointers: nothing to launch)
             if not 0 <= int(n_classes) <= 16 or K < 1 or K > 65536:
                 raise RhccqError("palette_remap: K must be 1..65536 and n_classes 0..16")
+            if grid is not None:
+                grid.overflow = self.zeros((1,), torch.int64)
             return idx, sums.zero_()
+        if grid is not None:
+            work = self.empty((int(self.lib.rhccq_palette_remap_grid_bytes(n)),), torch.uint8)
+            grid.overflow = self.empty((1,), torch.int64)
+            self._check(self.lib.rhccq_palette_remap_grid(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), int(n_classes), self._p(grid.work),
+                                                          grid.entries, self._p(idx), idx.element_size(), self._p(sums), self._p(work), work.numel(),
+                                                          self._p(grid.overflow)), "palette_remap")
+            return idx, sums
         self._check(self.lib.rhccq_palette_remap(self.ctx, self._p(rgb), n, self._p(palette), K, self._p(cls), int(n_classes), self._p(idx),
                                                  idx.element_size(), self._p(sums)), "palette_remap")
         return idx, sums
