@@ -700,7 +700,11 @@ int rhccq_px_expand(rhccq_ctx* ctx, const uint8_t* rgb, int32_t H, int32_t W, in
 
 /* ---- EXTENSION (no reference counterpart): block DCT-II + region quantisation --
  * plane: float32[H*W]; block in {8,16}; qstep: float32 per tile [(H/block)*(W/block)];
- * coef_out float32[H*W] (may be NULL), q_out int16[H*W]. */
+ * coef_out float32[H*W] (may be NULL), q_out int16[H*W].  The coefficients are accumulated in float64 and rounded to float32
+ * once; q = rint(coef / qstep) from the float64 coefficient.  RHCCQ_E_ARG for another block size, for H or W that block does not
+ * divide and for a plane off 16-byte alignment.  NOT checked, on the host or on the device: every qstep must be positive (a zero
+ * or negative step gives a division by zero or mirrored integers, without an error), and q is undefined where |coef / qstep|
+ * exceeds 32 767 (the conversion to int16 does not saturate).  |coef| is at most block * max |plane|. */
 int rhccq_dct_quant(rhccq_ctx* ctx, const float* plane, int32_t H, int32_t W, int32_t block,
                     const float* qstep, float* coef_out, int16_t* q_out);
 /* RGB u8 -> luma float32 (BT.601) plus per-tile qstep from a ROI mask (u8, may be NULL) */

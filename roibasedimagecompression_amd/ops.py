@@ -1009,15 +1009,19 @@ class Rhccq:
         self._check(self.lib.rhccq_error_tables(self.ctx, self._p(a), self._p(b), a.numel() // 3, self._p(tab), self._p(me)), "error_tables")
         return tab.cpu().numpy(), me
 
-    def ssim7(self, a, b):
-        """mean SSIM per channel (float64[3]) with skimage's defaults for win_size=7, data_range=255."""
+    def ssim7(self, a, b, return_partial=False):
+        """mean SSIM per channel (float64[3]) with skimage's defaults for win_size=7, data_range=255.  return_partial=True:
+        (mean, float64[tile rows, tile columns, 3]), the sum of S per channel over each 32 x 32 tile of window centres as the
+        workgroups wrote them (the mean is their sum over the (H - 6) * (W - 6) windows)."""
         H, W = int(a.shape[0]), int(a.shape[1])
         nb = int(self.lib.rhccq_ssim7_blocks(H, W))
         if nb == 0:
             raise ValueError("win_size exceeds image extent")          # skimage's message
         part = self.empty((nb, 3), torch.float64)
         self._check(self.lib.rhccq_ssim7_sums(self.ctx, self._p(a), self._p(b), H, W, self._p(part), nb), "ssim7")
-        return part.cpu().numpy().sum(axis=0) / float((H - 6) * (W - 6))
+        part = part.cpu().numpy()
+        mean = part.sum(axis=0) / float((H - 6) * (W - 6))
+        return (mean, part.reshape(-1, (W - 6 + 31) // 32, 3)) if return_partial else mean
 
     # -- per-class quality metrics (EXTENSION: csrc/region_metrics.hip) ------------------------------------
     def _class_map(self, cls, shape):
