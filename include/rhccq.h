@@ -1411,6 +1411,21 @@ int rhccq_png_decode_host(const uint8_t* file, int64_t n, int32_t flags, uint8_t
  *                 follows, Clear goes out at `width` bits and the segment's state starts again.  Behind its last data code a segment emits,
  *                 at the width that step left, Clear if another segment follows and End otherwise.  Codes are packed least significant
  *                 bit first; the stream is padded with zero bits to a byte.
+ *   lossy         the rhccq_gif_*_lossy entries only; everything above holds.  slack is 0..195075, a squared RGB distance; D(p, q) is the
+ *                 squared Euclidean distance of rows p and q of the frame's table, in exact integers.  The lossy step applies only where
+ *                 the greedy LZW would emit: the segment has a current string cur, the pixel to write is p (after clamp and delta
+ *                 substitution) and (cur, p) is not in the dictionary.  The candidates are the rows q < K, q != p, D(p, q) <= slack for
+ *                 which (cur, q) IS in the dictionary.  If there is one, the candidate with the least (D(p, q), q) is taken: the current
+ *                 string becomes that entry's and the pixel is WRITTEN AS q; no code goes out and no entry is added.  If there is none
+ *                 the plain step runs unchanged: the code goes out, entry (cur, p) with the true p is added while next < 4096, and p opens
+ *                 the next string.  (cur, p) itself always wins when present; a segment's first pixel is never substituted; under
+ *                 RHCCQ_GIF_DELTA the transparent index T = K is never a candidate and a pixel written as T is never substituted.
+ *                 So: the file is a valid GIF any decoder reads; every decoded index w satisfies w == p or D(p, w) <= slack, and by
+ *                 induction over the frames the same holds under delta for the pixel the screen shows; with slack = 0 and pairwise
+ *                 distinct rows the file is byte for byte the lossless one; device form and host form agree byte for byte.  The hash
+ *                 dictionary only: RHCCQ_GIF_TRIE with a lossy entry is RHCCQ_E_ARG, as is a slack outside its range.  written (device,
+ *                 host in the host forms; uint8[n_frames][H][W]; may be NULL) receives the pixel every position was written as (T where it
+ *                 went out transparent).  rhccq_gif_lzw_lossy reads palettes and k_stride as rhccq_gif_encode does.
  * RHCCQ_E_ARG (before any device work): n_frames < 1 (or above 2^20), H or W outside 1..65535, a table of 0 or more than 256 rows or more than
  * k_stride, idx_elem_bytes not 1, 2 or 4, unknown flag bits, RHCCQ_GIF_DELTA with RHCCQ_GIF_LOCAL or with 256 rows, a delay or loop outside
  * 0..65535, a null pointer, an idx not aligned to its element, a workspace not aligned to 256, out_len / stream_bytes not aligned to 8.
@@ -1445,6 +1460,19 @@ int rhccq_gif_lzw_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames
 int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
                           const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
                           int64_t* stream_bytes);
+/* the lossy forms ("lossy" above): sizes and workspace are rhccq_gif_sizes'; offsets, layout, join and framing are the lossless launches */
+int rhccq_gif_lzw_lossy(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                        int32_t k_stride, const int32_t* k_rows, int32_t flags, int64_t slack, void* workspace, uint8_t* streams, int64_t stream_stride,
+                        int64_t* stream_bytes, uint8_t* written);
+int rhccq_gif_encode_lossy(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                           int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, int64_t slack, void* workspace,
+                           uint8_t* out, int64_t out_cap, int64_t* out_len, uint8_t* written);
+int rhccq_gif_lzw_lossy_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                             const int32_t* k_rows, int32_t flags, int64_t slack, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes,
+                             uint8_t* written);
+int rhccq_gif_encode_lossy_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                                const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, int64_t slack, uint8_t* out, int64_t out_cap,
+                                int64_t* out_len, int64_t* stream_bytes, uint8_t* written);
 
 /* ---- EXTENSION: GIF files read on the device (no reference counterpart; csrc/gif_read.hip, csrc/gif_read.h) --------------------------------
  * Framing.  "GIF87a" or "GIF89a", the logical screen descriptor (W, H, packed, background, aspect), a global colour table of 2 << (packed & 7)

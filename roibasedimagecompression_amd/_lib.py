@@ -326,6 +326,14 @@ PROTOTYPES = {
     "rhccq_gif_lzw_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "rhccq_gif_encode_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
                                         c_int64, c_void_p, c_void_p]),
+    "rhccq_gif_lzw_lossy": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_void_p,
+                                      c_int64, c_void_p, c_void_p]),
+    "rhccq_gif_encode_lossy": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                         c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_gif_lzw_lossy_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int64, c_void_p, c_int64,
+                                           c_void_p, c_void_p]),
+    "rhccq_gif_encode_lossy_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                              c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "rhccq_gif_parse_host": (c_int32, [c_void_p, c_int64, C.POINTER(GifInfo), c_void_p, c_int64, C.POINTER(c_int64), c_void_p, c_int64, C.POINTER(c_int64)]),
     "rhccq_gif_read_tile": (c_int32, []),
     "rhccq_gif_read_scan_step": (c_int32, []),

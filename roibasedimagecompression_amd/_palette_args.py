@@ -137,6 +137,18 @@ def index_map(indices, H, W, device, fn):
     return (t.to(torch.int32) if t.dtype == torch.int64 else t).contiguous()
 
 
+GIF_MAX_SLACK = 3 * 255 * 255
+
+
+def gif_lossy(lossy, fn, what="lossy"):
+    """the lossy LZW's slack (include/rhccq.h "lossy"): None = the lossless path, else an integer 0..195075 (0 is a value) -> None or int"""
+    if lossy is None:
+        return None
+    if isinstance(lossy, bool) or not isinstance(lossy, (int, np.integer)) or not 0 <= int(lossy) <= GIF_MAX_SLACK:
+        raise ValueError(f"{fn}: {what} must be None or an integer 0..{GIF_MAX_SLACK} (a squared RGB distance)")
+    return int(lossy)
+
+
 def k_out_rows(k, fn, empty="every count is zero", over="the counts add up to more than 2^32 - 1"):
     """the k_out a chain wrote: the rows it made, or the negative code of an error only the counts (the table) show"""
     if k < 0:

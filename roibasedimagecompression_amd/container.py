@@ -190,29 +190,51 @@ def _gif_frames(results, rh, delta):
     return rh, idx, len(frames), h, w, block, [len(p) for p in pals]
 
 
-def gif_file(results, rh=None, delay=4, loop=0, delta=False):
+def gif_moved(written, idx, rows, delta):
+    """written uint8[n, H, W] of a lossy GIF call, idx its index maps, rows: one K or one a frame -> a device count of the pixels whose
+    written index is not the lossless one (the clamped index, or the transparent index K under delta, which lossy never touches)"""
+    n = written.shape[0]
+    k = torch.as_tensor(rows, dtype=torch.int64, device=written.device).reshape(-1, 1).expand(n, 1)
+    wr, asked = written.reshape(n, -1).to(torch.int64), idx.reshape(n, -1).to(torch.int64)
+    asked = torch.where((asked >= 0) & (asked < k), asked, torch.zeros_like(asked))
+    return ((wr != asked) & ~((wr == k) & bool(delta))).sum()
+
+
+def gif_file(results, rh=None, delay=4, loop=0, delta=False, lossy=None):
     """gif_bytes with what the file is: -> (bytes, {"bytes": their number, "frames", "table": "global" | "local", "colours": rows of the
-    largest table, "delta", "stream_bytes": [bytes of every frame's code stream]}); the file and the stream lengths come down together"""
+    largest table, "delta", "stream_bytes": [bytes of every frame's code stream]}); the file and the stream lengths come down together.
+    With lossy the row gains "lossy": {"slack", "moved": pixels written as another index than the lossless file's, "pixels"}."""
     rh, idx, n, h, w, pals, rows = _gif_frames(results, rh, delta)
-    out, length, lens = rh.gif_encode_async(idx, n, h, w, pals, rows, delay, loop, delta)
+    if lossy is None:
+        out, length, lens = rh.gif_encode_async(idx, n, h, w, pals, rows, delay, loop, delta)
+        moved = None
+    else:
+        out, length, lens, written = rh.gif_encode_async(idx, n, h, w, pals, rows, delay, loop, delta, lossy=lossy, written=True)
+        moved = gif_moved(written, idx if idx.dtype != torch.int16 else idx.to(torch.int32) & 0xFFFF, rows or [len(pals)], delta)
     size = int(length.item())
     data, lens = rh.to_host(out[:size], lens)
-    return data.tobytes(), {"bytes": size, "frames": n, "table": "global" if rows is None else "local", "colours": int(pals.shape[-2]),
-                            "delta": bool(delta), "stream_bytes": [int(v) for v in lens]}
+    row = {"bytes": size, "frames": n, "table": "global" if rows is None else "local", "colours": int(pals.shape[-2]),
+           "delta": bool(delta), "stream_bytes": [int(v) for v in lens]}
+    if moved is not None:
+        row["lossy"] = {"slack": int(lossy), "moved": int(moved.item()), "pixels": n * h * w}
+    return data.tobytes(), row
 
 
-def gif_bytes(results, rh=None, delay=4, loop=0, delta=False):
+def gif_bytes(results, rh=None, delay=4, loop=0, delta=False, lossy=None):
     """the GIF89a file of one result (palette, indices, shape: what write_png takes) or of a list of them of one shape as bytes, built
     on the device (include/rhccq.h "GIF files written on the device").  One global colour table when every result carries the same
     palette (the same object, or equal rows), else a local table a frame.  delay: centiseconds, one number or one a frame; loop: the
     animation's repeat count, 0 for ever.  delta=True (global table, at most 255 rows): a pixel that equals the frame in front is
-    written as the transparent index.  An index past the palette shows row 0, as in write_png."""
-    return gif_file(results, rh, delay, loop, delta)[0]
+    written as the transparent index.  An index past the palette shows row 0, as in write_png.  lossy (default None = lossless; 0 is a
+    value): the slack 0..195075 of the bounded-error LZW step (include/rhccq.h "lossy"): where the greedy LZW would emit, the nearest
+    row within that squared RGB distance whose string is in the dictionary is written instead; every pixel the file shows stays within
+    the slack of the row it was asked to show."""
+    return gif_file(results, rh, delay, loop, delta, lossy)[0]
 
 
-def write_gif(results, filename, rh=None, delay=4, loop=0, delta=False):
+def write_gif(results, filename, rh=None, delay=4, loop=0, delta=False, lossy=None):
     """gif_bytes written to `filename`; returns the file's length in bytes"""
-    data = gif_bytes(results, rh, delay, loop, delta)
+    data = gif_bytes(results, rh, delay, loop, delta, lossy)
     with open(filename, "wb") as f:
         f.write(data)
     return len(data)
@@ -368,17 +390,17 @@ def read_gif(src, rh=None):
                       "stream_bytes": [table[f].stream_bytes for f in range(info.n_frames)], "seconds": round(time.perf_counter() - t0, 4)}}
 
 
-def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4):
+def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4, lossy=None):
     """an animated GIF to one of at most `colours` colours, on the device from end to end: read_gif, then ImageEncoder.animate over the
     composed frames with the file's own delays and loop count (0 where it has none), written to dst.  The frames enter as the viewer
     shows them, so cropped rectangles, transparency and disposal methods are gone from the result; a pixel no frame has covered enters
-    as colour (0, 0, 0).  -> animate's dict, with stats["read"] = read_gif's stats."""
+    as colour (0, 0, 0).  lossy: as animate takes it.  -> animate's dict, with stats["read"] = read_gif's stats."""
     from .image import ImageEncoder
     rh = rh or default_context()
     src = read_gif(src, rh)
     enc = ImageEncoder(rh)
     res = enc.animate(src["images"], colours, gif_path=dst, delay=src["delays"], loop=src["loop"] or 0, delta=delta, refine=refine, pattern=pattern,
-                      pattern_size=pattern_size)
+                      pattern_size=pattern_size, lossy=lossy)
     res["stats"]["read"] = src["stats"]
     return res
 

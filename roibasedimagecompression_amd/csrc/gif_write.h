@@ -6,7 +6,8 @@
 //   LZW         one segment's state (Lzw), its output (BitSink: codes packed least significant bit first into 32-bit words) and the steps
 //               lzw_begin / lzw_pixel / lzw_finish over a dictionary of kDictSlots open-addressed 32-bit slots (lzw_pixel_trie: of kTrieNodes
 //               trie nodes) that the caller owns (LDS on the device, an array on the host) and clears to zero at the start and whenever
-//               the step says so;
+//               the step says so; lzw_pixel_lossy: the bounded-error step over the hash dictionary, generic over the candidate search
+//               (RowSearch: the host's loop over the rows; the device passes its wave search);
 //   framing     gif_put_head / gif_put_frame_head: every byte outside the code streams.
 #pragma once
 #include <stdint.h>
@@ -166,6 +167,84 @@ RHCCQ_GIF_HD bool lzw_pixel(Lzw& z, Dict dict, uint32_t px, BitSink& s) {
   if (z.next < (uint32_t)kMaxCode) dict[h] = key << 12 | z.next;
   return lzw_after_code(z, px, s);
 }
+// ---- the lossy step (include/rhccq.h "lossy") ------------------------------------------------------------------------------------------
+constexpr uint32_t kMaxSlack = 3u * 255u * 255u;           // 195 075: the squared distance of black and white
+constexpr uint32_t kNoCandidate = 0xFFFFFFFFu;
+// a palette row as the searches hold it: r | g << 8 | b << 16, bit 24 set on a row that may stand in for another (q < K)
+constexpr uint32_t kRowLive = 1u << 24;
+RHCCQ_GIF_HD uint32_t gif_row_pack(const uint8_t* pal, uint32_t q, uint32_t K) {
+  return q < K ? (uint32_t)pal[3 * q] | (uint32_t)pal[3 * q + 1] << 8 | (uint32_t)pal[3 * q + 2] << 16 | kRowLive : 0u;
+}
+RHCCQ_GIF_HD uint32_t gif_row_dist(uint32_t a, uint32_t b) {
+  const int dr = (int)(a & 255u) - (int)(b & 255u), dg = (int)(a >> 8 & 255u) - (int)(b >> 8 & 255u), db = (int)(a >> 16 & 255u) - (int)(b >> 16 & 255u);
+  return (uint32_t)(dr * dr + dg * dg + db * db);
+}
+// the code of `key` in the hash dictionary, 0 when it has none.  `dict` may be each lane's own view (a plain pointer: the lanes probe
+// different keys at once) or the chain's uniform one
+template <typename Dict>
+RHCCQ_GIF_HD uint32_t lzw_find(Dict dict, uint32_t key) {
+  uint32_t h = lzw_hash(key);
+  for (int probe = 0; probe < kDictSlots; ++probe) {       // (bounded: an empty slot is met long before)
+    const uint32_t slot = dict[h];
+    if (slot == 0u) return 0u;
+    if (slot >> 12 == key) return slot & 4095u;
+    h = (h + 1) & (kDictSlots - 1);
+  }
+  return 0u;
+}
+// lzw_pixel with the lossy step on its miss path.  search(cur, px) -> q << 12 | code of the candidate with the least (D(px, q), q) among
+// the rows q < K, q != px, D <= slack whose (cur, q) is in the dictionary, or kNoCandidate; it is asked only for px < K (under delta
+// the transparent index K is never substituted) and never for a segment's first pixel.  wrote: the pixel the decoder will read here.
+template <typename Dict, typename Search>
+RHCCQ_GIF_HD bool lzw_pixel_lossy(Lzw& z, Dict dict, uint32_t px, uint32_t K, BitSink& s, const Search& search, uint32_t& wrote) {
+  wrote = px;
+  if (z.cur < 0) {
+    z.cur = (int32_t)px;
+    return false;
+  }
+  const uint32_t key = (uint32_t)z.cur << 8 | px;
+  uint32_t h = lzw_hash(key);
+  for (int probe = 0; probe < kDictSlots; ++probe) {       // (bounded: an empty slot is met long before)
+    const uint32_t slot = dict[h];
+    if (slot == 0u) break;
+    if (slot >> 12 == key) {
+      z.cur = (int32_t)(slot & 4095u);
+      return false;
+    }
+    h = (h + 1) & (kDictSlots - 1);
+  }
+  if (px < K) {
+    const uint32_t c = search((uint32_t)z.cur, px);
+    if (c != kNoCandidate) {
+      z.cur = (int32_t)(c & 4095u);
+      wrote = c >> 12;
+      return false;
+    }
+  }
+  sink_put(s, (uint32_t)z.cur, z.width);
+  if (z.next < (uint32_t)kMaxCode) dict[h] = key << 12 | z.next;
+  return lzw_after_code(z, px, s);
+}
+// the host's search: every row in turn
+struct RowSearch {
+  const uint32_t* dict;
+  const uint32_t* rows;      // gif_row_pack of the frame's table, kMaxRows of them
+  uint32_t K, slack;
+  uint32_t operator()(uint32_t cur, uint32_t px) const {
+    uint32_t best = kNoCandidate, found = kNoCandidate;
+    for (uint32_t q = 0; q < K; ++q) {
+      if (q == px) continue;
+      const uint32_t d = gif_row_dist(rows[px], rows[q]);
+      if (d > slack || (d << 8 | q) >= best) continue;
+      if (const uint32_t code = lzw_find(dict, cur << 8 | q)) {
+        best = d << 8 | q;
+        found = q << 12 | code;
+      }
+    }
+    return found;
+  }
+};
+
 // the same step over the other dictionary (RHCCQ_GIF_TRIE): kTrieNodes 32-bit nodes, one a code, first child << 20 | next sibling << 8 |
 // pixel; no entry's code is 0, so 0 ends a chain.  A step walks the children of the current string, at most one a palette row; a new
 // entry goes in front of its siblings.  The codes that go out are the same: which strings exist does not depend on how they are found.

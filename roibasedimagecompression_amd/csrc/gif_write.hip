@@ -21,6 +21,7 @@
 //                       table, loop extension, trailer and the file's length.
 #include "gif_write.h"
 #include "palette_remap.h"
+#include "wave_dpp.h"
 
 #include <algorithm>
 #include <string>
@@ -68,9 +69,83 @@ struct UniformDict {
   __device__ __forceinline__ Slot operator[](uint32_t h) const { return Slot{d + h}; }
 };
 
-template <typename T, bool TRIE>
+// The lossy step's search, by the whole wave (include/rhccq.h "lossy").  A frame's table lives in four registers a lane: lane l holds the
+// rows l, l + 64, l + 128 and l + 192 (gif_row_pack: dead at or past K, so the transparent index is no candidate).  On a miss the pixel's
+// colour comes from its owner by lane number, every lane measures its own live rows against it, and each lane with a row in reach walks
+// the dictionary for (cur, its row) ITSELF: up to 255 probe chains run side by side, divergent and bounded, where the serial form walks
+// them one behind the other.  A lane that finds an entry keeps D << 8 | q and the entry's code; one wave-wide minimum picks the winner
+// (the least D, then the least row), whose code comes back from lane q & 63.  Everything returned is scalar again.
+struct WaveSearch {
+  const uint32_t* dict;                                               // (each lane's own view: no broadcast)
+  uint32_t row0, row1, row2, row3;                                    // (named, not an array: they stay in registers)
+  uint32_t slack;
+  int lane, slots;                                                    // slots: 64-row groups that hold a row below K
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ pal, uint32_t K, int l) {
+    lane = l;
+    slots = (int)(K + 63u) >> 6;
+    row0 = gif_row_pack(pal, (uint32_t)l, K);
+    row1 = gif_row_pack(pal, (uint32_t)l + 64u, K);
+    row2 = gif_row_pack(pal, (uint32_t)l + 128u, K);
+    row3 = gif_row_pack(pal, (uint32_t)l + 192u, K);
+  }
+  // this lane's row q against the pixel's colour: its probe chain if it is in reach, and the better of (best, code) and what it finds
+  __device__ __forceinline__ void probe(uint32_t held, uint32_t q, uint32_t colour, uint32_t cur, uint32_t px, uint32_t& best, uint32_t& code) const {
+    const uint32_t d = gif_row_dist(colour, held);
+    if ((held & kRowLive) && q != px && d <= slack) {
+      const uint32_t c = lzw_find(dict, cur << 8 | q);
+      if (c != 0u && (d << 8 | q) < best) {
+        best = d << 8 | q;
+        code = c;
+      }
+    }
+  }
+  __device__ __forceinline__ uint32_t operator()(uint32_t cur, uint32_t px) const {
+    // the owner's four rows, then the pixel's among them on scalars (a select between the registers themselves would make the
+    // compiler index them in memory)
+    const int owner = (int)(px & 63u);
+    const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)row0, owner), c1 = (uint32_t)__builtin_amdgcn_readlane((int)row1, owner);
+    const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane((int)row2, owner), c3 = (uint32_t)__builtin_amdgcn_readlane((int)row3, owner);
+    const uint32_t sp = px >> 6;
+    const uint32_t colour = sp == 0u ? c0 : sp == 1u ? c1 : sp == 2u ? c2 : c3;
+    uint32_t best = kNoCandidate, code = 0u;
+    probe(row0, (uint32_t)lane, colour, cur, px, best, code);
+    if (slots > 1) probe(row1, (uint32_t)lane + 64u, colour, cur, px, best, code);      // (uniform)
+    if (slots > 2) probe(row2, (uint32_t)lane + 128u, colour, cur, px, best, code);
+    if (slots > 3) probe(row3, (uint32_t)lane + 192u, colour, cur, px, best, code);
+    const uint32_t win = wave_min_u32(best);
+    if (win == kNoCandidate) return kNoCandidate;
+    const uint32_t q = win & 255u;
+    return q << 12 | (uint32_t)__builtin_amdgcn_readlane((int)code, (int)(q & 63u));
+  }
+};
+
+// what the lossy launch takes beside the lossless one's arguments (NoLossy: nothing, and gif_lzw_kernel is the lossless kernel as it was)
+struct NoLossy {};
+struct LossyArgs {
+  const uint8_t* palettes;
+  int k_stride;
+  uint32_t slack;
+  uint8_t* written;                                                   // [n_frames][P] or null
+};
+
+// a tile's written pixels from LDS to their place: byte stores up to the first aligned word and behind the last, whole words between
+// them, a word a lane (the wave stores 256 consecutive bytes at a time)
+__device__ __forceinline__ void gif_store_tile(uint8_t* __restrict__ dst, const uint8_t* tile, int cnt, int lane) {
+  const int head = min(cnt, (int)(-(uintptr_t)dst & 3)), nw = (cnt - head) >> 2, tail = cnt - head - 4 * nw;
+  if (lane < head) dst[lane] = tile[lane];
+  uint32_t* w = (uint32_t*)(dst + head);
+  for (int i = lane; i < nw; i += 64) {
+    const uint8_t* b = tile + head + 4 * i;
+    w[i] = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+  }
+  if (lane < tail) dst[head + 4 * nw + lane] = tile[head + 4 * nw + lane];
+}
+
+template <typename T, bool TRIE, typename Lossy>
 __global__ __launch_bounds__(64) void gif_lzw_kernel(const T* __restrict__ idx, long long P, int nseg, const uint32_t* __restrict__ ftab, int flags,
-                                                     uint32_t* __restrict__ words, long long slot, uint32_t* __restrict__ seg_bits) {
+                                                     uint32_t* __restrict__ words, long long slot, uint32_t* __restrict__ seg_bits, Lossy lossy) {
+  constexpr bool LOSSY = !std::is_same<Lossy, NoLossy>::value;
+  static_assert(!(LOSSY && TRIE), "the trie has no lossy form");
   constexpr int EB = sizeof(T), PPB = 16 / EB, TB = kTile / PPB;      // pixels of a block, blocks of a tile: 64 EB
   constexpr int kWords = TRIE ? kTrieNodes : kDictSlots;             // the dictionary: 16 KiB of trie nodes or 32 KiB of hash slots
   __shared__ uint32_t dict[kWords];
@@ -114,6 +189,12 @@ __global__ __launch_bounds__(64) void gif_lzw_kernel(const T* __restrict__ idx, 
   lzw_begin(z, m, s == 0, sink);
   zero_dict();
   load(0);
+  WaveSearch search;
+  if constexpr (LOSSY) {
+    search.dict = dict;
+    search.slack = lossy.slack;
+    search.load(lossy.palettes + (flags & RHCCQ_GIF_LOCAL ? 3ll * f * lossy.k_stride : 0ll), K, lane);
+  }
   const int ntiles = (len + kTile - 1) / kTile;
   for (int t = 0; t < ntiles; ++t) {
     __syncthreads();                                                  // the chain has left the tile in front
@@ -138,13 +219,38 @@ __global__ __launch_bounds__(64) void gif_lzw_kernel(const T* __restrict__ idx, 
     for (int c = 0; c < cnt; c += 64) {                               // (uniform: all lanes walk together)
       const int mine = (int)fin[c + lane];                            // 64 pixels of the tile, one a lane: the chain reads them by lane number
       const int run = cnt - c < 64 ? cnt - c : 64;
-      for (int j = 0; j < run; ++j) {
-        const uint32_t px = (uint32_t)__builtin_amdgcn_readlane(mine, j);
-        if (TRIE ? lzw_pixel_trie(z, UniformDict{dict}, px, sink) : lzw_pixel(z, UniformDict{dict}, px, sink)) {
-          __syncthreads();
-          zero_dict();
-          __syncthreads();
+      if constexpr (LOSSY) {
+        int wrote_run = mine;                                         // what the decoder reads: a substitute goes into its pixel's lane
+        bool moved = false;
+        for (int j = 0; j < run; ++j) {
+          const uint32_t px = (uint32_t)__builtin_amdgcn_readlane(mine, j);
+          uint32_t wrote;
+          if (lzw_pixel_lossy(z, UniformDict{dict}, px, K, sink, search, wrote)) {
+            __syncthreads();
+            zero_dict();
+            __syncthreads();
+          }
+          if (wrote != px) {                                          // (uniform)
+            wrote_run = lane == j ? (int)wrote : wrote_run;
+            moved = true;
+          }
         }
+        if (moved && lossy.written) fin[c + lane] = (uint8_t)wrote_run;   // (the tile is the written one from here on)
+      } else {
+        for (int j = 0; j < run; ++j) {
+          const uint32_t px = (uint32_t)__builtin_amdgcn_readlane(mine, j);
+          if (TRIE ? lzw_pixel_trie(z, UniformDict{dict}, px, sink) : lzw_pixel(z, UniformDict{dict}, px, sink)) {
+            __syncthreads();
+            zero_dict();
+            __syncthreads();
+          }
+        }
+      }
+    }
+    if constexpr (LOSSY) {
+      if (lossy.written) {
+        __syncthreads();
+        gif_store_tile(lossy.written + f * P + p0 + (long long)t * kTile, fin, cnt, lane);
       }
     }
   }
@@ -334,7 +440,8 @@ static int gif_times(rhccq_ctx* ctx, const char* fn, int n, const int32_t* delay
 static inline int rows_of(const int32_t* k_rows, int flags, int f) { return k_rows[flags & RHCCQ_GIF_LOCAL ? f : 0]; }
 
 // the launches both device entries share: table, LZW, offsets
-static int lzw_launch(rhccq_ctx* ctx, const void* idx, int eb, int n, const Sizes& s, const int32_t* k_rows, const int32_t* delays, int flags, uint8_t* ws) {
+static int lzw_launch(rhccq_ctx* ctx, const void* idx, int eb, int n, const Sizes& s, const int32_t* k_rows, const int32_t* delays, int flags, uint8_t* ws,
+                      const LossyArgs* lossy = nullptr) {
   uint32_t* ftab = (uint32_t*)(ws + s.o_ftab);
   for (int f0 = 0; f0 < n; f0 += kTableChunk) {
     TableChunk c{};
@@ -344,12 +451,15 @@ static int lzw_launch(rhccq_ctx* ctx, const void* idx, int eb, int n, const Size
   }
   index_dispatch(eb, [&](auto* t) {
     using T = std::remove_pointer_t<decltype(t)>;
-    if (flags & RHCCQ_GIF_TRIE)
-      hipLaunchKernelGGL((gif_lzw_kernel<T, true>), dim3((unsigned)(n * s.nseg)), dim3(64), 0, ctx->stream, (const T*)idx, (long long)s.P, (int)s.nseg,
-                         (const uint32_t*)ftab, flags, (uint32_t*)(ws + s.o_words), (long long)s.slot, (uint32_t*)(ws + s.o_bits));
+    if (lossy)
+      hipLaunchKernelGGL((gif_lzw_kernel<T, false, LossyArgs>), dim3((unsigned)(n * s.nseg)), dim3(64), 0, ctx->stream, (const T*)idx, (long long)s.P, (int)s.nseg,
+                         (const uint32_t*)ftab, flags, (uint32_t*)(ws + s.o_words), (long long)s.slot, (uint32_t*)(ws + s.o_bits), *lossy);
+    else if (flags & RHCCQ_GIF_TRIE)
+      hipLaunchKernelGGL((gif_lzw_kernel<T, true, NoLossy>), dim3((unsigned)(n * s.nseg)), dim3(64), 0, ctx->stream, (const T*)idx, (long long)s.P, (int)s.nseg,
+                         (const uint32_t*)ftab, flags, (uint32_t*)(ws + s.o_words), (long long)s.slot, (uint32_t*)(ws + s.o_bits), NoLossy{});
     else
-      hipLaunchKernelGGL((gif_lzw_kernel<T, false>), dim3((unsigned)(n * s.nseg)), dim3(64), 0, ctx->stream, (const T*)idx, (long long)s.P, (int)s.nseg,
-                         (const uint32_t*)ftab, flags, (uint32_t*)(ws + s.o_words), (long long)s.slot, (uint32_t*)(ws + s.o_bits));
+      hipLaunchKernelGGL((gif_lzw_kernel<T, false, NoLossy>), dim3((unsigned)(n * s.nseg)), dim3(64), 0, ctx->stream, (const T*)idx, (long long)s.P, (int)s.nseg,
+                         (const uint32_t*)ftab, flags, (uint32_t*)(ws + s.o_words), (long long)s.slot, (uint32_t*)(ws + s.o_bits), NoLossy{});
   });
   hipLaunchKernelGGL(gif_offsets_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, (const uint32_t*)(ws + s.o_bits), (int)s.nseg,
                      (unsigned long long*)(ws + s.o_off), (long long*)(ws + s.o_flen));
@@ -368,13 +478,22 @@ static int join_launch(rhccq_ctx* ctx, int n, const Sizes& s, int flags, uint8_t
 
 // ---- host forms ----------------------------------------------------------------------------------------------------------------------
 // frame f's code stream appended to `stream` (bytes)
+// lossy: the frame's table, the slack and where the frame's written pixels go (may be null); a null `lossy` is the lossless step
+struct HostLossy {
+  const uint8_t* pal;
+  uint32_t slack;
+  uint8_t* written;
+};
 template <typename T>
-static void lzw_frame_host(const T* idx, int64_t P, int f, int K, int flags, std::vector<uint8_t>& stream) {
+static void lzw_frame_host(const T* idx, int64_t P, int f, int K, int flags, std::vector<uint8_t>& stream, const HostLossy* lossy = nullptr) {
   const int m = gif_min_code(gif_table_bits(gif_entries(K, flags)));
   const bool delta = (flags & RHCCQ_GIF_DELTA) && f > 0;
   const int64_t nseg = gif_segments(P);
   const bool trie = flags & RHCCQ_GIF_TRIE;
-  std::vector<uint32_t> dict(trie ? kTrieNodes : kDictSlots), words((size_t)gif_slot_words(P));
+  std::vector<uint32_t> dict(trie ? kTrieNodes : kDictSlots), words((size_t)gif_slot_words(P)), rows(kMaxRows);
+  if (lossy)
+    for (int q = 0; q < kMaxRows; ++q) rows[q] = gif_row_pack(lossy->pal, (uint32_t)q, (uint32_t)K);
+  const RowSearch search{dict.data(), rows.data(), (uint32_t)K, lossy ? lossy->slack : 0u};
   uint64_t acc = 0;
   int fill = 0;
   stream.clear();
@@ -388,7 +507,13 @@ static void lzw_frame_host(const T* idx, int64_t P, int f, int K, int flags, std
     const T* cur = idx + (int64_t)f * P + p0;
     for (int64_t i = 0; i < len; ++i) {
       const uint32_t px = gif_substitute((uint32_t)cur[i], delta ? (uint32_t)cur[i - P] : 0u, (uint32_t)K, delta);
-      if (trie ? lzw_pixel_trie(z, dict.data(), px, sink) : lzw_pixel(z, dict.data(), px, sink)) std::fill(dict.begin(), dict.end(), 0u);
+      if (lossy) {
+        uint32_t wrote;
+        if (lzw_pixel_lossy(z, dict.data(), px, (uint32_t)K, sink, search, wrote)) std::fill(dict.begin(), dict.end(), 0u);
+        if (lossy->written) lossy->written[p0 + i] = (uint8_t)wrote;
+      } else if (trie ? lzw_pixel_trie(z, dict.data(), px, sink) : lzw_pixel(z, dict.data(), px, sink)) {
+        std::fill(dict.begin(), dict.end(), 0u);
+      }
     }
     const int64_t bits = lzw_finish(z, s == nseg - 1, sink);
     for (int64_t r = 0; r < bits; r += 32) {                          // the join, serially
@@ -424,9 +549,18 @@ int rhccq_gif_sizes(int32_t n_frames, int32_t H, int32_t W, int32_t flags, int64
   return RHCCQ_OK;
 }
 
-int rhccq_gif_lzw(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
-                  void* workspace, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes) {
-  if (!ctx) return RHCCQ_E_ARG;
+// what the lossy entries refuse beside the lossless ones' refusals; -> the launch's arguments
+static int gif_lossy_check(rhccq_ctx* ctx, int n, const uint8_t* palettes, int k_stride, const int32_t* k_rows, int flags, int64_t slack) {
+  if (flags & RHCCQ_GIF_TRIE) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: the trie dictionary has no lossy form");
+  if (slack < 0 || slack > (int64_t)kMaxSlack) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: slack must be 0..195075");
+  if (!palettes || k_stride < 1 || k_stride > kMaxRows) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: a null palettes or a k_stride outside 1..256");
+  for (int f = 0; f < (flags & RHCCQ_GIF_LOCAL ? n : 1); ++f)
+    if (k_rows[f] > k_stride) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: a table of more rows than k_stride");
+  return 0;
+}
+
+static int gif_lzw_device(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                          void* workspace, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes, const LossyArgs* lossy) {
   Sizes s;
   if (const int rc = gif_shape(ctx, "gif_lzw", n_frames, H, W, flags, s)) return rc;
   if (const int rc = gif_check(ctx, "gif_lzw", idx, idx_elem_bytes, n_frames, k_rows, flags)) return rc;
@@ -434,16 +568,32 @@ int rhccq_gif_lzw(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32
     return rhccq_fail(ctx, RHCCQ_E_ARG, "gif_lzw: a null workspace, streams or stream_bytes, a workspace not aligned to 256 or a misaligned stream_bytes");
   if (stream_stride < s.stream) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "gif_lzw: stream_stride below the stream bound of rhccq_gif_sizes");
   uint8_t* ws = (uint8_t*)workspace;
-  if (const int rc = lzw_launch(ctx, idx, idx_elem_bytes, n_frames, s, k_rows, nullptr, flags, ws)) return rc;
+  if (lossy)
+    if (const int rc = gif_lossy_check(ctx, n_frames, lossy->palettes, lossy->k_stride, k_rows, flags, (int64_t)lossy->slack)) return rc;
+  if (const int rc = lzw_launch(ctx, idx, idx_elem_bytes, n_frames, s, k_rows, nullptr, flags, ws, lossy)) return rc;
   if (const int rc = join_launch(ctx, n_frames, s, flags, ws, 0, stream_stride, streams)) return rc;
   RHCCQ_HIP(ctx, hipMemcpyAsync(stream_bytes, ws + s.o_flen, 8 * (size_t)n_frames, hipMemcpyDeviceToDevice, ctx->stream));
   return RHCCQ_OK;
 }
 
-int rhccq_gif_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
-                     int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, void* workspace, uint8_t* out,
-                     int64_t out_cap, int64_t* out_len) {
+int rhccq_gif_lzw(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                  void* workspace, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes) {
   if (!ctx) return RHCCQ_E_ARG;
+  return gif_lzw_device(ctx, idx, idx_elem_bytes, n_frames, H, W, k_rows, flags, workspace, streams, stream_stride, stream_bytes, nullptr);
+}
+
+int rhccq_gif_lzw_lossy(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                        int32_t k_stride, const int32_t* k_rows, int32_t flags, int64_t slack, void* workspace, uint8_t* streams, int64_t stream_stride,
+                        int64_t* stream_bytes, uint8_t* written) {
+  if (!ctx) return RHCCQ_E_ARG;
+  if (slack < 0 || slack > (int64_t)kMaxSlack) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: slack must be 0..195075");
+  const LossyArgs lossy{palettes, (int)k_stride, (uint32_t)slack, written};
+  return gif_lzw_device(ctx, idx, idx_elem_bytes, n_frames, H, W, k_rows, flags, workspace, streams, stream_stride, stream_bytes, &lossy);
+}
+
+static int gif_encode_device(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                             int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, void* workspace, uint8_t* out,
+                             int64_t out_cap, int64_t* out_len, const LossyArgs* lossy) {
   Sizes s;
   if (const int rc = gif_shape(ctx, "gif_encode", n_frames, H, W, flags, s)) return rc;
   if (const int rc = gif_check(ctx, "gif_encode", idx, idx_elem_bytes, n_frames, k_rows, flags)) return rc;
@@ -455,7 +605,9 @@ int rhccq_gif_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, in
     return rhccq_fail(ctx, RHCCQ_E_ARG, "gif_encode: a null workspace, out or out_len, a workspace not aligned to 256 or a misaligned out_len");
   if (out_cap < s.bound) return rhccq_fail(ctx, RHCCQ_E_LIMIT, "gif_encode: out_cap below the bound of rhccq_gif_sizes");
   uint8_t* ws = (uint8_t*)workspace;
-  if (const int rc = lzw_launch(ctx, idx, idx_elem_bytes, n_frames, s, k_rows, delays, flags, ws)) return rc;
+  if (lossy)
+    if (const int rc = gif_lossy_check(ctx, n_frames, palettes, k_stride, k_rows, flags, (int64_t)lossy->slack)) return rc;
+  if (const int rc = lzw_launch(ctx, idx, idx_elem_bytes, n_frames, s, k_rows, delays, flags, ws, lossy)) return rc;
   hipLaunchKernelGGL(gif_layout_kernel, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t*)(ws + s.o_ftab), (const long long*)(ws + s.o_flen), (int)n_frames,
                      (int)flags, (long long)gif_front_bytes(n_frames, k_rows[0], flags), (long long*)(ws + s.o_foff), (long long*)out_len);
   hipLaunchKernelGGL(gif_frame_kernel, dim3((unsigned)n_frames), dim3(256), 0, ctx->stream, palettes, (int)k_stride, (const uint32_t*)(ws + s.o_ftab),
@@ -464,25 +616,62 @@ int rhccq_gif_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, in
   return join_launch(ctx, n_frames, s, flags, ws, 1, 0, out);
 }
 
-int rhccq_gif_lzw_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
-                       uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes) {
+int rhccq_gif_encode(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                     int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, void* workspace, uint8_t* out,
+                     int64_t out_cap, int64_t* out_len) {
+  if (!ctx) return RHCCQ_E_ARG;
+  return gif_encode_device(ctx, idx, idx_elem_bytes, n_frames, H, W, palettes, k_stride, k_rows, delays, loop, flags, workspace, out, out_cap, out_len, nullptr);
+}
+
+int rhccq_gif_encode_lossy(rhccq_ctx* ctx, const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes,
+                           int32_t k_stride, const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, int64_t slack, void* workspace,
+                           uint8_t* out, int64_t out_cap, int64_t* out_len, uint8_t* written) {
+  if (!ctx) return RHCCQ_E_ARG;
+  if (slack < 0 || slack > (int64_t)kMaxSlack) return rhccq_fail(ctx, RHCCQ_E_ARG, "gif lossy: slack must be 0..195075");
+  const LossyArgs lossy{palettes, (int)k_stride, (uint32_t)slack, written};
+  return gif_encode_device(ctx, idx, idx_elem_bytes, n_frames, H, W, palettes, k_stride, k_rows, delays, loop, flags, workspace, out, out_cap, out_len, &lossy);
+}
+
+// a frame's HostLossy from a call's (lc: null for the lossless forms)
+static HostLossy host_lossy(const LossyArgs* lc, int64_t P, int flags, int f) {
+  return HostLossy{lc->palettes + (flags & RHCCQ_GIF_LOCAL ? 3ll * f * lc->k_stride : 0ll), lc->slack, lc->written ? lc->written + (int64_t)f * P : nullptr};
+}
+
+static int gif_lzw_on_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                           uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes, const LossyArgs* lc) {
   Sizes s;
   if (const int rc = gif_shape(nullptr, "gif_lzw", n_frames, H, W, flags, s)) return rc;
   if (const int rc = gif_check(nullptr, "gif_lzw", idx, idx_elem_bytes, n_frames, k_rows, flags)) return rc;
   if (!streams || !stream_bytes) return RHCCQ_E_ARG;
   if (stream_stride < s.stream) return RHCCQ_E_LIMIT;
+  if (lc)
+    if (const int rc = gif_lossy_check(nullptr, n_frames, lc->palettes, lc->k_stride, k_rows, flags, (int64_t)lc->slack)) return rc;
   std::vector<uint8_t> stream;
   for (int f = 0; f < n_frames; ++f) {
-    index_dispatch(idx_elem_bytes, [&](auto* t) { lzw_frame_host((decltype(t))idx, s.P, f, rows_of(k_rows, flags, f), flags, stream); });
+    const HostLossy hl = lc ? host_lossy(lc, s.P, flags, f) : HostLossy{};
+    index_dispatch(idx_elem_bytes, [&](auto* t) { lzw_frame_host((decltype(t))idx, s.P, f, rows_of(k_rows, flags, f), flags, stream, lc ? &hl : nullptr); });
     std::copy(stream.begin(), stream.end(), streams + (int64_t)f * stream_stride);
     stream_bytes[f] = (int64_t)stream.size();
   }
   return RHCCQ_OK;
 }
 
-int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
-                          const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
-                          int64_t* stream_bytes) {
+int rhccq_gif_lzw_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const int32_t* k_rows, int32_t flags,
+                       uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes) {
+  return gif_lzw_on_host(idx, idx_elem_bytes, n_frames, H, W, k_rows, flags, streams, stream_stride, stream_bytes, nullptr);
+}
+
+int rhccq_gif_lzw_lossy_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                             const int32_t* k_rows, int32_t flags, int64_t slack, uint8_t* streams, int64_t stream_stride, int64_t* stream_bytes,
+                             uint8_t* written) {
+  if (slack < 0 || slack > (int64_t)kMaxSlack) return RHCCQ_E_ARG;
+  const LossyArgs lc{palettes, (int)k_stride, (uint32_t)slack, written};
+  return gif_lzw_on_host(idx, idx_elem_bytes, n_frames, H, W, k_rows, flags, streams, stream_stride, stream_bytes, &lc);
+}
+
+static int gif_encode_on_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                              const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
+                              int64_t* stream_bytes, const LossyArgs* lc) {
   Sizes s;
   if (const int rc = gif_shape(nullptr, "gif_encode", n_frames, H, W, flags, s)) return rc;
   if (const int rc = gif_check(nullptr, "gif_encode", idx, idx_elem_bytes, n_frames, k_rows, flags)) return rc;
@@ -491,6 +680,8 @@ int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_fra
   for (int f = 0; f < (flags & RHCCQ_GIF_LOCAL ? n_frames : 1); ++f)
     if (k_rows[f] > k_stride) return RHCCQ_E_ARG;
   if (out_cap < s.bound) return RHCCQ_E_LIMIT;
+  if (lc)
+    if (const int rc = gif_lossy_check(nullptr, n_frames, palettes, k_stride, k_rows, flags, (int64_t)lc->slack)) return rc;
   const bool local = flags & RHCCQ_GIF_LOCAL;
   gif_put_head(out, W, H, n_frames, k_rows[0], flags, loop);
   if (!local)
@@ -503,7 +694,8 @@ int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_fra
     if (local)
       for (int e = 0; e < 1 << gif_table_bits(k); ++e) gif_put_entry(p + kFrameHeadBytes, palettes + 3ll * f * k_stride, k, e);
     p += gif_frame_front(k, flags);
-    index_dispatch(idx_elem_bytes, [&](auto* t) { lzw_frame_host((decltype(t))idx, s.P, f, k, flags, stream); });
+    const HostLossy hl = lc ? host_lossy(lc, s.P, flags, f) : HostLossy{};
+    index_dispatch(idx_elem_bytes, [&](auto* t) { lzw_frame_host((decltype(t))idx, s.P, f, k, flags, stream, lc ? &hl : nullptr); });
     const int64_t L = (int64_t)stream.size();
     for (int64_t b = 0; b < L; ++b) {
       if (b % 255 == 0) p[gif_sub_pos(b) - 1] = (uint8_t)(L - b < 255 ? L - b : 255);
@@ -516,6 +708,20 @@ int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_fra
   *p++ = 0x3B;
   *out_len = p - out;
   return RHCCQ_OK;
+}
+
+int rhccq_gif_encode_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                          const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, uint8_t* out, int64_t out_cap, int64_t* out_len,
+                          int64_t* stream_bytes) {
+  return gif_encode_on_host(idx, idx_elem_bytes, n_frames, H, W, palettes, k_stride, k_rows, delays, loop, flags, out, out_cap, out_len, stream_bytes, nullptr);
+}
+
+int rhccq_gif_encode_lossy_host(const void* idx, int32_t idx_elem_bytes, int32_t n_frames, int32_t H, int32_t W, const uint8_t* palettes, int32_t k_stride,
+                                const int32_t* k_rows, const int32_t* delays, int32_t loop, int32_t flags, int64_t slack, uint8_t* out, int64_t out_cap,
+                                int64_t* out_len, int64_t* stream_bytes, uint8_t* written) {
+  if (slack < 0 || slack > (int64_t)kMaxSlack) return RHCCQ_E_ARG;
+  const LossyArgs lc{palettes, (int)k_stride, (uint32_t)slack, written};
+  return gif_encode_on_host(idx, idx_elem_bytes, n_frames, H, W, palettes, k_stride, k_rows, delays, loop, flags, out, out_cap, out_len, stream_bytes, &lc);
 }
 
 }  // extern "C"

@@ -46,7 +46,7 @@ __device__ __forceinline__ unsigned dpp_incscan_u32(unsigned v) {
   return v;
 }
 
-// wave-uniform results (scalar): sum (< 2^32 required) / max over the 64 lanes
+// wave-uniform results (scalar): sum (< 2^32 required) / max / min over the 64 lanes
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
   v = dpp_group_sum<16>(v);
   return (unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned)__builtin_amdgcn_readlane((int)v, 16) +
@@ -56,6 +56,11 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   v = dpp_group_max<16>(v);
   return max(max((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
              max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
+  v = dpp_group_min<16>(v);
+  return min(min((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
+             min((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
 }
 // exact u64 inclusive scan of values < 2^32 from two u32 scans of 16-bit limbs (limb totals < 2^32)
 __device__ __forceinline__ unsigned long long wave_incscan_limbs(unsigned v) {

@@ -1,5 +1,5 @@
 """python -m roibasedimagecompression_amd.gif IN1.png IN2.png ... OUT.gif --colours N [--delay CS] [--loop N] [--no-delta] [--refine R]
-       [--pattern S --pattern-size N]
+       [--pattern S --pattern-size N] [--lossy SLACK]
    python -m roibasedimagecompression_amd.gif IN.gif OUT.gif --colours N [the same options]
 
 PNG files of one size to an animated GIF on the device: every IN is read with container.read_png, ImageEncoder.animate builds one palette
@@ -22,6 +22,8 @@ def parser():
     p.add_argument("--refine", type=int, default=0, metavar="R", help="Lloyd iterations over the shared palette (0..64)")
     p.add_argument("--pattern", type=int, default=None, metavar="S", help="pattern dithering of strength S (0..256): frame-stable")
     p.add_argument("--pattern-size", type=int, default=4, metavar="N", help="side of the threshold matrix (2, 4 or 8)")
+    p.add_argument("--lossy", type=int, default=None, metavar="SLACK",
+                   help="bounded-error LZW: a pixel may be written as a row within this squared RGB distance (0..195075) when that lengthens a string")
     return p
 
 
@@ -43,7 +45,7 @@ def main(argv=None):
     else:
         frames = [container.read_png(name, enc.rh)["image"] for name in args.files[:-1]]
     res = enc.animate(frames, args.colours, gif_path=args.files[-1], delay=args.delay, loop=args.loop, delta=not args.no_delta, refine=args.refine,
-                      pattern=args.pattern, pattern_size=args.pattern_size)
+                      pattern=args.pattern, pattern_size=args.pattern_size, lossy=args.lossy)
     print(json.dumps(res["stats"], sort_keys=True))
     return 0
 

@@ -403,7 +403,8 @@ class ImageEncoder:
 
     # ---- the whole flow --------------------------------------------------------------------------------------------------------
     def encode(self, image, roi_quality=20, nonroi_quality=10, out_path=None, exact=False, roi_mask=None, report=False, max_colours=None,
-               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None):
+               target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None,
+               gif_lossy=None):
         """image: uint8[H,W,3] (numpy or device tensor) -> the FrameEncoder result dict (palette, indices device tensor,
         indices_dtype, shape, top_left) equal to script_flow(image, roi_quality, nonroi_quality)'s `final`, plus `classes`
         ([(call, ClassSpec)], the label layers subregion_quantization builds) and `stats`.  out_path: the file is written through
@@ -442,6 +443,7 @@ class ImageEncoder:
         rh = self.rh
         png_path = self._png_arg("ImageEncoder.encode", png_path)
         gif_path = self._png_arg("ImageEncoder.encode", gif_path, "gif_path")
+        gif_lossy = A.gif_lossy(gif_lossy, "ImageEncoder.encode", "gif_lossy")
         searching = target_bytes is not None or target_psnr is not None
         if searching and max_colours is not None:
             raise ValueError("ImageEncoder.encode: target_bytes / target_psnr and max_colours are exclusive")
@@ -513,7 +515,7 @@ class ImageEncoder:
             stats["png"] = self._png_write(res, png_path, exact)
             lap("png")
         if gif_path:
-            stats["gif"] = self._gif_write(res, gif_path)
+            stats["gif"] = self._gif_write(res, gif_path, lossy=gif_lossy)
             lap("gif")
         if report:
             stats["quality"] = self.quality(rgb, res, region_map)
@@ -557,10 +559,11 @@ class ImageEncoder:
         return row
 
     # ---- results as a GIF file (EXTENSION: csrc/gif_write.hip) ------------------------------------------------------------------
-    def _gif_write(self, results, gif_path, delay=4, loop=0, delta=False):
-        """container.gif_file written to gif_path -> its row for stats["gif"]"""
+    def _gif_write(self, results, gif_path, delay=4, loop=0, delta=False, lossy=None):
+        """container.gif_file written to gif_path -> its row for stats["gif"] (lossy: the gif_lossy keyword, the slack of the bounded-error
+        LZW step or None)"""
         from . import container
-        data, row = container.gif_file(results, self.rh, delay=delay, loop=loop, delta=delta)
+        data, row = container.gif_file(results, self.rh, delay=delay, loop=loop, delta=delta, lossy=lossy)
         with open(gif_path, "wb") as f:
             f.write(data)
         return row
@@ -908,7 +911,7 @@ class ImageEncoder:
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
                             target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4,
-                            png_path=None, gif_path=None, search="full"):
+                            png_path=None, gif_path=None, search="full", gif_lossy=None):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -1010,6 +1013,7 @@ class ImageEncoder:
             raise ValueError("ImageEncoder.encode_with_palette: a given grid cannot be combined with refine or colours, which change the palette")
         png_path = self._png_arg("ImageEncoder.encode_with_palette", png_path)
         gif_path = self._png_arg("ImageEncoder.encode_with_palette", gif_path, "gif_path")
+        gif_lossy = A.gif_lossy(gif_lossy, "ImageEncoder.encode_with_palette", "gif_lossy")
         refine, roi_weight = int(refine), int(roi_weight)
         searching = target_bytes is not None or target_psnr is not None
         if refine < 0 or refine > 64:
@@ -1085,7 +1089,7 @@ class ImageEncoder:
             stats["png"] = self._png_write(res, png_path, exact)
             lap("png")
         if gif_path:
-            stats["gif"] = self._gif_write(res, gif_path)
+            stats["gif"] = self._gif_write(res, gif_path, lossy=gif_lossy)
             lap("gif")
         if report:
             host = image.cpu().numpy() if torch.is_tensor(image) else np.ascontiguousarray(image, dtype=np.uint8)
@@ -1115,7 +1119,8 @@ class ImageEncoder:
         return rh.palette_cells(rgb, region_map_from_mask(rgb, roi_mask, rh), 2, [1, roi_weight, 1], into=into)
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
-                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None):
+                 target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None,
+                 gif_lossy=None):
         """image: uint8[H,W,3] (numpy or device tensor) or the name of a PNG file (read on the device by container.read_png; its alpha is
         ignored and stats["png_in"] says what the file was), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
@@ -1133,6 +1138,7 @@ class ImageEncoder:
         rh = self.rh
         png_path = self._png_arg("ImageEncoder.quantize", png_path)
         gif_path = self._png_arg("ImageEncoder.quantize", gif_path, "gif_path")
+        gif_lossy = A.gif_lossy(gif_lossy, "ImageEncoder.quantize", "gif_lossy")
         if gif_path and int(colours) > 256:
             raise ValueError("ImageEncoder.quantize: gif_path needs colours <= 256 (a GIF colour table has at most 256 rows)")
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
@@ -1157,7 +1163,7 @@ class ImageEncoder:
         res = self.encode_with_palette(rgb, pal, out_path=out_path, exact=exact, roi_mask=roi_mask, report=report, refine=refine,
                                        roi_weight=roi_weight if (refine or searching) else 1, target_bytes=target_bytes, target_psnr=target_psnr,
                                        run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size,
-                                       png_path=png_path, gif_path=gif_path)
+                                       png_path=png_path, gif_path=gif_path, gif_lossy=gif_lossy)
         res["stats"]["build"] = build
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         if png_in is not None:
@@ -1169,7 +1175,7 @@ class ImageEncoder:
     QUANTIZE_BATCH_SLICE = 128
 
     def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False, pattern=None, pattern_size=4,
-                       gif_path=None, delay=4):
+                       gif_path=None, delay=4, gif_lossy=None):
         """images: a list of uint8[H,W,3] images of any sizes (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor
         (a contiguous device tensor is used in place, nothing is concatenated) -> a list with one result dict per image: what
         quantize(image, colours, refine=refine, roi_mask=mask, roi_weight=...) returns for that image alone, bit for bit (palette
@@ -1198,6 +1204,7 @@ class ImageEncoder:
         fn = "ImageEncoder.quantize_batch"
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         gif_path = self._png_arg(fn, gif_path, "gif_path")
+        gif_lossy = A.gif_lossy(gif_lossy, fn, "gif_lossy")
         if gif_path and colours > 256:
             raise ValueError(f"{fn}: gif_path needs colours <= 256 (a GIF colour table has at most 256 rows)")
         if colours < 1:
@@ -1290,7 +1297,7 @@ class ImageEncoder:
                 if p:
                     container.write_frame(res, p, rh, exact=exact)
         if gif_path:
-            row = self._gif_write(out, gif_path, delay=delay)
+            row = self._gif_write(out, gif_path, delay=delay, lossy=gif_lossy)
             for res in out:
                 res["stats"]["gif"] = row
         seconds = {"batch": round(time.perf_counter() - t0, 4)}
@@ -1318,7 +1325,7 @@ class ImageEncoder:
         return self.rh.palette_build(cells, colours)[0]
 
     def animate(self, images, colours=256, gif_path=None, delay=None, loop=None, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
-                pattern_size=4):
+                pattern_size=4, lossy=None):
         """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor ->
         {"palette": uint8[k, 3], "indices": device uint8[B, H, W], "indices_dtype": "uint8", "shape": (H, W), "stats"}: an animated GIF89a built on the device from end to end.  One shared_palette over all frames (at most `colours` rows,
         1..256; with delta at most 255, because the transparent index is one more table entry: stats["gif"]["colours"] says what was
@@ -1331,6 +1338,9 @@ class ImageEncoder:
         frame; a pixel inside weighs roi_weight (1..255) in the shared histogram and the refinement.  gif_path: where the file is written
         (None: it is built, stats["gif"] says what it is, and it is dropped).  stats = {"build": {asked, rows}, "remap": [a row a frame], "pattern": [a row a frame] with pattern, "refine" with refine,
         "gif": container.gif_file's row, "seconds"}.
+        lossy (default None = lossless; 0 is a value): the slack 0..195075 of the bounded-error LZW step (container.gif_bytes).  stats["gif"]
+        then carries "lossy": {slack, moved, pixels, "shown": the pixels / sse / mse / psnr row of what the file SHOWS against the
+        frames (the written indices, a transparent pixel resolved frame by frame), beside stats["remap"], which is of the index maps}.
         dither, run_slack, run_penalty and the targets are not parameters: error diffusion is not frame-stable (a changed pixel moves
         the indices of everything to its right and below, so delta would find nothing), and the run rules and targets decide per
         image on the host.
@@ -1341,6 +1351,7 @@ class ImageEncoder:
         fn = "ImageEncoder.animate"
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         gif_path = self._png_arg(fn, gif_path, "gif_path")
+        lossy = A.gif_lossy(lossy, fn)
         if not 1 <= colours <= 256:
             raise ValueError(f"{fn}: colours must be 1..256 (a GIF colour table has at most 256 rows)")
         if refine < 0 or refine > 64:
@@ -1396,7 +1407,17 @@ class ImageEncoder:
             idx, sums = rh.palette_pattern_batch(rgb, off, [W] * B, pals, k, self._slack_table(runs, masked), runs["size"], cls, nc, px_off_dev=off_dev)
         else:
             idx, sums = rh.palette_remap_batch(rgb, off, pals, k, cls, nc, px_off_dev=off_dev)
-        out, length, lens = rh.gif_encode_async(idx, B, H, W, pal, None, delay, loop, bool(delta))
+        shown_sums = moved = None
+        if lossy is None:
+            out, length, lens = rh.gif_encode_async(idx, B, H, W, pal, None, delay, loop, bool(delta))
+        else:
+            from . import container
+            out, length, lens, written = rh.gif_encode_async(idx, B, H, W, pal, None, delay, loop, bool(delta), lossy=lossy, written=True)
+            moved = container.gif_moved(written, idx, [K], delta)
+            shown = [written[0]]
+            for b in range(1, B):                                               # the screen: a transparent pixel keeps what it showed
+                shown.append(torch.where(written[b] == K, shown[-1], written[b]) if delta else written[b])
+            shown_sums = rh.error_sums(rgb.reshape(1, -1, 3), pal[torch.stack(shown).reshape(-1).long()].reshape(1, -1, 3))
         host = rh.to_host(*([sums, pal, length, lens] + ([hist, nit] if refine else [])))
         sums, pal_host, size, lens = host[0], host[1], int(host[2][0]), host[3]
         stats = {"build": {"asked": asked, "rows": K}, "remap": []}
@@ -1412,6 +1433,9 @@ class ImageEncoder:
             stats["refine"] = {"iterations": n, "converged": n == 0 or int(host[4][n - 1, 1]) == 0, "sse": [int(v) for v in host[4][:n, 0]],
                                "changed": [int(v) for v in host[4][:n, 1]]}
         stats["gif"] = {"bytes": size, "frames": B, "table": "global", "colours": K, "delta": bool(delta), "stream_bytes": [int(v) for v in lens]}
+        if lossy is not None:
+            stats["gif"]["lossy"] = {"slack": lossy, "moved": int(moved.item()), "pixels": B * H * W,
+                                     "shown": self._remap_row(B * H * W, int(shown_sums[:3].sum().item()))}
         if gif_path:
             with open(gif_path, "wb") as f:
                 f.write(rh.to_host(out[:size]).tobytes())

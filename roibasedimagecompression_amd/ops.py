@@ -2046,28 +2046,17 @@ class Rhccq:
             raise RhccqError(f"gif_sizes: rhccq_gif_sizes({n}, {H}, {W}) failed ({rc})")
         return ws.value, stream.value, bound.value
 
-    def gif_lzw(self, frames, n, H, W, rows, local=False, delta=False, dictionary="hash"):
-        """frames: n * H * W indices (uint8, int16 holding uint16, int32 / int64; numpy or device), rows: [K] or, local, one K a frame ->
-        (streams uint8[n, bound] device, lengths int64[n] device): frame f's GIF code stream is streams[f, :lengths[f]] (include/rhccq.h:
-        segments of gif_segment_pixels() pixels, each an LZW problem of one wave).  delta: a pixel that equals the frame in front is
-        written as the transparent index K.  dictionary: "hash" (the open-addressed table, 32 KiB of LDS a segment) or "trie" (sibling-linked,
-        16 KiB); the streams are the same.  Nothing waits for the device."""
-        fn = "gif_lzw"
-        idx, k_rows, flags = self._gif_args(fn, frames, n, H, W, rows, local, delta, dictionary)
-        ws, stream, _ = self.gif_sizes(n, H, W, local, delta)
-        work = self.empty((ws,), torch.uint8)
-        out = self.empty((int(n), stream), torch.uint8)
-        lengths = self.empty((int(n),), torch.int64)
-        self._check(self.lib.rhccq_gif_lzw(self.ctx, self._p(idx), idx.element_size(), int(n), int(H), int(W), k_rows, flags, self._p(work), self._p(out),
-                                           stream, self._p(lengths)), fn)
-        return out, lengths
+    def _gif_lossy(self, fn, lossy, written, dictionary, n, H, W):
+        """lossy and written as the GIF calls take them -> (slack or None, the written buffer uint8[n, H, W] or None)"""
+        slack = A.gif_lossy(lossy, fn)
+        if slack is None and written:
+            raise ValueError(f"{fn}: written needs lossy (the lossless file writes the clamped indices themselves)")
+        if slack is not None and dictionary != "hash":
+            raise ValueError(f"{fn}: lossy needs the hash dictionary (the trie has no lossy form)")
+        return slack, self.empty((int(n), int(H), int(W)), torch.uint8) if written else None
 
-    def gif_encode_async(self, frames, n, H, W, palettes, rows=None, delays=4, loop=0, delta=False, dictionary="hash"):
-        """frames as gif_lzw takes them; palettes uint8[K, 3] (ONE global table) or uint8[n, K_stride, 3] with rows = the rows of every
-        frame's local table; delays: centiseconds, one number or one a frame -> (uint8 device buffer, int64 device length, int64[n] device
-        stream lengths: a view of the call's workspace).  The GIF89a file is out[:length], built on the device; nothing waits for it.
-        dictionary: as gif_lzw takes it."""
-        fn = "gif_encode"
+    def _gif_palettes(self, fn, palettes, n, rows=None):
+        """palettes [K, 3] or [n, K_stride, 3] -> (uint8 device palettes, local, rows)"""
         palettes = A.as_uint8(palettes, self.device, fn, "palettes")
         local = palettes.ndim == 3
         if palettes.ndim not in (2, 3) or palettes.shape[-1] != 3 or (local and palettes.shape[0] != int(n)):
@@ -2078,6 +2067,47 @@ class Rhccq:
             rows = [palettes.shape[0]]
         if palettes.shape[-2] > 256 or max(int(k) for k in rows) > palettes.shape[-2]:
             raise ValueError(f"{fn}: a table must have 1..256 rows, all of them in palettes")
+        return palettes, local, rows
+
+    def gif_lzw(self, frames, n, H, W, rows, local=False, delta=False, dictionary="hash", lossy=None, written=False, palettes=None):
+        """frames: n * H * W indices (uint8, int16 holding uint16, int32 / int64; numpy or device), rows: [K] or, local, one K a frame ->
+        (streams uint8[n, bound] device, lengths int64[n] device): frame f's GIF code stream is streams[f, :lengths[f]] (include/rhccq.h:
+        segments of gif_segment_pixels() pixels, each an LZW problem of one wave).  delta: a pixel that equals the frame in front is
+        written as the transparent index K.  dictionary: "hash" (the open-addressed table, 32 KiB of LDS a segment) or "trie" (sibling-linked,
+        16 KiB); the streams are the same.  Nothing waits for the device.
+        lossy (default None = the lossless step; 0 is a value): the slack 0..195075 of the bounded-error step (include/rhccq.h "lossy"): on
+        a miss the wave takes the nearest row within that squared RGB distance whose string IS in the dictionary.  It needs palettes
+        (uint8[K, 3], or [n, K_stride, 3] with local) and the hash dictionary.  written=True adds a third result: uint8[n, H, W] device,
+        the pixel every position was written as (the transparent index under delta)."""
+        fn = "gif_lzw"
+        slack, wr = self._gif_lossy(fn, lossy, written, dictionary, n, H, W)
+        idx, k_rows, flags = self._gif_args(fn, frames, n, H, W, rows, local, delta, dictionary)
+        ws, stream, _ = self.gif_sizes(n, H, W, local, delta)
+        work = self.empty((ws,), torch.uint8)
+        out = self.empty((int(n), stream), torch.uint8)
+        lengths = self.empty((int(n),), torch.int64)
+        if slack is None:
+            self._check(self.lib.rhccq_gif_lzw(self.ctx, self._p(idx), idx.element_size(), int(n), int(H), int(W), k_rows, flags, self._p(work),
+                                               self._p(out), stream, self._p(lengths)), fn)
+            return out, lengths
+        if palettes is None:
+            raise ValueError(f"{fn}: lossy needs palettes (the distances are between their rows)")
+        palettes, pal_local, _ = self._gif_palettes(fn, palettes, n, [int(k) for k in rows])
+        if pal_local != bool(local):
+            raise ValueError(f"{fn}: palettes [K, 3] go with a global table, [n, K, 3] with local")
+        self._check(self.lib.rhccq_gif_lzw_lossy(self.ctx, self._p(idx), idx.element_size(), int(n), int(H), int(W), self._p(palettes),
+                                                 int(palettes.shape[-2]), k_rows, flags, slack, self._p(work), self._p(out), stream, self._p(lengths),
+                                                 self._p(wr) if wr is not None else None), fn)
+        return (out, lengths, wr) if written else (out, lengths)
+
+    def gif_encode_async(self, frames, n, H, W, palettes, rows=None, delays=4, loop=0, delta=False, dictionary="hash", lossy=None, written=False):
+        """frames as gif_lzw takes them; palettes uint8[K, 3] (ONE global table) or uint8[n, K_stride, 3] with rows = the rows of every
+        frame's local table; delays: centiseconds, one number or one a frame -> (uint8 device buffer, int64 device length, int64[n] device
+        stream lengths: a view of the call's workspace).  The GIF89a file is out[:length], built on the device; nothing waits for it.
+        dictionary, lossy, written: as gif_lzw takes them; written=True adds a fourth result, uint8[n, H, W] device."""
+        fn = "gif_encode"
+        slack, wr = self._gif_lossy(fn, lossy, written, dictionary, n, H, W)
+        palettes, local, rows = self._gif_palettes(fn, palettes, n, rows)
         idx, k_rows, flags = self._gif_args(fn, frames, n, H, W, rows, local, delta, dictionary)
         n, H, W = int(n), int(H), int(W)
         delays = [int(delays)] * n if np.ndim(delays) == 0 else [int(d) for d in delays]
@@ -2089,9 +2119,15 @@ class Rhccq:
         work = self.empty((ws,), torch.uint8)
         out = self.empty((bound,), torch.uint8)
         length = self.empty((1,), torch.int64)
-        self._check(self.lib.rhccq_gif_encode(self.ctx, self._p(idx), idx.element_size(), n, H, W, self._p(palettes), int(palettes.shape[-2]), k_rows,
-                                              (C.c_int32 * n)(*delays), int(loop), flags, self._p(work), self._p(out), bound, self._p(length)), fn)
-        return out, length, work[:8 * n].view(torch.int64)
+        if slack is None:
+            self._check(self.lib.rhccq_gif_encode(self.ctx, self._p(idx), idx.element_size(), n, H, W, self._p(palettes), int(palettes.shape[-2]), k_rows,
+                                                  (C.c_int32 * n)(*delays), int(loop), flags, self._p(work), self._p(out), bound, self._p(length)), fn)
+            return out, length, work[:8 * n].view(torch.int64)
+        self._check(self.lib.rhccq_gif_encode_lossy(self.ctx, self._p(idx), idx.element_size(), n, H, W, self._p(palettes), int(palettes.shape[-2]), k_rows,
+                                                    (C.c_int32 * n)(*delays), int(loop), flags, slack, self._p(work), self._p(out), bound, self._p(length),
+                                                    self._p(wr) if wr is not None else None), fn)
+        lens = work[:8 * n].view(torch.int64)
+        return (out, length, lens, wr) if written else (out, length, lens)
 
     def gif_encode(self, frames, n, H, W, palettes, rows=None, delays=4, loop=0, delta=False):
         """gif_encode_async's file as bytes: one read of the length, one copy of the file"""
