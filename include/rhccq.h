@@ -1604,6 +1604,43 @@ int rhccq_gif_compose_host(const uint8_t* pixels, int64_t n_pixels, const uint8_
 /* file in host memory; parses it itself; outputs sized by the parse (they may be NULL for a file the parser refuses); status: host int32[2] */
 int rhccq_gif_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, uint8_t* alpha, uint8_t* idx, int32_t* status);
 
+/* ---- resize: separable convolution resampling of uint8 images in exact integers (EXTENSION: csrc/resize.hip, csrc/resize.h) ----
+ * The filter is stretched by the scale factor when shrinking; this is the algorithm of Pillow's Image.resize(reducing_gap=None) for
+ * 8-bit images.  filter: 0 box (1 on (-0.5, 0.5], support 0.5), 1 triangle (1 - |x|, support 1), 2 cubic (Keys' kernel with a = -0.5,
+ * support 2), 3 lanczos (sinc(x) sinc(x / 3) on [-3, 3), support 3).
+ * An axis of n samples resized to m: scale = n / m, fs = max(scale, 1), support = filter_support * fs, all in double.  Output sample i:
+ *   centre = (i + 0.5) * scale;  lo = max((int)(centre - support + 0.5), 0);  hi = min((int)(centre + support + 0.5), n);
+ *   tap t in [0, hi - lo) has the real weight filter((t + lo - centre + 0.5) / fs); the weights are divided by their sum if it is not 0;
+ *   each becomes an integer (int)(0.5 + w * 2^22) for w >= 0 and (int)(-0.5 + w * 2^22) for w < 0 (truncation toward zero);
+ *   out = clamp((2^21 + sum_t weight_t * in[lo + t]) >> 22, 0, 255), the shift arithmetic.
+ * The rows pass comes first: it resamples the width into a uint8 intermediate [H][OW]; the columns pass resamples the height.  An axis
+ * whose size does not change is not resampled.  Channels are independent bytes: C is 1, 3 or 4 interleaved bytes a pixel.  H, W, OH, OW
+ * are 1..65535 each; B >= 1 images of one size lie back to back.  The real weights are computed once per axis on the host, in double;
+ * everything that touches pixels reads only the integer table (first tap, tap count, int32 weights per output sample), so the device
+ * form and the host form agree bit for bit.  A table in which 255 * sum|weight| + 2^21 >= 2^31 for some output sample is refused
+ * (RHCCQ_E_LIMIT): the 32-bit sum cannot overflow.
+ * rhccq_resize_taps_host: the table of one axis.  first and count: int32[n_out]; weights: the samples' weights one after another, at
+ *   most weights_cap of them; *n_weights: how many the axis has.  With weights == NULL only *n_weights is written (the sizing query).
+ *   RHCCQ_E_ARG: n_in or n_out outside 1..65535, a filter outside 0..3, a null n_weights, a negative weights_cap, weights without first
+ *   and count.  RHCCQ_E_LIMIT: weights_cap below *n_weights (which is written), or the overflow test above.
+ * rhccq_resize: src uint8[B][H][W][C] -> dst uint8[B][OH][OW][C], both on the device and aligned to 4.  Builds both tables on the host (the last 16 axes
+ *   asked for are kept for the process) and uploads them into the workspace on the context's stream; two launches; waits for nothing on the device and reads nothing back.  The
+ *   workspace (rhccq_resize_workspace_bytes, aligned to 256; negative for bad arguments) holds the intermediate [B][H][OW C rounded up to
+ *   4] and the tables.  RHCCQ_E_ARG (before any work): a null pointer, B < 1, a side outside 1..65535, C not 1, 3 or 4, a filter outside
+ *   0..3, a misaligned src, dst or workspace, a short workspace.  RHCCQ_E_LIMIT: B > 65535 (slice the batch), the overflow test.
+ * rhccq_resize_host: the same step functions serially on host memory, any alignment.
+ * rhccq_resize_tile_rows / _run_cols / _strip_bytes: image rows (64) and output columns (32) of a workgroup of the rows pass; bytes of
+ *   a row (1024) a workgroup of the columns pass owns. */
+int32_t rhccq_resize_tile_rows(void);
+int32_t rhccq_resize_run_cols(void);
+int32_t rhccq_resize_strip_bytes(void);
+int rhccq_resize_taps_host(int32_t n_in, int32_t n_out, int32_t filter, int32_t* first, int32_t* count, int32_t* weights, int64_t weights_cap,
+                           int64_t* n_weights);
+int64_t rhccq_resize_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW);
+int rhccq_resize(rhccq_ctx* ctx, const uint8_t* src, int32_t B, int32_t H, int32_t W, int32_t C, uint8_t* dst, int32_t OH, int32_t OW, int32_t filter,
+                 void* workspace, int64_t workspace_bytes);
+int rhccq_resize_host(const uint8_t* src, int32_t B, int32_t H, int32_t W, int32_t C, uint8_t* dst, int32_t OH, int32_t OW, int32_t filter);
+
 #ifdef __cplusplus
 }
 #endif

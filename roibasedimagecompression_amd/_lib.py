@@ -348,6 +348,13 @@ PROTOTYPES = {
     "rhccq_gif_unlzw_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, C.POINTER(c_int64)]),
     "rhccq_gif_compose_host": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rhccq_gif_decode_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_resize_tile_rows": (c_int32, []),
+    "rhccq_resize_run_cols": (c_int32, []),
+    "rhccq_resize_strip_bytes": (c_int32, []),
+    "rhccq_resize_taps_host": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_resize_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "rhccq_resize": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64]),
+    "rhccq_resize_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32]),
 }
 
 

@@ -149,6 +149,45 @@ def gif_lossy(lossy, fn, what="lossy"):
     return int(lossy)
 
 
+RESIZE_FILTERS = ("box", "triangle", "cubic", "lanczos")      # (ops.RESIZE_FILTERS; a filter's place is its number in the C ABI)
+RESIZE_MAX_SIDE = 65535
+
+
+def resize_filter(name, fn, what="filter"):
+    """filter= / resample= of a resize -> the filter's number in the C ABI"""
+    if not isinstance(name, str) or name not in RESIZE_FILTERS:
+        raise ValueError(f"{fn}: {what} must be one of {', '.join(RESIZE_FILTERS)}, got {name!r}")
+    return RESIZE_FILTERS.index(name)
+
+
+def resize_size(size, H, W, fn):
+    """size= of everything that resizes: None = off -> None; (OH, OW) -> that; one integer s = the longest side becomes s and the
+    other side max(1, (other * s + longest // 2) // longest) -> (OH, OW).  Every side is 1..65535."""
+    if size is None:
+        return None
+
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if whole(size):
+        s, longest = int(size), max(H, W)
+        OH, OW = (s, max(1, (W * s + longest // 2) // longest)) if H >= W else (max(1, (H * s + longest // 2) // longest), s)
+    elif isinstance(size, (tuple, list)) and len(size) == 2 and all(whole(v) for v in size):
+        OH, OW = int(size[0]), int(size[1])
+    else:
+        raise ValueError(f"{fn}: size must be None, one integer (the longest side) or (OH, OW), got {size!r}")
+    if not (1 <= OH <= RESIZE_MAX_SIDE and 1 <= OW <= RESIZE_MAX_SIDE):
+        raise ValueError(f"{fn}: a resized side must be 1..{RESIZE_MAX_SIDE}, got {(OH, OW)}")
+    return OH, OW
+
+
+def cli_size(text):
+    """--size of the command lines: "HxW" -> (H, W), "N" -> N (argparse turns the ValueError into its usage message)"""
+    parts = text.lower().split("x")
+    if len(parts) > 2 or not all(p.isdigit() for p in parts):
+        raise ValueError(f"HxW or N is expected, got {text!r}")
+    return int(parts[0]) if len(parts) == 1 else (int(parts[0]), int(parts[1]))
+
+
 def k_out_rows(k, fn, empty="every count is zero", over="the counts add up to more than 2^32 - 1"):
     """the k_out a chain wrote: the rows it made, or the negative code of an error only the counts (the table) show"""
     if k < 0:

@@ -390,17 +390,19 @@ def read_gif(src, rh=None):
                       "stream_bytes": [table[f].stream_bytes for f in range(info.n_frames)], "seconds": round(time.perf_counter() - t0, 4)}}
 
 
-def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4, lossy=None):
+def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4, lossy=None, size=None, resample="lanczos"):
     """an animated GIF to one of at most `colours` colours, on the device from end to end: read_gif, then ImageEncoder.animate over the
     composed frames with the file's own delays and loop count (0 where it has none), written to dst.  The frames enter as the viewer
     shows them, so cropped rectangles, transparency and disposal methods are gone from the result; a pixel no frame has covered enters
-    as colour (0, 0, 0).  lossy: as animate takes it.  -> animate's dict, with stats["read"] = read_gif's stats."""
+    as colour (0, 0, 0).  lossy: as animate takes it.  size (None = off, (OH, OW), or one integer for the longest side) and resample: the
+    composed frames are resized on the device first, as animate takes them.  -> animate's dict, with stats["read"] = read_gif's stats."""
     from .image import ImageEncoder
     rh = rh or default_context()
+    ImageEncoder._resize_args("reduce_gif", size, resample)                  # (before the file is read)
     src = read_gif(src, rh)
     enc = ImageEncoder(rh)
     res = enc.animate(src["images"], colours, gif_path=dst, delay=src["delays"], loop=src["loop"] or 0, delta=delta, refine=refine, pattern=pattern,
-                      pattern_size=pattern_size, lossy=lossy)
+                      pattern_size=pattern_size, lossy=lossy, size=size, resample=resample)
     res["stats"]["read"] = src["stats"]
     return res
 

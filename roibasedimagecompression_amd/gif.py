@@ -1,5 +1,5 @@
 """python -m roibasedimagecompression_amd.gif IN1.png IN2.png ... OUT.gif --colours N [--delay CS] [--loop N] [--no-delta] [--refine R]
-       [--pattern S --pattern-size N] [--lossy SLACK]
+       [--pattern S --pattern-size N] [--lossy SLACK] [--size HxW|N] [--resample NAME]
    python -m roibasedimagecompression_amd.gif IN.gif OUT.gif --colours N [the same options]
 
 PNG files of one size to an animated GIF on the device: every IN is read with container.read_png, ImageEncoder.animate builds one palette
@@ -24,6 +24,9 @@ def parser():
     p.add_argument("--pattern-size", type=int, default=4, metavar="N", help="side of the threshold matrix (2, 4 or 8)")
     p.add_argument("--lossy", type=int, default=None, metavar="SLACK",
                    help="bounded-error LZW: a pixel may be written as a row within this squared RGB distance (0..195075) when that lengthens a string")
+    from ._palette_args import RESIZE_FILTERS, cli_size
+    p.add_argument("--size", type=cli_size, default=None, metavar="HxW|N", help="resize the frames on the device first: to H x W, or the longest side to N")
+    p.add_argument("--resample", choices=RESIZE_FILTERS, default="lanczos", metavar="NAME", help="the resize filter: " + ", ".join(RESIZE_FILTERS))
     return p
 
 
@@ -45,7 +48,7 @@ def main(argv=None):
     else:
         frames = [container.read_png(name, enc.rh)["image"] for name in args.files[:-1]]
     res = enc.animate(frames, args.colours, gif_path=args.files[-1], delay=args.delay, loop=args.loop, delta=not args.no_delta, refine=args.refine,
-                      pattern=args.pattern, pattern_size=args.pattern_size, lossy=args.lossy)
+                      pattern=args.pattern, pattern_size=args.pattern_size, lossy=args.lossy, size=args.size, resample=args.resample)
     print(json.dumps(res["stats"], sort_keys=True))
     return 0
 

@@ -911,7 +911,7 @@ class ImageEncoder:
 
     def encode_with_palette(self, image, palette, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, colours=None,
                             target_bytes=None, target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4,
-                            png_path=None, gif_path=None, search="full", gif_lossy=None):
+                            png_path=None, gif_path=None, search="full", gif_lossy=None, size=None, resample="lanczos"):
         """image: uint8[H,W,3] (numpy or device tensor); palette: uint8[K,3] (numpy or device tensor) or a dict with "palette" (an
         earlier result, container.read_frame's) -> the FrameEncoder result dict (palette, indices device tensor [H,W], indices_dtype,
         shape, top_left = (0, 0)) whose every index is the nearest palette row (Rhccq.palette_remap: exact integers, ties to the
@@ -1004,8 +1004,14 @@ class ImageEncoder:
         Rhccq.palette_grid built from this very palette may be given instead of "grid" and is reused (encode_sequence does so);
         refine and colours change the palette and raise ValueError with it.  stats["search"] = {kind: "grid", listed, flagged,
         entries, longest, overflow_pixels}.  It serves the plain remap only: with run_slack, run_penalty, dither, pattern or a
-        target it raises ValueError."""
+        target it raises ValueError.
+        size (default None = off; (OH, OW), or one integer for the longest side) with resample in ops.RESIZE_FILTERS (default "lanczos"):
+        the image is first resized on the device (Rhccq.resize: separable convolution resampling in exact integers, Pillow's
+        Image.resize(reducing_gap=None) byte for byte), and roi_mask with it, as a 0 / 255 image under the same filter that holds
+        where the result is >= 128; everything above then runs on the resized image.  stats["resize"] = {"from": (H, W), "to":
+        (OH, OW), "filter"}."""
         rh = self.rh
+        resizing = self._resize_args("ImageEncoder.encode_with_palette", size, resample)
         search = A.search_kind(search, "ImageEncoder.encode_with_palette")
         if search != "full" and any(v is not None for v in (run_slack, run_penalty, dither, pattern, target_bytes, target_psnr)):
             raise ValueError("ImageEncoder.encode_with_palette: search other than \"full\" serves the plain remap only")
@@ -1033,6 +1039,10 @@ class ImageEncoder:
         rgb = image.to(rh.device).contiguous() if torch.is_tensor(image) else rh.dev(np.asarray(image))
         if rgb.dtype != torch.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError("ImageEncoder.encode_with_palette: a uint8 H x W x 3 image is expected")
+        resized = None
+        if resizing:
+            (rgb,), (roi_mask,), _, (resized,) = self._resize_frames("ImageEncoder.encode_with_palette", [rgb], [roi_mask], size, resample)
+            image = rgb
         H, W = int(rgb.shape[0]), int(rgb.shape[1])
         t, t0 = {}, time.perf_counter()
 
@@ -1098,6 +1108,8 @@ class ImageEncoder:
             stats["quality"] = self.quality(rgb_r, res, self.region_map)
             lap("report")
         stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
+        if resized is not None:
+            stats["resize"] = resized
         if png_in is not None:
             stats["png_in"] = png_in
         res["stats"] = stats
@@ -1110,6 +1122,52 @@ class ImageEncoder:
             raise ValueError(f"ImageEncoder.{fn}: a uint8 H x W x 3 image is expected")
         return rgb
 
+    # ---- resizing in front of the palette calls (EXTENSION: csrc/resize.hip) -----------------------------------------------------
+    @staticmethod
+    def _resize_args(fn, size, resample):
+        """size= / resample= as quantize, quantize_batch, encode_with_palette and animate take them, tested before anything runs:
+        size None = off, (OH, OW), or one integer for the longest side; resample in ops.RESIZE_FILTERS -> is a resize asked for"""
+        if size is None:
+            return False
+        A.resize_size(size, 1, 1, fn)
+        A.resize_filter(resample, fn, "resample")
+        return True
+
+    def _resize_frames(self, fn, frames, masks, size, resample, stacked=None):
+        """frames: device uint8[H, W, 3] each (stacked: the same frames as ONE [B, H, W, 3] tensor, or None), masks: one mask (or None) a
+        frame -> (frames, masks, stacked, rows) resized.  Frames that share a size go through one Rhccq.resize call (one launch pair
+        for all of them).  A mask is resized as a 0 / 255 one-channel image with the same filter and holds where that gives >= 128.
+        rows: stats["resize"] = {"from": (H, W), "to": (OH, OW), "filter"} of every frame."""
+        rh = self.rh
+        from .api.roi import region_map_from_mask
+        groups = {}
+        for i, f in enumerate(frames):
+            groups.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(i)
+        out, out_masks, rows = list(frames), list(masks), [None] * len(frames)
+        whole = stacked is not None and len(groups) == 1
+        for (H, W), members in groups.items():
+            to = A.resize_size(size, H, W, fn)
+            batch = stacked if whole else torch.stack([frames[i] for i in members])
+            small = rh.resize(batch, to, resample)
+            if whole:
+                stacked = small
+            masked = [i for i in members if masks[i] is not None]
+            if masked:
+                m = torch.stack([region_map_from_mask(frames[i], masks[i], rh) * 255 for i in masked])
+                m = rh.resize(m.unsqueeze(-1), to, resample)[..., 0] >= 128
+                for j, i in enumerate(masked):
+                    out_masks[i] = m[j]
+            for j, i in enumerate(members):
+                out[i], rows[i] = small[j], {"from": (H, W), "to": to, "filter": resample}
+        return out, out_masks, stacked if whole else None, rows
+
+    def resize(self, image_or_file, size, filter="lanczos"):
+        """image_or_file: uint8 [H, W], [H, W, C] or [B, H, W, C] (numpy or device tensor), or the name of a PNG file (read on the device,
+        alpha ignored) -> the device tensor Rhccq.resize gives: size (OH, OW) or one integer for the longest side, filter in
+        ops.RESIZE_FILTERS.  Exact integers, Pillow's Image.resize(reducing_gap=None) byte for byte (include/rhccq.h "resize")."""
+        image, _ = self._png_in(image_or_file)
+        return self.rh.resize(image, size, filter)
+
     def _cells(self, fn, rgb, roi_mask, roi_weight, into=None):
         """the frame's histogram table (Rhccq.palette_cells); with a mask a pixel inside it weighs roi_weight and one outside 1"""
         rh = self.rh
@@ -1120,7 +1178,7 @@ class ImageEncoder:
 
     def quantize(self, image, colours=256, out_path=None, exact=False, roi_mask=None, report=False, refine=0, roi_weight=1, target_bytes=None,
                  target_psnr=None, run_slack=None, run_penalty=None, dither=None, pattern=None, pattern_size=4, png_path=None, gif_path=None,
-                 gif_lossy=None):
+                 gif_lossy=None, size=None, resample="lanczos"):
         """image: uint8[H,W,3] (numpy or device tensor) or the name of a PNG file (read on the device by container.read_png; its alpha is
         ignored and stats["png_in"] says what the file was), colours = N -> the result dict of encode_with_palette for a palette of at most N
         rows made from the image itself: one pass over the pixels into a 32 x 32 x 32 colour histogram (Rhccq.palette_cells), greedy
@@ -1134,8 +1192,11 @@ class ImageEncoder:
         channel) are never separated, so fewer than N rows come back when fewer cells are occupied, and two boxes may round to the
         same row.  stats["build"] = {asked: N, rows: rows built, cells: occupied cells, steps: splits}; everything else as
         encode_with_palette fills it.  png_path, gif_path: as encode_with_palette takes them (gif_path raises ValueError when
-        colours is above 256, before anything runs)."""
+        colours is above 256, before anything runs).
+        size (default None = off), resample: the image and its mask are first resized on the device, as encode_with_palette takes them;
+        the palette is built from the resized image."""
         rh = self.rh
+        resizing = self._resize_args("ImageEncoder.quantize", size, resample)
         png_path = self._png_arg("ImageEncoder.quantize", png_path)
         gif_path = self._png_arg("ImageEncoder.quantize", gif_path, "gif_path")
         gif_lossy = A.gif_lossy(gif_lossy, "ImageEncoder.quantize", "gif_lossy")
@@ -1155,6 +1216,9 @@ class ImageEncoder:
                         pattern_size=pattern_size)
         image, png_in = self._png_in(image)
         rgb = self._frame_tensor("quantize", image)
+        resized = None
+        if resizing:
+            (rgb,), (roi_mask,), _, (resized,) = self._resize_frames("ImageEncoder.quantize", [rgb], [roi_mask], size, resample)
         t0 = time.perf_counter()
         cells = self._cells("quantize", rgb, roi_mask, roi_weight)
         pal, _, splits, _ = rh.palette_build(cells, colours)
@@ -1165,6 +1229,8 @@ class ImageEncoder:
                                        run_slack=run_slack, run_penalty=run_penalty, dither=dither, pattern=pattern, pattern_size=pattern_size,
                                        png_path=png_path, gif_path=gif_path, gif_lossy=gif_lossy)
         res["stats"]["build"] = build
+        if resized is not None:
+            res["stats"]["resize"] = resized
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         if png_in is not None:
             res["stats"]["png_in"] = png_in
@@ -1175,7 +1241,7 @@ class ImageEncoder:
     QUANTIZE_BATCH_SLICE = 128
 
     def quantize_batch(self, images, colours=256, refine=0, roi_masks=None, roi_weight=1, out_paths=None, exact=False, pattern=None, pattern_size=4,
-                       gif_path=None, delay=4, gif_lossy=None):
+                       gif_path=None, delay=4, gif_lossy=None, size=None, resample="lanczos"):
         """images: a list of uint8[H,W,3] images of any sizes (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor
         (a contiguous device tensor is used in place, nothing is concatenated) -> a list with one result dict per image: what
         quantize(image, colours, refine=refine, roi_mask=mask, roi_weight=...) returns for that image alone, bit for bit (palette
@@ -1199,9 +1265,12 @@ class ImageEncoder:
         gif_path (default None = off), delay (centiseconds, one number or one an image): the results are also written as ONE GIF89a
         file on the device (container.write_gif), every image a frame with its own palette in a local colour table, no delta; the
         images must then be of one size and colours at most 256 (ValueError).  stats["gif"] (the same row in every result) =
-        {bytes, frames, table: "local" ("global" when all palettes came out equal), colours, delta: False, stream_bytes}."""
+        {bytes, frames, table: "local" ("global" when all palettes came out equal), colours, delta: False, stream_bytes}.
+        size (default None = off), resample: every image and its mask are first resized on the device, as quantize takes them; images
+        that share a size share one Rhccq.resize call.  stats["resize"] per image."""
         rh = self.rh
         fn = "ImageEncoder.quantize_batch"
+        resizing = self._resize_args(fn, size, resample)
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         gif_path = self._png_arg(fn, gif_path, "gif_path")
         gif_lossy = A.gif_lossy(gif_lossy, fn, "gif_lossy")
@@ -1224,6 +1293,9 @@ class ImageEncoder:
         paths = [None] * B if out_paths is None else list(out_paths)
         if B < 1 or len(masks) != B or len(paths) != B:
             raise ValueError(f"{fn}: at least one image, and one mask and one path (or None) per image, are expected")
+        resized = None
+        if resizing:
+            frames, masks, stacked, resized = self._resize_frames(fn, frames, masks, size, resample, stacked)
         if gif_path and any(f.shape[:2] != frames[0].shape[:2] for f in frames):
             raise ValueError(f"{fn}: gif_path needs images of one size")
         masked = any(m is not None for m in masks)
@@ -1289,6 +1361,8 @@ class ImageEncoder:
                     stats["refine"] = {"iterations": n, "converged": n == 0 or int(hist[b][n - 1, 1]) == 0,
                                        "sse": [int(v) for v in hist[b][:n, 0]], "changed": [int(v) for v in hist[b][:n, 1]]}
                 stats["build"] = {"asked": colours, "rows": rows, "cells": int(occupied[b]), "steps": rows - 1}
+                if resized is not None:
+                    stats["resize"] = resized[i]
                 out.append({"palette": np.ascontiguousarray(pal[b][:rows]), "indices": ind, "indices_dtype": "uint8" if ind.dtype == torch.uint8 else "uint16",
                             "shape": (H, W), "top_left": (0, 0), "stats": stats})
         if any(p for p in paths):
@@ -1325,7 +1399,7 @@ class ImageEncoder:
         return self.rh.palette_build(cells, colours)[0]
 
     def animate(self, images, colours=256, gif_path=None, delay=None, loop=None, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
-                pattern_size=4, lossy=None):
+                pattern_size=4, lossy=None, size=None, resample="lanczos"):
         """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor ->
         {"palette": uint8[k, 3], "indices": device uint8[B, H, W], "indices_dtype": "uint8", "shape": (H, W), "stats"}: an animated GIF89a built on the device from end to end.  One shared_palette over all frames (at most `colours` rows,
         1..256; with delta at most 255, because the transparent index is one more table entry: stats["gif"]["colours"] says what was
@@ -1346,12 +1420,17 @@ class ImageEncoder:
         image on the host.
         images may also be an animated GIF itself: a file name ending in .gif, or bytes that start with "GIF8".  It is read on the device
         (container.read_gif: the composed frames, an uncovered pixel as colour 0), and delay and loop default to the file's own (loop 0
-        where the file has no loop count); otherwise they default to 4 and 0."""
+        where the file has no loop count); otherwise they default to 4 and 0.
+        size (default None = off; (OH, OW), or one integer for the longest side) with resample in ops.RESIZE_FILTERS: the frames (a GIF's
+        composed frames too) are first resized on the device in one batch (Rhccq.resize: exact integers, Pillow's resize byte for
+        byte), the masks with them (_resize_frames); everything behind is what animate of the resized frames does.  stats["resize"] =
+        {"from": (H, W), "to": (OH, OW), "filter"}."""
         rh = self.rh
         fn = "ImageEncoder.animate"
         colours, refine, roi_weight = int(colours), int(refine), int(roi_weight)
         gif_path = self._png_arg(fn, gif_path, "gif_path")
         lossy = A.gif_lossy(lossy, fn)
+        resizing = self._resize_args(fn, size, resample)
         if not 1 <= colours <= 256:
             raise ValueError(f"{fn}: colours must be 1..256 (a GIF colour table has at most 256 rows)")
         if refine < 0 or refine > 64:
@@ -1377,6 +1456,10 @@ class ImageEncoder:
             raise ValueError(f"{fn}: at least one frame, and one mask (or None) per frame, are expected")
         if any(f.shape[:2] != frames[0].shape[:2] for f in frames):
             raise ValueError(f"{fn}: every frame must have the same shape")
+        resized = None
+        if resizing:
+            frames, masks, stacked, rows = self._resize_frames(fn, frames, masks, size, resample, stacked)
+            resized = rows[0]
         H, W = int(frames[0].shape[0]), int(frames[0].shape[1])
         if H > 65535 or W > 65535:
             raise ValueError(f"{fn}: a GIF frame is at most 65535 x 65535")
@@ -1421,6 +1504,8 @@ class ImageEncoder:
         host = rh.to_host(*([sums, pal, length, lens] + ([hist, nit] if refine else [])))
         sums, pal_host, size, lens = host[0], host[1], int(host[2][0]), host[3]
         stats = {"build": {"asked": asked, "rows": K}, "remap": []}
+        if resized is not None:
+            stats["resize"] = resized
         for b in range(B):
             row = {"all": self._remap_row(*sums[b][-1][:2])}
             if masks[b] is not None:

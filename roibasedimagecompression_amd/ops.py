@@ -271,6 +271,32 @@ def gif_frames_array(frames, n):
     return np.frombuffer(C.string_at(C.addressof(frames), n * C.sizeof(_lib.GifFrame)), np.uint8).copy()
 
 
+RESIZE_FILTERS = A.RESIZE_FILTERS     # ("box", "triangle", "cubic", "lanczos"): the filters Rhccq.resize takes; a filter's place is its number in the C ABI
+
+
+def resize_tile():
+    """(image rows, output columns) of a workgroup of Rhccq.resize's rows pass, and the bytes of a row a workgroup of its columns pass owns"""
+    lib = _lib.load()
+    return int(lib.rhccq_resize_tile_rows()), int(lib.rhccq_resize_run_cols()), int(lib.rhccq_resize_strip_bytes())
+
+
+def resize_taps(n_in, n_out, filter="lanczos"):
+    """rhccq_resize_taps_host (host only): the integer tap table of an axis of n_in samples resized to n_out -> (first int32[n_out],
+    count int32[n_out], weights int32[sum of count]: sample i's weights, 22 fraction bits, start at count[:i].sum())"""
+    lib = _lib.load()
+    f = A.resize_filter(filter, "resize_taps")
+    n = C.c_int64()
+    rc = lib.rhccq_resize_taps_host(int(n_in), int(n_out), f, None, None, None, 0, C.byref(n))
+    if rc:
+        raise RhccqError(f"resize_taps: rhccq_resize_taps_host failed ({rc})")
+    first, count, weights = np.zeros(int(n_out), np.int32), np.zeros(int(n_out), np.int32), np.zeros(max(n.value, 1), np.int32)
+    rc = lib.rhccq_resize_taps_host(int(n_in), int(n_out), f, C.c_void_p(first.ctypes.data), C.c_void_p(count.ctypes.data), C.c_void_p(weights.ctypes.data),
+                                    n.value, C.byref(n))
+    if rc:
+        raise RhccqError(f"resize_taps: rhccq_resize_taps_host failed ({rc})")
+    return first, count, weights[:n.value]
+
+
 PALETTE_CELLS_SHAPE = (4, 32, 32, 32)  # Rhccq.palette_cells' table: planes {N, Sr, Sg, Sb} over the cells (r >> 3, g >> 3, b >> 3)
 
 
@@ -1244,6 +1270,37 @@ class Rhccq:
         self._check(self.lib.rhccq_palette_pattern(self.ctx, self._p(rgb), H, W, self._p(palette), K, self._p(cls), n_classes, table, size,
                                                    self._p(idx), idx.element_size(), self._p(sums)), fn)
         return idx, sums
+
+    # -- image resampling in exact integers (EXTENSION: csrc/resize.hip) ----------------------------------------------------------
+    def resize(self, images, size, filter="lanczos"):
+        """images: uint8 [H, W], [H, W, C] or [B, H, W, C] (C = 1, 3 or 4; numpy or device), size: (OH, OW), or one integer for the
+        longest side (_palette_args.resize_size), filter in RESIZE_FILTERS -> a device uint8 tensor of the same rank with H, W replaced
+        by OH, OW.  Separable convolution resampling, the filter stretched by the scale when shrinking (Pillow's
+        Image.resize(reducing_gap=None) byte for byte; include/rhccq.h pins the integers).  The images of a batch share one size and
+        one launch pair.  The tap tables are built on the host and uploaded on the stream; nothing is read back."""
+        fn = "resize"
+        f = A.resize_filter(filter, fn)
+        t = A.as_uint8(images, self.device, fn, "images")
+        if t.ndim not in (2, 3, 4) or (t.ndim > 2 and int(t.shape[-1]) not in (1, 3, 4)):
+            raise ValueError(f"{fn}: uint8 [H, W], [H, W, C] or [B, H, W, C] with C = 1, 3 or 4 is expected")
+        B = int(t.shape[0]) if t.ndim == 4 else 1
+        H, W = (int(v) for v in (t.shape[:2] if t.ndim < 4 else t.shape[1:3]))
+        Cn = 1 if t.ndim == 2 else int(t.shape[-1])
+        if B < 1 or not (1 <= H <= 65535 and 1 <= W <= 65535):
+            raise ValueError(f"{fn}: at least one image, and sides of 1..65535, are expected")
+        if size is None:
+            raise ValueError(f"{fn}: a size is expected")
+        OH, OW = A.resize_size(size, H, W, fn)
+        lead = (B,) if t.ndim == 4 else ()
+        out = self.empty(lead + (OH, OW) + (() if t.ndim == 2 else (Cn,)), torch.uint8)
+        step = 65535                                                                   # (the C ABI's batch: a grid dimension)
+        for b0 in range(0, B, step):
+            n = min(step, B - b0)
+            need = int(self._raw.rhccq_resize_workspace_bytes(n, H, W, Cn, OH, OW))
+            work = self.empty((need,), torch.uint8)
+            src, dst = (t[b0:b0 + n], out[b0:b0 + n]) if t.ndim == 4 else (t, out)
+            self._check(self.lib.rhccq_resize(self.ctx, self._p(src), n, H, W, Cn, self._p(dst), OH, OW, f, self._p(work), need), fn)
+        return out
 
     # -- refinement of a given palette: exact integer Lloyd iterations (EXTENSION: csrc/palette_refine.hip) ----------
     def palette_refine(self, rgb, palette, class_map=None, weights=None, max_iter=8):

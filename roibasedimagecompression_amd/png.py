@@ -1,4 +1,4 @@
-"""python -m roibasedimagecompression_amd.png IN.png OUT.png --colours N [--refine R] [--dither S | --pattern S] [--exact]
+"""python -m roibasedimagecompression_amd.png IN.png OUT.png --colours N [--refine R] [--dither S | --pattern S] [--exact] [--size HxW|N] [--resample NAME]
 
 A PNG file to a quantised PNG file on the device: ImageEncoder.quantize(IN, N, png_path=OUT) reads IN with container.read_png and
 writes OUT with container.write_png; the host only reads and writes the files' bytes.  Prints the stats as one JSON line."""
@@ -17,13 +17,17 @@ def parser():
     g.add_argument("--dither", type=int, default=None, metavar="S", help="error diffusion of strength S (0..256)")
     g.add_argument("--pattern", type=int, default=None, metavar="S", help="pattern dithering of strength S (0..256)")
     p.add_argument("--exact", action="store_true", help="IDAT through the level-9 encoder: the file is a function of the input alone")
+    from ._palette_args import RESIZE_FILTERS, cli_size
+    p.add_argument("--size", type=cli_size, default=None, metavar="HxW|N", help="resize the image on the device first: to H x W, or the longest side to N")
+    p.add_argument("--resample", choices=RESIZE_FILTERS, default="lanczos", metavar="NAME", help="the resize filter: " + ", ".join(RESIZE_FILTERS))
     return p
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
     from .image import ImageEncoder
-    res = ImageEncoder().quantize(args.src, args.colours, refine=args.refine, dither=args.dither, pattern=args.pattern, exact=args.exact, png_path=args.dst)
+    res = ImageEncoder().quantize(args.src, args.colours, refine=args.refine, dither=args.dither, pattern=args.pattern, exact=args.exact, png_path=args.dst,
+                                  size=args.size, resample=args.resample)
     print(json.dumps(res["stats"], sort_keys=True))
     return 0
 
