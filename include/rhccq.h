@@ -1641,6 +1641,128 @@ int rhccq_resize(rhccq_ctx* ctx, const uint8_t* src, int32_t B, int32_t H, int32
                  void* workspace, int64_t workspace_bytes);
 int rhccq_resize_host(const uint8_t* src, int32_t B, int32_t H, int32_t W, int32_t C, uint8_t* dst, int32_t OH, int32_t OW, int32_t filter);
 
+/* ---- EXTENSION: JPEG files read on the device (no reference counterpart; csrc/jpeg_read.hip, csrc/jpeg_read.h) ------------------------------
+ * Files.  Baseline sequential Huffman JPEG.  SOI; APPn and COM segments are skipped (an APP14 "Adobe" segment is looked at: with three
+ * components its transform byte must be 1; without it and without an APP0 "JFIF" segment, three components whose ids are 'R', 'G', 'B'
+ * are refused, because libjpeg takes them as RGB samples and converts nothing); DQT with 8- or 16-bit entries, tables 0..3; DHT with classes 0 (DC) and 1 (AC), tables 0..3:
+ * the sixteen counts (0..255 each, at most 256 symbols in all) must not over-subscribe the code space: walking the lengths with
+ * code = (code + count) << 1 the code never passes 2^length; SOF0 or SOF1 with 8-bit samples, H and W in 1..65535, one component (grey; its
+ * sampling factors are ignored) or three (Y Cb Cr; the first 1x1, 2x1 or 2x2, the others 1x1); DRI; exactly one SOS that names all
+ * components in the frame's order with tables that were defined, Ss = 0, Se = 63, Ah = Al = 0; then the entropy-coded bytes: 0xFF 0x00 is
+ * a data byte 0xFF, 0xFF 0xD0+m is RSTm (m counts 0..7 round and round), 0xFF 0xD9 ends the file (bytes behind it are ignored), 0xFF
+ * bytes in front of a marker are fill.  One RHCCQ_JPEG_* status and one detail word; the host parse reports the first that applies:
+ *   BAD_SIGNATURE  no SOI; detail 0
+ *   BAD_SEGMENT    a segment whose length runs past the file or is below 2, a byte that is no marker where one must stand, the file's
+ *                  end before EOI, SOS before SOF, a second SOF, a quantisation or Huffman table the scan names and no segment defined,
+ *                  DRI, DQT, DHT, SOF or SOS segments of the wrong length; detail: the segment's offset (n where EOI is missing)
+ *   BAD_HEADER     W = 0, a quantisation or Huffman table number above 3 in SOF or SOS, sampling factors of 0; detail: the segment's offset
+ *   BAD_TABLE      a DQT precision above 1 or table number above 3, a DHT class above 1 or table above 3, counts that
+ *                  over-subscribe or name more than 256 symbols, a DC symbol above 15; detail: the segment's offset
+ *   UNSUPPORTED    SOF2 and every other SOF (arithmetic coding included), samples that are not 8 bits, H = 0 (DNL), 2 or 4 components,
+ *                  other sampling factors, a scan that does not hold all components in the frame's order or has Ss, Se, Ah, Al for
+ *                  another mode, a marker
+ *                  other than RSTm and EOI behind the scan (several scans), fill bytes in front of a stuffed zero, an Adobe transform
+ *                  other than 1 with three components; detail: the offset
+ *   LIMIT          a file of 2^31 bytes or more; detail 0
+ *   BAD_RESTART    RSTm out of sequence, RSTm without DRI, or a number of intervals that is not ceil(MCUs / interval); detail: the
+ *                  marker's number in the file (the interval count for the last case)
+ * and the device, for a file the parse accepts:
+ *   BAD_SCAN       a bit pattern that is no code, a run or a ZRL that passes coefficient 63, a DC category above 11, or an interval whose
+ *                  bits end inside a block, before or behind its MCUs, or leave 8 pad bits or more; detail: the lowest such interval.
+ * An interval ends where the next symbol (code and value bits) would pass the interval's last bit, where fewer than 16 bits are left and
+ * they start no code; the decoder goes on at the next interval's first bit.  At a fault it goes on one bit further on, in front of a
+ * block, in the same interval (so that a lane that guessed its state wrongly can still fall into step).  (Pad bits are ones and no code is all ones
+ * in the files encoders write, so no symbol fits in the pad.  A file whose pad decodes as whole symbols is BAD_SCAN here.)  After BAD_SCAN the pixels mean nothing; no stage leaves its buffers.
+ * Arithmetic: libjpeg's, so that Pillow (libjpeg-turbo) decodes to the same bytes.
+ *   coefficients   DC: category s <= 11, then s bits v: the difference is v if v >= 2^(s-1), else v - 2^s + 1.  AC: symbol (run r, size
+ *                  s): s = 0, r = 15 skips 16, s = 0 otherwise ends the block; else r zeros and a value of s bits.  The DC predictor is per
+ *                  component, 0 at every interval's start, summed in 32 bits; coefficients are stored as int16 (truncated).
+ *   IDCT           jidctint.c's "islow" on coefficient x quantiser in 32 bits, CONST_BITS 13, PASS1_BITS 2, constants 2446 3196 4433 6270
+ *                  7373 9633 12299 15137 16069 16819 20995 25172; columns first, descaled by 11 with rounding ((x + 1024) >> 11), then rows,
+ *                  descaled by 18 with rounding, + 128, clamped to 0..255 (a plain clamp: libjpeg's C code masks to 10 bits first, its SIMD
+ *                  code saturates; they differ only for coefficients no encoder writes).
+ *   upsampling     "fancy", over the component's true width cw = ceil(W / 2) and, for 2x2, true height ch = ceil(H / 2).  2x1, row by
+ *                  row: out[0] = s[0], out[2 cw - 1] = s[cw - 1], else out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] +
+ *                  2) >> 2.  2x2: output row y takes c[i] = 3 s[y >> 1][i] + s[nb][i] with nb = (y >> 1) - 1 for even y, + 1 for odd y,
+ *                  clamped to 0..ch - 1; out[0] = (4 c[0] + 8) >> 4, out[2 cw - 1] = (4 c[cw-1] + 7) >> 4, else out[2i] = (3 c[i] + c[i-1] +
+ *                  8) >> 4, out[2i+1] = (3 c[i] + c[i+1] + 7) >> 4.  Found against Pillow: with cw <= 2 (W <= 4) libjpeg-turbo does not
+ *                  filter at all, it replicates: out[y][x] = s[y >> 1][x >> 1] (s[y][x >> 1] for 2x1); so does this reader.
+ *   colour         cb = Cb - 128, cr = Cr - 128; R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *                  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), arithmetic shifts, clamped.  Grey: R = G = B = Y.
+ * Stages (one stream, no workgroup waits for another, every loop bounded by numbers the parse gives):
+ *   unstuff   a lane takes 16 bytes of the scan; a byte stays unless the byte in front is 0xFF, or it is 0xFF and the next is not 0: stuffed
+ *             zeros, markers and fill go.  Counts a tile of 4096 bytes, a prefix sum over the tiles, then the scatter.  The intervals'
+ *             places in the unstuffed stream (rhccq_segment.dst) come from the parse, which walks the scan for its markers anyway.
+ *   sync      the unstuffed stream is cut every subsequence_bits bits (a multiple of 32 in 128..65536; 0: rhccq_jpeg_subsequence_bits()),
+ *             interval or not.  A decoder state is (bit, block within the MCU, zig-zag index).  A lane decodes its subsequence from the
+ *             guess (its first bit, 0, 0) without writing and records the state in which it leaves and the blocks it completed; when it
+ *             crosses an interval's start its count turns absolute (the interval's first block is known).  Then every lane takes its
+ *             predecessor's leaving state as its entry and decodes again until no entry in the workgroup changes (256 subsequences a
+ *             workgroup, over LDS).  One more launch of one workgroup walks the workgroups' boundaries: a lane a boundary re-decodes
+ *             from the true entry until it meets a recorded one, in rounds until no workgroup's last state changes.
+ *   place     a prefix sum (absolute counts restart it) gives every subsequence its first block.
+ *   write     every lane decodes once more and writes coefficients, de-zig-zagged, into int16 [component][block row][block col][64];
+ *             the planes are whole MCUs.  Position 0 holds the DC difference.
+ *   dc        a segmented inclusive sum per component in decode order, restarted at every interval: tiles, the tiles' carries, tiles.
+ *   idct      eight lanes a block, a column each, the transpose through LDS, a row each -> uint8 planes.
+ *   colour    a lane four pixels of a row: upsampling and colour conversion -> rgb[H][W][3].
+ * The workspace starts with uint32[8]: the lowest bad interval (2^32 - 1: none), subsequences, the most rounds a workgroup took, the
+ * rounds of the boundary walk, the longest walk in subsequences. */
+#define RHCCQ_JPEG_OK 0
+#define RHCCQ_JPEG_BAD_SIGNATURE 1
+#define RHCCQ_JPEG_BAD_SEGMENT 2
+#define RHCCQ_JPEG_BAD_HEADER 3
+#define RHCCQ_JPEG_BAD_TABLE 4
+#define RHCCQ_JPEG_UNSUPPORTED 5
+#define RHCCQ_JPEG_LIMIT 6
+#define RHCCQ_JPEG_BAD_RESTART 7
+#define RHCCQ_JPEG_BAD_SCAN 8
+typedef struct rhccq_jpeg_info {
+  int32_t status, detail;                 /* RHCCQ_JPEG_OK .. RHCCQ_JPEG_BAD_RESTART */
+  int32_t width, height;
+  int32_t n_comp, hs, vs;                 /* 1 or 3; the first component's sampling (1 x 1 for grey) */
+  int32_t mcus_x, mcus_y, blocks_per_mcu;
+  int32_t restart_interval, n_intervals;  /* MCUs an interval (0: no DRI, one interval) */
+  int64_t scan_offset, scan_bytes;        /* the entropy-coded bytes in the file up to EOI's 0xFF, markers and stuffing included */
+  int64_t stream_bytes;                   /* of them unstuffed */
+  int64_t blocks;                         /* of all components: 64 int16 coefficients and 64 plane bytes each */
+} rhccq_jpeg_info;
+/* what the kernels keep in LDS.  Table t of component c: 2 c (DC), 2 c + 1 (AC).  look: the code's first 9 bits -> length << 8 | symbol, 0
+   where the code is longer; then length l = 10..16 holds the symbol vals[valoff[l] + first l bits] if the bits are <= maxcode[l] (-1: none) */
+typedef struct rhccq_jpeg_tables {
+  uint16_t quant[3][64];                  /* row-major, per component */
+  uint16_t look[6][512];
+  int32_t maxcode[6][18], valoff[6][18];
+  uint8_t vals[6][256];
+} rhccq_jpeg_tables;
+/* host only, a pure function of the bytes.  intervals: a row a restart interval (offset and length of its bytes in the file, first_piece
+   its first MCU, dst its first byte in the unstuffed stream); the first `cap` rows are written, *n_intervals is the full number.
+   RHCCQ_E_ARG for a null file (n > 0), info, tables or counter, or a negative size; else RHCCQ_OK with info->status set */
+int rhccq_jpeg_parse_host(const uint8_t* file, int64_t n, rhccq_jpeg_info* info, rhccq_jpeg_tables* tables, rhccq_segment* intervals, int64_t cap,
+                          int64_t* n_intervals);
+int32_t rhccq_jpeg_subsequence_bits(void);  /* the default */
+int32_t rhccq_jpeg_tables_bytes(void);      /* sizeof(rhccq_jpeg_tables) */
+/* host only: the workspaces of rhccq_jpeg_decode, rhccq_jpeg_coefficients and rhccq_jpeg_pixels for a parsed file of n bytes */
+int rhccq_jpeg_read_sizes(const rhccq_jpeg_info* info, int64_t n, int32_t subsequence_bits, int64_t* decode_bytes, int64_t* coefficients_bytes,
+                          int64_t* pixels_bytes);
+/* Device forms: file, tables_dev (a copy of the parse's tables), intervals_dev (of its n_intervals rows), workspace (aligned to 256), coef
+   (aligned to 4), rgb and status (int32[2]) are device memory; async on the context's stream, nothing allocated, nothing read back.
+   RHCCQ_E_ARG: a null pointer, a misaligned one, an info that is not the parse's for n bytes, subsequence_bits not 0 or a multiple of 32
+   in 128..65536.  With info->status set nothing runs but the launch that writes it to status.
+   rhccq_jpeg_coefficients: unstuff .. dc -> coef[info->blocks][64], the DC sums taken.  rhccq_jpeg_pixels: idct, colour.
+   rhccq_jpeg_decode: both, the coefficients in its workspace. */
+int rhccq_jpeg_coefficients(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables_dev,
+                            const rhccq_segment* intervals_dev, int32_t subsequence_bits, void* workspace, int16_t* coef, int32_t* status);
+int rhccq_jpeg_pixels(rhccq_ctx* ctx, const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables_dev, const int16_t* coef, void* workspace,
+                      uint8_t* rgb);
+int rhccq_jpeg_decode(rhccq_ctx* ctx, const uint8_t* file, int64_t n, const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables_dev,
+                      const rhccq_segment* intervals_dev, int32_t subsequence_bits, void* workspace, uint8_t* rgb, int32_t* status);
+/* Host forms (serial, no GPU, host memory): the same step functions of csrc/jpeg_read.h.  They parse the file themselves; coef and rgb are
+   sized by the parse (they may be NULL for a file it refuses); status: int32[2] */
+int rhccq_jpeg_coefficients_host(const uint8_t* file, int64_t n, int16_t* coef, int32_t* status);
+int rhccq_jpeg_pixels_host(const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables, const int16_t* coef, uint8_t* rgb);
+int rhccq_jpeg_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

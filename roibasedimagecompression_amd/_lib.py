@@ -59,6 +59,13 @@ class GifFrame(C.Structure):
                 ("table_offset", c_int64), ("stream_offset", c_int64), ("stream_bytes", c_int64), ("pixel_offset", c_int64), ("first_row", c_int64)]
 
 
+class JpegInfo(C.Structure):
+    """struct rhccq_jpeg_info (include/rhccq.h): what rhccq_jpeg_parse_host reads from a file's framing"""
+    _fields_ = [("status", c_int32), ("detail", c_int32), ("width", c_int32), ("height", c_int32), ("n_comp", c_int32), ("hs", c_int32), ("vs", c_int32),
+                ("mcus_x", c_int32), ("mcus_y", c_int32), ("blocks_per_mcu", c_int32), ("restart_interval", c_int32), ("n_intervals", c_int32),
+                ("scan_offset", c_int64), ("scan_bytes", c_int64), ("stream_bytes", c_int64), ("blocks", c_int64)]
+
+
 class FrameResult(C.Structure):
     """struct rhccq_frame_result (include/rhccq.h)"""
     _fields_ = [("n_colours", c_int32), ("index_bytes", c_int32), ("shape", c_int32 * 2), ("top_left", c_int32 * 2), ("quality3", c_int32),
@@ -355,6 +362,16 @@ PROTOTYPES = {
     "rhccq_resize_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "rhccq_resize": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64]),
     "rhccq_resize_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32]),
+    "rhccq_jpeg_parse_host": (c_int32, [c_void_p, c_int64, C.POINTER(JpegInfo), c_void_p, c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_jpeg_subsequence_bits": (c_int32, []),
+    "rhccq_jpeg_tables_bytes": (c_int32, []),
+    "rhccq_jpeg_read_sizes": (c_int32, [C.POINTER(JpegInfo), c_int64, c_int32, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rhccq_jpeg_coefficients": (c_int32, [c_void_p, c_void_p, c_int64, C.POINTER(JpegInfo), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_jpeg_pixels": (c_int32, [c_void_p, C.POINTER(JpegInfo), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rhccq_jpeg_decode": (c_int32, [c_void_p, c_void_p, c_int64, C.POINTER(JpegInfo), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rhccq_jpeg_coefficients_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_jpeg_pixels_host": (c_int32, [C.POINTER(JpegInfo), c_void_p, c_void_p, c_void_p]),
+    "rhccq_jpeg_decode_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -390,6 +390,51 @@ def read_gif(src, rh=None):
                       "stream_bytes": [table[f].stream_bytes for f in range(info.n_frames)], "seconds": round(time.perf_counter() - t0, 4)}}
 
 
+def read_jpeg(src, rh=None, subsequence_bits=None):
+    """a baseline JPEG file (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, with or without restart markers) -> read_png's dict: {"image": uint8[H, W, 3]
+    device, "alpha": None, "shape": (H, W), "info": {components, sampling, restart_interval, intervals}, "stats": {bytes, subsequences,
+    subsequence_bits, sync_rounds, worst_walk, seconds}} decoded on the device to the bytes Pillow gives (include/rhccq.h "JPEG files read
+    on the device": unstuff, self-synchronising Huffman decode, DC sums, IDCT, upsampling and colour).  src: a file name or bytes.  The host
+    reads the file once, parses its framing (rhccq_jpeg_parse_host) and uploads it once; one read of the status and the statistics is
+    the only wait.  sync_rounds: the rounds the slowest workgroup and the boundary walk took to agree; worst_walk: the most subsequences
+    a wrong start took to fall into step.  A file the definition refuses raises RhccqError naming status and detail.  Not read:
+    progressive, arithmetic-coded, 12-bit, CMYK / YCCK files, other samplings; EXIF orientation and ICC profiles are ignored."""
+    from .ops import JPEG_STATUS, jpeg_parse, jpeg_subsequence_bits
+    rh = rh or default_context()
+    t0 = time.perf_counter()
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytearray(src)
+    else:
+        with open(src, "rb") as f:
+            data = bytearray(os.fstat(f.fileno()).st_size)
+            del data[f.readinto(data):]
+    parsed = jpeg_parse(data)
+    info = parsed[0]
+
+    def refuse(status, detail):
+        e = RhccqError(f"read_jpeg: RHCCQ_JPEG_{JPEG_STATUS[status]} (status {status}), detail {detail}")
+        e.status, e.detail = status, detail
+        raise e
+    if info.status:
+        refuse(info.status, info.detail)
+    out = rh.jpeg_decode(np.frombuffer(data, np.uint8), parsed, subsequence_bits=subsequence_bits)
+    status, head = rh.to_host(out["status"], out["head"])
+    if int(status[0]):
+        refuse(int(status[0]), int(status[1]))
+    rounds, walk = int(head[2]) + int(head[3]), max(int(head[2]), int(head[4]))
+    return {"image": out["rgb"], "alpha": None, "shape": (info.height, info.width),
+            "info": {"components": info.n_comp, "sampling": (info.hs, info.vs), "restart_interval": info.restart_interval, "intervals": info.n_intervals},
+            "stats": {"bytes": len(data), "subsequences": int(head[1]) & 0xFFFFFFFF, "subsequence_bits": int(subsequence_bits or jpeg_subsequence_bits()),
+                      "sync_rounds": rounds, "worst_walk": walk, "seconds": round(time.perf_counter() - t0, 4)}}
+
+
+def read_image(src, rh=None):
+    """a PNG or a JPEG file by its first bytes -> read_png's or read_jpeg's dict"""
+    with open(src, "rb") as f:
+        magic = f.read(2)
+    return read_jpeg(src, rh) if magic == b"\xff\xd8" else read_png(src, rh)
+
+
 def reduce_gif(src, dst, colours, rh=None, delta=True, refine=0, pattern=None, pattern_size=4, lossy=None, size=None, resample="lanczos"):
     """an animated GIF to one of at most `colours` colours, on the device from end to end: read_gif, then ImageEncoder.animate over the
     composed frames with the file's own delays and loop count (0 where it has none), written to dst.  The frames enter as the viewer

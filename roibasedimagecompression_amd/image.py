@@ -522,7 +522,7 @@ class ImageEncoder:
             lap("report")
         stats["seconds"] = {k: round(v, 4) for k, v in t.items()}
         if png_in is not None:
-            stats["png_in"] = png_in
+            stats[png_in[0]] = png_in[1]
         res["classes"] = classes
         res["stats"] = stats
         return res
@@ -530,14 +530,20 @@ class ImageEncoder:
     # ---- a PNG file as the image (EXTENSION: csrc/png_read.hip) -----------------------------------------------------------------
     def _png_in(self, image):
         """image as encode, encode_with_palette and quantize take it -> (the image, stats["png_in"] or None): a file name is read on the
-        device (container.read_png); the file's alpha, if any, is ignored and reported"""
+        device (container.read_png); the file's alpha, if any, is ignored and reported.  A file that starts with JPEG's SOI is read by
+        container.read_jpeg instead.  What the file was comes back as the pair (its key in stats: "png_in" or "jpeg_in", the entry)"""
         if not isinstance(image, (str, os.PathLike)):
             return image, None
         from . import container
+        with open(os.fspath(image), "rb") as f:
+            magic = f.read(2)
+        if magic == b"\xff\xd8":
+            fr = container.read_jpeg(os.fspath(image), self.rh)
+            return fr["image"], ("jpeg_in", {"shape": list(fr["shape"]), **fr["info"], **{k: fr["stats"][k] for k in ("subsequences", "sync_rounds")}})
         fr = container.read_png(os.fspath(image), self.rh)
         info = fr["info"]
-        return fr["image"], {"shape": list(fr["shape"]), "colour_type": info["colour_type"], "depth": info["depth"], "alpha_ignored": fr["alpha"] is not None,
-                             "chunks": info["chunks"], "idat_chunks": info["idat_chunks"]}
+        return fr["image"], ("png_in", {"shape": list(fr["shape"]), "colour_type": info["colour_type"], "depth": info["depth"],
+                                        "alpha_ignored": fr["alpha"] is not None, "chunks": info["chunks"], "idat_chunks": info["idat_chunks"]})
 
     # ---- the result as a PNG file (EXTENSION: csrc/png_write.hip) ---------------------------------------------------------------
     @staticmethod
@@ -1111,7 +1117,7 @@ class ImageEncoder:
         if resized is not None:
             stats["resize"] = resized
         if png_in is not None:
-            stats["png_in"] = png_in
+            stats[png_in[0]] = png_in[1]
         res["stats"] = stats
         return res
 
@@ -1233,7 +1239,7 @@ class ImageEncoder:
             res["stats"]["resize"] = resized
         res["stats"]["seconds"] = dict({"build": round(seconds, 4)}, **res["stats"]["seconds"])
         if png_in is not None:
-            res["stats"]["png_in"] = png_in
+            res["stats"][png_in[0]] = png_in[1]
         return res
 
     # images of one slice of quantize_batch: a slice holds 1 MiB of histogram and 1.1 MiB of summed-volume table per image beside its
@@ -1400,7 +1406,8 @@ class ImageEncoder:
 
     def animate(self, images, colours=256, gif_path=None, delay=None, loop=None, delta=True, refine=0, roi_masks=None, roi_weight=1, pattern=None,
                 pattern_size=4, lossy=None, size=None, resample="lanczos"):
-        """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors), or one uint8[B,H,W,3] array or device tensor ->
+        """images: a list of uint8[H,W,3] frames of ONE size (numpy or device tensors, or names of PNG or JPEG files, which are read on the
+        device as quantize reads them; stats["png_in"] / stats["jpeg_in"] then list what those files were), or one uint8[B,H,W,3] array or device tensor ->
         {"palette": uint8[k, 3], "indices": device uint8[B, H, W], "indices_dtype": "uint8", "shape": (H, W), "stats"}: an animated GIF89a built on the device from end to end.  One shared_palette over all frames (at most `colours` rows,
         1..256; with delta at most 255, because the transparent index is one more table entry: stats["gif"]["colours"] says what was
         built), refine = N > 0 Lloyd iterations of that ONE palette over the pixels of all frames (Rhccq.palette_refine), every frame
@@ -1442,14 +1449,16 @@ class ImageEncoder:
             delay = src["delays"] if delay is None else delay
             loop = (src["loop"] or 0) if loop is None else loop
         delay, loop = 4 if delay is None else delay, 0 if loop is None else loop
-        stacked = None
+        stacked, files = None, []
         if (torch.is_tensor(images) or isinstance(images, np.ndarray)) and images.ndim == 4:
             stacked = images.to(rh.device).contiguous() if torch.is_tensor(images) else rh.dev(images)
             if stacked.dtype != torch.uint8 or stacked.shape[3] != 3:
                 raise ValueError(f"{fn}: a uint8 B x H x W x 3 tensor is expected")
             frames = list(stacked)                                               # views
         else:
-            frames = [self._frame_tensor("animate", im) for im in images]
+            read =[self._png_in(im) for im in images]                          # (a file name among them: a PNG or a JPEG file, read on the device)
+            files = [entry for _, entry in read if entry is not None]
+            frames = [self._frame_tensor("animate", im) for im, _ in read]
         B = len(frames)
         masks = [None] * B if roi_masks is None else list(roi_masks)
         if B < 1 or len(masks) != B:
@@ -1506,6 +1515,8 @@ class ImageEncoder:
         stats = {"build": {"asked": asked, "rows": K}, "remap": []}
         if resized is not None:
             stats["resize"] = resized
+        for key, entry in files:
+            stats.setdefault(key, []).append(entry)
         for b in range(B):
             row = {"all": self._remap_row(*sums[b][-1][:2])}
             if masks[b] is not None:

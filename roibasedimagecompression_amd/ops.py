@@ -271,6 +271,32 @@ def gif_frames_array(frames, n):
     return np.frombuffer(C.string_at(C.addressof(frames), n * C.sizeof(_lib.GifFrame)), np.uint8).copy()
 
 
+JPEG_STATUS = ("OK", "BAD_SIGNATURE", "BAD_SEGMENT", "BAD_HEADER", "BAD_TABLE", "UNSUPPORTED", "LIMIT", "BAD_RESTART", "BAD_SCAN")
+
+
+def jpeg_subsequence_bits():
+    """bits of a subsequence of Rhccq.jpeg_decode's synchronising decode where the caller names none: a lane decodes one"""
+    return int(_lib.load().rhccq_jpeg_subsequence_bits())
+
+
+def jpeg_parse(data):
+    """rhccq_jpeg_parse_host (host only, a pure function of the bytes) -> (_lib.JpegInfo, the decoder's tables as uint8 bytes (struct
+    rhccq_jpeg_tables), the restart intervals int64[n_intervals, 4]: offset and length in the file, first MCU, first byte in the unstuffed
+    stream)"""
+    a = np.frombuffer(data, dtype=np.uint8)
+    lib = _lib.load()
+    info, ni = _lib.JpegInfo(), C.c_int64()
+    tables = np.zeros(int(lib.rhccq_jpeg_tables_bytes()), np.uint8)
+    ptr = C.c_void_p(a.ctypes.data if a.size else 0)
+    rc = lib.rhccq_jpeg_parse_host(ptr, a.size, C.byref(info), C.c_void_p(tables.ctypes.data), None, 0, C.byref(ni))
+    if rc:
+        raise RhccqError(f"jpeg_parse: rhccq_jpeg_parse_host failed ({rc})")
+    intervals = np.zeros((max(ni.value, 1), 4), np.int64)
+    if info.status == 0:
+        lib.rhccq_jpeg_parse_host(ptr, a.size, C.byref(info), C.c_void_p(tables.ctypes.data), C.c_void_p(intervals.ctypes.data), ni.value, C.byref(ni))
+    return info, tables, intervals[:ni.value]
+
+
 RESIZE_FILTERS = A.RESIZE_FILTERS     # ("box", "triangle", "cubic", "lanczos"): the filters Rhccq.resize takes; a filter's place is its number in the C ABI
 
 
@@ -2393,6 +2419,67 @@ class Rhccq:
                                               self._p(work), self._p(rgb), self._p(alpha), self._p(idx), self._p(status)), fn)
         return {"rgb": rgb, "alpha": alpha, "indices": idx, "status": status, "head": work[:16].view(torch.int32), "file": file, "info": info,
                 "frames": frames}
+
+    # -- JPEG files read on the device (EXTENSION: csrc/jpeg_read.hip; include/rhccq.h pins the definition) ---------------
+    def _jpeg_args(self, fn, file, parsed, subsequence_bits):
+        """-> (the file on the device, info, tables and intervals on the device, subsequence_bits as the C call takes it, the three
+        workspace sizes); None in the file's place with a status the framing shows"""
+        if parsed is None:
+            host = self.to_host(file).tobytes() if torch.is_tensor(file) else bytearray(file)
+            parsed = jpeg_parse(host)
+            if not torch.is_tensor(file):
+                file = np.frombuffer(host, np.uint8)
+        info, tables, intervals = parsed
+        S = 0 if subsequence_bits is None else int(subsequence_bits)
+        if S and not (128 <= S <= 65536 and S % 32 == 0):
+            raise ValueError(f"{fn}: subsequence_bits must be a multiple of 32 in 128..65536")
+        if info.status:
+            return None, info, None, None, S, None
+        if not torch.is_tensor(file) and not isinstance(file, np.ndarray):
+            file = np.frombuffer(bytes(file), np.uint8).copy()
+        file = A.as_uint8(file, self.device, fn, "file").reshape(-1)                 # (any alignment: the kernels read it byte by byte)
+        sizes = [C.c_int64(), C.c_int64(), C.c_int64()]
+        rc = self._raw.rhccq_jpeg_read_sizes(C.byref(info), file.numel(), S, *[C.byref(s) for s in sizes])
+        intervals = np.ascontiguousarray(intervals, dtype=np.int64).reshape(-1, 4)
+        if rc or len(intervals) != info.n_intervals:
+            raise RhccqError(f"{fn}: rhccq_jpeg_read_sizes failed ({rc}): parsed is not jpeg_parse's for a file of {file.numel()} bytes")
+        return file, info, self.dev(np.ascontiguousarray(tables, dtype=np.uint8)), self.dev(intervals.reshape(-1)), S, [s.value for s in sizes]
+
+    def jpeg_coefficients(self, file, parsed=None, subsequence_bits=None):
+        """the entropy decode alone.  file: the JPEG file's bytes (a uint8 device tensor, or bytes / numpy, uploaded); parsed: jpeg_parse's
+        triple -> {"coef" int16[blocks, 64] device: the components' planes of blocks one after another, row-major in a block, the DC sums
+        taken, "status" int32[2] (JPEG_STATUS index, detail), "head" int32[8] (the bad interval, subsequences, rounds, boundary rounds,
+        longest walk), "info"}; nothing waits for the device"""
+        fn = "jpeg_coefficients"
+        file, info, tables, intervals, S, sizes = self._jpeg_args(fn, file, parsed, subsequence_bits)
+        status = self.empty((2,), torch.int32)
+        null = C.c_void_p(0)
+        if file is None:
+            self._check(self.lib.rhccq_jpeg_coefficients(self.ctx, null, 0, C.byref(info), null, null, S, null, null, self._p(status)), fn)
+            return {"coef": None, "status": status, "head": None, "info": info}
+        work = self.empty((sizes[1],), torch.uint8)
+        coef = self.empty((info.blocks, 64), torch.int16)
+        self._check(self.lib.rhccq_jpeg_coefficients(self.ctx, self._p(file), file.numel(), C.byref(info), self._p(tables), self._p(intervals), S, self._p(work),
+                                                     self._p(coef), self._p(status)), fn)
+        return {"coef": coef, "status": status, "head": work[:32].view(torch.int32), "info": info}
+
+    def jpeg_decode(self, file, parsed=None, rgb=None, subsequence_bits=None):
+        """file: the JPEG file's bytes (a uint8 device tensor, or bytes / numpy, uploaded); parsed: jpeg_parse's triple (parsed from the
+        bytes when None, which reads a device tensor back) -> {"rgb" uint8[H, W, 3] device, "status" int32[2] (JPEG_STATUS index, detail),
+        "head" int32[8] (as jpeg_coefficients), "info"}; nothing waits for the device.  With a status the framing shows (info.status)
+        there is no image.  rgb: a caller's buffer.  subsequence_bits: a multiple of 32 in 128..65536 (None: jpeg_subsequence_bits())."""
+        fn = "jpeg_decode"
+        file, info, tables, intervals, S, sizes = self._jpeg_args(fn, file, parsed, subsequence_bits)
+        status = self.empty((2,), torch.int32)
+        null = C.c_void_p(0)
+        if file is None:
+            self._check(self.lib.rhccq_jpeg_decode(self.ctx, null, 0, C.byref(info), null, null, S, null, null, self._p(status)), fn)
+            return {"rgb": None, "status": status, "head": None, "info": info}
+        work = self.empty((sizes[0],), torch.uint8)
+        rgb = self._gif_out(fn, "rgb", rgb, (info.height, info.width, 3))
+        self._check(self.lib.rhccq_jpeg_decode(self.ctx, self._p(file), file.numel(), C.byref(info), self._p(tables), self._p(intervals), S, self._p(work),
+                                               self._p(rgb), self._p(status)), fn)
+        return {"rgb": rgb.view(info.height, info.width, 3), "status": status, "head": work[:32].view(torch.int32), "info": info}
 
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
     ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
