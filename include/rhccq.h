@@ -1763,6 +1763,85 @@ int rhccq_jpeg_coefficients_host(const uint8_t* file, int64_t n, int16_t* coef, 
 int rhccq_jpeg_pixels_host(const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables, const int16_t* coef, uint8_t* rgb);
 int rhccq_jpeg_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, int32_t* status);
 
+/* ---- EXTENSION: JPEG files written on the device (no reference counterpart; csrc/jpeg_write.hip, csrc/jpeg_write.h) ---------------------------
+ * Files.  Baseline sequential Huffman JPEG, byte for byte what Pillow 12.2 (libjpeg-turbo) saves from a uint8 RGB image with quality q,
+ * subsampling 4:4:4, 4:2:2 or 4:2:0, optimize=False and restart_marker_rows r, and from a uint8 grey image.  In this order: SOI; APP0
+ * ffe0 0010 "JFIF\0" 0101 00 0001 0001 0000; one DQT segment of 67 bytes per table, 8-bit entries in zig-zag order (two tables for
+ * colour; found against Pillow: ONE for grey); SOF0 with 8-bit samples, H, W, components 1 (0x11, table 0) or 1, 2, 3 (the first 0x11,
+ * 0x21 or 0x22 with table 0, the others 0x11 with table 1); DHT segments DC0, AC0, DC1, AC1 of 31, 181, 31, 181 bytes, the Annex K
+ * tables (found against Pillow: grey files carry DC0 and AC0 only); DRI ffdd 0004 and the interval, only with r > 0; SOS naming all
+ * components with tables 0x00, 0x11, 0x11, then 00 3f 00; the scan; EOI.
+ * Arithmetic: libjpeg's.
+ *   quantisers     Annex K base tables; scale = 5000 / q for q < 50, else 200 - 2 q; entry = (base * scale + 50) / 100 clamped to 1..255.
+ *   colour         Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *                  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16, each a byte before any averaging.
+ *   edges          the image's last column and last row are repeated to whole MCUs.  Found against Pillow: below the image a 4:2:0
+ *                  chroma plane repeats ITS OWN last row (the average of image rows 2 ch - 2 and min(2 ch - 1, H - 1), ch = ceil(H / 2)),
+ *                  not the average of two copies of the image's last row; the two differ when H is even (8 x 8 and 8 x 4 in 4:2:0).
+ *   downsampling   2 x 1: (a + b + bias) >> 1 with bias 0, 1, 0, 1 .. along the output row; 2 x 2: (a + b + c + d + bias) >> 2 with bias
+ *                  1, 2, 1, 2 ..
+ *   dummy blocks   a block of the first component whose column is past ceil(W / 8) or whose row is past ceil(H / 8) is not transformed: all
+ *                  AC are 0; in a row of the image its DC is that of its left neighbour; in a row below the image (4:2:0) it is the DC
+ *                  of the upper right block of its MCU, which may itself be a dummy block and then repeats its left neighbour (17 x 33:
+ *                  block column 5 of every row and block row 3; 33 x 15: block column 1 and block row 5).  Chroma and grey planes have none.
+ *   FDCT           jfdctint.c's "islow" on samples - 128, in 32 bits, CONST_BITS 13, PASS1_BITS 2, the constants of the reader's IDCT; rows
+ *                  first: out0 = (t10 + t11) << 2, out4 = (t10 - t11) << 2, the others descaled by 11 with rounding; then columns:
+ *                  out0, out4 descaled by 2, the others by 15.  The result is the DCT scaled by 8.
+ *   quantiser      (|c| + (8 Q >> 1)) / (8 Q) with the sign restored (libjpeg-turbo's reciprocal form gives the same quotients).
+ *   entropy coding the inverse of the reader's "coefficients": DC category and value bits of the difference to the component's previous block
+ *                  of the scan, 0 at every interval's start; AC symbols (run, size) in zig-zag order, ZRL for each full 16 zeros in
+ *                  front of a value, EOB unless coefficient 63 is non-zero; a negative value v sends the low bits of v - 1.  Every
+ *                  interval is padded with one bits to a byte; an 0xFF data byte is followed by 0x00; RSTm (m = 0..7 round and round)
+ *                  stands between intervals.  The interval is min(r * MCUs a row, 65535) MCUs.
+ * Stages (one stream, no workgroup waits for another, every loop bounded by numbers the host knows):
+ *   blocks    a workgroup a strip of at most 32 blocks of one MCU row; the strip's pixels arrive as aligned 16-byte loads in LDS; eight lanes
+ *             a block: a row each (conversion, averaging, first pass), the transpose through LDS, a column each, the divisors in LDS ->
+ *             int16 coef[component][block row][block col][64] in natural order over planes of whole MCUs, dummy blocks filled in, the DC
+ *             in place: the layout rhccq_jpeg_coefficients gives for the file.
+ *   count     a wave a block, a lane a zig-zag position: one ballot gives the non-zero mask, a lane's run is the distance to the next set
+ *             bit below it; ZRL count, symbol, code length from LDS and value bits follow; lane 0 carries the DC difference, lane 63
+ *             EOB; a wave sum gives the block's bits.  Blocks in scan order by an index from the frame's geometry.
+ *   place     a prefix sum of the blocks' bits in scan order, restarted at every interval (tiles of 256, the tiles' carries, the tiles
+ *             again) gives every block its first bit in its interval and every interval its bytes; a prefix sum over the intervals
+ *             gives their first bytes in the unstuffed stream, and its length.
+ *   pack      count's pass again: a wave scan of the lanes' lengths places each lane's ZRLs, code and value bits, ORed with 32-bit LDS
+ *             atomics into the workgroup's window (32 blocks); pad bits are ones; whole words go out big-endian, a workgroup's first and
+ *             last word by a global atomic OR into the zeroed stream.
+ *   stuff     a lane 16 bytes of the stream: 0xFF bytes a tile of 4096, their prefix sum, then the scatter behind the header with the
+ *             0x00 bytes and the RSTm markers put in; EOI; the file's length is one device word.
+ * The header and the tables are built on the host (rhccq_jpeg_write_tables_host: a struct of rhccq_jpeg_write_tables_bytes() bytes holding
+ * the divisors, code and length per symbol, and SOI .. SOS) and uploaded by the caller.  Workspace of rhccq_jpeg_entropy: uint64[32] head
+ * (the unstuffed stream's bytes, its 0xFF bytes), then uint32 bits a block, uint64 first bit a block, the place tiles, uint32 bytes and
+ * uint64 first byte an interval, the stuff tiles' counts and prefix, the unstuffed stream, each at a multiple of 256;
+ * rhccq_jpeg_encode's holds the coefficients behind that.  The sizes assume at most 1658 bits a block (a DC code of 9 bits and 11 value
+ * bits, 63 AC codes of 16 bits and 10), which no coefficient array can pass.
+ * Not built: optimised Huffman tables (optimize=True), progressive files, CMYK, EXIF and ICC segments, a batch writer.
+ * mode: RHCCQ_JPEG_GREY (image uint8[H][W]) or RHCCQ_JPEG_444 / _422 / _420 (image uint8[H][W][3]).  RHCCQ_E_ARG: quality outside 1..100,
+ * an unknown mode, H or W outside 1..65535, negative restart_rows, a null pointer, an image or coef not aligned to 16, a workspace not
+ * aligned to 256, cap below file_bytes, or a largest possible file of 2^31 bytes or more.  The RHCCQ_JPEG_* statuses are the reader's alone. */
+#define RHCCQ_JPEG_GREY 0
+#define RHCCQ_JPEG_444 1
+#define RHCCQ_JPEG_422 2
+#define RHCCQ_JPEG_420 3
+/* host only: the table struct's size; the struct for these parameters (restart_rows decides DRI; rhccq_jpeg_blocks reads the divisors only) */
+int32_t rhccq_jpeg_write_tables_bytes(void);
+int rhccq_jpeg_write_tables_host(int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, void* tables);
+/* host only: int16 coefficients of the planes, the workspaces of rhccq_jpeg_entropy and rhccq_jpeg_encode, the file's largest possible size */
+int rhccq_jpeg_write_sizes(int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, int64_t* coefficients, int64_t* entropy_bytes,
+                           int64_t* encode_bytes, int64_t* file_bytes);
+/* Device forms: image, tables_dev, coef, workspace, out (cap bytes) and length (one int64) are device memory; async on the context's
+   stream, nothing allocated, nothing read back.  rhccq_jpeg_blocks: image -> coef.  rhccq_jpeg_entropy: coef -> the whole file in out,
+   its length in *length.  rhccq_jpeg_encode: both, the coefficients in its workspace. */
+int rhccq_jpeg_blocks(rhccq_ctx* ctx, const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, const void* tables_dev, int16_t* coef);
+int rhccq_jpeg_entropy(rhccq_ctx* ctx, const int16_t* coef, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, const void* tables_dev,
+                       void* workspace, uint8_t* out, int64_t cap, int64_t* length);
+int rhccq_jpeg_encode(rhccq_ctx* ctx, const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, const void* tables_dev,
+                      void* workspace, uint8_t* out, int64_t cap, int64_t* length);
+/* Host forms (serial, no GPU, host memory): the same step functions of csrc/jpeg_write.h.  RHCCQ_E_ARG also where cap is too small */
+int rhccq_jpeg_blocks_host(const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int16_t* coef);
+int rhccq_jpeg_encode_host(const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, uint8_t* out, int64_t cap,
+                           int64_t* length);
+
 #ifdef __cplusplus
 }
 #endif

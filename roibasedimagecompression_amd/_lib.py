@@ -372,6 +372,14 @@ PROTOTYPES = {
     "rhccq_jpeg_coefficients_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
     "rhccq_jpeg_pixels_host": (c_int32, [C.POINTER(JpegInfo), c_void_p, c_void_p, c_void_p]),
     "rhccq_jpeg_decode_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_jpeg_write_tables_bytes": (c_int32, []),
+    "rhccq_jpeg_write_tables_host": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "rhccq_jpeg_write_sizes": (c_int32, [c_int32] * 5 + [C.POINTER(c_int64)] * 4),
+    "rhccq_jpeg_blocks": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rhccq_jpeg_entropy": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_jpeg_encode": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_jpeg_blocks_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "rhccq_jpeg_encode_host": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_int64, C.POINTER(c_int64)]),
 }
 
 

@@ -1167,12 +1167,23 @@ class ImageEncoder:
                 out[i], rows[i] = small[j], {"from": (H, W), "to": to, "filter": resample}
         return out, out_masks, stacked if whole else None, rows
 
-    def resize(self, image_or_file, size, filter="lanczos"):
+    def resize(self, image_or_file, size, filter="lanczos", jpeg_path=None, quality=75, subsampling="420"):
         """image_or_file: uint8 [H, W], [H, W, C] or [B, H, W, C] (numpy or device tensor), or the name of a PNG file (read on the device,
         alpha ignored) -> the device tensor Rhccq.resize gives: size (OH, OW) or one integer for the longest side, filter in
-        ops.RESIZE_FILTERS.  Exact integers, Pillow's Image.resize(reducing_gap=None) byte for byte (include/rhccq.h "resize")."""
+        ops.RESIZE_FILTERS.  Exact integers, Pillow's Image.resize(reducing_gap=None) byte for byte (include/rhccq.h "resize").
+        jpeg_path (default None = off): what is returned ([H, W] or [H, W, 3]) is also written there as a JPEG file on the device
+        (container.write_jpeg with quality and subsampling), so a thumbnail of a JPEG file never leaves the card between its read and
+        its write."""
+        jpeg_path = self._png_arg("ImageEncoder.resize", jpeg_path, "jpeg_path")
         image, _ = self._png_in(image_or_file)
-        return self.rh.resize(image, size, filter)
+        small = self.rh.resize(image, size, filter)
+        if jpeg_path:
+            from . import container
+            if small.ndim == 3 and int(small.shape[2]) == 1:
+                container.write_jpeg(small[..., 0], jpeg_path, self.rh, quality=quality, subsampling=subsampling)
+            else:
+                container.write_jpeg(small, jpeg_path, self.rh, quality=quality, subsampling=subsampling)
+        return small
 
     def _cells(self, fn, rgb, roi_mask, roi_weight, into=None):
         """the frame's histogram table (Rhccq.palette_cells); with a mask a pixel inside it weighs roi_weight and one outside 1"""

@@ -274,6 +274,9 @@ def gif_frames_array(frames, n):
 JPEG_STATUS = ("OK", "BAD_SIGNATURE", "BAD_SEGMENT", "BAD_HEADER", "BAD_TABLE", "UNSUPPORTED", "LIMIT", "BAD_RESTART", "BAD_SCAN")
 
 
+JPEG_MODES = ("grey", "444", "422", "420")                    # RHCCQ_JPEG_GREY .. RHCCQ_JPEG_420
+
+
 def jpeg_subsequence_bits():
     """bits of a subsequence of Rhccq.jpeg_decode's synchronising decode where the caller names none: a lane decodes one"""
     return int(_lib.load().rhccq_jpeg_subsequence_bits())
@@ -2481,8 +2484,48 @@ class Rhccq:
                                                self._p(rgb), self._p(status)), fn)
         return {"rgb": rgb.view(info.height, info.width, 3), "status": status, "head": work[:32].view(torch.int32), "info": info}
 
+    # -- JPEG files written on the device (EXTENSION: csrc/jpeg_write.hip; include/rhccq.h pins the definition) -------------
+    def _jpeg_write_args(self, fn, image, subsampling, quality, restart_rows):
+        """-> (the image on the device, aligned to 16, H, W, mode, quality, restart rows, the writer's tables on the device, the four sizes
+        of rhccq_jpeg_write_sizes); ValueError for what the definition refuses"""
+        img = A.as_uint8(image, self.device, fn, "image")
+        if img.ndim not in (2, 3) or (img.ndim == 3 and int(img.shape[2]) != 3):
+            raise ValueError(f"{fn}: uint8 [H, W, 3] or [H, W] is expected")
+        if img.ndim == 3 and subsampling not in JPEG_MODES[1:]:
+            raise ValueError(f"{fn}: subsampling must be one of {JPEG_MODES[1:]}")
+        mode = JPEG_MODES.index(subsampling) if img.ndim == 3 else 0
+        H, W, quality, restart_rows = int(img.shape[0]), int(img.shape[1]), int(quality), int(restart_rows)
+        sizes = [C.c_int64() for _ in range(4)]
+        if not (0 <= restart_rows < 2 ** 31) or self._raw.rhccq_jpeg_write_sizes(H, W, mode, quality, restart_rows, *[C.byref(s) for s in sizes]):
+            raise ValueError(f"{fn}: quality must be 1..100, H and W 1..65535, restart_rows >= 0, and the largest possible file below 2 GiB")
+        tables = np.zeros(int(self._raw.rhccq_jpeg_write_tables_bytes()), np.uint8)
+        self._raw.rhccq_jpeg_write_tables_host(H, W, mode, quality, restart_rows, C.c_void_p(tables.ctypes.data))
+        return self._aligned_bytes(img, fn, "image"), H, W, mode, quality, restart_rows, self.dev(tables), [s.value for s in sizes]
+
+    def jpeg_blocks(self, image, subsampling="420", quality=75):
+        """image: uint8 [H, W, 3] or [H, W] (grey; numpy or device) -> int16[blocks, 64] device: the quantised coefficients in the layout
+        jpeg_coefficients gives for the file (the components' planes of whole MCUs one after another, row-major in a block, dummy blocks
+        filled in).  Colour conversion, downsampling, FDCT and quantiser as libjpeg does them (include/rhccq.h)."""
+        fn = "jpeg_blocks"
+        img, H, W, mode, quality, _, tables, sizes = self._jpeg_write_args(fn, image, subsampling, quality, 0)
+        coef = self.empty((sizes[0] // 64, 64), torch.int16)
+        self._check(self.lib.rhccq_jpeg_blocks(self.ctx, self._p(img), H, W, mode, quality, self._p(tables), self._p(coef)), fn)
+        return coef
+
+    def jpeg_encode(self, image, subsampling="420", quality=75, restart_rows=0):
+        """image: uint8 [H, W, 3] or [H, W] (grey; numpy or device) -> (out uint8 device, length int64[1] device): the baseline JPEG file
+        Pillow saves with quality, subsampling, optimize=False and restart_marker_rows is out[:length].  Nothing waits for the device."""
+        fn = "jpeg_encode"
+        img, H, W, mode, quality, restart_rows, tables, sizes = self._jpeg_write_args(fn, image, subsampling, quality, restart_rows)
+        work = self.empty((sizes[2],), torch.uint8)
+        out = self.empty((sizes[3],), torch.uint8)
+        length = self.empty((1,), torch.int64)
+        self._check(self.lib.rhccq_jpeg_encode(self.ctx, self._p(img), H, W, mode, quality, restart_rows, self._p(tables), self._p(work), self._p(out), out.numel(),
+                                               self._p(length)), fn)
+        return out, length
+
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
-    ZS_OK, ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
+    ZS_OK,ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
     _ZS_MSG = {1: "incorrect header check", 2: "invalid block type, code lengths, symbol or distance",
                3: "incomplete or truncated stream", 4: "incorrect data check"}
 
