@@ -1815,7 +1815,8 @@ int rhccq_jpeg_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, int32_t
  * uint64 first byte an interval, the stuff tiles' counts and prefix, the unstuffed stream, each at a multiple of 256;
  * rhccq_jpeg_encode's holds the coefficients behind that.  The sizes assume at most 1658 bits a block (a DC code of 9 bits and 11 value
  * bits, 63 AC codes of 16 bits and 10), which no coefficient array can pass.
- * Not built: optimised Huffman tables (optimize=True), progressive files, CMYK, EXIF and ICC segments, a batch writer.
+ * Optimised Huffman tables (optimize=True) are the next section's, with a bound of their own.
+ * Not built: progressive files, CMYK, EXIF and ICC segments, a batch writer.
  * mode: RHCCQ_JPEG_GREY (image uint8[H][W]) or RHCCQ_JPEG_444 / _422 / _420 (image uint8[H][W][3]).  RHCCQ_E_ARG: quality outside 1..100,
  * an unknown mode, H or W outside 1..65535, negative restart_rows, a null pointer, an image or coef not aligned to 16, a workspace not
  * aligned to 256, cap below file_bytes, or a largest possible file of 2^31 bytes or more.  The RHCCQ_JPEG_* statuses are the reader's alone. */
@@ -1841,6 +1842,66 @@ int rhccq_jpeg_encode(rhccq_ctx* ctx, const uint8_t* image, int32_t H, int32_t W
 int rhccq_jpeg_blocks_host(const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int16_t* coef);
 int rhccq_jpeg_encode_host(const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, uint8_t* out, int64_t cap,
                            int64_t* length);
+
+/* ---- EXTENSION: JPEG files written with optimised Huffman tables (no reference counterpart; csrc/jpeg_optimize.hip, csrc/jpeg_optimize.h) -------
+ * Files.  Byte for byte what Pillow 12.2 (libjpeg-turbo) saves with optimize=True and otherwise the writer's parameters: the file of the
+ * section above with its four (grey: two) DHT segments replaced, in the same order DC0, AC0, DC1, AC1, by tables made from the scan's own
+ * symbol counts, each segment ffc4, 19 + codes, class << 4 | table, bits[1..16], huffval; every other byte of the header as it was.
+ * A stage between the writer's blocks and entropy stages: it reads the coefficients and writes a second table struct on the device, which
+ * the entropy stage reads in place of the first.  Nothing is read back.
+ * Counts.  uint32 counts[4][256], table DC0, AC0, DC1, AC1 (component c counts into tables 2 (c > 0) and 2 (c > 0) + 1): per block of
+ * the scan the DC category of the difference the scan codes (0 at every restart interval's start, dummy blocks included), every AC symbol
+ * (run, size), one 0xF0 for each ZRL code, and symbol 0 (EOB) unless coefficient 63 is non-zero.
+ * Tables.  libjpeg's jpeg_gen_optimal_table, which is the definition:
+ *   reserved    a symbol 256 with count 1 joins the counts, so that no real symbol gets the code of all ones;
+ *   merging     while two trees are left: c1 is the symbol with the least non-zero count, the LARGER symbol among equal counts; c2 the
+ *               same among the symbols other than c1; c1's count becomes their sum, c2's becomes 0, and every symbol of both trees
+ *               gets one bit longer (libjpeg walks its others[] chains; here every symbol carries its tree's root: a symbol whose root
+ *               is c1 or c2 adds one, root c2 becomes c1);
+ *   fold        bits[l] counts the symbols of length l, 256's included.  From the deepest length down to 17, while bits[i] > 0: j is the
+ *               deepest length <= i - 2 with a code; bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1.  (libjpeg gives up
+ *               at a length above 32; these functions fold any depth.)
+ *   reserved    the longest length <= 16 that has a code loses one: the reserved symbol's;
+ *   huffval     the real symbols with a count, by their length before the fold, then by value; bits[] hands them their final lengths in
+ *               that order, and the codes are the canonical ones (first code of a length: (first + count of the length before) << 1).
+ * libjpeg's search for the least count starts from 1000000000, so a count above that would never be picked.  Every count is kept in 32
+ * bits and a frame with 64 * blocks + 1 >= 1000000000 is refused with RHCCQ_E_LIMIT (the host table form: a table whose counts with the
+ * reserved 1 reach that).  Counts that pass it on the device give some table, not libjpeg's.
+ * Kernels.  histogram: a wave a block, a lane a zig-zag position; the ballot mask gives every lane its run; lanes of a wave holding
+ * the same symbol are matched by eight ballots and their lowest adds their number with one LDS atomic into the workgroup's 4 x 256
+ * words; a grid sized to the card strides over the blocks; every workgroup adds its non-zero words to the global counts once.
+ * huffman: one launch of four waves, a wave a table; lane l holds symbols l, l + 64, l + 128, l + 192 and lane 0 also 256; a merge step is
+ * two wave arg-minima (DPP) and a register update, at most 256 steps; bits[] by ballots, the fold by one lane in LDS, ranks and canonical
+ * codes by all; after a workgroup barrier the output struct: the divisors copied, code and length per symbol (0 for a symbol without a
+ * count), the header, header_len.  A header above 640 bytes (only counts no scan can give: more than 12 DC or 162 AC symbols) is left
+ * out: header_len 0.
+ * Sizes.  A DC table made for the picture has up to 12 symbols and the reserved one, so a DC code can take 12 bits where Annex K's take 9:
+ * a block takes at most 12 + 11 + 63 * (16 + 10) = 1661 bits.  rhccq_jpeg_optimize_sizes sizes stream, file and workspaces by that;
+ * rhccq_jpeg_write_sizes and the stages sized by it are what they were, and are not to be given the tables made here.
+ * rhccq_jpeg_encode_optimize's workspace: rhccq_jpeg_entropy_optimized's, the coefficients, the counts, the second struct.
+ * Not built: progressive files; a lossless re-pack of an existing file's coefficients (it needs a header made from that file's own
+ * tables); a batch writer. */
+/* host only: as rhccq_jpeg_write_sizes, for the stages below.  RHCCQ_E_LIMIT at 64 * blocks + 1 >= 1000000000 */
+int rhccq_jpeg_optimize_sizes(int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, int64_t* coefficients, int64_t* entropy_bytes,
+                              int64_t* encode_bytes, int64_t* file_bytes);
+/* Device forms, as the writer's.  rhccq_jpeg_histogram: coef -> counts uint32[4][256].  rhccq_jpeg_huffman: counts and the struct of
+   rhccq_jpeg_write_tables_host for the same frame -> tables_out, another struct of rhccq_jpeg_write_tables_bytes() bytes.
+   rhccq_jpeg_optimize: both.  rhccq_jpeg_entropy_optimized: rhccq_jpeg_entropy with workspace and cap of rhccq_jpeg_optimize_sizes.
+   rhccq_jpeg_encode_optimize: optimize 0 is rhccq_jpeg_encode itself, launch for launch; else blocks, optimize and entropy, with
+   workspace and cap of rhccq_jpeg_optimize_sizes. */
+int rhccq_jpeg_histogram(rhccq_ctx* ctx, const int16_t* coef, int32_t H, int32_t W, int32_t mode, int32_t restart_rows, uint32_t* counts);
+int rhccq_jpeg_huffman(rhccq_ctx* ctx, const uint32_t* counts, int32_t H, int32_t W, int32_t mode, int32_t restart_rows, const void* tables_dev, void* tables_out);
+int rhccq_jpeg_optimize(rhccq_ctx* ctx, const int16_t* coef, int32_t H, int32_t W, int32_t mode, int32_t restart_rows, const void* tables_dev, uint32_t* counts,
+                        void* tables_out);
+int rhccq_jpeg_entropy_optimized(rhccq_ctx* ctx, const int16_t* coef, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows,
+                                 const void* tables_dev, void* workspace, uint8_t* out, int64_t cap, int64_t* length);
+int rhccq_jpeg_encode_optimize(rhccq_ctx* ctx, const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, int32_t optimize,
+                               const void* tables_dev, void* workspace, uint8_t* out, int64_t cap, int64_t* length);
+/* Host forms (serial, no GPU, host memory): the same functions of csrc/jpeg_optimize.h */
+int rhccq_jpeg_histogram_host(const int16_t* coef, int32_t H, int32_t W, int32_t mode, int32_t restart_rows, uint32_t* counts);
+int rhccq_jpeg_huffman_host(const uint32_t* counts, int32_t H, int32_t W, int32_t mode, int32_t restart_rows, const void* tables, void* tables_out);
+int rhccq_jpeg_encode_optimize_host(const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, int32_t optimize, uint8_t* out,
+                                    int64_t cap, int64_t* length);
 
 #ifdef __cplusplus
 }

@@ -380,6 +380,15 @@ PROTOTYPES = {
     "rhccq_jpeg_encode": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rhccq_jpeg_blocks_host": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "rhccq_jpeg_encode_host": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_int64, C.POINTER(c_int64)]),
+    "rhccq_jpeg_optimize_sizes": (c_int32, [c_int32] * 5 + [C.POINTER(c_int64)] * 4),
+    "rhccq_jpeg_histogram": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p]),
+    "rhccq_jpeg_huffman": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p]),
+    "rhccq_jpeg_optimize": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "rhccq_jpeg_entropy_optimized": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_jpeg_encode_optimize": (c_int32, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rhccq_jpeg_histogram_host": (c_int32, [c_void_p] + [c_int32] * 4 + [c_void_p]),
+    "rhccq_jpeg_huffman_host": (c_int32, [c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p]),
+    "rhccq_jpeg_encode_optimize_host": (c_int32, [c_void_p] + [c_int32] * 6 + [c_void_p, c_int64, C.POINTER(c_int64)]),
 }
 
 

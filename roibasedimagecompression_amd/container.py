@@ -428,25 +428,27 @@ def read_jpeg(src, rh=None, subsequence_bits=None):
                       "sync_rounds": rounds, "worst_walk": walk, "seconds": round(time.perf_counter() - t0, 4)}}
 
 
-def jpeg_bytes(image, rh=None, quality=75, subsampling="420", restart_rows=0):
-    """a baseline JPEG file as bytes, built on the device: byte for byte what Pillow's save(quality=, subsampling=, optimize=False,
+def jpeg_bytes(image, rh=None, quality=75, subsampling="420", restart_rows=0, optimize=False):
+    """a baseline JPEG file as bytes, built on the device: byte for byte what Pillow's save(quality=, subsampling=, optimize=,
     restart_marker_rows=) gives (include/rhccq.h "JPEG files written on the device": colour conversion, downsampling, FDCT and quantiser,
     a wave a block for the Huffman codes, a prefix sum for their places, packing, byte stuffing).  image: uint8 [H, W, 3], or [H, W] for
     a grey file (numpy or device tensor), or a result dict (palette, indices, shape), shown as palette[indices] on the device.
     subsampling: "444", "422" or "420"; a grey file ignores it.  restart_rows: rows of MCUs a restart interval (0: no markers).  One read
-    of the file's length is the only wait.  Not written: optimised Huffman tables, progressive files, CMYK, EXIF and ICC segments."""
+    of the file's length is the only wait.  optimize: Huffman tables made from the scan's own symbol counts on the device (a histogram
+    launch and one table launch between the blocks and the entropy coding) in place of the Annex K tables: a smaller file, the same
+    pixels.  Not written: progressive files, CMYK, EXIF and ICC segments."""
     rh = rh or default_context()
     if isinstance(image, dict):
         rh, idx, h, w, pal = _png_frame(image, rh, "write_jpeg")
         pal = pal if isinstance(pal, torch.Tensor) else rh.dev(pal)
         image = rh.decode(idx, pal.to(rh.device).contiguous()).reshape(h, w, 3)
-    out, length = rh.jpeg_encode(image, subsampling, quality, restart_rows)
+    out, length = rh.jpeg_encode(image, subsampling, quality, restart_rows, optimize)
     return rh.to_host(out[:int(length.item())]).tobytes()
 
 
-def write_jpeg(image, filename, rh=None, quality=75, subsampling="420", restart_rows=0):
+def write_jpeg(image, filename, rh=None, quality=75, subsampling="420", restart_rows=0, optimize=False):
     """jpeg_bytes written to `filename`; returns the file's length in bytes"""
-    data = jpeg_bytes(image, rh, quality=quality, subsampling=subsampling, restart_rows=restart_rows)
+    data = jpeg_bytes(image, rh, quality=quality, subsampling=subsampling, restart_rows=restart_rows, optimize=optimize)
     with open(filename, "wb") as f:
         f.write(data)
     return len(data)

@@ -3,7 +3,7 @@
 //   frame      args_ok, frame_of: the planes of whole MCUs (jpeg_read.h's Geo), the first component's true size in blocks, the intervals;
 //   tables     quant_tables, tables_build: the divisors, the Annex K codes as code / length per symbol, the file's header;
 //   blocks     ycc, sample_at (edge replication, chroma downsampling), fdct8 (one pass of the islow FDCT), quantise, dummy_source;
-//   entropy    dc_pred, lane_symbol: what one zig-zag position of one block puts into the scan;
+//   entropy    dc_pred, lane_sym, lane_symbol: what one zig-zag position of one block puts into the scan (the symbol; its code and bits);
 //   serial     blocks_serial, encode_serial: the host forms.
 #pragma once
 #include "jpeg_read.h"
@@ -20,7 +20,9 @@ using jpegr::zigzag;
 constexpr int kThreads = 256;
 constexpr int kPackBlocks = 32;                            // blocks of a workgroup of the count and pack launches: 8 a wave
 constexpr int kBlockBits = 20 + 63 * 26;                   // the most a block takes: a DC code of 9 bits and 11 value bits, 63 codes of 16 and 10
-constexpr int kWindowWords = (kPackBlocks * (kBlockBits + 7) + 31) / 32 + 2;   // LDS words of a pack workgroup, pads and both ragged ends included
+constexpr int kBlockBitsOpt = 23 + 63 * 26;                // with tables made for the picture (jpeg_optimize.h): a DC code of 12 bits
+constexpr int window_words(int block_bits) { return (kPackBlocks * (block_bits + 7) + 31) / 32 + 2; }
+constexpr int kWindowWords = window_words(kBlockBits);     // LDS words of a pack workgroup, pads and both ragged ends included
 constexpr int kTileBytes = 16 * kThreads;                  // stream bytes of a workgroup of the stuff launches
 constexpr int kHeaderMax = 640;                            // SOI .. SOS is 623 bytes at most (colour, with DRI)
 constexpr int kStripPx = 128;                              // the widest strip of the blocks launch in pixels of a colour frame (grey: 256)
@@ -79,8 +81,8 @@ RHCCQ_JPEG_HD int64_t interval_of(const Geo& g, int64_t A) { return g.R ? A / g.
 RHCCQ_JPEG_HD bool starts_interval(const Geo& g, int64_t A) { return g.R ? A % ((int64_t)g.bpm * g.R) == 0 : A == 0; }
 RHCCQ_JPEG_HD bool ends_interval(const Geo& g, int64_t A) { return A + 1 == g.blocks || starts_interval(g, A + 1); }
 // the most bytes of the unstuffed stream, and of the file
-RHCCQ_JPEG_HD int64_t stream_cap(const Frame& f) { return (f.g.blocks * kBlockBits + 7) / 8 + f.n_iv; }
-RHCCQ_JPEG_HD int64_t file_cap(const Frame& f) { return kHeaderMax + 2 * stream_cap(f) + 2 * f.n_iv + 2; }
+RHCCQ_JPEG_HD int64_t stream_cap(const Frame& f, int block_bits = kBlockBits) { return (f.g.blocks * block_bits + 7) / 8 + f.n_iv; }
+RHCCQ_JPEG_HD int64_t file_cap(const Frame& f, int block_bits = kBlockBits) { return kHeaderMax + 2 * stream_cap(f, block_bits) + 2 * f.n_iv + 2; }
 
 // ---- tables --------------------------------------------------------------------------------------------------------------------------
 // what the kernels read: table t of code / len is DC0, AC0, DC1, AC1; component c codes with tables 2 (c > 0) and 2 (c > 0) + 1
@@ -253,32 +255,40 @@ RHCCQ_JPEG_HD int32_t dc_pred(const Geo& g, const int16_t* coef, int64_t A) {
   return coef[64 * block_at(g, b == 0 ? (mcu - 1) * g.bpm + ny - 1 : A - g.bpm)];
 }
 // What zig-zag position k of a block puts into the scan.  v: the coefficient there (k = 0: the DC difference); mask: bit j set where
-// position j >= 1 holds a non-zero coefficient; code, len: the component's DC table and, 256 entries on, its AC table.  -> the number of
-// ZRL codes in front, then `n` bits `bits` (the code and the value bits).  Position 63 carries EOB when its coefficient is 0.
+// position j >= 1 holds a non-zero coefficient.  -> the symbol (-1: none), its value bits' count, and the number of ZRL codes in front.
+// Position 63 carries EOB when its coefficient is 0.
+struct LaneSym {
+  int32_t sym, s, zrl;
+};
+RHCCQ_JPEG_HD LaneSym lane_sym(int k, int32_t v, uint64_t mask) {
+  LaneSym o{-1, 0, 0};
+  if (k == 0) {
+    o.sym = o.s = bit_size(v);
+  } else if (v != 0) {
+    const uint64_t below = mask & (((uint64_t)1 << k) - 2);
+    const int run = k - 1 - (below ? top_bit(below) : 0);
+    o.zrl = run >> 4;
+    o.s = bit_size(v);
+    o.sym = (run & 15) << 4 | o.s;
+  } else if (k == 63) {
+    o.sym = 0;
+  }
+  return o;
+}
+// code, len: the component's DC table and, 256 entries on, its AC table.  -> the number of ZRL codes in front, then `n` bits `bits` (the
+// code and the value bits)
 struct LaneBits {
   uint32_t bits;
   int32_t n, zrl;
 };
 RHCCQ_JPEG_HD LaneBits lane_symbol(const uint16_t* code, const uint8_t* len, int k, int32_t v, uint64_t mask) {
-  LaneBits o{0u, 0, 0};
-  int sym, s = 0, t = 256;
-  if (k == 0) {
-    sym = s = bit_size(v);
-    t = 0;
-  } else if (v != 0) {
-    const uint64_t below = mask & (((uint64_t)1 << k) - 2);
-    const int run = k - 1 - (below ? top_bit(below) : 0);
-    o.zrl = run >> 4;
-    s = bit_size(v);
-    sym = (run & 15) << 4 | s;
-  } else if (k == 63) {
-    sym = 0;
-  } else {
-    return o;
-  }
-  const uint32_t value = (uint32_t)(v < 0 ? v - 1 : v) & (((uint32_t)1 << s) - 1);
-  o.bits = (uint32_t)code[t + sym] << s | value;
-  o.n = len[t + sym] + s;
+  const LaneSym y = lane_sym(k, v, mask);
+  LaneBits o{0u, 0, y.zrl};
+  if (y.sym < 0) return o;
+  const int at = (k ? 256 : 0) + y.sym;
+  const uint32_t value = (uint32_t)(v < 0 ? v - 1 : v) & (((uint32_t)1 << y.s) - 1);
+  o.bits = (uint32_t)code[at] << y.s | value;
+  o.n = len[at] + y.s;
   return o;
 }
 RHCCQ_JPEG_HD int lane_length(const LaneBits& b, const uint8_t* len) { return b.zrl * len[256 + 0xF0] + b.n; }
@@ -345,6 +355,12 @@ inline int64_t encode_serial(const Frame& f, const Tables& T, const int16_t* coe
   byte(0xFF), byte(0xD9);
   return full ? -1 : n;
 }
+
+// ---- what jpeg_optimize.hip takes from jpeg_write.hip ---------------------------------------------------------------------------------
+// the entropy stage sized for block_bits a block (kBlockBits or kBlockBitsOpt): its workspace's bytes, its launches
+int64_t entropy_workspace(const Frame& f, int block_bits);
+int entropy_launch(rhccq_ctx* ctx, const Frame& f, int block_bits, const Tables* tables_dev, const int16_t* coef, void* workspace, uint8_t* out, int64_t cap, int64_t* length);
+int blocks_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_dev, const uint8_t* img, int16_t* coef);
 
 }  // namespace jpegw
 }  // namespace rhccq

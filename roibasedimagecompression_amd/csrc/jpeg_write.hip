@@ -226,16 +226,18 @@ __device__ __forceinline__ void window_put(uint32_t* win, uint32_t at, uint32_t 
   if ((uint32_t)w) atomicOr(&win[(at >> 5) + 1], (uint32_t)w);
 }
 
+// kWin: window_words of the most bits a block takes with the tables in use
+template <int kWin>
 __global__ __launch_bounds__(kThreads) void pack_kernel(Frame f, const Tables* __restrict__ tables, const int16_t* __restrict__ coef, const uint64_t* __restrict__ within,
                                                         const uint64_t* __restrict__ iv_start, const uint64_t* __restrict__ head, uint32_t* __restrict__ stream) {
   __shared__ Codes s_cd;
-  __shared__ uint32_t s_win[kWindowWords];
+  __shared__ uint32_t s_win[kWin];
   const Geo& g = f.g;
   const long long g0 = (long long)blockIdx.x * kPackBlocks, g1 = min(g0 + kPackBlocks, (long long)g.blocks);
   auto first_bit = [&](long long A) { return 8 * iv_start[interval_of(g, A)] + within[A]; };
   const uint64_t lo = first_bit(g0), hi = g1 < g.blocks ? first_bit(g1) : 8 * head[kHeadStream];
   const long long base = (long long)(lo >> 5);
-  const int words = (int)min((long long)((hi + 31) >> 5) - base, (long long)kWindowWords - 1);   // (kBlockBits bounds it; never cut)
+  const int words = (int)min((long long)((hi + 31) >> 5) - base, (long long)kWin - 1);   // (the bound on a block's bits bounds it; never cut)
   for (int i = threadIdx.x; i <= words; i += kThreads) s_win[i] = 0u;
   codes_to_lds(&s_cd, tables);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -247,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(Frame f, const Tables* _
     const uint32_t incl = dpp_incscan_u32<64>((uint32_t)length);
     const uint32_t start = (uint32_t)(first_bit(A) - 32 * (uint64_t)base);
     uint32_t at = start + incl - (uint32_t)length;
-    if (at + (uint32_t)length > 32u * (uint32_t)words) continue;       // (never: the window holds kBlockBits a block)
+    if (at + (uint32_t)length > 32u * (uint32_t)words) continue;       // (never: the window holds every block's most bits)
     for (int z = 0; z < lb.zrl; ++z) {                     // (at most 3)
       window_put(s_win, at, s_cd.code[t + 1][0xF0], s_cd.len[t + 1][0xF0]);
       at += s_cd.len[t + 1][0xF0];
@@ -329,10 +331,10 @@ __global__ __launch_bounds__(kThreads) void stuff_kernel(Frame f, const Tables* 
 // the entropy stage's workspace: the head, the blocks' bits and places, the place tiles, the intervals' bytes and first bytes, the stuff
 // tiles' counts and their prefix, the unstuffed stream (a tile's worth behind it: the stuff launches read whole 16 bytes)
 struct Layout { int64_t place_tiles, stuff_tiles, o_bits, o_within, o_agg, o_ivb, o_ivs, o_tiles, o_tff, o_stream, total; };
-static Layout layout_of(const Frame& f) {
+static Layout layout_of(const Frame& f, int block_bits = kBlockBits) {
   Layout l;
   l.place_tiles = (f.g.blocks + kThreads - 1) / kThreads;
-  l.stuff_tiles = (stream_cap(f) + kTileBytes - 1) / kTileBytes;
+  l.stuff_tiles = (stream_cap(f, block_bits) + kTileBytes - 1) / kTileBytes;
   l.o_bits = 256;
   l.o_within = align256(l.o_bits + 4 * f.g.blocks);
   l.o_agg = align256(l.o_within + 8 * f.g.blocks);
@@ -349,7 +351,7 @@ static int strip_of(const Geo& g) {
   return by_blocks < by_px ? by_blocks : by_px;
 }
 
-static int blocks_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_dev, const uint8_t* img, int16_t* coef) {
+int blocks_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_dev, const uint8_t* img, int16_t* coef) {
   const int strip = strip_of(f.g);
   hipLaunchKernelGGL(blocks_kernel, dim3((unsigned)((f.g.mcus_x + strip - 1) / strip), (unsigned)(f.g.mcus / f.g.mcus_x)), dim3(kThreads), 0, ctx->stream, f, tables_dev,
                      img, strip, coef);
@@ -357,8 +359,10 @@ static int blocks_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_de
   return 0;
 }
 
-static int entropy_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_dev, const int16_t* coef, void* workspace, uint8_t* out, int64_t cap, int64_t* length) {
-  const Layout l = layout_of(f);
+int64_t entropy_workspace(const Frame& f, int block_bits) { return layout_of(f, block_bits).total; }
+
+int entropy_launch(rhccq_ctx* ctx, const Frame& f, int block_bits, const Tables* tables_dev, const int16_t* coef, void* workspace, uint8_t* out, int64_t cap, int64_t* length) {
+  const Layout l = layout_of(f, block_bits);
   uint8_t* ws = (uint8_t*)workspace;
   uint64_t* head = (uint64_t*)ws;
   uint32_t* bits = (uint32_t*)(ws + l.o_bits);
@@ -378,7 +382,11 @@ static int entropy_launch(rhccq_ctx* ctx, const Frame& f, const Tables* tables_d
   hipLaunchKernelGGL(place_kernel<true>, per_place, wg, 0, st, f, (const uint32_t*)bits, agg, within, iv_bytes);
   hipLaunchKernelGGL(scan_kernel, one, wg, 0, st, (const uint32_t*)iv_bytes, (long long)f.n_iv, iv_start, head + kHeadStream);
   hipLaunchKernelGGL(zero_kernel, dim3((unsigned)(l.stuff_tiles + 1)), wg, 0, st, (const uint64_t*)head, (uint4*)stream);
-  hipLaunchKernelGGL(pack_kernel, per_pack, wg, 0, st, f, tables_dev, coef, (const uint64_t*)within, (const uint64_t*)iv_start, (const uint64_t*)head, (uint32_t*)stream);
+  if (block_bits == kBlockBits)
+    hipLaunchKernelGGL(pack_kernel<kWindowWords>, per_pack, wg, 0, st, f, tables_dev, coef, (const uint64_t*)within, (const uint64_t*)iv_start, (const uint64_t*)head, (uint32_t*)stream);
+  else
+    hipLaunchKernelGGL(pack_kernel<window_words(kBlockBitsOpt)>, per_pack, wg, 0, st, f, tables_dev, coef, (const uint64_t*)within, (const uint64_t*)iv_start, (const uint64_t*)head,
+                       (uint32_t*)stream);
   hipLaunchKernelGGL(ff_kernel, per_stuff, wg, 0, st, (const uint8_t*)stream, (const uint64_t*)head, tiles);
   hipLaunchKernelGGL(scan_kernel, one, wg, 0, st, (const uint32_t*)tiles, (long long)l.stuff_tiles, tile_ff, head + kHeadFF);
   hipLaunchKernelGGL(stuff_kernel, per_stuff, wg, 0, st, f, tables_dev, (const uint8_t*)stream, head, (const uint64_t*)tile_ff, (const uint64_t*)iv_start, out,
@@ -434,7 +442,7 @@ int rhccq_jpeg_entropy(rhccq_ctx* ctx, const int16_t* coef, int32_t H, int32_t W
   if (!coef || !tables_dev || !workspace || !out || !length || (uintptr_t)coef % 16 || (uintptr_t)tables_dev % 4 || (uintptr_t)workspace % 256 || (uintptr_t)length % 8 ||
       !sized(f) || cap < file_cap(f))
     return rhccq_fail(ctx, RHCCQ_E_ARG, "jpeg_entropy: a null or misaligned pointer, or cap below rhccq_jpeg_write_sizes' file_bytes");
-  return entropy_launch(ctx, f, (const Tables*)tables_dev, coef, workspace, out, cap, length);
+  return entropy_launch(ctx, f, kBlockBits, (const Tables*)tables_dev, coef, workspace, out, cap, length);
 }
 
 int rhccq_jpeg_encode(rhccq_ctx* ctx, const uint8_t* image, int32_t H, int32_t W, int32_t mode, int32_t quality, int32_t restart_rows, const void* tables_dev,

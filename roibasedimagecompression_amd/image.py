@@ -1167,22 +1167,22 @@ class ImageEncoder:
                 out[i], rows[i] = small[j], {"from": (H, W), "to": to, "filter": resample}
         return out, out_masks, stacked if whole else None, rows
 
-    def resize(self, image_or_file, size, filter="lanczos", jpeg_path=None, quality=75, subsampling="420"):
+    def resize(self, image_or_file, size, filter="lanczos", jpeg_path=None, quality=75, subsampling="420", optimize=False):
         """image_or_file: uint8 [H, W], [H, W, C] or [B, H, W, C] (numpy or device tensor), or the name of a PNG file (read on the device,
         alpha ignored) -> the device tensor Rhccq.resize gives: size (OH, OW) or one integer for the longest side, filter in
         ops.RESIZE_FILTERS.  Exact integers, Pillow's Image.resize(reducing_gap=None) byte for byte (include/rhccq.h "resize").
         jpeg_path (default None = off): what is returned ([H, W] or [H, W, 3]) is also written there as a JPEG file on the device
-        (container.write_jpeg with quality and subsampling), so a thumbnail of a JPEG file never leaves the card between its read and
-        its write."""
+        (container.write_jpeg with quality, subsampling and optimize), so a thumbnail of a JPEG file never leaves the card between its
+        read and its write."""
         jpeg_path = self._png_arg("ImageEncoder.resize", jpeg_path, "jpeg_path")
         image, _ = self._png_in(image_or_file)
         small = self.rh.resize(image, size, filter)
         if jpeg_path:
             from . import container
             if small.ndim == 3 and int(small.shape[2]) == 1:
-                container.write_jpeg(small[..., 0], jpeg_path, self.rh, quality=quality, subsampling=subsampling)
+                container.write_jpeg(small[..., 0], jpeg_path, self.rh, quality=quality, subsampling=subsampling, optimize=optimize)
             else:
-                container.write_jpeg(small, jpeg_path, self.rh, quality=quality, subsampling=subsampling)
+                container.write_jpeg(small, jpeg_path, self.rh, quality=quality, subsampling=subsampling, optimize=optimize)
         return small
 
     def _cells(self, fn, rgb, roi_mask, roi_weight, into=None):

@@ -2485,9 +2485,9 @@ class Rhccq:
         return {"rgb": rgb.view(info.height, info.width, 3), "status": status, "head": work[:32].view(torch.int32), "info": info}
 
     # -- JPEG files written on the device (EXTENSION: csrc/jpeg_write.hip; include/rhccq.h pins the definition) -------------
-    def _jpeg_write_args(self, fn, image, subsampling, quality, restart_rows):
+    def _jpeg_write_args(self, fn, image, subsampling, quality, restart_rows, optimize=False):
         """-> (the image on the device, aligned to 16, H, W, mode, quality, restart rows, the writer's tables on the device, the four sizes
-        of rhccq_jpeg_write_sizes); ValueError for what the definition refuses"""
+        of rhccq_jpeg_write_sizes, with optimize of rhccq_jpeg_optimize_sizes); ValueError for what the definition refuses"""
         img = A.as_uint8(image, self.device, fn, "image")
         if img.ndim not in (2, 3) or (img.ndim == 3 and int(img.shape[2]) != 3):
             raise ValueError(f"{fn}: uint8 [H, W, 3] or [H, W] is expected")
@@ -2496,7 +2496,8 @@ class Rhccq:
         mode = JPEG_MODES.index(subsampling) if img.ndim == 3 else 0
         H, W, quality, restart_rows = int(img.shape[0]), int(img.shape[1]), int(quality), int(restart_rows)
         sizes = [C.c_int64() for _ in range(4)]
-        if not (0 <= restart_rows < 2 ** 31) or self._raw.rhccq_jpeg_write_sizes(H, W, mode, quality, restart_rows, *[C.byref(s) for s in sizes]):
+        query = self._raw.rhccq_jpeg_optimize_sizes if optimize else self._raw.rhccq_jpeg_write_sizes
+        if not (0 <= restart_rows < 2 ** 31) or query(H, W, mode, quality, restart_rows, *[C.byref(s) for s in sizes]):
             raise ValueError(f"{fn}: quality must be 1..100, H and W 1..65535, restart_rows >= 0, and the largest possible file below 2 GiB")
         tables = np.zeros(int(self._raw.rhccq_jpeg_write_tables_bytes()), np.uint8)
         self._raw.rhccq_jpeg_write_tables_host(H, W, mode, quality, restart_rows, C.c_void_p(tables.ctypes.data))
@@ -2512,17 +2513,60 @@ class Rhccq:
         self._check(self.lib.rhccq_jpeg_blocks(self.ctx, self._p(img), H, W, mode, quality, self._p(tables), self._p(coef)), fn)
         return coef
 
-    def jpeg_encode(self, image, subsampling="420", quality=75, restart_rows=0):
+    def jpeg_encode(self, image, subsampling="420", quality=75, restart_rows=0, optimize=False):
         """image: uint8 [H, W, 3] or [H, W] (grey; numpy or device) -> (out uint8 device, length int64[1] device): the baseline JPEG file
-        Pillow saves with quality, subsampling, optimize=False and restart_marker_rows is out[:length].  Nothing waits for the device."""
+        Pillow saves with quality, subsampling, optimize and restart_marker_rows is out[:length].  optimize: Huffman tables made from the
+        scan's own symbol counts on the device (csrc/jpeg_optimize.hip) in place of the Annex K tables.  Nothing waits for the device."""
         fn = "jpeg_encode"
-        img, H, W, mode, quality, restart_rows, tables, sizes = self._jpeg_write_args(fn, image, subsampling, quality, restart_rows)
+        img, H, W, mode, quality, restart_rows, tables, sizes = self._jpeg_write_args(fn, image, subsampling, quality, restart_rows, optimize)
         work = self.empty((sizes[2],), torch.uint8)
         out = self.empty((sizes[3],), torch.uint8)
         length = self.empty((1,), torch.int64)
+        if optimize:
+            self._check(self.lib.rhccq_jpeg_encode_optimize(self.ctx, self._p(img), H, W, mode, quality, restart_rows, 1, self._p(tables), self._p(work), self._p(out),
+                                                            out.numel(), self._p(length)), fn)
+            return out, length
         self._check(self.lib.rhccq_jpeg_encode(self.ctx, self._p(img), H, W, mode, quality, restart_rows, self._p(tables), self._p(work), self._p(out), out.numel(),
                                                self._p(length)), fn)
         return out, length
+
+    def _jpeg_mode(self, fn, shape, subsampling, restart_rows):
+        H, W, restart_rows = int(shape[0]), int(shape[1]), int(restart_rows)
+        if subsampling not in JPEG_MODES or not (0 <= restart_rows < 2 ** 31):
+            raise ValueError(f"{fn}: subsampling must be one of {JPEG_MODES} and restart_rows >= 0")
+        return H, W, JPEG_MODES.index(subsampling), restart_rows
+
+    def jpeg_histogram(self, coef, shape, subsampling="420", restart_rows=0):
+        """coef: jpeg_blocks' int16[blocks, 64] of an image of shape (H, W); subsampling: "grey", "444", "422" or "420" -> uint32-valued
+        int32[4, 256] device: how often the scan holds every symbol of the tables DC0, AC0, DC1, AC1 (include/rhccq.h "optimised Huffman
+        tables")"""
+        fn = "jpeg_histogram"
+        H, W, mode, restart_rows = self._jpeg_mode(fn, shape, subsampling, restart_rows)
+        coef = A.as_dtype(coef, torch.int16, self.device, fn, "coef")
+        sizes = [C.c_int64() for _ in range(4)]
+        rc = self._raw.rhccq_jpeg_optimize_sizes(H, W, mode, 75, restart_rows, *[C.byref(s) for s in sizes])
+        if rc or coef.numel() != sizes[0].value:
+            raise ValueError(f"{fn}: coef is not jpeg_blocks' of a {H} x {W} {subsampling} image, or the image is too large ({rc})")
+        counts = self.empty((4, 256), torch.int32)
+        self._check(self.lib.rhccq_jpeg_histogram(self.ctx, self._p(coef), H, W, mode, restart_rows, self._p(counts)), fn)
+        return counts
+
+    def jpeg_huffman(self, counts, shape, subsampling="420", quality=75, restart_rows=0):
+        """counts: [4, 256] (numpy or device) -> uint8 device: the writer's table struct for an image of shape (H, W) with libjpeg's optimal
+        codes for these counts (jpeg_gen_optimal_table) and the header that carries them"""
+        fn = "jpeg_huffman"
+        H, W, mode, restart_rows = self._jpeg_mode(fn, shape, subsampling, restart_rows)
+        if not torch.is_tensor(counts):
+            counts = np.ascontiguousarray(counts).astype(np.uint32).view(np.int32)
+        counts = A.as_dtype(counts, torch.int32, self.device, fn, "counts")
+        if tuple(counts.shape) != (4, 256):
+            raise ValueError(f"{fn}: counts must be [4, 256]")
+        tables = np.zeros(int(self._raw.rhccq_jpeg_write_tables_bytes()), np.uint8)
+        if self._raw.rhccq_jpeg_write_tables_host(H, W, mode, int(quality), restart_rows, C.c_void_p(tables.ctypes.data)):
+            raise ValueError(f"{fn}: quality must be 1..100, H and W 1..65535")
+        made = self.empty((tables.size,), torch.uint8)
+        self._check(self.lib.rhccq_jpeg_huffman(self.ctx, self._p(counts), H, W, mode, restart_rows, self._p(self.dev(tables)), self._p(made)), fn)
+        return made
 
     # -- zlib inflate (csrc/zlib_inflate.hip) ------------------------------------------------------------
     ZS_OK,ZS_BAD_HEADER, ZS_BAD_DATA, ZS_TRUNCATED, ZS_ADLER, ZS_CAPACITY = 0, 1, 2, 3, 4, 5
