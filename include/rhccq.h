@@ -1763,6 +1763,58 @@ int rhccq_jpeg_coefficients_host(const uint8_t* file, int64_t n, int16_t* coef, 
 int rhccq_jpeg_pixels_host(const rhccq_jpeg_info* info, const rhccq_jpeg_tables* tables, const int16_t* coef, uint8_t* rgb);
 int rhccq_jpeg_decode_host(const uint8_t* file, int64_t n, uint8_t* rgb, int32_t* status);
 
+/* ---- EXTENSION: JPEG files read as a batch (no reference counterpart; csrc/jpeg_batch.hip, csrc/jpeg_read.h) -----------------------------
+ * n_files files in, n_files images out: every file decodes to exactly the bytes rhccq_jpeg_decode gives for it alone, with one upload,
+ * one set of launches whose number does not depend on n_files (fourteen and the clearing of the coefficients), and one status array.
+ * The stages and their arithmetic are those of "JPEG files read on the device"; what is new is whom a workgroup belongs to.
+ * Layout.  Every file is parsed on the host (rhccq_jpeg_parse_host), so its subsequences, tiles and blocks are known before anything
+ * runs.  A file's units of every stage are padded to whole workgroups: no workgroup holds two files, and each loads one file's tables
+ * into LDS as the single-file kernels do.  Five maps, a row {file, first unit in the file} a workgroup, say whose a workgroup is:
+ *   RHCCQ_JPEG_MAP_UNSTUFF  a tile of 4096 scan bytes (unit: the tile)          RHCCQ_JPEG_MAP_IDCT    32 blocks (unit: the block)
+ *   RHCCQ_JPEG_MAP_SUB      256 subsequences (unit: the subsequence)            RHCCQ_JPEG_MAP_COLOUR  256 quads of pixels (unit: the quad)
+ *   RHCCQ_JPEG_MAP_DC       256 DC differences (unit: the tile, counted through the file's components)
+ * The scan between the two unstuff passes, the boundary walk, place and the DC carries run one workgroup a file (grid n_files); the
+ * tiles' prefix sum, the subsequences' first blocks and the DC carries so restart with every file, and the walks of different files'
+ * boundaries run side by side.  A file's first subsequence starts from the truth, state (0, 0, 0) at its block 0.
+ * The upload (one host buffer, one copy): the job table (rhccq_jpeg_job[n_files]) at 0, the maps, then per file its tables (aligned to
+ * 16), its interval rows (aligned to 8) and its bytes, at the offsets the job holds.  rhccq_jpeg_batch_plan_host writes the job table and
+ * the maps; the caller copies the parse's tables and intervals and the file behind them.  The workspace: uint32[n_files][8] heads (as the
+ * single-file workspace's eight words, per file), every file's tiles, stream, rows, first blocks and DC tiles, then all coefficients
+ * (cleared by one memset), then all planes.  Every image starts at a multiple of 16 bytes of rgb.
+ * A file whose parse set a status takes part in no launch but the last, which writes its status and detail; the others decode. */
+#define RHCCQ_JPEG_MAP_UNSTUFF 0
+#define RHCCQ_JPEG_MAP_SUB 1
+#define RHCCQ_JPEG_MAP_DC 2
+#define RHCCQ_JPEG_MAP_IDCT 3
+#define RHCCQ_JPEG_MAP_COLOUR 4
+typedef struct rhccq_jpeg_job {
+  rhccq_jpeg_info info;                   /* the parse's */
+  int64_t file_offset, file_bytes;        /* in the upload */
+  int64_t tables_offset, intervals_offset;
+  int64_t n_tiles, n_sub, n_dc_tiles;     /* unstuff tiles, subsequences, DC tiles: 0 for a file with a status */
+  int64_t o_tiles, o_stream, o_rows, o_first, o_agg, o_coef, o_planes; /* in the workspace, each aligned to 256 */
+  int64_t o_rgb;                          /* in rgb, aligned to 16 */
+} rhccq_jpeg_job;
+typedef struct rhccq_jpeg_batch {
+  int64_t upload_bytes, workspace_bytes, rgb_bytes;
+  int64_t o_maps[5], map_rows[5];         /* a map's place in the upload (rows of uint32[2]) and its rows: the workgroups of its launches */
+  int64_t o_coef, coef_bytes;             /* all files' coefficients in the workspace */
+} rhccq_jpeg_batch;
+int32_t rhccq_jpeg_batch_max_files(void);   /* 65536 */
+/* host only: the layout's sizes for these parsed files (file_bytes[i]: file i's length).  RHCCQ_E_ARG: a null pointer, n_files < 1, a bad
+   subsequence_bits, an info without status that is not the parse's for file_bytes[i].  RHCCQ_E_LIMIT: more than
+   rhccq_jpeg_batch_max_files() files, a map of 2^31 rows or more, or an upload or an rgb of 2^31 bytes or more. */
+int rhccq_jpeg_batch_sizes(const rhccq_jpeg_info* infos, const int64_t* file_bytes, int32_t n_files, int32_t subsequence_bits, rhccq_jpeg_batch* batch);
+/* host only: as rhccq_jpeg_batch_sizes, and writes the job table and the maps into upload (host memory of cap >= upload_bytes bytes,
+   aligned to 16), so that every caller builds the same layout */
+int rhccq_jpeg_batch_plan_host(const rhccq_jpeg_info* infos, const int64_t* file_bytes, int32_t n_files, int32_t subsequence_bits, void* upload, int64_t cap,
+                               rhccq_jpeg_batch* batch);
+/* upload_dev: the planned and filled upload on the device (aligned to 256); jobs: its job table in host memory, checked against the
+   layout before anything runs (RHCCQ_E_ARG where it is not rhccq_jpeg_batch_plan_host's).  workspace (aligned to 256), rgb (aligned to
+   16) and status (int32[n_files][2]) are device memory; async on the context's stream, nothing allocated, nothing read back. */
+int rhccq_jpeg_decode_batch(rhccq_ctx* ctx, const void* upload_dev, const rhccq_jpeg_job* jobs, int32_t n_files, int32_t subsequence_bits, void* workspace,
+                            uint8_t* rgb, int32_t* status);
+
 /* ---- EXTENSION: JPEG files written on the device (no reference counterpart; csrc/jpeg_write.hip, csrc/jpeg_write.h) ---------------------------
  * Files.  Baseline sequential Huffman JPEG, byte for byte what Pillow 12.2 (libjpeg-turbo) saves from a uint8 RGB image with quality q,
  * subsampling 4:4:4, 4:2:2 or 4:2:0, optimize=False and restart_marker_rows r, and from a uint8 grey image.  In this order: SOI; APP0

@@ -66,6 +66,18 @@ class JpegInfo(C.Structure):
                 ("scan_offset", c_int64), ("scan_bytes", c_int64), ("stream_bytes", c_int64), ("blocks", c_int64)]
 
 
+class JpegJob(C.Structure):
+    """struct rhccq_jpeg_job (include/rhccq.h): a file of a batch, as rhccq_jpeg_batch_plan_host lays it out"""
+    _fields_ = [("info", JpegInfo)] + [(k, c_int64) for k in ("file_offset", "file_bytes", "tables_offset", "intervals_offset", "n_tiles", "n_sub", "n_dc_tiles",
+                                                              "o_tiles", "o_stream", "o_rows", "o_first", "o_agg", "o_coef", "o_planes", "o_rgb")]
+
+
+class JpegBatch(C.Structure):
+    """struct rhccq_jpeg_batch (include/rhccq.h): the sizes of a batch's upload, workspace and output, and where its maps lie"""
+    _fields_ = [("upload_bytes", c_int64), ("workspace_bytes", c_int64), ("rgb_bytes", c_int64), ("o_maps", c_int64 * 5), ("map_rows", c_int64 * 5),
+                ("o_coef", c_int64), ("coef_bytes", c_int64)]
+
+
 class FrameResult(C.Structure):
     """struct rhccq_frame_result (include/rhccq.h)"""
     _fields_ = [("n_colours", c_int32), ("index_bytes", c_int32), ("shape", c_int32 * 2), ("top_left", c_int32 * 2), ("quality3", c_int32),
@@ -372,6 +384,10 @@ PROTOTYPES = {
     "rhccq_jpeg_coefficients_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
     "rhccq_jpeg_pixels_host": (c_int32, [C.POINTER(JpegInfo), c_void_p, c_void_p, c_void_p]),
     "rhccq_jpeg_decode_host": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rhccq_jpeg_batch_max_files": (c_int32, []),
+    "rhccq_jpeg_batch_sizes": (c_int32, [C.POINTER(JpegInfo), C.POINTER(c_int64), c_int32, c_int32, C.POINTER(JpegBatch)]),
+    "rhccq_jpeg_batch_plan_host": (c_int32, [C.POINTER(JpegInfo), C.POINTER(c_int64), c_int32, c_int32, c_void_p, c_int64, C.POINTER(JpegBatch)]),
+    "rhccq_jpeg_decode_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rhccq_jpeg_write_tables_bytes": (c_int32, []),
     "rhccq_jpeg_write_tables_host": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "rhccq_jpeg_write_sizes": (c_int32, [c_int32] * 5 + [C.POINTER(c_int64)] * 4),

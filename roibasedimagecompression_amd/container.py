@@ -390,6 +390,16 @@ def read_gif(src, rh=None):
                       "stream_bytes": [table[f].stream_bytes for f in range(info.n_frames)], "seconds": round(time.perf_counter() - t0, 4)}}
 
 
+def _file_bytes(src):
+    """bytes as they are given, or a named file's, as a bytearray"""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytearray(src)
+    with open(src, "rb") as f:
+        data = bytearray(os.fstat(f.fileno()).st_size)
+        del data[f.readinto(data):]
+    return data
+
+
 def read_jpeg(src, rh=None, subsequence_bits=None):
     """a baseline JPEG file (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, with or without restart markers) -> read_png's dict: {"image": uint8[H, W, 3]
     device, "alpha": None, "shape": (H, W), "info": {components, sampling, restart_interval, intervals}, "stats": {bytes, subsequences,
@@ -402,12 +412,7 @@ def read_jpeg(src, rh=None, subsequence_bits=None):
     from .ops import JPEG_STATUS, jpeg_parse, jpeg_subsequence_bits
     rh = rh or default_context()
     t0 = time.perf_counter()
-    if isinstance(src, (bytes, bytearray, memoryview)):
-        data = bytearray(src)
-    else:
-        with open(src, "rb") as f:
-            data = bytearray(os.fstat(f.fileno()).st_size)
-            del data[f.readinto(data):]
+    data = _file_bytes(src)
     parsed = jpeg_parse(data)
     info = parsed[0]
 
@@ -426,6 +431,74 @@ def read_jpeg(src, rh=None, subsequence_bits=None):
             "info": {"components": info.n_comp, "sampling": (info.hs, info.vs), "restart_interval": info.restart_interval, "intervals": info.n_intervals},
             "stats": {"bytes": len(data), "subsequences": int(head[1]) & 0xFFFFFFFF, "subsequence_bits": int(subsequence_bits or jpeg_subsequence_bits()),
                       "sync_rounds": rounds, "worst_walk": walk, "seconds": round(time.perf_counter() - t0, 4)}}
+
+
+def read_jpeg_batch(srcs, rh=None, subsequence_bits=None, strict=True):
+    """many baseline JPEG files (a list of file names or bytes, of any sizes and samplings) decoded together on the device, each to the
+    bytes read_jpeg gives for it alone (include/rhccq.h "JPEG files read as a batch": every workgroup belongs to one file) -> {"images": a
+    list of uint8[H_i, W_i, 3] device tensors, views of one buffer, "shapes": [(H_i, W_i)], "infos": read_jpeg's "info" per file,
+    "status": [(status, detail)] per file, "stats": {"files": read_jpeg's stats per file without its seconds, "seconds": the call's}}.
+    When all shapes agree "batch" holds the images as one uint8[B, H, W, 3] tensor: a view where 3 H W is a multiple of 16, else a
+    stacked copy.  The host parses every file, fills one page-locked buffer and uploads it once; the launches are as many as for one
+    file, and one read of the statuses and the statistics is the only wait.  strict: a file the definition refuses raises RhccqError
+    naming the first such file (.index, .status, .detail); with strict=False its images, shapes, infos and stats entries are None and
+    its status stands, and the others are decoded."""
+    from .ops import JPEG_STATUS, jpeg_parse, jpeg_subsequence_bits
+    if isinstance(srcs, (str, bytes, bytearray, memoryview, os.PathLike)) or len(srcs) < 1:
+        raise ValueError("read_jpeg_batch: a list of at least one file name or bytes object is expected")
+    for i, src in enumerate(srcs):
+        if not isinstance(src, (str, os.PathLike, bytes, bytearray, memoryview)):
+            raise TypeError(f"read_jpeg_batch: entry {i} is neither a file name nor bytes ({type(src).__name__})")
+    rh = rh or default_context()
+    t0 = time.perf_counter()
+    datas = [_file_bytes(src) for src in srcs]
+    parsed = [jpeg_parse(d) for d in datas]
+    out = rh.jpeg_decode_batch(datas, parsed, subsequence_bits=subsequence_bits)
+    status, head = rh.to_host(out["status"], out["head"])
+    bits = int(subsequence_bits or jpeg_subsequence_bits())
+    images, shapes, infos, stats = [], [], [], []
+    for i, (info, st, hd) in enumerate(zip(out["infos"], status.tolist(), head.tolist())):
+        if st[0]:
+            if strict:
+                e = RhccqError(f"read_jpeg_batch: file {i}: RHCCQ_JPEG_{JPEG_STATUS[st[0]]} (status {st[0]}), detail {st[1]}")
+                e.status, e.detail, e.index = st[0], st[1], i
+                raise e
+            images.append(None), shapes.append(None), infos.append(None), stats.append(None)
+            continue
+        images.append(out["rgb"][i])
+        shapes.append((info.height, info.width))
+        infos.append({"components": info.n_comp, "sampling": (info.hs, info.vs), "restart_interval": info.restart_interval, "intervals": info.n_intervals})
+        stats.append({"bytes": len(datas[i]), "subsequences": hd[1] & 0xFFFFFFFF, "subsequence_bits": bits, "sync_rounds": hd[2] + hd[3],
+                      "worst_walk": max(hd[2], hd[4])})
+    res = {"images": images, "shapes": shapes, "infos": infos, "status": [tuple(st) for st in status.tolist()]}
+    if all(sh is not None and sh == shapes[0] for sh in shapes):
+        H, W = shapes[0]
+        if (3 * H * W) % 16 == 0:                            # the images lie one behind the other
+            res["batch"] = out["buffer"][out["offsets"][0]:out["offsets"][0] + len(images) * 3 * H * W].view(len(images), H, W, 3)
+        else:
+            res["batch"] = torch.stack(images)
+    res["stats"] = {"files": stats, "seconds": round(time.perf_counter() - t0, 4)}
+    return res
+
+
+def read_images(srcs, rh=None):
+    """PNG and JPEG files by their first bytes -> read_image's dict for each, in order; the JPEG files among them are read together
+    (read_jpeg_batch), the PNG files one by one"""
+    srcs = [os.fspath(src) for src in srcs]
+    magics = []
+    for src in srcs:
+        with open(src, "rb") as f:
+            magics.append(f.read(2))
+    which = [i for i, m in enumerate(magics) if m == b"\xff\xd8"]
+    res = [None if m == b"\xff\xd8" else read_png(src, rh) for src, m in zip(srcs, magics)]
+    if len(which) == 1:
+        res[which[0]] = read_jpeg(srcs[which[0]], rh)
+    elif which:
+        got = read_jpeg_batch([srcs[i] for i in which], rh)
+        for k, i in enumerate(which):
+            res[i] = {"image": got["images"][k], "alpha": None, "shape": got["shapes"][k], "info": got["infos"][k],
+                      "stats": {**got["stats"]["files"][k], "seconds": got["stats"]["seconds"]}}
+    return res
 
 
 def jpeg_bytes(image, rh=None, quality=75, subsampling="420", restart_rows=0, optimize=False):

@@ -5,7 +5,9 @@
 //   entropy    pack / unpack (a decoder state in 64 bits), run: the one decoder every stage uses -- from a state to a bit, counting or
 //              writing;
 //   pixels     idct8 (one pass of the islow IDCT), idct_block, rgb_at (upsampling and colour for one pixel);
-//   serial     unstuff_serial, dc_serial, planes_serial, rgb_serial: the host forms.
+//   serial     unstuff_serial, dc_serial, planes_serial, rgb_serial: the host forms;
+//   kernels    (under hipcc only) SubRow, seg_combine / seg_block_scan (sums that restart), tables_to_lds, sub_end, dc_seq: what the kernels
+//              of jpeg_read.hip and of jpeg_batch.hip share.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -537,6 +539,69 @@ inline void rgb_serial(const Geo& g, const uint8_t* planes, uint8_t* rgb) {
   for (int y = 0; y < g.H; ++y)
     for (int x = 0; x < g.W; ++x) rgb_at(g, planes, y, x, rgb + 3 * ((int64_t)y * g.W + x));
 }
+
+// ---- what the kernels of jpeg_read.hip and jpeg_batch.hip share ----------------------------------------------------------------------
+// the DC tiles of all components
+inline int64_t dc_tiles(const Geo& g) {
+  int64_t t = 0;
+  for (int c = 0; c < g.n_comp; ++c) t += (g.mcus * (c == 0 && g.n_comp == 3 ? g.hs * g.vs : 1) + kThreads - 1) / kThreads;
+  return t;
+}
+
+#if defined(__HIPCC__)
+// what the sync launch records of a subsequence
+struct SubRow {
+  uint64_t entry, leave;
+  uint32_t count, pad;
+};
+
+constexpr int kIdctBlocks = kThreads / 8;                   // blocks of a workgroup of the idct launch: eight lanes a block
+
+// ---- sums that restart ---------------------------------------------------------------------------------------------------------------
+// an element is flag << 32 | value; a flagged one restarts the sum.  (a then b) -> b if b is flagged, else a's flag and both values' sum
+__device__ __forceinline__ uint64_t seg_combine(uint64_t a, uint64_t b) {
+  return b >> 32 ? b : (a & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)a + (uint32_t)b);
+}
+// inclusive over the workgroup's kThreads lanes; s_w: kThreads / 64 words; *total: all of them
+__device__ __forceinline__ uint64_t seg_block_scan(uint64_t x, uint64_t* s_w, uint64_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t t = __shfl_up((unsigned long long)x, o, 64);
+    if (lane >= o) x = seg_combine(t, x);
+  }
+  __syncthreads();                                                   // (the words' last readers are done)
+  if (lane == 63) s_w[wave] = x;
+  __syncthreads();
+  uint64_t pre = 0, tot = 0;
+  for (int i = 0; i < kThreads / 64; ++i) {
+    if (i < wave) pre = seg_combine(pre, s_w[i]);
+    tot = seg_combine(tot, s_w[i]);
+  }
+  *total = tot;
+  return seg_combine(pre, x);
+}
+
+__device__ __forceinline__ void tables_to_lds(rhccq_jpeg_tables* dst, const rhccq_jpeg_tables* __restrict__ src) {
+  for (int i = threadIdx.x; i < (int)(sizeof(rhccq_jpeg_tables) / 4); i += kThreads) ((uint32_t*)dst)[i] = ((const uint32_t*)src)[i];
+  __syncthreads();
+}
+__device__ __forceinline__ long long sub_end(const Dec& d, int S, long long g) {
+  const long long e = (g + 1) * S;
+  return e < d.total_bits ? e : d.total_bits;
+}
+
+// a component's blocks in decode order: nb of them an MCU, the MCU's blocks b0 ..
+struct DcSeq { int nb, b0; long long len, tiles; };
+__device__ __forceinline__ DcSeq dc_seq(const Geo& g, int c) {
+  DcSeq s;
+  s.nb = c == 0 && g.n_comp == 3 ? g.hs * g.vs : 1;
+  s.b0 = c == 0 ? 0 : g.hs * g.vs + c - 1;
+  s.len = g.mcus * s.nb;
+  s.tiles = (s.len + kThreads - 1) / kThreads;
+  return s;
+}
+#endif
 
 }  // namespace jpegr
 }  // namespace rhccq

@@ -30,11 +30,6 @@
 namespace rhccq {
 namespace jpegr {
 
-struct SubRow {
-  uint64_t entry, leave;
-  uint32_t count, pad;
-};
-
 __global__ void head_kernel(uint32_t* __restrict__ head, uint32_t n_sub) {
   if (threadIdx.x < 8) head[threadIdx.x] = threadIdx.x == 0 ? kNoInterval : threadIdx.x == 1 ? n_sub : 0u;
 }
@@ -84,41 +79,7 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(uint32_t* __restrict__ v
   }
 }
 
-// ---- sums that restart ---------------------------------------------------------------------------------------------------------------
-// an element is flag << 32 | value; a flagged one restarts the sum.  (a then b) -> b if b is flagged, else a's flag and both values' sum
-__device__ __forceinline__ uint64_t seg_combine(uint64_t a, uint64_t b) {
-  return b >> 32 ? b : (a & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)a + (uint32_t)b);
-}
-// inclusive over the workgroup's kThreads lanes; s_w: kThreads / 64 words; *total: all of them
-__device__ __forceinline__ uint64_t seg_block_scan(uint64_t x, uint64_t* s_w, uint64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up((unsigned long long)x, o, 64);
-    if (lane >= o) x = seg_combine(t, x);
-  }
-  __syncthreads();                                                   // (the words' last readers are done)
-  if (lane == 63) s_w[wave] = x;
-  __syncthreads();
-  uint64_t pre = 0, tot = 0;
-  for (int i = 0; i < kThreads / 64; ++i) {
-    if (i < wave) pre = seg_combine(pre, s_w[i]);
-    tot = seg_combine(tot, s_w[i]);
-  }
-  *total = tot;
-  return seg_combine(pre, x);
-}
-
 // ---- sync ----------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tables_to_lds(rhccq_jpeg_tables* dst, const rhccq_jpeg_tables* __restrict__ src) {
-  for (int i = threadIdx.x; i < (int)(sizeof(rhccq_jpeg_tables) / 4); i += kThreads) ((uint32_t*)dst)[i] = ((const uint32_t*)src)[i];
-  __syncthreads();
-}
-__device__ __forceinline__ long long sub_end(const Dec& d, int S, long long g) {
-  const long long e = (g + 1) * S;
-  return e < d.total_bits ? e : d.total_bits;
-}
-
 __global__ __launch_bounds__(kThreads) void sync_kernel(Dec d, const rhccq_jpeg_tables* __restrict__ tables, int S, long long n_sub, SubRow* __restrict__ rows,
                                                         uint32_t* __restrict__ head) {
   __shared__ rhccq_jpeg_tables s_T;
@@ -223,16 +184,6 @@ __global__ __launch_bounds__(kThreads) void write_kernel(Dec d, const rhccq_jpeg
 }
 
 // ---- dc ------------------------------------------------------------------------------------------------------------------------------
-// a component's blocks in decode order: nb of them an MCU, the MCU's blocks b0 ..
-struct DcSeq { int nb, b0; long long len, tiles; };
-__device__ __forceinline__ DcSeq dc_seq(const Geo& g, int c) {
-  DcSeq s;
-  s.nb = c == 0 && g.n_comp == 3 ? g.hs * g.vs : 1;
-  s.b0 = c == 0 ? 0 : g.hs * g.vs + c - 1;
-  s.len = g.mcus * s.nb;
-  s.tiles = (s.len + kThreads - 1) / kThreads;
-  return s;
-}
 template <bool FINAL>
 __global__ __launch_bounds__(kThreads) void dc_kernel(Geo g, int16_t* __restrict__ coef, uint64_t* __restrict__ agg) {
   __shared__ uint64_t s_w[kThreads / 64];
@@ -281,7 +232,6 @@ __global__ __launch_bounds__(kThreads) void dc_carry_kernel(Geo g, uint64_t* __r
 }
 
 // ---- idct, colour --------------------------------------------------------------------------------------------------------------------
-constexpr int kIdctBlocks = kThreads / 8;
 __global__ __launch_bounds__(kThreads) void idct_kernel(Geo g, const rhccq_jpeg_tables* __restrict__ tables, const int16_t* __restrict__ coef,
                                                         uint8_t* __restrict__ planes) {
   __shared__ uint16_t s_q[3][64];
@@ -328,11 +278,6 @@ __global__ __launch_bounds__(kThreads) void colour_kernel(Geo g, const uint8_t* 
 }
 
 // ---- layouts and launches ------------------------------------------------------------------------------------------------------------
-static int64_t dc_tiles(const Geo& g) {
-  int64_t t = 0;
-  for (int c = 0; c < g.n_comp; ++c) t += (g.mcus * (c == 0 && g.n_comp == 3 ? g.hs * g.vs : 1) + kThreads - 1) / kThreads;
-  return t;
-}
 // rhccq_jpeg_coefficients' workspace: the head, the unstuff tiles, the stream, the subsequences' rows and first blocks, the DC tiles
 struct CoefLayout { int64_t n_tiles, n_sub, o_tiles, o_stream, o_rows, o_first, o_agg, total; };
 static CoefLayout coef_layout(const rhccq_jpeg_info& f, int S) {

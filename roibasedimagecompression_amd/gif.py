@@ -46,7 +46,7 @@ def main(argv=None):
     if gif_input(args.files[:-1]):
         frames = args.files[0]
     else:
-        frames = [container.read_image(name, enc.rh)["image"] for name in args.files[:-1]]
+        frames = [fr["image"] for fr in container.read_images(args.files[:-1], enc.rh)]
     res = enc.animate(frames, args.colours, gif_path=args.files[-1], delay=args.delay, loop=args.loop, delta=not args.no_delta, refine=args.refine,
                       pattern=args.pattern, pattern_size=args.pattern_size, lossy=args.lossy, size=args.size, resample=args.resample)
     print(json.dumps(res["stats"], sort_keys=True))

@@ -545,6 +545,25 @@ class ImageEncoder:
         return fr["image"], ("png_in", {"shape": list(fr["shape"]), "colour_type": info["colour_type"], "depth": info["depth"],
                                         "alpha_ignored": fr["alpha"] is not None, "chunks": info["chunks"], "idat_chunks": info["idat_chunks"]})
 
+    def _png_in_many(self, images):
+        """_png_in for every entry of a list; the JPEG file names among them are read together (container.read_jpeg_batch)"""
+        from . import container
+        images = list(images)
+        jpegs = []
+        for i, im in enumerate(images):
+            if isinstance(im, (str, os.PathLike)):
+                with open(os.fspath(im), "rb") as f:
+                    if f.read(2) == b"\xff\xd8":
+                        jpegs.append(i)
+        if len(jpegs) < 2:
+            return [self._png_in(im) for im in images]
+        got = container.read_jpeg_batch([os.fspath(images[i]) for i in jpegs], self.rh)
+        read = [None if i in jpegs else self._png_in(im) for i, im in enumerate(images)]
+        for k, i in enumerate(jpegs):
+            read[i] = (got["images"][k], ("jpeg_in", {"shape": list(got["shapes"][k]), **got["infos"][k],
+                                                      **{key: got["stats"]["files"][k][key] for key in ("subsequences", "sync_rounds")}}))
+        return read
+
     # ---- the result as a PNG file (EXTENSION: csrc/png_write.hip) ---------------------------------------------------------------
     @staticmethod
     def _png_arg(fn, png_path, what="png_path"):
@@ -1467,7 +1486,7 @@ class ImageEncoder:
                 raise ValueError(f"{fn}: a uint8 B x H x W x 3 tensor is expected")
             frames = list(stacked)                                               # views
         else:
-            read =[self._png_in(im) for im in images]                          # (a file name among them: a PNG or a JPEG file, read on the device)
+            read = self._png_in_many(images)                                     # (a file name among them: a PNG or a JPEG file, read on the device)
             files = [entry for _, entry in read if entry is not None]
             frames = [self._frame_tensor("animate", im) for im, _ in read]
         B = len(frames)

@@ -282,6 +282,11 @@ def jpeg_subsequence_bits():
     return int(_lib.load().rhccq_jpeg_subsequence_bits())
 
 
+def jpeg_batch_max_files():
+    """the most files Rhccq.jpeg_decode_batch takes in one call"""
+    return int(_lib.load().rhccq_jpeg_batch_max_files())
+
+
 def jpeg_parse(data):
     """rhccq_jpeg_parse_host (host only, a pure function of the bytes) -> (_lib.JpegInfo, the decoder's tables as uint8 bytes (struct
     rhccq_jpeg_tables), the restart intervals int64[n_intervals, 4]: offset and length in the file, first MCU, first byte in the unstuffed
@@ -2483,6 +2488,56 @@ class Rhccq:
         self._check(self.lib.rhccq_jpeg_decode(self.ctx, self._p(file), file.numel(), C.byref(info), self._p(tables), self._p(intervals), S, self._p(work),
                                                self._p(rgb), self._p(status)), fn)
         return {"rgb": rgb.view(info.height, info.width, 3), "status": status, "head": work[:32].view(torch.int32), "info": info}
+
+    # -- JPEG files read as a batch (EXTENSION: csrc/jpeg_batch.hip; include/rhccq.h "JPEG files read as a batch") -------------
+    def jpeg_decode_batch(self, files, parsed=None, subsequence_bits=None):
+        """files: a list of JPEG files' bytes (bytes, bytearray, memoryview or uint8 numpy); parsed: jpeg_parse's triple for each (parsed
+        here when None) -> {"rgb": a list of uint8[H_i, W_i, 3] views of one device buffer, each at a multiple of 16 bytes (None for a
+        file the parse refuses), "buffer": that buffer, "offsets": the images' places in it, "status" int32[B, 2] (JPEG_STATUS index,
+        detail), "head" int32[B, 8] (jpeg_coefficients' eight words, per file), "infos"}.  One host buffer (page-locked) and one copy
+        carry every file, its tables and intervals, the job table and the workgroup maps; the launches are as many as for one file;
+        nothing waits for the device.  A file with a status the framing shows keeps it and the rest decodes."""
+        fn = "jpeg_decode_batch"
+        B = len(files)
+        if B < 1:
+            raise ValueError(f"{fn}: at least one file is expected")
+        S = 0 if subsequence_bits is None else int(subsequence_bits)
+        if S and not (128 <= S <= 65536 and S % 32 == 0):
+            raise ValueError(f"{fn}: subsequence_bits must be a multiple of 32 in 128..65536")
+        datas = [np.frombuffer(f, np.uint8) if not isinstance(f, np.ndarray) else np.ascontiguousarray(f, np.uint8).reshape(-1) for f in files]
+        parsed = [jpeg_parse(d) for d in datas] if parsed is None else list(parsed)
+        if len(parsed) != B:
+            raise ValueError(f"{fn}: parsed must hold one jpeg_parse result per file")
+        infos = (_lib.JpegInfo * B)(*[p[0] for p in parsed])
+        sizes = (C.c_int64 * B)(*[d.size for d in datas])
+        batch = _lib.JpegBatch()
+        rc = self._raw.rhccq_jpeg_batch_sizes(infos, sizes, B, S, C.byref(batch))
+        if rc:
+            raise RhccqError(f"{fn}: rhccq_jpeg_batch_sizes failed ({rc}): " + (f"more than {jpeg_batch_max_files()} files, or a batch beyond the kernels' 32-bit counters"
+                                                                              if rc == -3 else "parsed is not jpeg_parse's for these files"))
+        host = torch.empty((batch.upload_bytes,), dtype=torch.uint8, pin_memory=True)
+        up = host.numpy()
+        rc = self._raw.rhccq_jpeg_batch_plan_host(infos, sizes, B, S, C.c_void_p(host.data_ptr()), batch.upload_bytes, C.byref(batch))
+        if rc:
+            raise RhccqError(f"{fn}: rhccq_jpeg_batch_plan_host failed ({rc})")
+        jobs = (_lib.JpegJob * B).from_buffer_copy(up[:B * C.sizeof(_lib.JpegJob)])
+        for j, d, (info, tables, intervals) in zip(jobs, datas, parsed):
+            if info.status:
+                continue
+            iv = np.ascontiguousarray(intervals, dtype=np.int64).reshape(-1)
+            if len(iv) != 4 * info.n_intervals or len(tables) != j.intervals_offset - j.tables_offset:
+                raise RhccqError(f"{fn}: parsed is not jpeg_parse's for these files")
+            up[j.tables_offset:j.intervals_offset] = tables
+            up[j.intervals_offset:j.file_offset] = iv.view(np.uint8)
+            up[j.file_offset:j.file_offset + d.size] = d
+        dev = host.to(self.device, non_blocking=True)
+        work = self.empty((batch.workspace_bytes,), torch.uint8)
+        buf = self.empty((batch.rgb_bytes,), torch.uint8)
+        status = self.empty((B, 2), torch.int32)
+        self._check(self.lib.rhccq_jpeg_decode_batch(self.ctx, self._p(dev), C.cast(jobs, C.c_void_p), B, S, self._p(work), self._p(buf), self._p(status)), fn)
+        rgb = [None if j.info.status else buf[j.o_rgb:j.o_rgb + 3 * j.info.height * j.info.width].view(j.info.height, j.info.width, 3) for j in jobs]
+        return {"rgb": rgb, "buffer": buf, "offsets": [int(j.o_rgb) for j in jobs], "status": status, "head": work[:32 * B].view(torch.int32).view(B, 8),
+                "infos": [p[0] for p in parsed]}
 
     # -- JPEG files written on the device (EXTENSION: csrc/jpeg_write.hip; include/rhccq.h pins the definition) -------------
     def _jpeg_write_args(self, fn, image, subsampling, quality, restart_rows, optimize=False):
